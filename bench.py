@@ -17,6 +17,10 @@ beside the measured `value`), `one_gpu_same_grid_steps_per_s` / `vs_1gpu_same_gr
 and `configs_run`: at N = 4 also 8192^2 gaussian (BASELINE configs[3]), at N = 8 also 16384^2 source-forced (configs[4]), each with
 its own single-GPU rate.  At N=1 a `driver` leg times the C++ drop-in driver itself (1000 steps, record_step 100).
 
+`--steps K` is the number of timed steps and `ms_per_step` the time of one of them.  At N=1, `--dump-outputs DIR` writes the
+vorticity field the last timed step left (W + K steps from the initial field) to DIR as .npy files, so that two builds can be
+compared output for output on identical inputs.
+
 Roofline conventions: `roofline.achieved` uses the contract's algorithmic bytes (SURVEY.md
 8(d): 8 N^2 per 1-D pass over a field, 320 N^2 per step); next to it the line carries the bytes the kernels really
 move (`traffic`, from the committed rocprofv3 PMC passes), `traffic_frac` = those bytes / launch time / peak, and at
@@ -34,6 +38,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s measured achievable
+DUMP_FIELD_BYTES = 32 << 20    # --dump-outputs: a larger field is written as a seeded sample of its rows (the files stay under 64 MB)
 
 # algorithmic bytes per launch, in units of N^2 bytes (every 1-D pass over a field
 # reads + writes one N^2 float-equivalent array = 8 N^2 B; the x pass is two sub-pass kernels, each
@@ -165,7 +170,18 @@ def parse_args(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=540.0,
                     help="N>1 started from a plain shell: seconds before the child job (its whole process group) is ended; the headline line rank 0 has "
                          "left by then is still printed, marked incomplete (an 8-rank job with its two configs takes about 1.5 minutes)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--gpus 1: after the timed steps, write the vorticity field the timed path left (what a caller reads back with "
+                         "Model.vort()) as DIR/vort.npy, float32, with the indices of its rows as DIR/vort_rows.npy, float64; above %d MiB "
+                         "the field is a fixed, seeded sample of its rows" % (DUMP_FIELD_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs is implemented for --gpus 1")
+    return args
 
 
 def self_launch(args):
@@ -442,6 +458,21 @@ def driver_leg(X, n, kind, with_source, dt, steps, record_step=100):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def dump_outputs(d, vort):
+    """--dump-outputs: the vorticity field after the last timed step as d/vort.npy (float32) and the indices of its rows as
+    d/vort_rows.npy (float64).  Above DUMP_FIELD_BYTES the rows are a sample fixed by the grid alone (seed 0, ascending), so that two
+    runs with the same arguments write the same rows.  Returns {name: shape} of what was written."""
+    import numpy as np
+    nx, ny = vort.shape
+    rows = min(nx, max(1, DUMP_FIELD_BYTES // (4 * ny)))
+    idx = np.arange(nx) if rows == nx else np.sort(np.random.default_rng(0).choice(nx, size=rows, replace=False))
+    os.makedirs(d, exist_ok=True)
+    files = {"vort": np.ascontiguousarray(vort[idx], dtype=np.float32), "vort_rows": idx.astype(np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -522,6 +553,9 @@ def main():
     model, elapsed, spinup = single_gpu_run(X, torch, n, kind, with_source, dt, K, W, args.spinup_steps)
     out = base_line(K / elapsed, 1e3 * elapsed / K, spinup)
     steps_per_s = K / elapsed
+    if args.dump_outputs:                   # before the profiling pass below steps the model on
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "after_steps": W + K,
+                                 "files": dump_outputs(args.dump_outputs, model.vort().cpu().numpy())}
 
     # per-kernel HIP-event timing over a second pass of the same K steps (events on the launch stream)
     prof = model.profile_steps(K)

@@ -418,22 +418,32 @@ short = np.zeros(20000, np.float32); rd(b"field.bin", fp(short), short.size)    
 """
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFDIR, "libfieldio.so")), reason="oracle/_ref not built")
+def _ref_io():
+    """What the reference's own programs in oracle/_ref wrote for the inputs of the tests below (tests/golden/make_ref_io.py)."""
+    with np.load(os.path.join(HERE, "golden", "ref_io.npz")) as z:
+        return {k: z[k].tobytes() for k in z.files}
+
+
+def _run_fieldio_child(lib, d):
+    import sys
+    d.mkdir()
+    res = subprocess.run([sys.executable, "-c", _FIELDIO_CHILD, lib], cwd=str(d), stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True)
+    return open(str(d / "field.bin"), "rb").read(), res.stderr
+
+
 def test_product_fieldio_library_matches_reference_library(tmp_path):
     """lib/libfieldio.so (csrc/fb_fieldio.cpp) exports the reference's mangled writeField/readField (fieldio.hpp:5-6)
     and behaves byte for byte like the reference's own fieldio.cpp compiled into oracle/_ref: same file, same
-    stderr lines, including the short read that reports the element count as "bytes" (fieldio.cpp:32)."""
-    import sys
+    stderr lines, including the short read that reports the element count as "bytes" (fieldio.cpp:32).  The reference
+    library's file and stderr are stored in tests/golden/ref_io.npz; where oracle/_ref is built it runs side by side as well."""
     import xlab_fftbarotropic_amd as X
     X.build_lib()
-    outs = {}
-    for tag, lib in (("ref", os.path.join(REFDIR, "libfieldio.so")), ("mine", os.path.join(LIBDIR, "libfieldio.so")),
-                     ("abi", os.path.join(LIBDIR, "libfftbaro.so"))):
-        d = tmp_path / tag
-        d.mkdir()
-        res = subprocess.run([sys.executable, "-c", _FIELDIO_CHILD, lib], cwd=str(d), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                             check=True)
-        outs[tag] = (open(str(d / "field.bin"), "rb").read(), res.stderr)
+    gold = _ref_io()
+    outs = {"ref": (gold["fieldio_rng7_12345"], gold["fieldio_rng7_12345_stderr"])}
+    for tag, lib in (("mine", os.path.join(LIBDIR, "libfieldio.so")), ("abi", os.path.join(LIBDIR, "libfftbaro.so"))):
+        outs[tag] = _run_fieldio_child(lib, tmp_path / tag)
+    if os.path.exists(os.path.join(REFDIR, "libfieldio.so")):                   # build container: the reference's own library
+        assert _run_fieldio_child(os.path.join(REFDIR, "libfieldio.so"), tmp_path / "ref") == outs["ref"]
     assert outs["mine"][0] == outs["ref"][0] and outs["abi"][0] == outs["ref"][0] and len(outs["ref"][0]) == 4 * 12345
     assert outs["mine"][1] == outs["ref"][1] == b"Output field.bin\n12345 bytes read: field.bin\n12345 bytes read: field.bin\n"
     assert outs["abi"][1] == outs["ref"][1]
@@ -453,24 +463,34 @@ def test_fftw_shim_exports_every_declared_name():
     assert not [n for n in names if not hasattr(L, n)]
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFDIR, "find_min.out")), reason="oracle/_ref not built")
-def test_find_min_matches_reference_build(tmp_path):
-    """host/find_min.cpp against the reference's find_min.cpp:67-101 compiled from its own source (grid fixed at
-    768^2 there): same 30 lines in the same (replacement) order, ties and all; also under ASan/UBSan."""
+def _find_min_input(d, n=768):
+    """Two pressure files with many exact ties in d; returns (the field, find_min's stdin)."""
     import oracle_py as O
-    _build()
-    subprocess.check_call(["make", "-s", "-C", HOST, "asan"])
-    n = 768
     rng = np.random.default_rng(3)
     f = (O.make_field("kuo2004", n) * np.float32(-1e3)).astype(np.float32)
     f += rng.integers(0, 4, size=(n, n)).astype(np.float32) * np.float32(1e-3)          # many exact ties
     names = []
     for i in range(2):
-        (f + np.float32(i)).astype(np.float32).tofile(str(tmp_path / ("pres_%d.bin" % i)))
+        (f + np.float32(i)).astype(np.float32).tofile(os.path.join(str(d), "pres_%d.bin" % i))
         names.append("pres_%d.bin" % i)
-    inp = "\n".join(names) + "\n"
+    return f, "\n".join(names) + "\n"
+
+
+def test_find_min_matches_reference_build(tmp_path):
+    """host/find_min.cpp against the reference's find_min.cpp:67-101 compiled from its own source (grid fixed at
+    768^2 there): same 30 lines in the same (replacement) order, ties and all; also under ASan/UBSan.  The reference
+    build's stdout and stderr are stored in tests/golden/ref_io.npz; where oracle/_ref is built it runs side by side as well."""
+    import types
+    _build()
+    subprocess.check_call(["make", "-s", "-C", HOST, "asan"])
+    n = 768
+    f, inp = _find_min_input(tmp_path, n)
     run = lambda cmd: subprocess.run(cmd, cwd=str(tmp_path), input=inp, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, check=True)
-    ref = run([os.path.join(REFDIR, "find_min.out")])
+    gold = _ref_io()
+    ref = types.SimpleNamespace(stdout=gold["find_min_stdout"].decode(), stderr=gold["find_min_stderr"].decode())
+    if os.path.exists(os.path.join(REFDIR, "find_min.out")):                    # build container: the reference's own program
+        live = run([os.path.join(REFDIR, "find_min.out")])
+        assert (live.stdout, live.stderr) == (ref.stdout, ref.stderr)
     mine = run([os.path.join(HOST, "find_min.out"), "--npts", str(n)])
     asan = run([os.path.join(HOST, "asan", "find_min.out"), "--npts", str(n)])
     assert mine.stdout == ref.stdout and len(ref.stdout.splitlines()) == 60

@@ -2,7 +2,8 @@
 
 Pins, in order of strength:
   1. reference's own fieldio / generators / FIFO producer (oracle/_ref, built from the
-     reference sources unmodified; committed hashes in tests/golden/ref_meta.json);
+     reference sources unmodified; committed hashes and outputs in tests/golden/ref_meta.json
+     and tests/golden/ref_io.npz, so that these tests run without oracle/_ref);
   2. mathematical definition of the DFT (numpy fp64) and analytic known answers for the
      operators -- the FFT-dependent part of the reference is unbuildable here (no FFTW), and
      the reference ships no fixtures: "parity unpinned" by the reference for that part;
@@ -23,6 +24,7 @@ import ref_numpy as R
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = np.load(os.path.join(HERE, "golden", "golden.npz"))
 META = json.load(open(os.path.join(HERE, "golden", "ref_meta.json")))
+REF_IO = np.load(os.path.join(HERE, "golden", "ref_io.npz"))
 REFDIR = os.path.join(os.path.dirname(HERE), "oracle", "_ref")
 L = 600000.0
 
@@ -36,24 +38,29 @@ def test_generators_match_reference_hash(kind):
     assert np.array_equal(f[::16, ::16], GOLD["ref_gen_%s_sub16" % kind])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFDIR, "libfieldio.so")), reason="oracle/_ref not built")
 def test_fieldio_bytes_match_reference_library(tmp_path):
-    """writeField/readField of the reference's own fieldio.cpp (fieldio.cpp:7-33) vs oracle."""
-    ref = ctypes.CDLL(os.path.join(REFDIR, "libfieldio.so"))
-    wr = getattr(ref, "_Z10writeFieldPKcPfm")
-    rd = getattr(ref, "_Z9readFieldPKcPfm")
-    for fn in (wr, rd):
-        fn.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
-        fn.restype = None
+    """writeField/readField of the reference's own fieldio.cpp (fieldio.cpp:7-33) vs oracle.  The file the reference library
+    wrote is stored in tests/golden/ref_io.npz; where oracle/_ref is built the library itself runs as well."""
     a = np.random.default_rng(1).standard_normal(1000).astype(np.float32)
     p_ref, p_mine = str(tmp_path / "ref.bin"), str(tmp_path / "mine.bin")
-    wr(p_ref.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size)
+    open(p_ref, "wb").write(REF_IO["fieldio_rng1_1000"].tobytes())
     assert O.write_field(p_mine, a) == 0
     assert open(p_ref, "rb").read() == open(p_mine, "rb").read() == a.tobytes()
-    b = np.zeros_like(a)
-    rd(p_mine.encode(), b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), b.size)
     rc, c = O.read_field(p_ref, a.size)
-    assert rc == 0 and np.array_equal(b, a) and np.array_equal(c, a)
+    assert rc == 0 and np.array_equal(c, a)
+    if os.path.exists(os.path.join(REFDIR, "libfieldio.so")):                  # build container: the reference's own library
+        ref = ctypes.CDLL(os.path.join(REFDIR, "libfieldio.so"))
+        wr = getattr(ref, "_Z10writeFieldPKcPfm")
+        rd = getattr(ref, "_Z9readFieldPKcPfm")
+        for fn in (wr, rd):
+            fn.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
+            fn.restype = None
+        p_live = str(tmp_path / "live.bin")
+        wr(p_live.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size)
+        assert open(p_live, "rb").read() == open(p_ref, "rb").read()
+        b = np.zeros_like(a)
+        rd(p_mine.encode(), b.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), b.size)
+        assert np.array_equal(b, a)
 
 
 def test_fieldio_error_paths(tmp_path):
@@ -65,11 +72,14 @@ def test_fieldio_error_paths(tmp_path):
     assert rc == -2                      # short read is reported, unlike fieldio.cpp:26
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFDIR, "vort_src_input.out")), reason="oracle/_ref not built")
 def test_fifo_protocol_against_reference_producer(tmp_path):
-    """The reference producer's byte stream (vort_src_input.cpp:43-61) is consumed flag by flag."""
-    raw = subprocess.run([os.path.join(REFDIR, "vort_src_input.out")], stdout=subprocess.PIPE,
-                         stderr=subprocess.DEVNULL, check=True).stdout
+    """The reference producer's byte stream (vort_src_input.cpp:43-61) is consumed flag by flag.  The stream is stored in
+    tests/golden/ref_io.npz; where oracle/_ref is built the producer itself runs as well."""
+    raw = REF_IO["fifo_stream"].tobytes()
+    if os.path.exists(os.path.join(REFDIR, "vort_src_input.out")):            # build container: the reference's own producer
+        live = subprocess.run([os.path.join(REFDIR, "vort_src_input.out")], stdout=subprocess.PIPE,
+                              stderr=subprocess.DEVNULL, check=True).stdout
+        assert live == raw
     assert hashlib.sha256(raw).hexdigest() == META["fifo_stream"]["sha256"]
     p = tmp_path / "stream.bin"
     p.write_bytes(raw)
