@@ -85,9 +85,6 @@ FB_DEV void cf_xchg_lanes(cf *lds, cf *v, int w, int l, int c)
     cf *reg = lds + w * (16 * CF_X2_STR);
 #pragma unroll
     for (int r = 0; r < 16; ++r) lds_wr(&reg[r * CF_X2_STR + l * 4 + c], v[r]);
-#ifdef CF_LANES_WAIT     /* not needed: the DS operations of a wave execute in order, the reads below see these writes (as in r8_xch_wave) */
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int r = 0; r < 16; ++r) v[r] = lds_rd(&reg[l * CF_X2_STR + r * 4 + c]);
@@ -100,14 +97,8 @@ FB_DEV void cf_xchg_lanes(cf *lds, cf *v, int w, int l, int c)
 // 1024-thread workgroup has.
 #define CF_FENCE() __builtin_amdgcn_sched_barrier(0)
 // complex multiplies as two asm statements here (fb_fft_core.h, cmul_split): measured faster in this kernel
-#ifndef CF_BFLY_SPLIT
-#define CF_BFLY_SPLIT 1
-#endif
-#ifndef CF_TW_SPLIT
-#define CF_TW_SPLIT 1
-#endif
-FB_DEV cf cf_mul(cf a, cf b) { return CF_TW_SPLIT ? cmul_split(a, b) : cmul(a, b); }
-FB_DEV cf cf_mulc(cf a, cf b) { return CF_TW_SPLIT ? cmulc_split(a, b) : cmulc(a, b); }
+FB_DEV cf cf_mul(cf a, cf b) { return cmul_split(a, b); }
+FB_DEV cf cf_mulc(cf a, cf b) { return cmulc_split(a, b); }
 
 // radix-16 butterfly with a scheduling fence after every radix-4 sub-butterfly: same arithmetic as
 // Bfly<16>, but the four independent sub-butterflies are not interleaved (a few temporaries
@@ -118,9 +109,9 @@ template <int DIR> FB_DEV void cf_bfly16(cf *v)
     fft4<DIR>(v[1], v[5], v[9], v[13]);  CF_FENCE();
     fft4<DIR>(v[2], v[6], v[10], v[14]); CF_FENCE();
     fft4<DIR>(v[3], v[7], v[11], v[15]); CF_FENCE();
-    v[5]  = mul_w16<1, DIR, CF_BFLY_SPLIT != 0>(v[5]);  v[6]  = mul_w16<2, DIR, CF_BFLY_SPLIT != 0>(v[6]);  v[7]  = mul_w16<3, DIR, CF_BFLY_SPLIT != 0>(v[7]);
-    v[9]  = mul_w16<2, DIR, CF_BFLY_SPLIT != 0>(v[9]);  v[10] = mul_w16<4, DIR, CF_BFLY_SPLIT != 0>(v[10]); v[11] = mul_w16<6, DIR, CF_BFLY_SPLIT != 0>(v[11]);
-    v[13] = mul_w16<3, DIR, CF_BFLY_SPLIT != 0>(v[13]); v[14] = mul_w16<6, DIR, CF_BFLY_SPLIT != 0>(v[14]); v[15] = mul_w16<9, DIR, CF_BFLY_SPLIT != 0>(v[15]);
+    v[5]  = mul_w16<1, DIR, true>(v[5]);  v[6]  = mul_w16<2, DIR, true>(v[6]);  v[7]  = mul_w16<3, DIR, true>(v[7]);
+    v[9]  = mul_w16<2, DIR, true>(v[9]);  v[10] = mul_w16<4, DIR, true>(v[10]); v[11] = mul_w16<6, DIR, true>(v[11]);
+    v[13] = mul_w16<3, DIR, true>(v[13]); v[14] = mul_w16<6, DIR, true>(v[14]); v[15] = mul_w16<9, DIR, true>(v[15]);
     CF_FENCE();
     fft4<DIR>(v[0], v[1], v[2], v[3]);     CF_FENCE();
     fft4<DIR>(v[4], v[5], v[6], v[7]);     CF_FENCE();
@@ -189,27 +180,11 @@ FB_DEV void cf_fft4096(cf *lds, const cf *tabA, const cf *tabB, cf (*v)[16], int
 // of sixteen 64-bit per-lane addresses.
 FB_DEV float4 cf_ld4(const void *ubase, unsigned voff) { return *reinterpret_cast<const float4 *>(static_cast<const char *>(ubase) + voff); }
 FB_DEV void cf_st4(void *ubase, unsigned voff, float4 x) { *reinterpret_cast<float4 *>(static_cast<char *>(ubase) + voff) = x; }
-// the derivative fields are read next by the row pass, a full sweep later: stream them (CF_NT_W4) so that they do
-// not push this tile's freshly written state, which the next field re-reads, out of L2
-#ifndef CF_NT_W4
-#define CF_NT_W4 1     /* measured: 0.192 -> 0.166 ms per launch, and the row pass that follows 0.094 -> 0.087 ms */
-#endif
-#ifndef CF_NT_TIN      /* tendency rows (read once): -1.8 % per launch at 4096^2, -1.6 % at 8192^2 (no gain in round 1, before the other streams were sorted out) */
-#define CF_NT_TIN 1
-#endif
-#ifndef CF_NT_Z0       /* vort_c0 (read once per stage): neutral to slightly worse */
-#define CF_NT_Z0 0
-#endif
-#ifndef CF_NT_ZC       /* the previous stage state, read by stages 2 and 3 for the viscous term */
-#define CF_NT_ZC 0
-#endif
-#ifndef CF_NT_RR3      /* the last of the three re-reads of the new state: -1 % alone, nothing on top of CF_NT_TIN */
-#define CF_NT_RR3 0
-#endif
-#ifndef CF_NT_ACC      /* RK accumulator (next touched a whole stage later) */
-#define CF_NT_ACC 1
-#endif
-FB_DEV void cf_st4_w4(void *ubase, unsigned voff, float4 x) { st4<CF_NT_W4 != 0>(static_cast<char *>(ubase) + voff, x); }
+// Streamed ("nontemporal") accesses: the derivative fields, read next by the row pass a full sweep later, so that they do not push
+// this tile's freshly written state, which the next field re-reads, out of L2 (0.192 -> 0.166 ms per launch, and the row pass that
+// follows 0.094 -> 0.087 ms); the tendency rows, read once (-1.8 % per launch at 4096^2, -1.6 % at 8192^2); the RK accumulator, next
+// touched a whole stage later.  vort_c0, the previous stage state and the re-reads of the new state stay cached (nt: no gain).
+FB_DEV void cf_st4_w4(void *ubase, unsigned voff, float4 x) { st4<true>(static_cast<char *>(ubase) + voff, x); }
 
 template <int STAGE, int NSUB>
 __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
@@ -246,7 +221,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
         float4 tin[16];
         if (!PRIME) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) tin[i] = ld4<CF_NT_TIN != 0>(src + i * rstep + voff_m);
+            for (int i = 0; i < 16; ++i) tin[i] = ld4<true>(src + i * rstep + voff_m);
         }
         float g4[4];
 #pragma unroll
@@ -277,14 +252,11 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
     const bool pada = PRIME_ && ky0 >= a.coef.hy, padb = PRIME_ && ky0 + 1 >= a.coef.hy;      // PRIME's last tile: columns beyond ny/2 are zero padding
     constexpr int stage = STAGE;
     const float nu = a.nu, dt = a.dt, hdt = (stage == 2) ? a.dt : a.dt / 2.0f;
-    // The state arrays move one k3 at a time, CF_DEPTH k3 ahead: the loads of k3 + CF_DEPTH are issued before the stores of k3,
+    // The state arrays move one k3 at a time, DEPTH k3 ahead: the loads of k3 + DEPTH are issued before the stores of k3,
     // so no load is ever queued right behind a store (whose acknowledgement it would have to wait for).
     // Two k3 ahead where the registers allow it: stage 0 reads one array (0.140 -> 0.137 ms); with three arrays a depth of 2 spills
     // 100-250 B per lane and loses 3-6 %.
-#ifndef CF_DEPTH
-#define CF_DEPTH (STAGE == 0 ? 2 : 1)
-#endif
-    constexpr int DEPTH = CF_DEPTH;
+    constexpr int DEPTH = STAGE == 0 ? 2 : 1;
     // Stage 1 does not read its stage state back: what stage 0 stored is fma(rk1, dt/2, vort_c0) with rk1 == the accumulator it also
     // stored, so the same instruction on the same bits gives it again (one array read less, 0.94 C of this launch's 12.6 C).
 #ifndef CF_REMAKE_ZC
@@ -294,9 +266,9 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
     float4 q0[DEPTH], q1[DEPTH], q2[DEPTH];
     auto load_k3 = [&](int k3) {
         const int sl = k3 % DEPTH;
-        q0[sl] = ld4<CF_NT_Z0 != 0>(Z0 + k3 * sstep + voff_s);
-        if (stage != 0) q2[sl] = ld4<CF_NT_ACC != 0>(AC + k3 * sstep + voff_s);
-        if (stage != 0 && !REMAKE_ZC) q1[sl] = ld4<CF_NT_ZC != 0>(ZC + k3 * sstep + voff_s);
+        q0[sl] = ld4<false>(Z0 + k3 * sstep + voff_s);
+        if (stage != 0) q2[sl] = ld4<true>(AC + k3 * sstep + voff_s);
+        if (stage != 0 && !REMAKE_ZC) q1[sl] = ld4<false>(ZC + k3 * sstep + voff_s);
     };
     if (!PRIME) {
 #pragma unroll
@@ -335,7 +307,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
         }
         v[0][k3] = cf_make(zn.x, zn.y); v[1][k3] = cf_make(zn.z, zn.w);
         if (k3 + DEPTH < 16) load_k3(k3 + DEPTH);
-        if (stage < 3) { st4<CF_NT_ACC != 0>(AC + k3 * sstep + voff_s, acc); cf_st4(ZC + k3 * sstep, voff_s, zn); }
+        if (stage < 3) { st4<true>(AC + k3 * sstep + voff_s, acc); cf_st4(ZC + k3 * sstep, voff_s, zn); }
         else cf_st4(ZO + k3 * sstep, voff_s, zn);
         CF_FENCE();
     }
@@ -348,7 +320,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
             const unsigned vs = (unsigned)launder((int)voff_s);
 #pragma unroll
             for (int k3 = 0; k3 < 16; ++k3) {
-                const float4 z = (CF_NT_RR3 && f == 3) ? ld4<true>(ZN + k3 * sstep + vs) : cf_ld4(ZN + k3 * sstep, vs);
+                const float4 z = cf_ld4(ZN + k3 * sstep, vs);
                 v[0][k3] = cf_make(z.x, z.y); v[1][k3] = cf_make(z.z, z.w);
             }
         }

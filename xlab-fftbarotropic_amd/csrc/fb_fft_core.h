@@ -20,16 +20,9 @@ FB_DEV cf cf_make(float x, float y) { cf r = {x, y}; return r; }
 // table: 8 cycles against 2 + 2).  Measured on k_row8: 0.0867 -> 0.0832 ms per launch.
 typedef const volatile __attribute__((address_space(3))) cf *lds_vcf_ptr;
 typedef volatile __attribute__((address_space(3))) cf *lds_vcf_wptr;
-#ifndef FB_PAIRED_LDS_WRITES   /* ds_write2_b64: 13 cycles against 6 + 6 -- a small but repeatable gain (1080 -> 1094 steps/s) */
+// The same for writes: ds_write2_b64 costs 13 cycles against 6 + 6 -- a small but repeatable gain (1080 -> 1094 steps/s).
 FB_DEV void lds_wr(cf *p, cf v) { *(lds_vcf_wptr)p = v; }
-#else
-FB_DEV void lds_wr(cf *p, cf v) { *p = v; }
-#endif
-#ifndef FB_PAIRED_LDS_READS
 FB_DEV cf lds_rd(const cf *p) { return *(lds_vcf_ptr)p; }
-#else
-FB_DEV cf lds_rd(const cf *p) { return *p; }
-#endif
 
 FB_DEV cf cadd(cf a, cf b) { return a + b; }
 FB_DEV cf csub(cf a, cf b) { return a - b; }
@@ -38,17 +31,12 @@ FB_DEV cf csub(cf a, cf b) { return a - b; }
 // it cannot look into writes its result with a destination select and pads every dependent pair of statements with
 // s_nop 0 (gfx940 dst-sel forwarding rule; v_pk_*_f32 has no such hazard).  204 of k_rowq's 2492 instructions were
 // such padding.  The early-clobber result keeps a and b alive for the second instruction.
-#define FB_CMUL_ASM_FUSED(MODS, BC) \
+#define FB_CMUL_ASM(MODS, BC) \
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]\n\tv_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1] " MODS \
         : "=&v"(r) : "v"(a), BC(b))
 #define FB_CMUL_ASM_SPLIT(MODS, BC) \
     { cf t_; asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,0]" : "=v"(t_) : "v"(a), BC(b)); \
       asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] " MODS : "=v"(r) : "v"(a), BC(b), "v"(t_)); }
-#ifndef FB_SPLIT_CMUL_ASM
-#define FB_CMUL_ASM(MODS, BC) FB_CMUL_ASM_FUSED(MODS, BC)
-#else
-#define FB_CMUL_ASM(MODS, BC) FB_CMUL_ASM_SPLIT(MODS, BC)
-#endif
 // a*b = (a.x b.x - a.y b.y, a.x b.y + a.y b.x):  t = (a.y b.y, a.y b.x);  r = (a.x b.x - t.x, a.x b.y + t.y)
 FB_DEV cf cmul(cf a, cf b)
 {
@@ -79,7 +67,6 @@ FB_DEV cf cmul_k_split(cf a, cf k) { const cf b = k; cf r; FB_CMUL_ASM_SPLIT("ne
 FB_DEV cf cadd_conj(cf a, cf b) { cf r; asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 FB_DEV cf csub_conj(cf a, cf b) { cf r; asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
 // a + i b = (a.x - b.y, a.y + b.x) ;  a - i b = (a.x + b.y, a.y - b.x)
-#ifndef FB_SCALAR_ROT
 FB_DEV cf cadd_ib(cf a, cf b)
 {
     cf r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
@@ -88,10 +75,6 @@ FB_DEV cf csub_ib(cf a, cf b)
 {
     cf r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
 }
-#else
-FB_DEV cf cadd_ib(cf a, cf b) { return cf_make(a.x - b.y, a.y + b.x); }
-FB_DEV cf csub_ib(cf a, cf b) { return cf_make(a.x + b.y, a.y - b.x); }
-#endif
 #else
 FB_DEV cf cmul(cf a, cf b) { return cf_make(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 FB_DEV cf cmulc(cf a, cf b) { return cf_make(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }
@@ -113,15 +96,8 @@ template <int DIR> FB_DEV cf cadd_rot(cf a, cf b) { return DIR < 0 ? csub_ib(a, 
 template <int DIR> FB_DEV cf csub_rot(cf a, cf b) { return DIR < 0 ? cadd_ib(a, b) : csub_ib(a, b); }
 
 // ---- streaming ("nontemporal") global accesses --------------------------------------------------
-// FB_NT is a bit mask that selects which streams carry the nt hint (tuning switch):
-//   1 strided sub-pass loads   2 strided sub-pass stores   4 row-pass LDS-DMA loads   8 row-pass stores
-//   16 middle kernel tendency loads   32 middle kernel derivative stores   64 middle kernel state arrays
-#ifndef FB_NT
-#define FB_NT 0
-#endif
-#ifndef FB_NT_FWD      /* nt hint on the forward strided sub-pass: 4 % on that kernel at 4096^2, nothing on the step, worse at 8192^2 */
-#define FB_NT_FWD 0
-#endif
+// Streamed where k_col_full says so; elsewhere NT = false (the hint on the forward strided sub-pass: 4 % on that kernel at 4096^2,
+// nothing on the step, worse at 8192^2).
 typedef float f4v __attribute__((ext_vector_type(4)));
 template <bool NT> FB_DEV float4 ld4(const void *p)
 {
@@ -250,9 +226,6 @@ template <int DIR> struct Bfly<16, DIR> {
 // ============================================================================================
 #define WT_PSTR 144   /* [p][g(8)][col(16)] + 16 complex pad: keeps the LB accesses conflict-free */
 
-#ifndef FB_MID128_WAVES
-#define FB_MID128_WAVES 2     /* k_col_mid<128> (nx = 16384): 256 registers, two workgroups per CU */
-#endif
 template <int n> struct WaveTile {
     static constexpr int R1 = n / 8;
     static constexpr int NP = R1 >= 4 ? R1 / 4 : 1;
@@ -264,7 +237,8 @@ template <int n> struct WaveTile {
     static constexpr bool TM = R1 >= 4;       // state arrays in the tile-major layout (fb_kernels.h)
     static FB_DEV bool lb_active(int lane) { return R1 >= 4 || (lane >> 4) < R1; }
     // register-allocation target of the fused middle kernel (waves per SIMD)
-    static constexpr int MID_MIN_WAVES = n >= 128 ? FB_MID128_WAVES : (n >= 64 ? 2 : (n >= 32 ? 4 : 2));   // n < 32: row-layout state path, tiny grids
+    // (k_col_mid<128>, nx = 16384: 256 registers, two workgroups per CU; n < 32: row-layout state path, tiny grids)
+    static constexpr int MID_MIN_WAVES = n >= 64 ? 2 : (n >= 32 ? 4 : 2);
 };
 
 template <int n, int DIR>
@@ -357,11 +331,6 @@ FB_DEV void wave_fft_B2A(const cf *in /*[NLB]*/, float4 *out /*[n/8]*/, cf *lds,
 // radix R when fed from registers):  reg[m*R + q]  <->  position (t + m*T) + q*N/R.
 // ============================================================================================
 FB_DEV int lds_pad(int e) { return e + (e >> 4); }
-// Pacing of the strided x sub-pass: a wave's eight loads (or stores) touch rows ~1 MB apart; issued in one
-// burst they measured 0.118 ms per launch at 4096^2, with 256 idle cycles between them 0.093 ms (128 and 384
-// cycles: 0.106 / 0.094; 512+: slower again) -- most likely DRAM bank/channel conflicts of the large power-of-
-// two-ish stride.  Applied only when the arrays are far larger than the caches (ColArgs::pace).
-FB_DEV void access_gap(int pace) { if (pace) __builtin_amdgcn_s_sleep(4); }
 
 // Opaque copy of a per-thread index: address arithmetic derived from it cannot be hoisted out
 // of the enclosing loop (LICM would otherwise keep dozens of invariant addresses live in VGPRs).
@@ -369,11 +338,7 @@ FB_DEV int launder(int v) { asm volatile("" : "+v"(v)); return v; }
 
 // Workgroup barrier that orders LDS traffic only: waits lgkmcnt(0), not vmcnt, so LDS-DMA
 // prefetches and global stores stay in flight across it (cdna_hip_programming.md, section 5).
-#ifdef FB_NO_LDS_BARRIER   /* timing experiment only (results are wrong): what the workgroup barriers cost */
-FB_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-#else
 FB_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
 
 // Row plans: radices of the BACKWARD (c2r) row transform; the forward transform walks them
 // reversed, so that the backward pass's final register distribution feeds the forward pass.

@@ -218,10 +218,8 @@ template <int N> struct RowCfg {
     // takes in one thread group.  There the fused pass gives a pair TWO groups, one per x row, side by side: each runs its row's two
     // backward transforms, they hand their tendency values to each other through LDS, both run the packed forward transform (its
     // barriers must be met by every wave), the even group stores.  (As k_row3 at 768^2: 0.054 -> 0.035 ms per launch.)
-#ifndef FB_PAIR2_MAXN
-#define FB_PAIR2_MAXN 1024   /* 2048^2 has enough row pairs to fill the chip: measured below */
-#endif
-    static constexpr bool PAIR2 = N <= FB_PAIR2_MAXN && G >= 2;
+    // 2048^2 has enough row pairs to fill the chip: measured below.
+    static constexpr bool PAIR2 = N <= 1024 && G >= 2;
     static constexpr int VALB = PAIR2 ? G * 8 * T : 0;                     // complex: 16 floats per thread and group
     static constexpr size_t LDS_BYTES = ((size_t)G * GSTR + TWL_B + TWL_F + VALB) * sizeof(cf);
     static constexpr int MIN_WAVES = HALFX ? 3 : (THREADS == 256 ? 2 : (THREADS == 512 ? 2 : 4));
@@ -293,8 +291,8 @@ FB_DEV void row_store_pair(cf *lds, int t, const cf *reg, bool valid, const RowV
             const cf zk = reg[e];
             const cf zn = (i == 0 && t == 0) ? zk : lds_rd(&lds[lds_pad(N - k - HOFF)]);
             if (!row_keep<SLAB>(v, t_frozen, k)) continue;
-            st2<(FB_NT & 8) != 0>(const_cast<cf *>(row_ptr<SLAB>(v, 0, rowA, k)), cf_make(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
-            st2<(FB_NT & 8) != 0>(const_cast<cf *>(row_ptr<SLAB>(v, 0, rowB, k)), cf_make(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)));
+            st2<false>(const_cast<cf *>(row_ptr<SLAB>(v, 0, rowA, k)), cf_make(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
+            st2<false>(const_cast<cf *>(row_ptr<SLAB>(v, 0, rowB, k)), cf_make(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)));
         } else if (i == 8 && t == 0 && row_keep<SLAB>(v, t_frozen, N / 2)) {      // Nyquist: its own mirror
             *const_cast<cf *>(row_ptr<SLAB>(v, 0, rowA, N / 2)) = cf_make(reg[e].x, 0.f);
             *const_cast<cf *>(row_ptr<SLAB>(v, 0, rowB, N / 2)) = cf_make(reg[e].y, 0.f);
@@ -314,9 +312,9 @@ FB_DEV void row_dma_issue(cf *stg, int t, const RowView &v, int fA, int fB, int 
         const int ch = w + c * NW, k = ch * 128 + lane * 2;
         cf *dstA = stg + ch * 128, *dstB = stg + N / 2 + ch * 128;   // wave-uniform; the DMA adds lane*16 B
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)row_ptr<SLAB>(v, fA, rowA, k),
-                                         (void __attribute__((address_space(3))) *)dstA, 16, 0, (FB_NT & 4) ? 2 : 0);
+                                         (void __attribute__((address_space(3))) *)dstA, 16, 0, 0);
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)row_ptr<SLAB>(v, fB, rowB, k),
-                                         (void __attribute__((address_space(3))) *)dstB, 16, 0, (FB_NT & 4) ? 2 : 0);
+                                         (void __attribute__((address_space(3))) *)dstB, 16, 0, 0);
     }
     if (t == 0) { nyqA = *row_ptr<SLAB>(v, fA, rowA, N / 2); nyqB = *row_ptr<SLAB>(v, fB, rowB, N / 2); }
 }
@@ -378,11 +376,7 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
     if (!SHARE) twf_own.init(a.tw_fwd, twl + C::TWL_B, t, threadIdx.x, C::THREADS);
     __syncthreads();
 
-#ifdef FB_ROW_SAMEROW   /* timing experiment only: every workgroup works on rows 0,1 (no HBM traffic); results are wrong */
-    auto pair_of = [&](int it, bool &valid) { const int pr = (it * gridDim.x + blockIdx.x) * PPW + pgrp; valid = pr < npairs; return a.x0; };
-#else
     auto pair_of = [&](int it, bool &valid) { const int pr = (it * gridDim.x + blockIdx.x) * PPW + pgrp; valid = pr < npairs; return a.x0 + (valid ? 2 * pr : 0); };
-#endif
     cf nyqA = cf_make(0.f, 0.f), nyqB = nyqA;
     if (DMA && iters > 0) {                                   // prologue: phase 0 of the first pair
         bool v; const int x = pair_of(0, v) + half;
@@ -542,7 +536,6 @@ struct ColArgs {
     long fstride;
     RowMap rm;
     int ct0, nct;      // column tiles [ct0, ct0+nct) are processed (frozen high-ky tiles are skipped per stage)
-    int pace;          // 1: idle 256 cycles between a wave's consecutive strided accesses (large grids)
     int nfields;
     int P;             // pitch (complex)
     int N1, N2;        // nx = N1*N2
@@ -569,10 +562,7 @@ __global__ void __launch_bounds__(256) k_col_strided(ColArgs a)
         cf *base = a.data + (size_t)f * a.fstride + ct * 16;
         float4 in[W::NLA];
 #pragma unroll
-        for (int m = 0; m < W::NLA; ++m) {
-            in[m] = ld4<(FB_NT & 1) != 0 || (FB_NT_FWD && DIR < 0)>(base + a.rm.off((g + 8 * m) * a.N2 + b, a.P) + 2 * cp);
-            access_gap(a.pace);
-        }
+        for (int m = 0; m < W::NLA; ++m) in[m] = ld4<false>(base + a.rm.off((g + 8 * m) * a.N2 + b, a.P) + 2 * cp);
         cf out[W::NLB];
         wave_fft_A2B<n, DIR>(in, out, lds, a.tw_n, lane);
         if (W::lb_active(lane)) {
@@ -581,8 +571,7 @@ __global__ void __launch_bounds__(256) k_col_strided(ColArgs a)
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int k = h + 4 * s + W::R1 * q;
-                    st2<(FB_NT & 2) != 0 || (FB_NT_FWD && DIR < 0)>(&base[a.rm.off(k * a.N2 + b, a.P) + c], out[s * 8 + q]);
-                    access_gap(a.pace);
+                    st2<false>(&base[a.rm.off(k * a.N2 + b, a.P) + c], out[s * 8 + q]);
                 }
         }
     }
@@ -709,7 +698,7 @@ __global__ void __launch_bounds__(256, WaveTile<n>::MID_MIN_WAVES) k_col_mid(Mid
         if (a.stage >= 0) {
 #pragma unroll
             for (int m = 0; m < W::NLA; ++m)
-                in[m] = ld4<(FB_NT & 16) != 0>(a.Tin + tbase + (size_t)(g + 8 * m) * a.P + 2 * cp);
+                in[m] = ld4<false>(a.Tin + tbase + (size_t)(g + 8 * m) * a.P + 2 * cp);
         }
         __builtin_amdgcn_wave_barrier();                        // the previous tile's table readers are done
 #pragma unroll
@@ -773,13 +762,13 @@ __global__ void __launch_bounds__(256, WaveTile<n>::MID_MIN_WAVES) k_col_mid(Mid
 #pragma unroll
                         for (int j = 0; j < JH; ++j) {
                             const int jp = hb * JH + j;
-                            q0[j] = ld4<(FB_NT & 64) != 0>(reinterpret_cast<const float4 *>(a.Zbase) + sb + jp * 64);
+                            q0[j] = ld4<false>(reinterpret_cast<const float4 *>(a.Zbase) + sb + jp * 64);
                             q1[j] = q2[j] = make_float4(0.f, 0.f, 0.f, 0.f);            // never looked at when masked, or at stage 0
                             if (!frozen[j] && a.stage != 0) {
-                                q2[j] = ld4<(FB_NT & 64) != 0>(reinterpret_cast<const float4 *>(a.Acc) + sb + jp * 64);
+                                q2[j] = ld4<false>(reinterpret_cast<const float4 *>(a.Acc) + sb + jp * 64);
                                 // stage 1 does not read its stage state back: stage 0 stored fma(rk1, dt/2, vort_c0) and, next to it, rk1 as
                                 // the accumulator -- the same instruction on the same bits gives it again (as in k_col_full)
-                                if (a.stage != 1 || !FB_MID_REMAKE_ZC) q1[j] = ld4<(FB_NT & 64) != 0>(reinterpret_cast<const float4 *>(a.Zcur) + sb + jp * 64);
+                                if (a.stage != 1 || !FB_MID_REMAKE_ZC) q1[j] = ld4<false>(reinterpret_cast<const float4 *>(a.Zcur) + sb + jp * 64);
                             }
                         }
 #pragma unroll
@@ -803,9 +792,9 @@ __global__ void __launch_bounds__(256, WaveTile<n>::MID_MIN_WAVES) k_col_mid(Mid
                             if (frozen[j] || (split && wv != 0)) continue;
                             const float4 zo = make_float4(zn[e].x, zn[e].y, zn[e + 1].x, zn[e + 1].y);
                             if (a.stage < 3) {
-                                st4<(FB_NT & 64) != 0>(reinterpret_cast<float4 *>(a.Acc) + sb + jp * 64, q2[j]);
-                                st4<(FB_NT & 64) != 0>(reinterpret_cast<float4 *>(a.Zcur) + sb + jp * 64, zo);
-                            } else st4<(FB_NT & 64) != 0>(reinterpret_cast<float4 *>(a.Zout) + sb + jp * 64, zo);
+                                st4<false>(reinterpret_cast<float4 *>(a.Acc) + sb + jp * 64, q2[j]);
+                                st4<false>(reinterpret_cast<float4 *>(a.Zcur) + sb + jp * 64, zo);
+                            } else st4<false>(reinterpret_cast<float4 *>(a.Zout) + sb + jp * 64, zo);
                         }
                     }
                 } else {
@@ -884,7 +873,7 @@ __global__ void __launch_bounds__(256, WaveTile<n>::MID_MIN_WAVES) k_col_mid(Mid
             for (int m = 0; m < W::NLA; ++m) {
                 const cf wb = twb[gf + 8 * m];
                 cf p0 = cmulc(cf_make(out[m].x, out[m].y), wb), p1 = cmulc(cf_make(out[m].z, out[m].w), wb);
-                st4<(FB_NT & 32) != 0>(dst + (size_t)(gf + 8 * m) * a.P + 2 * cpf, make_float4(p0.x, p0.y, p1.x, p1.y));
+                st4<false>(dst + (size_t)(gf + 8 * m) * a.P + 2 * cpf, make_float4(p0.x, p0.y, p1.x, p1.y));
             }
         }
     }

@@ -33,9 +33,6 @@ template <int M> struct Row3Cfg {
     static constexpr int STG = 4 * HP;
     static constexpr size_t LDS_BYTES = ((size_t)GP * 3 * LSTR + TWL_B + TWL_F + (size_t)GP * STG + VALB) * sizeof(cf);
 };
-#ifndef FB_ROW3_STAGE
-#define FB_ROW3_STAGE 1
-#endif
 
 // the four fields' half-spectrum rows of x row `row` -> stg[f * HP + k]; q = thread within the pair's PT threads
 template <int M, bool SLAB>
@@ -204,17 +201,14 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
             for (int rr = 0; rr < 2; ++rr) {
                 const int x = x0 + rr;
                 float zx[16], zy[16];
-                if (FB_ROW3_STAGE) {
-                    __syncthreads();                                  // the previous row's readers are done with the staged rows
-                    row3_stage4<M, SLAB>(stg, launder(q), a.M, x);
-                    __syncthreads();
-                    row3_load_lds<M>(reg, r, launder(t), stg, stg + C::HP, twN);
-                } else row3_load<M, SLAB>(reg, r, launder(t), a.M, 0, 1, x, x, twN);
+                __syncthreads();                                      // the previous row's readers are done with the staged rows
+                row3_stage4<M, SLAB>(stg, launder(q), a.M, x);
+                __syncthreads();
+                row3_load_lds<M>(reg, r, launder(t), stg, stg + C::HP, twN);
                 row_fft<M, false>(lds, launder(t), twb, reg);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) { zx[e] = reg[e].x * a.scale; zy[e] = reg[e].y * a.scale; }   // main.cpp:154,168
-                if (FB_ROW3_STAGE) row3_load_lds<M>(reg, r, launder(t), stg + 2 * C::HP, stg + 3 * C::HP, twN);
-                else row3_load<M, SLAB>(reg, r, launder(t), a.M, 2, 3, x, x, twN);
+                row3_load_lds<M>(reg, r, launder(t), stg + 2 * C::HP, stg + 3 * C::HP, twN);
                 row_fft<M, false>(lds, launder(t), twb, reg);
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {

@@ -36,9 +36,6 @@ struct Row8 {
 // swap the register index with the wave index (workgroup-wide)
 template <bool LEAD = true> FB_DEV void r8_xch_group(cf *v, cf *xbuf, int w, int l)
 {
-#ifdef FB_R8_NOXG   /* timing experiment only */
-    return;
-#endif
     if (LEAD) lds_barrier();                          // every wave is done with its slice (LEAD = false: the caller has had a workgroup barrier since the slices were last read -- the backward transforms, which start right behind the staging barriers of their phase)
 #pragma unroll
     for (int p = 0; p < 8; ++p) lds_wr(&xbuf[p * Row8::SLICE + w * 64 + l], v[p]);
@@ -49,9 +46,6 @@ template <bool LEAD = true> FB_DEV void r8_xch_group(cf *v, cf *xbuf, int w, int
 // swap the register index with l_hi (HI) or l_lo (!HI) inside the wave's own slice
 template <bool HI> FB_DEV void r8_xch_wave(cf *v, cf *slice, int l_hi, int l_lo)
 {
-#ifdef FB_R8_NOXW   /* timing experiment only */
-    return;
-#endif
     constexpr int PITCH = HI ? Row8::PITCH_HI : Row8::PITCH_LO;
     cf *wr = slice + l_hi * 8 + l_lo;
 #pragma unroll
@@ -136,10 +130,6 @@ FB_DEV void r8_dma_issue(cf *stg, int t, const RowView &v, int fA, int fB, int r
 // Hermitian extension Z = A_ext + i B_ext into the first backward stage's registers (SURVEY note N2)
 FB_DEV void r8_ext(cf *v, int t, const cf *stg)
 {
-#ifdef FB_R8_NOEXT  /* timing experiment only */
-    for (int e = 0; e < 8; ++e) v[e] = cf_make(1.f + e, 1.f + t);
-    return;
-#endif
     constexpr int N = Row8::N, T = Row8::T;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -178,11 +168,7 @@ __global__ void __launch_bounds__(512, 4) k_row8(RowArgs a, const cf *__restrict
 
     const int npairs = a.nx >> 1;
     const int iters = (npairs + gridDim.x - 1) / gridDim.x;
-#ifdef FB_ROW_SAMEROW   /* timing experiment only: every workgroup works on rows 0,1 (no HBM traffic); results are wrong */
-    auto pair_of = [&](int it, bool &valid) { const int pr = it * gridDim.x + blockIdx.x; valid = pr < npairs; return a.x0; };
-#else
     auto pair_of = [&](int it, bool &valid) { const int pr = it * gridDim.x + blockIdx.x; valid = pr < npairs; return a.x0 + (valid ? 2 * pr : 0); };
-#endif
     if (iters > 0) {
         bool v; const int x = pair_of(0, v);
         r8_dma_issue<SLAB>(stg, t, a.M, 0, 1, x);
@@ -243,19 +229,15 @@ __global__ void __launch_bounds__(512, 4) k_row8(RowArgs a, const cf *__restrict
 #pragma unroll
         for (int e = 4; e < 8; ++e) xbuf[tt + (e - 4) * T] = v[e];
         lds_barrier();
-#ifdef FB_R8_NOST   /* timing experiment only: (almost) no stores */
-        if (valid && v[0].x == 123.456f) {
-#else
         if (valid) {
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int k = tt + e * T;
                 const cf zk = v[e];
                 const cf zn = (e == 0 && tt == 0) ? zk : lds_rd(&xbuf[N / 2 - k]);            // Z[N - k] sits at N - k - N/2
                 if (!row_keep<SLAB>(a.T, a.t_frozen, k)) continue;
-                st2<(FB_NT & 8) != 0>(const_cast<cf *>(row_ptr<SLAB>(a.T, 0, x0, k)), cf_make(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
-                st2<(FB_NT & 8) != 0>(const_cast<cf *>(row_ptr<SLAB>(a.T, 0, x1, k)), cf_make(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)));
+                st2<false>(const_cast<cf *>(row_ptr<SLAB>(a.T, 0, x0, k)), cf_make(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y)));
+                st2<false>(const_cast<cf *>(row_ptr<SLAB>(a.T, 0, x1, k)), cf_make(0.5f * (zk.y + zn.y), 0.5f * (zn.x - zk.x)));
             }
             if (tt == 0 && row_keep<SLAB>(a.T, a.t_frozen, N / 2)) {  // Nyquist: its own mirror
                 *const_cast<cf *>(row_ptr<SLAB>(a.T, 0, x0, N / 2)) = cf_make(v[4].x, 0.f);

@@ -23,14 +23,8 @@
 
 // Opaque thread id per phase (launder, see fb_rowq.h): needed where the registers are short (V = 1: 122 of 128); at V = 2 the kernel runs two
 // waves per SIMD with up to 256 registers and the one-GPU instance can keep its LDS addresses (246, no scratch; the slab-blocked one would spill
-// 600 B).  RH_LAUNDER_ALL=1: always.
-#ifndef RH_LAUNDER_ALL
-#define RH_LAUNDER_ALL 0
-#endif
-#define RH_LAUNDER(t) ((V == 1 || SLAB || RH_LAUNDER_ALL) ? launder(t) : (t))
-#ifndef RH_NT      /* nontemporal hint on the LDS-DMA loads of the four fields (as RQ_NT in fb_rowq.h) */
-#define RH_NT 0
-#endif
+// 600 B).
+#define RH_LAUNDER(t) ((V == 1 || SLAB) ? launder(t) : (t))
 template <int V> struct RowH {
     static constexpr int M = 4096 * V, N = 2 * M, T = 512;
     static constexpr int SLICE = Row8::SLICE;                  // complex per (wave, sub-sequence) slice of the exchange buffer
@@ -43,34 +37,23 @@ template <int V> struct RowH {
 };
 
 // ---- the M-point transforms on v[V][8]: sub-sequence s holds Z[V q + s], q = t + 512 e (natural order) ----------------
-struct RhNothing { FB_DEV void operator()() const {} };
-template <int V, bool LEAD = true, class F = RhNothing> FB_DEV void rh_xch_group(cf (*v)[8], cf *xbuf, int w, int l, F &&behind_barrier = F())
+template <int V, bool LEAD = true> FB_DEV void rh_xch_group(cf (*v)[8], cf *xbuf, int w, int l)
 {
-#ifdef FB_R8_NOXG   /* timing experiment only (results are wrong) */
-    behind_barrier();
-    return;
-#endif
     if (LEAD) lds_barrier();                          // every wave is done with its slices (not needed by the backward transforms: r8_xch_group)
 #pragma unroll
     for (int s = 0; s < V; ++s)
 #pragma unroll
         for (int p = 0; p < 8; ++p) lds_wr(&xbuf[s * RowH<V>::XSUB + p * Row8::SLICE + w * 64 + l], v[s][p]);
     lds_barrier();
-    behind_barrier();                                 // (backward: every wave has also left the staged row behind -- send for the next one)
 #pragma unroll
     for (int s = 0; s < V; ++s)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[s][e] = lds_rd(&xbuf[s * RowH<V>::XSUB + w * Row8::SLICE + e * 64 + l]);
 }
 
-// The wave-private exchanges of the V sub-sequences, issued TOGETHER: all writes, one scheduling fence, all reads.  The sub-sequences
-// are independent (slices of their own), so the LDS round trip of one hides behind the other's instead of being paid V times, and
-// the butterflies that follow have two independent chains to schedule (a wave has one partner on its SIMD at ny = 16384).
-#ifndef RH_INTERLEAVE
-#define RH_INTERLEAVE 2
-#endif
-// one sub-sequence's wave-private exchange in two halves (RH_INTERLEAVE == 2: the other sub-sequence's butterfly is issued between
-// them, so that the LDS round trip of one hides behind the arithmetic of the other inside the same wave)
+// The wave-private exchanges of the V sub-sequences are interleaved with each other's arithmetic: sub-sequence s is written and read
+// back while the butterfly of s + 1 is issued, so that the LDS round trip of one hides behind the other inside the same wave, and the
+// butterflies have two independent chains to schedule (a wave has one partner on its SIMD at ny = 16384).
 template <int V, bool HI> FB_DEV void rh_xw_write(const cf *v, cf *xbuf, int s, int w, int l_hi, int l_lo)
 {
     constexpr int PITCH = HI ? Row8::PITCH_HI : Row8::PITCH_LO;
@@ -86,36 +69,12 @@ template <int V, bool HI> FB_DEV void rh_xw_read(cf *v, const cf *xbuf, int s, i
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = lds_rd(&rd[e * (HI ? 8 : 1)]);
 }
-template <int V, bool HI> FB_DEV void rh_xch_wave_all(cf (*v)[8], cf *xbuf, int w, int l_hi, int l_lo)
-{
-#ifdef FB_R8_NOXW   /* timing experiment only (results are wrong) */
-    return;
-#endif
-    constexpr int PITCH = HI ? Row8::PITCH_HI : Row8::PITCH_LO;
-#pragma unroll
-    for (int s = 0; s < V; ++s) {
-        cf *wr = xbuf + s * RowH<V>::XSUB + w * Row8::SLICE + l_hi * 8 + l_lo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) lds_wr(&wr[e * PITCH], v[s][e]);
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int s = 0; s < V; ++s) {
-        const cf *slice = xbuf + s * RowH<V>::XSUB + w * Row8::SLICE;
-        const cf *rd = HI ? slice + l_hi * PITCH + l_lo : slice + l_lo * PITCH + l_hi * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[s][e] = lds_rd(&rd[e * (HI ? 8 : 1)]);
-    }
-    __builtin_amdgcn_wave_barrier();
-}
-
 // backward: natural order in, digit-reversed out: sub-transform output F_s[j'] with j' = w + 8 l_hi + 64 l_lo + 512 e; then
 // (V = 2) z[j'] = F_0 + W^{-j'} F_1 and z[j' + 4096] = F_0 - W^{-j'} F_1 with W = exp(-2 pi i/M), left in v[0][e], v[1][e]
-template <int V, class F> FB_DEV void rh_bwd(cf (*v)[8], cf *xbuf, const Row8Tw &tw, cf wq, int w, int l, F &&behind_barrier)
+template <int V> FB_DEV void rh_bwd(cf (*v)[8], cf *xbuf, const Row8Tw &tw, cf wq, int w, int l)
 {
     const int l_hi = l >> 3, l_lo = l & 7;
-#if !defined(FB_R8_NOXG)
-    if (V > 1 && RH_INTERLEAVE == 2) {                    // the group exchange with sub-sequence s's values leaving while s + 1 is transformed
+    if (V > 1) {                                          // the group exchange with sub-sequence s's values leaving while s + 1 is transformed
 #pragma unroll
         for (int s = 0; s < V; ++s) {
             Bfly<8, +1>::run(v[s]);
@@ -125,13 +84,11 @@ template <int V, class F> FB_DEV void rh_bwd(cf (*v)[8], cf *xbuf, const Row8Tw 
             for (int p = 0; p < 8; ++p) lds_wr(&xbuf[s * RowH<V>::XSUB + p * Row8::SLICE + w * 64 + l], v[s][p]);
         }
         lds_barrier();
-        behind_barrier();
 #pragma unroll
         for (int s = 0; s < V; ++s)
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[s][e] = lds_rd(&xbuf[s * RowH<V>::XSUB + w * Row8::SLICE + e * 64 + l]);
     } else
-#endif
     {
 #pragma unroll
     for (int s = 0; s < V; ++s) {
@@ -139,9 +96,9 @@ template <int V, class F> FB_DEV void rh_bwd(cf (*v)[8], cf *xbuf, const Row8Tw 
 #pragma unroll
         for (int p = 1; p < 8; ++p) v[s][p] = cmulc(v[s][p], tw.w0[p - 1]);
     }
-    rh_xch_group<V, false>(v, xbuf, w, l, behind_barrier);
+    rh_xch_group<V, false>(v, xbuf, w, l);
     }
-    if (V > 1 && RH_INTERLEAVE == 2) {
+    if (V > 1) {
         cf w2[7];
 #pragma unroll
         for (int p = 1; p < 8; ++p) w2[p - 1] = lds_rd(&tw.w2[p * 8 + l_lo]);
@@ -161,26 +118,6 @@ template <int V, class F> FB_DEV void rh_bwd(cf (*v)[8], cf *xbuf, const Row8Tw 
             rh_xw_write<V, false>(v[s], xbuf, s, w, l_hi, l_lo);
             rh_xw_read<V, false>(v[s], xbuf, s, w, l_hi, l_lo);
         }
-#pragma unroll
-        for (int s = 0; s < V; ++s) Bfly<8, +1>::run(v[s]);
-    } else if (V > 1 && RH_INTERLEAVE) {
-#pragma unroll
-        for (int s = 0; s < V; ++s) {
-            Bfly<8, +1>::run(v[s]);
-#pragma unroll
-            for (int p = 1; p < 8; ++p) v[s][p] = cmulc(v[s][p], tw.w1[p - 1]);
-        }
-        rh_xch_wave_all<V, true>(v, xbuf, w, l_hi, l_lo);
-        cf w2[7];
-#pragma unroll
-        for (int p = 1; p < 8; ++p) w2[p - 1] = lds_rd(&tw.w2[p * 8 + l_lo]);
-#pragma unroll
-        for (int s = 0; s < V; ++s) {
-            Bfly<8, +1>::run(v[s]);
-#pragma unroll
-            for (int p = 1; p < 8; ++p) v[s][p] = cmulc(v[s][p], w2[p - 1]);
-        }
-        rh_xch_wave_all<V, false>(v, xbuf, w, l_hi, l_lo);
 #pragma unroll
         for (int s = 0; s < V; ++s) Bfly<8, +1>::run(v[s]);
     } else {
@@ -233,7 +170,7 @@ template <int V> FB_DEV void rh_fwd(cf (*v)[8], cf *xbuf, const Row8Tw &tw, cf w
             v[V - 1][e] = d;
         }
     }
-    if (V > 1 && RH_INTERLEAVE == 2) {
+    if (V > 1) {
         cf w2[7];
 #pragma unroll
         for (int p = 1; p < 8; ++p) w2[p - 1] = lds_rd(&tw.w2[p * 8 + l_lo]);
@@ -251,26 +188,6 @@ template <int V> FB_DEV void rh_fwd(cf (*v)[8], cf *xbuf, const Row8Tw &tw, cf w
             rh_xw_write<V, true>(v[s], xbuf, s, w, l_hi, l_lo);
             rh_xw_read<V, true>(v[s], xbuf, s, w, l_hi, l_lo);
         }
-#pragma unroll
-        for (int s = 0; s < V; ++s) {
-#pragma unroll
-            for (int p = 1; p < 8; ++p) v[s][p] = cmul(v[s][p], tw.w1[p - 1]);
-            Bfly<8, -1>::run(v[s]);
-        }
-    } else if (V > 1 && RH_INTERLEAVE) {
-#pragma unroll
-        for (int s = 0; s < V; ++s) Bfly<8, -1>::run(v[s]);
-        rh_xch_wave_all<V, false>(v, xbuf, w, l_hi, l_lo);
-        cf w2[7];
-#pragma unroll
-        for (int p = 1; p < 8; ++p) w2[p - 1] = lds_rd(&tw.w2[p * 8 + l_lo]);
-#pragma unroll
-        for (int s = 0; s < V; ++s) {
-#pragma unroll
-            for (int p = 1; p < 8; ++p) v[s][p] = cmul(v[s][p], w2[p - 1]);
-            Bfly<8, -1>::run(v[s]);
-        }
-        rh_xch_wave_all<V, true>(v, xbuf, w, l_hi, l_lo);
 #pragma unroll
         for (int s = 0; s < V; ++s) {
 #pragma unroll
@@ -316,7 +233,7 @@ FB_DEV void rh_dma_issue(cf *stg, int t, const RowView &view, int field, int row
     for (int c = 0; c < 4 * V; ++c) {                 // 32 V chunks of 1 KiB, 4 V per wave
         const int ch = w + c * 8, k = ch * 128 + lane * 2;
         __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)row_ptr<SLAB>(view, field, row, k),
-                                         rh_to_lds(stg + ch * 128), 16, 0, RH_NT ? 2 : 0);
+                                         rh_to_lds(stg + ch * 128), 16, 0, 0);
     }
     // X[M]: one dword per lane (lanes 0, 1)
     rh_lds_ptr nyq = rh_to_lds(stg + M);
@@ -329,13 +246,6 @@ FB_DEV void rh_dma_issue(cf *stg, int t, const RowView &view, int field, int row
 template <int V> FB_DEV void rh_ext(cf (*v)[8], int t, const cf *stg, const cf *wx /*[V]: exp(+2 pi i (V t + s)/N)*/)
 {
     constexpr int M = RowH<V>::M;
-#ifdef FB_R8_NOEXT  /* timing experiment only (results are wrong): no staging reads, no pre-processing */
-#pragma unroll
-    for (int s = 0; s < V; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[s][e] = cf_make(wx[s].x + (float)e, wx[s].y);
-    return;
-#endif
 #pragma unroll
     for (int s = 0; s < V; ++s)
 #pragma unroll
@@ -395,11 +305,7 @@ __global__ void __launch_bounds__(512, RowH<V>::MIN_WAVES) k_rowh(RowArgs a, con
     __syncthreads();
 
     const int iters = (a.nx + gridDim.x - 1) / gridDim.x;
-#ifdef FB_ROW_SAMEROW   /* timing experiment only: every workgroup works on row 0 (no HBM traffic); results are wrong */
-    auto row_of = [&](int it, bool &valid) { const int r = it * gridDim.x + blockIdx.x; valid = r < a.nx; return a.x0; };
-#else
     auto row_of = [&](int it, bool &valid) { const int r = it * gridDim.x + blockIdx.x; valid = r < a.nx; return a.x0 + (valid ? r : 0); };
-#endif
     if (iters > 0) {
         bool vld; const int x = row_of(0, vld);
         rh_dma_issue<V, SLAB>(stg, t, a.M, 0, x);
@@ -420,15 +326,9 @@ __global__ void __launch_bounds__(512, RowH<V>::MIN_WAVES) k_rowh(RowArgs a, con
             if (wait) RH_WAIT_ROW();                                  // (the first phase's row was waited for before the previous stores)
             lds_barrier();
             rh_ext<V>(v, tp, stg, wx);
-#ifndef RH_LATE_DMA   /* -DRH_LATE_DMA: the next row is sent for behind the exchange barrier instead (one barrier fewer per phase; measured: no gain at ny = 4096 and 16384, 2 % slower in k_rowh2) */
-            lds_barrier();
-            if (next_row >= 0) rh_dma_issue<V, SLAB>(stg, tp, a.M, next_field, next_row);
-            rh_bwd<V>(v, xbuf, tw, wq, tp >> 6, tp & 63, RhNothing());
-#else
-            // the next row is sent for behind the barrier of the transform's own workgroup-wide exchange: by then every wave has
-            // read what it needs of the staged row
-            rh_bwd<V>(v, xbuf, tw, wq, tp >> 6, tp & 63, [&] { if (next_row >= 0) rh_dma_issue<V, SLAB>(stg, tp, a.M, next_field, next_row); });
-#endif
+            lds_barrier();                                            // (sending for the next row behind the exchange barrier instead, one barrier
+            if (next_row >= 0) rh_dma_issue<V, SLAB>(stg, tp, a.M, next_field, next_row);   // fewer per phase: no gain at ny = 16384, 2 % slower in k_rowh2)
+            rh_bwd<V>(v, xbuf, tw, wq, tp >> 6, tp & 63);
         };
         c2r_phase(false, 2, x);                                       // d vort/dx                         main.cpp:154
 #pragma unroll
@@ -471,11 +371,7 @@ __global__ void __launch_bounds__(512, RowH<V>::MIN_WAVES) k_rowh(RowArgs a, con
 #pragma unroll
             for (int e = 4; e < 8; ++e) lds_wr(&xbuf[V * (tt + 512 * (e - 4)) + s], v[s][e]);
         lds_barrier();
-#ifdef FB_R8_NOST   /* timing experiment only: (almost) no stores */
-        if (valid && v[0][0].x == 123.456f) {
-#else
         if (valid) {
-#endif
 #pragma unroll
             for (int s = 0; s < V; ++s)
 #pragma unroll
@@ -588,13 +484,9 @@ __global__ void __launch_bounds__(1024) k_rowh2(RowArgs a, const cf *__restrict_
             if (wait) RH_WAIT_ROW();
             lds_barrier();
             rh2_ext(v, tp, stg0, stg1, wh, wx);
-#ifndef RH_LATE_DMA
             lds_barrier();
             if (next_x2 >= 0) rh_dma_issue<1, false>(stgh, tp, a.M, next_field, (int)(h * sub) + next_x2);
-            rh_bwd<1>(v1, xbuf, tw, wq, tp >> 6, tp & 63, RhNothing());
-#else
-            rh_bwd<1>(v1, xbuf, tw, wq, tp >> 6, tp & 63, [&] { if (next_x2 >= 0) rh_dma_issue<1, false>(stgh, tp, a.M, next_field, (int)(h * sub) + next_x2); });
-#endif
+            rh_bwd<1>(v1, xbuf, tw, wq, tp >> 6, tp & 63);
         };
         c2r_phase(false, 2, x2);                                      // d vort/dx                         main.cpp:154
 #pragma unroll
@@ -662,160 +554,3 @@ __global__ void __launch_bounds__(1024) k_rowh2(RowArgs a, const cf *__restrict_
 }
 
 
-#ifdef RH2_SPLIT_EXPERIMENT
-// =====================================================================================================================
-// k_rowh2s -- TIMING EXPERIMENT of round 4 (never compiled into the product: results are wrong, the forward
-// radix-2 step over x is left out).  k_rowh2 as TWO independent 512-thread workgroups per x2, two resident per CU as k_rowh<1>:
-// workgroup (x2, h) produces the physical row x = x2 + 4096 h alone.  It needs both half-transformed rows Y_0[x2], Y_1[x2] of every
-// field, and a CU's LDS holds one exchange buffer (37 KB) + ONE staged row (32 KB) per context when two contexts share it (two staged
-// rows: 101 KB, one context per CU).  So Y_0 arrives by LDS-DMA one phase ahead as before and Y_1 is read into registers at the
-// point of use (8 B per lane, 512 B per wave instruction); the partner workgroup (h' = 1 - h) is the block 8 ids further on, i.e. the
-// next one on the same XCD, so that the second reader of a row can find it in that XCD's L2.  The tendency row T_h is stored as it
-// is: in the real variant k_col_full<., 2> would form U_k1 = W^{k1 x2}(T_0 + (-1)^{k1} T_1) on load (a second read of the tendency).
-// =====================================================================================================================
-#ifndef RH2S_HALVES
-#define RH2S_HALVES 1      /* 1: Y_1 in two batches of four e (16 registers in flight, the second batch travels while the first is used); 0: all sixteen loads at once */
-#endif
-FB_DEV void rh2s_one(cf *v, int e, int t, const cf *stg0, cf y1k, cf y1m, cf wh, cf wx)
-{
-    constexpr int M = RowH2::M;
-    const int k = t + 512 * e;
-    cf a = cadd(lds_rd(&stg0[k]), cmul(y1k, wh));                                     // X_h[k]
-    cf b = cadd(lds_rd(&stg0[M - k]), cmul(y1m, wh));                                 // X_h[M-k]
-    if (e == 0 && t == 0) { a.y = 0.f; b.y = 0.f; }
-    const cf ev = cadd_conj(a, b);
-    cf d = cmul(csub_conj(a, b), wx);
-    switch (e) {
-    case 1: d = mul_w16<1, +1>(d); break; case 2: d = mul_w16<2, +1>(d); break; case 3: d = mul_w16<3, +1>(d); break;
-    case 4: d = mul_w16<4, +1>(d); break; case 5: d = mul_w16<5, +1>(d); break; case 6: d = mul_w16<6, +1>(d); break;
-    case 7: d = mul_w16<7, +1>(d); break; default: break;
-    }
-    v[e] = cadd_ib(ev, d);
-}
-FB_DEV void rh2s_ext(cf *v, int t, const cf *stg0, const cf *__restrict__ g1, cf wh, cf wx)
-{
-    constexpr int M = RowH2::M;
-#if RH2S_HALVES
-    cf ya[4], yb[4], yc[4], yd[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { const int k = t + 512 * e; ya[e] = g1[k]; yb[e] = g1[M - k]; }
-    RH_WAIT_ROW();                                                    // Y_0 (sent for a phase ago) and the eight loads above
-    lds_barrier();
-#pragma unroll
-    for (int e = 4; e < 8; ++e) { const int k = t + 512 * e; yc[e - 4] = g1[k]; yd[e - 4] = g1[M - k]; }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) rh2s_one(v, e, t, stg0, ya[e], yb[e], wh, wx);
-    RH_WAIT_ROW();
-#pragma unroll
-    for (int e = 4; e < 8; ++e) rh2s_one(v, e, t, stg0, yc[e - 4], yd[e - 4], wh, wx);
-#else
-    cf y1k[8], y1m[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const int k = t + 512 * e; y1k[e] = g1[k]; y1m[e] = g1[M - k]; }
-    RH_WAIT_ROW();                                                    // Y_0 (sent for a phase ago) and the sixteen loads above
-    lds_barrier();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) rh2s_one(v, e, t, stg0, y1k[e], y1m[e], wh, wx);
-#endif
-}
-
-__global__ void __launch_bounds__(512, 4) k_rowh2s(RowArgs a, const cf *__restrict__ root4096, const cf *__restrict__ rootN, int pairs_per_iter)
-{
-    using C = RowH<1>;
-    constexpr int M = C::M;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    cf *xbuf = reinterpret_cast<cf *>(smem_raw);
-    cf *stg = xbuf + C::XBUF;
-    const int t = threadIdx.x, w = t >> 6, l = t & 63;
-    Row8Tw tw;
-#pragma unroll
-    for (int p = 1; p < 8; ++p) tw.w0[p - 1] = root4096[p * t];
-    cf *tw2 = stg + C::STG;
-    if (t < 64) tw2[t] = root4096[64 * (t & 7) * (t >> 3)];
-    tw.w2 = tw2;
-    cf *tw1 = tw2 + C::TW2;                                          // W_512^{p l} at [p - 1][l]: read per phase instead of living in 14 registers
-    if (t < 448) tw1[t] = root4096[8 * (1 + (t >> 6)) * (t & 63)];
-    const cf wq = cf_make(1.f, 0.f);
-    cf wx;
-    { const cf r = rootN[t]; wx = cf_make(r.x, -r.y); }
-#pragma unroll
-    for (int p = 0; p < 7; ++p) asm volatile("" :: "v"(tw.w0[p]));
-    asm volatile("" :: "v"(wx));
-    __syncthreads();
-
-    // blocks b and b + 8 (the same XCD, consecutive there) are the two halves of one x2
-    const int b = blockIdx.x, xcd = b & 7, j = b >> 3, h = j & 1, q = (j >> 1) * 8 + xcd;
-    const long sub = a.sub_rows;
-    const int iters = (a.nx + pairs_per_iter - 1) / pairs_per_iter;
-    auto row_of = [&](int it, bool &valid) { const int r = it * pairs_per_iter + q; valid = r < a.nx; return a.x0 + (valid ? r : 0); };
-    if (iters > 0) { bool vld; const int x2 = row_of(0, vld); rh_dma_issue<1, false>(stg, t, a.M, 0, x2); }
-    for (int it = 0; it < iters; ++it) {
-        bool valid;
-        const int x2 = row_of(it, valid);
-        bool vn = false;
-        const int xn = (it + 1 < iters) ? row_of(it + 1, vn) : -1;
-        const cf wb = a.tw_x[x2];
-        const cf wh = h ? cf_make(-wb.x, wb.y) : cf_make(wb.x, -wb.y);
-        const int xrow = (int)(h * sub) + x2;
-        cf v1[1][8];
-        cf (&v)[8] = v1[0];
-        cf p[8];
-        auto c2r_phase = [&](int field, int next_field, int next_x2) {
-            const int tp = launder(t);
-            rh2s_ext(v, tp, stg, row_ptr<false>(a.M, field, (int)sub + x2, 0), wh, wx);
-            lds_barrier();
-            if (next_x2 >= 0) rh_dma_issue<1, false>(stg, tp, a.M, next_field, next_x2);
-#pragma unroll
-            for (int p = 0; p < 7; ++p) tw.w1[p] = lds_rd(&tw1[p * 64 + (tp & 63)]);
-            rh_bwd<1>(v1, xbuf, tw, wq, tp >> 6, tp & 63, RhNothing());
-        };
-        c2r_phase(0, 2, x2);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] = cf_make(v[e].x * a.scale, v[e].y * a.scale);
-        c2r_phase(2, 1, x2);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) p[e] = cf_make((v[e].x * a.scale) * p[e].x, (v[e].y * a.scale) * p[e].y);
-        c2r_phase(1, 3, x2);
-        {
-            cf zy[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) zy[e] = cf_make(v[e].x * a.scale, v[e].y * a.scale);
-            c2r_phase(3, 0, xn);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = cf_make(p[e].x - (v[e].x * a.scale) * zy[e].x, p[e].y - (v[e].y * a.scale) * zy[e].y);
-        }
-        const int tt = launder(t), wl = tt >> 6, ll = tt & 63;
-#pragma unroll
-        for (int p = 0; p < 7; ++p) tw.w1[p] = lds_rd(&tw1[p * 64 + ll]);
-        rh_fwd<1>(v1, xbuf, tw, wq, wl, ll);
-        lds_barrier();
-#pragma unroll
-        for (int e = 4; e < 8; ++e) lds_wr(&xbuf[tt + 512 * (e - 4)], v[e]);
-        lds_barrier();
-        if (valid) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int k = tt + 512 * e;
-                const cf wk = v[e];
-                if (k == 0) {
-                    *const_cast<cf *>(row_ptr<false>(a.T, 0, xrow, 0)) = cf_make(wk.x + wk.y, 0.f);
-                    *const_cast<cf *>(row_ptr<false>(a.T, 0, xrow, M)) = cf_make(wk.x - wk.y, 0.f);
-                    continue;
-                }
-                const cf wm = lds_rd(&xbuf[M / 2 - k]);
-                const cf ev = cf_make(0.5f * (wk.x + wm.x), 0.5f * (wk.y - wm.y));
-                const cf od = cf_make(0.5f * (wk.y + wm.y), 0.5f * (wm.x - wk.x));
-                cf co = cmulc(od, wx);
-                switch (e) {
-                case 1: co = mul_w16<1, -1>(co); break; case 2: co = mul_w16<2, -1>(co); break; case 3: co = mul_w16<3, -1>(co); break;
-                default: break;
-                }
-                st2<false>(const_cast<cf *>(row_ptr<false>(a.T, 0, xrow, k)), cadd(ev, co));
-                const cf tm = csub(ev, co);
-                st2<false>(const_cast<cf *>(row_ptr<false>(a.T, 0, xrow, M - k)), cf_make(tm.x, -tm.y));
-            }
-            if (tt == 0) { const cf wh2 = v[4]; *const_cast<cf *>(row_ptr<false>(a.T, 0, xrow, M / 2)) = cf_make(wh2.x, -wh2.y); }
-        }
-    }
-}
-#endif  // RH2_SPLIT_EXPERIMENT

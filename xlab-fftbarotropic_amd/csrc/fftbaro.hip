@@ -19,10 +19,6 @@
 #include "fb_rowh.h"
 #include "fb_rowq.h"
 
-#ifndef FB_ROWQ_DEFAULT
-#define FB_ROWQ_DEFAULT 1     /* ny = 4096 row pass: 1 = k_rowq (one row per 256-thread workgroup, four per CU), 0 = k_row8 (two rows per 512-thread workgroup) */
-#endif
-
 // --------------------------------------------------------------------------------------------
 // errors
 // --------------------------------------------------------------------------------------------
@@ -96,13 +92,14 @@ struct fb_ctx {
     bool use_row8;              // fused row pass of ny = 4096 through k_row8 (FB_NO_ROW8=1: the Stockham kernel)
     int rowh_v;                 // fused row pass of ny = 8192 (1) / 16384 (2) through k_rowh (FB_NO_ROWH=1: 0 = the Stockham kernel)
     cf *d_tw_4096;              // W_4096^j for k_rowh's sub-transforms
-    bool use_rowq;              // fused row pass of ny = 4096 through k_rowq (one real row per 4-wave workgroup) instead of k_row8
+    bool use_rowq;              // fused row pass of ny = 4096 through k_rowq (one real row per 4-wave workgroup; FB_ROWQ=0: k_row8)
     cf *d_tw_2048;              // k_rowq's per-thread twiddle table (make_rowq_table)
-    int pace_strided;           // pace the strided sub-pass's accesses (fields much larger than the caches)
-    int col_chunks;             // x pass of a stage is issued in this many column chunks ...
-    int col_streams;            // ... round-robin over this many streams, so that one chunk's kernel tails are filled by the next chunk
-    hipStream_t aux[3];         // the extra streams (created on demand) and the fork/join events
-    hipEvent_t ev_fork, ev_join[3];
+    // the environment switches ("Switches"), read once by read_switches() when the context is created
+    bool rowq_off, no_row8, no_rowh;                  // FB_ROWQ=0, FB_NO_ROW8, FB_NO_ROWH
+    bool full_pass_off, full_noskip;                  // FB_FULL_PASS=0, FB_FULL_NOSKIP
+    bool no_column_skip, no_prescale;                 // FB_NO_COLUMN_SKIP, FB_NO_PRESCALE
+    int pitch_extra;                                  // FB_PITCH_EXTRA (0 if unset)
+    bool no_pitch_tune, pitch_tune, tune_verbose;     // FB_NO_PITCH_TUNE or FB_PITCH_EXTRA set, FB_PITCH_TUNE, FB_TUNE_VERBOSE
     bool nyq_frozen;            // the ky = ny/2 column lies outside the dealiasing circle (always on square grids)
     cf *d_scratch;              // nx*P complex, lazily allocated (standalone r2c / c2r)
     // host copies of the 1-D tables (fb_get_tables)
@@ -124,11 +121,6 @@ static void split_nx(int nx, int &N1, int &N2)
     case 4096: N1 = 64; N2 = 64; break;
     case 8192: N1 = 128; N2 = 64; break;
     default: N1 = 128; N2 = 128; break;   // 16384
-    }
-    // tuning override: FB_SPLIT_N1=<8|16|32|64|128> (both factors must stay within 8..128)
-    if (const char *e = getenv("FB_SPLIT_N1")) {
-        const int n1 = atoi(e);
-        if (n1 >= 8 && n1 <= 128 && (n1 & (n1 - 1)) == 0 && nx % n1 == 0 && nx / n1 >= 8 && nx / n1 <= 128) { N1 = n1; N2 = nx / n1; }
     }
 }
 
@@ -218,6 +210,25 @@ template <typename T> static int upload(T **dptr, const std::vector<T> &h)
 
 static int autotune_pitch(fb_ctx *c);
 
+// The engine's environment switches, read here once per context; nothing else in this file but slab_active_groups (which
+// slab_plan also calls without a context) reads the environment.
+static void read_switches(fb_ctx *c)
+{
+    auto set = [](const char *name) { return getenv(name) != nullptr; };
+    const char *rowq = getenv("FB_ROWQ"), *full = getenv("FB_FULL_PASS"), *extra = getenv("FB_PITCH_EXTRA");
+    c->rowq_off = rowq && rowq[0] == '0';
+    c->no_row8 = set("FB_NO_ROW8");
+    c->no_rowh = set("FB_NO_ROWH");
+    c->full_pass_off = full && full[0] == '0';
+    c->full_noskip = set("FB_FULL_NOSKIP");
+    c->no_column_skip = set("FB_NO_COLUMN_SKIP");
+    c->no_prescale = set("FB_NO_PRESCALE");
+    c->pitch_extra = extra ? atoi(extra) : 0;
+    c->no_pitch_tune = extra || set("FB_NO_PITCH_TUNE");          // a fixed pitch (FB_PITCH_EXTRA) disables the autotuner too
+    c->pitch_tune = set("FB_PITCH_TUNE");
+    c->tune_verbose = set("FB_TUNE_VERBOSE");
+}
+
 extern "C" int fb_create(fb_ctx **out, int nx, int ny, float lx, float ly) { return fb_create_slab(out, nx, ny, lx, ly, 0, 1); }
 
 static int round16(int v) { return (v + 15) / 16 * 16; }
@@ -262,6 +273,7 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
         return fail(FB_EHIP, "fb_create: no HIP device (this engine has no CPU fallback)");
 
     fb_ctx *c = new fb_ctx();                              // value-initialised: every pointer NULL, so fb_destroy() is safe on any error path below
+    read_switches(c);
     c->nx = nx; c->ny = ny; c->hy = ny / 2 + 1;
     c->world = world; c->rank = rank; c->XL = nx / world;
     split_nx(nx, c->N1, c->N2);
@@ -277,7 +289,7 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
     int Ptot;                                              // table length: every global ky a local column can map to
     if (world == 1) {
         c->P = round16(c->hy);
-        if (const char *e = getenv("FB_PITCH_EXTRA")) c->P += 16 * atoi(e);   // tuning hook (disables the autotuner below)
+        c->P += 16 * c->pitch_extra;                       // tuning hook (disables the autotuner below)
         c->ngroups = c->nact = 1; c->grp[0] = ColGroup{c->P, 0, 0};
         c->KA = c->P; c->KF = 0; c->katot = c->P;
         Ptot = c->P + 96;                                  // room for the pitch candidates of autotune_pitch()
@@ -304,13 +316,6 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
     for (int j = 0; j < c->hy; ++j) c->h_ky2[j] = (double)c->h_gy[j] * (double)c->h_gy[j];
 
     c->nyq_frozen = ((double)(ny / 2) * (double)(ny / 2) >= c->gws);
-    c->col_chunks = 1;
-    c->pace_strided = 0;      // measured: only pays at the unlucky pitch 16*129; off by default (FB_PACE=1 to try)
-    if (const char *e = getenv("FB_PACE")) c->pace_strided = atoi(e) != 0;
-    if (const char *e = getenv("FB_COL_CHUNKS")) { int v = atoi(e); if (v >= 1 && v <= 16) c->col_chunks = v; }
-    c->col_streams = 1;
-    if (const char *e = getenv("FB_COL_STREAMS")) { int v = atoi(e); if (v >= 1 && v <= 4) c->col_streams = v; }
-    if (c->col_streams > c->col_chunks) c->col_streams = c->col_chunks;
     int rc;
     if ((rc = upload(&c->d_gx, c->h_gx)) || (rc = upload(&c->d_kx2, c->h_kx2)) ||
         (rc = upload(&c->d_gy, c->h_gy)) || (rc = upload(&c->d_ky2, c->h_ky2)) ||
@@ -321,10 +326,10 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
         fb_destroy(c); return rc;
     }
     if ((ny % 3 == 0 || ny >= 4096) && (rc = upload(&c->d_tw_row3, make_root_table(ny)))) { fb_destroy(c); return rc; }   // 4096: k_row8's W_ny^j; 8192, 16384: k_rowh's
-    c->use_row8 = ny == 4096 && !getenv("FB_NO_ROW8");
-    c->rowh_v = (ny == 8192 || ny == 16384) && !getenv("FB_NO_ROWH") ? ny / 8192 : 0;
+    c->use_row8 = ny == 4096 && !c->no_row8;
+    c->rowh_v = (ny == 8192 || ny == 16384) && !c->no_rowh ? ny / 8192 : 0;
     if (c->rowh_v && (rc = upload(&c->d_tw_4096, make_root_table(4096)))) { fb_destroy(c); return rc; }
-    { const char *e = getenv("FB_ROWQ"); c->use_rowq = ny == 4096 && !getenv("FB_NO_ROW8") && (e ? e[0] != '0' : FB_ROWQ_DEFAULT); }
+    c->use_rowq = c->use_row8 && !c->rowq_off;
     if (c->use_rowq && (rc = upload(&c->d_tw_2048, make_rowq_table()))) { fb_destroy(c); return rc; }
     hipDeviceProp_t prop;
     if (hipGetDevice(&c->dev) != hipSuccess || hipGetDeviceProperties(&prop, c->dev) != hipSuccess) {
@@ -342,8 +347,6 @@ extern "C" int fb_destroy(fb_ctx *c)
     void *tabs[] = {c->d_gx, c->d_kx2, c->d_gy, c->d_ky2, c->d_tw_n1, c->d_tw_n2, c->d_tw_big, c->d_tw_row_bwd, c->d_tw_row_fwd, c->d_tw_256, c->d_tw_row3, c->d_tw_4096, c->d_tw_2048};
     for (void *t : tabs) if (t) hipFree(t);
     if (c->d_scratch) hipFree(c->d_scratch);
-    for (int i = 0; i < 3; ++i) { if (c->aux[i]) hipStreamDestroy(c->aux[i]); if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]); }
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
     delete c;
     return FB_OK;
 }
@@ -557,16 +560,13 @@ template <int N, int MODE> static int launch_row_t(fb_ctx *c, const RowArgs &a)
     const int npairs = a.nx / 2;
     constexpr int ppw = (C::PAIR2 && MODE == ROW_FUSED) ? C::G / 2 : C::G;      // row pairs per workgroup (fb_kernels.h, RowCfg)
     int grid = (npairs + ppw - 1) / ppw;
-    int cap = c->max_wg / 2;                  // persistent-style grid: a few workgroups per CU, each loops over row pairs
-    if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64) cap = v; }
+    const int cap = c->max_wg / 2;            // persistent-style grid: a few workgroups per CU, each loops over row pairs
     if (grid > cap) grid = cap;
     const bool slab = c->world > 1;
     auto kern = slab ? k_row<N, MODE, true> : k_row<N, MODE, false>;
-    static size_t lds_extra = 0;              // experiment hook: FB_ROW_LDS_EXTRA=<bytes> lowers the workgroups per CU
-    if (const char *e = getenv("FB_ROW_LDS_EXTRA")) lds_extra = (size_t)atol(e);
-    int rc = set_max_lds(c, (const void *)kern, C::LDS_BYTES + lds_extra);
+    int rc = set_max_lds(c, (const void *)kern, C::LDS_BYTES);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES + lds_extra, c->stream, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, c->stream, a);
     HIPCHK(hipGetLastError());
     return FB_OK;
 }
@@ -591,7 +591,6 @@ static int launch_row8(fb_ctx *c, const RowArgs &a)
 {
     const int npairs = a.nx / 2;
     int grid = npairs, cap = c->max_wg / 4;   // two resident workgroups per CU, each loops over row pairs
-    if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64) cap = v; }
     if (grid > cap) grid = cap;
     auto kern = c->world > 1 ? k_row8<true> : k_row8<false>;
     int rc = set_max_lds(c, (const void *)kern, Row8::LDS_BYTES);
@@ -604,7 +603,6 @@ static int launch_row8(fb_ctx *c, const RowArgs &a)
 template <int V> static int launch_rowh(fb_ctx *c, const RowArgs &a)
 {
     int grid = a.nx, cap = c->max_wg / (4 * V);   // resident workgroups: two per CU at ny = 8192, one at 16384; each loops over rows
-    if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64) cap = v; }
     if (grid > cap) grid = cap;
     auto kern = c->world > 1 ? k_rowh<V, true> : k_rowh<V, false>;
     int rc = set_max_lds(c, (const void *)kern, RowH<V>::LDS_BYTES);
@@ -618,37 +616,17 @@ static int launch_rowq(fb_ctx *c, const RowArgs &a)
 {
     // one workgroup per row, four resident per CU: measured 0.076-0.078 ms per launch at 4096^2 against 0.081-0.084 with a persistent
     // grid of 1024 looping over rows (the dispatcher's refill keeps the four contexts of a CU out of step; the prologue is cheap)
-    int grid = a.nx;
-    if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64 && v < grid) grid = v; }
-    const bool loop = grid < a.nx;
-    auto kern = c->world > 1 ? (loop ? k_rowq<true, false, true> : k_rowq<true, false, false>)
-              : a.prescaled ? (loop ? k_rowq<false, true, true> : k_rowq<false, true, false>)
-                            : (loop ? k_rowq<false, false, true> : k_rowq<false, false, false>);
+    auto kern = c->world > 1 ? k_rowq<true, false> : a.prescaled ? k_rowq<false, true> : k_rowq<false, false>;
     int rc = set_max_lds(c, (const void *)kern, RowQ::LDS_BYTES);
     if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), RowQ::LDS_BYTES, c->stream, a, (const float4 *)c->d_tw_2048);
+    hipLaunchKernelGGL(kern, dim3(a.nx), dim3(256), RowQ::LDS_BYTES, c->stream, a, (const float4 *)c->d_tw_2048);
     HIPCHK(hipGetLastError());
     return FB_OK;
 }
 
 static int launch_rowh2(fb_ctx *c, const RowArgs &a)
 {
-#ifdef RH2_SPLIT_EXPERIMENT   /* timing experiment (fb_rowh.h, k_rowh2s): two 512-thread workgroups per x2; results are wrong */
-    if (getenv("FB_ROWH2_SPLIT")) {
-        int grid = 2 * a.nx, cap = c->max_wg / 4;              // two resident workgroups per CU; FB_ROW_GRID=16384: one workgroup per (x2, h)
-        if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64) cap = v; }
-        if (grid > cap) grid = cap;
-        grid &= ~15;
-        const size_t lds = RowH<1>::LDS_BYTES + 448 * sizeof(cf);
-        int rc = set_max_lds(c, (const void *)k_rowh2s, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_rowh2s, dim3(grid), dim3(512), lds, c->stream, a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3, grid / 2);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
-    }
-#endif
     int grid = a.nx, cap = c->max_wg / 8;         // one 1024-thread workgroup per CU, each loops over x2
-    if (const char *e = getenv("FB_ROW_GRID")) { int v = atoi(e); if (v >= 64) cap = v; }
     if (grid > cap) grid = cap;
     int rc = set_max_lds(c, (const void *)k_rowh2, RowH2::LDS_BYTES);
     if (rc) return rc;
@@ -709,7 +687,6 @@ template <int DIR> static int launch_col_strided(fb_ctx *c, const ColGroup &G, c
     if (nct < 0) nct = G.ncols / 16 - ct0;
     if (nct <= 0) return FB_OK;
     ColArgs a; a.data = data; a.fstride = fstride; a.rm = rm; a.ct0 = ct0; a.nct = nct; a.nfields = nfields; a.P = G.ncols; a.N1 = c->N1; a.N2 = c->N2;
-    a.pace = c->pace_strided;
     a.tw_n = c->d_tw_n1; a.tw_big = c->d_tw_big;
     const long ntiles = (long)nfields * c->N2 * nct;
     const dim3 g(col_grid(c, ntiles)), b(256);
@@ -730,7 +707,6 @@ template <int DIR> static int launch_col_block(fb_ctx *c, const ColGroup &G, cf 
 {
     if (G.ncols == 0) return FB_OK;
     ColArgs a; a.data = data; a.fstride = fstride; a.rm = rowmap_natural(); a.ct0 = 0; a.nct = G.ncols / 16; a.nfields = nfields; a.P = G.ncols; a.N1 = c->N1; a.N2 = c->N2;
-    a.pace = 0;
     a.tw_n = c->d_tw_n2; a.tw_big = c->d_tw_big;
     const long ntiles = (long)nfields * c->N1 * (G.ncols / 16);
     const dim3 g(col_grid(c, ntiles)), b(256);
@@ -753,9 +729,8 @@ static int launch_col_mid(fb_ctx *c, const MidArgs &a0)
     const long ntiles = (long)c->N1 * a.nct;
     // small launches of small tiles (grids up to 1024^2): one tile per workgroup, the derivative fields spread over its four waves
     // (fb_kernels.h, MidArgs::split): 256^2 9072 -> 9808 steps/s, 1024^2 6084 -> 6382.  Not for 64-row tiles (the slabs of a 4096^2
-    // multi-GPU rank: 0.336 -> 0.383 ms per step) nor for 2048^2 (0.026 -> 0.038 ms per launch).  FB_MID_SPLIT=0|1 overrides
+    // multi-GPU rank: 0.336 -> 0.383 ms per step) nor for 2048^2 (0.026 -> 0.038 ms per launch)
     a.split = (ntiles <= 2048 && c->N2 <= 32) ? 1 : 0;
-    if (const char *e = getenv("FB_MID_SPLIT")) a.split = e[0] == '1';
     const dim3 g(a.split ? (unsigned)(ntiles < c->max_wg ? ntiles : c->max_wg) : (unsigned)col_grid(c, ntiles)), b(256);
     switch (c->N2) {
     case 8: hipLaunchKernelGGL((k_col_mid<8>), g, b, 0, c->stream, a); break;
@@ -780,7 +755,7 @@ static void finish_groups(fb_ctx *c)
         ColGroup &G = c->grp[g];
         const int act = (jmax - G.ky0 + 15) / 16;
         G.nct_active = act < 0 ? 0 : (act > G.ncols / 16 ? G.ncols / 16 : act);
-        if (getenv("FB_NO_COLUMN_SKIP")) G.nct_active = G.ncols / 16;
+        if (c->no_column_skip) G.nct_active = G.ncols / 16;
     }
 }
 
@@ -792,8 +767,7 @@ static void finish_groups(fb_ctx *c)
 // 0: the model's x pass will be the three column kernels; 1 / 2: the single-pass k_col_full with nx = 4096 / 8192 (fb_col_full.h)
 static int full_pass_nsub(const fb_ctx *c)
 {
-    const char *fp = getenv("FB_FULL_PASS");
-    if (c->world != 1 || !c->nyq_frozen || ((c->ny / 2) % 8) != 0 || (fp && fp[0] == '0')) return 0;
+    if (c->world != 1 || !c->nyq_frozen || ((c->ny / 2) % 8) != 0 || c->full_pass_off) return 0;
     if (c->nx == 4096) return 1;
     if (c->nx == 8192 && c->rowh_v == 1) return 2;
     return 0;
@@ -802,7 +776,7 @@ static int full_pass_nsub(const fb_ctx *c)
 static int autotune_pitch(fb_ctx *c)
 {
     finish_groups(c);
-    if (c->world != 1 || getenv("FB_PITCH_EXTRA") || getenv("FB_NO_PITCH_TUNE")) return FB_OK;
+    if (c->world != 1 || c->no_pitch_tune) return FB_OK;
     if ((size_t)c->nx * c->P * sizeof(cf) < ((size_t)32 << 20)) return FB_OK;      // cache-resident grids: nothing to gain
     const int nsub = full_pass_nsub(c);
     const int P0 = c->P, NC = nsub ? 7 : 4;                                        // create_impl leaves room for P0 + 96
@@ -814,7 +788,7 @@ static int autotune_pitch(fb_ctx *c)
     hipDeviceProp_t prop;
     int dev = 0;
     const bool is_gfx950 = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-    if (nsub && is_gfx950 && !getenv("FB_PITCH_TUNE")) {
+    if (nsub && is_gfx950 && !c->pitch_tune) {
         // single-pass x transform: a fixed rule.  tools/pitch_scan.sh on three boxes: round16(ny/2 + 1) is the slowest pitch at
         // 4096^2 (k_col_full 0.1525-0.1556 ms against 0.148-0.152 for every other candidate) and, with + 16, at 8192^2 (0.75 / 0.79 ms
         // against 0.65-0.69 for + 32, + 64, + 96 and 0.69-0.72 for + 48, + 80).  The probe below (FB_PITCH_TUNE=1) sees the same
@@ -852,7 +826,7 @@ static int autotune_pitch(fb_ctx *c)
         else hipLaunchKernelGGL((k_col_full<1, 2>), g, b, CF_LDS_BYTES, c->stream, a);
         return hipGetLastError() == hipSuccess ? FB_OK : FB_EHIP;
     };
-    const bool verbose = getenv("FB_TUNE_VERBOSE") != nullptr;
+    const bool verbose = c->tune_verbose;
     // the device needs ~25 ms of this load to reach full speed: run the probe that long before timing it
     hipEventRecord(e0, c->stream);
     for (int it = 0; it < 400; ++it) {
@@ -1032,11 +1006,9 @@ static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool
     m->c = c; m->nu = nu; m->dt = dt; m->phase_flow = phase_flow;
     // single-pass x transform (fb_col_full.h) where it applies: one GPU, nx = 4096, frozen Nyquist column, whole
     // 8-column tiles.  0.177 ms per stage against 0.21 ms for the three column kernels; FB_FULL_PASS=0 keeps the latter.
-    const char *fp = getenv("FB_FULL_PASS");
-    (void)fp;
     m->nsub = phase_flow ? 0 : full_pass_nsub(c);
     m->full = m->nsub != 0;
-    m->prescale = m->full && c->world == 1 && c->use_rowq && !getenv("FB_NO_PRESCALE");      // use_rowq: ny == 4096, so GRIDS = nx * ny is a power of two
+    m->prescale = m->full && c->world == 1 && c->use_rowq && !c->no_prescale;      // use_rowq: ny == 4096, so GRIDS = nx * ny is a power of two
     int rc = FB_OK;
     auto alloc0 = [&](cf **p, size_t elems) {              // zero-initialised device array (pad columns stay zero: every pass is linear)
         if (rc || elems == 0) return;
@@ -1201,7 +1173,7 @@ static int launch_col_full(fb_model *m, int stage)
     a.nsub = m->nsub; a.sub_rows = 4096;
     a.wscale = m->prescale ? 1.0f / (float)((size_t)c->nx * c->ny) : 1.0f;
     a.ntiles_run = c->grp[0].nct_active * 2 < a.ntiles ? c->grp[0].nct_active * 2 : a.ntiles;   // 16-column tiles -> 8-column tiles
-    if (getenv("FB_FULL_NOSKIP")) a.ntiles_run = a.ntiles;
+    if (c->full_noskip) a.ntiles_run = a.ntiles;
     if (stage == 4) a.ntiles_run = a.ntiles + 1;
     a.coef = make_coef(c); a.tw256 = c->d_tw_256; a.tw4096 = m->nsub == 1 ? c->d_tw_big : c->d_tw_4096;
     const dim3 g(m->nsub * (stage == 4 ? a.ntiles + 1 : a.ntiles)), b(CF_THREADS);
@@ -1303,43 +1275,16 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
                 PROF_END(3);
                 continue;
             }
-            // ... then the x pass in column chunks, each chained forward -> update -> backward so that a
-            // chunk's derivative fields are still in the Infinity Cache when the backward sub-pass reads them
-            const int nchunk = c->col_chunks;
-            // chunks are independent of each other: spread over several streams their kernels overlap, and
-            // the drain of one kernel is filled by the next (not while profiling: the events would interleave)
-            const int nstr = (prof || m->use_graph) ? 1 : c->col_streams;
-            hipStream_t main_stream = c->stream;
-            if (nstr > 1) {
-                if (!c->ev_fork) HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-                for (int i = 0; i < nstr - 1; ++i) {
-                    if (!c->aux[i]) HIPCHK(hipStreamCreateWithFlags(&c->aux[i], hipStreamNonBlocking));
-                    if (!c->ev_join[i]) HIPCHK(hipEventCreateWithFlags(&c->ev_join[i], hipEventDisableTiming));
-                }
-                HIPCHK(hipEventRecord(c->ev_fork, main_stream));
-                for (int i = 0; i < nstr - 1; ++i) HIPCHK(hipStreamWaitEvent(c->aux[i], c->ev_fork, 0));
-            }
-            struct StreamGuard { fb_ctx *c; hipStream_t s; ~StreamGuard() { c->stream = s; } } guard{c, main_stream};
-            for (int h = 0; h < nchunk; ++h) {
-                const int ct0 = (int)((long)G.nct_active * h / nchunk), ct1 = (int)((long)G.nct_active * (h + 1) / nchunk);
-                if (ct1 == ct0) continue;
-                c->stream = (nstr > 1 && h % nstr) ? c->aux[h % nstr - 1] : main_stream;
-                PROF_BEGIN(2);
-                if ((rc = launch_col_strided<-1>(c, G, B.t_recv, 1, 0, rowmap_natural(), ct0, ct1 - ct0))) return rc;
-                PROF_END(2);
-                MidArgs ma = mid_args(m, 0, k); ma.ct0 = ct0; ma.nct = ct1 - ct0;
-                PROF_BEGIN(3);
-                if ((rc = launch_col_mid(c, ma))) return rc;
-                PROF_END(3);
-                PROF_BEGIN(0);
-                if ((rc = launch_col_strided<+1>(c, G, B.w4_send, 4, (long)priv_elems(c), rowmap_natural(), ct0, ct1 - ct0))) return rc;
-                PROF_END(0);
-            }
-            c->stream = main_stream;
-            for (int i = 0; i < nstr - 1; ++i) {
-                HIPCHK(hipEventRecord(c->ev_join[i], c->aux[i]));
-                HIPCHK(hipStreamWaitEvent(main_stream, c->ev_join[i], 0));
-            }
+            // ... then the x pass over the active column tiles: forward strided sub-pass, update + derivatives, backward strided sub-pass
+            PROF_BEGIN(2);
+            if ((rc = launch_col_strided<-1>(c, G, B.t_recv, 1, 0, rowmap_natural(), 0, G.nct_active))) return rc;
+            PROF_END(2);
+            PROF_BEGIN(3);
+            if ((rc = launch_col_mid(c, mid_args(m, 0, k)))) return rc;
+            PROF_END(3);
+            PROF_BEGIN(0);
+            if ((rc = launch_col_strided<+1>(c, G, B.w4_send, 4, (long)priv_elems(c), rowmap_natural(), 0, G.nct_active))) return rc;
+            PROF_END(0);
         }
     }
     return FB_OK;
