@@ -18,7 +18,7 @@
 //   C:     a2a T_A(0), T_B(0) | ...  T_A(last) | T_B(last)                 | a2a W4_A                | a2a W4_B |
 // x pass(A) starts when A's tendency is in (B's is still on the links) and A's four derivative fields leave while B is
 // computed: between the last tendency chunk and the first derivative message the links never wait for a kernel, and only the
-// first row chunk is exposed.  The granularity follows the local work a piece hides (fb_slab_plan, slab_active_groups): a
+// first row chunk is exposed.  The granularity follows the local work a piece hides (slab_layout in fftbaro.hip): a
 // piece that hides less than a collective's latency is not cut off.
 #pragma once
 #include "fb_transport.h"
@@ -42,57 +42,39 @@ struct fb_slab {
 #define FB_OP_XCHG_T    4       /* arg = row chunk   */
 #define FB_OP_COL_FWD   5       /* arg = column group (0 unless the stage is pipelined by column groups) */
 #define FB_OP_COL_ALL_BWD 6     /* backward x sub-pass of all four fields of column group arg */
-static void slab_plan(int nx, int ny, int world, int *nfg, int *nch, int *ncg = nullptr)
+// the geometry the host-side plan functions accept (fb_create_slab also needs an even nx/world)
+static int check_geometry(const char *fn, int nx, int ny, int world)
 {
-    const int dxw = (int)ceil(((double)(float)nx) / 3.0), dyw = (int)ceil(((double)(float)ny) / 3.0);
-    int jmax, KA, KF;
-    slab_split(ny, (double)(float)((double)dxw * dxw + (double)dyw * dyw), world, jmax, KA, KF);
-    const long XL = nx / world;
-    // Pipelining a transpose against the pass that feeds it hides that pass's time, minus one more collective's latency per
-    // extra piece (tens of microseconds for a grouped RCCL send/recv).  So the derivative exchange is cut by fields only where one
-    // field's backward sub-pass (2 * nx * KA * 8 bytes at ~5 TB/s) is worth an operation, and the tendency exchange by row chunks
-    // only where half the row pass (5 * XL * (ny/2+1) * 8 bytes at ~4 TB/s) is.
-    const double bwd_us = 2.0 * nx * KA * 8.0 / 5e6, row_us = 5.0 * XL * (ny / 2 + 1) * 8.0 / 4e6;
-    int fg = world == 1 ? 1 : (bwd_us >= 20.0 ? 4 : (bwd_us >= 10.0 ? 2 : 1));
-    int ch = world == 1 ? 1 : (row_us >= 100.0 ? 2 : 1);
-    if (const char *e = getenv("FB_SLAB_FIELD_GROUPS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) fg = v; }
-    if (const char *e = getenv("FB_SLAB_ROW_CHUNKS")) { const int v = atoi(e); if (v >= 1 && v <= 8) ch = v; }
-    while (ch > 1 && ((XL / ch) & 1 || XL % ch)) ch >>= 1;          // chunks are whole row pairs
-    const int cg = slab_active_groups(nx, world, KA);
-    if (cg > 1) fg = 1;                                             // pipelined by column groups instead: a group's four fields leave together
-    *nfg = fg; *nch = ch;
-    if (ncg) *ncg = cg;
+    if (!fb_size_supported(nx, ny) || world < 1 || !is_pow2(world) || nx / world < 2) return fail(FB_EINVAL, std::string(fn) + ": bad geometry");
+    return FB_OK;
 }
 
 extern "C" int fb_slab_plan(int nx, int ny, int world, int *field_groups, int *row_chunks, int *ops, int cap)
 {
-    if (!fb_size_supported(nx, ny) || world < 1 || !is_pow2(world) || nx / world < 2) { fail(FB_EINVAL, "fb_slab_plan: bad geometry"); return 0; }
-    int nfg, nch, ncg;
-    slab_plan(nx, ny, world, &nfg, &nch, &ncg);
-    if (field_groups) *field_groups = nfg;
-    if (row_chunks) *row_chunks = nch;
+    if (check_geometry("fb_slab_plan", nx, ny, world)) return 0;
+    const SlabLayout L = slab_layout(nx, ny, world);
+    if (field_groups) *field_groups = L.nfg;
+    if (row_chunks) *row_chunks = L.nch;
     int n = 0;
     auto put = [&](int op, int arg) { if (ops && n < cap) ops[n] = op * 16 + arg; ++n; };
-    if (ncg > 1) {                                         // pipelined by column groups (arguments of kinds 2 and 5/6: the column group)
-        for (int h = 0; h < nch; ++h) { put(FB_OP_ROW, h); put(FB_OP_XCHG_T, h); }
-        for (int g = 0; g < ncg; ++g) { put(FB_OP_COL_FWD, g); put(FB_OP_COL_ALL_BWD, g); put(FB_OP_XCHG_W4, g); }
+    if (L.nact > 1) {                                      // pipelined by column groups (arguments of kinds 2 and 5/6: the column group)
+        for (int h = 0; h < L.nch; ++h) { put(FB_OP_ROW, h); put(FB_OP_XCHG_T, h); }
+        for (int g = 0; g < L.nact; ++g) { put(FB_OP_COL_FWD, g); put(FB_OP_COL_ALL_BWD, g); put(FB_OP_XCHG_W4, g); }
         return n;
     }
-    for (int g = 0; g < nfg; ++g) { put(FB_OP_COL_BWD, g); if (world > 1) put(FB_OP_XCHG_W4, g); }
-    for (int h = 0; h < nch; ++h) { put(FB_OP_ROW, h); if (world > 1) put(FB_OP_XCHG_T, h); }
+    for (int g = 0; g < L.nfg; ++g) { put(FB_OP_COL_BWD, g); if (world > 1) put(FB_OP_XCHG_W4, g); }
+    for (int h = 0; h < L.nch; ++h) { put(FB_OP_ROW, h); if (world > 1) put(FB_OP_XCHG_T, h); }
     put(FB_OP_COL_FWD, 0);
     return n;                                              // number of operations of one RK stage (>= 0, not a status)
 }
 
 extern "C" int fb_slab_geometry(int nx, int ny, int world, int *rows_local, int *cols_active, int *cols_frozen)
 {
-    if (!fb_size_supported(nx, ny) || world < 1 || !is_pow2(world) || nx / world < 2) return fail(FB_EINVAL, "fb_slab_geometry: bad geometry");
-    const int dxw = (int)ceil(((double)(float)nx) / 3.0), dyw = (int)ceil(((double)(float)ny) / 3.0);
-    int jmax, KA, KF;
-    slab_split(ny, (double)(float)((double)dxw * dxw + (double)dyw * dyw), world, jmax, KA, KF);
-    if (rows_local) *rows_local = nx / world;
-    if (cols_active) *cols_active = KA;
-    if (cols_frozen) *cols_frozen = KF;
+    if (int rc = check_geometry("fb_slab_geometry", nx, ny, world)) return rc;
+    const SlabLayout L = slab_layout(nx, ny, world);
+    if (rows_local) *rows_local = L.XL;
+    if (cols_active) *cols_active = L.KA;
+    if (cols_frozen) *cols_frozen = L.KF;
     return FB_OK;
 }
 
@@ -100,13 +82,10 @@ extern "C" int fb_slab_geometry(int nx, int ny, int world, int *rows_local, int 
 // group takes the odd one).  Rank r's active slab is the global columns [r*KA, (r+1)*KA): group 0 its first cols2[0], group 1 the rest.
 extern "C" int fb_slab_col_groups(int nx, int ny, int world, int *ngroups, int *cols2)
 {
-    if (!fb_size_supported(nx, ny) || world < 1 || !is_pow2(world) || nx / world < 2) return fail(FB_EINVAL, "fb_slab_col_groups: bad geometry");
-    const int dxw = (int)ceil(((double)(float)nx) / 3.0), dyw = (int)ceil(((double)(float)ny) / 3.0);
-    int jmax, KA, KF;
-    slab_split(ny, (double)(float)((double)dxw * dxw + (double)dyw * dyw), world, jmax, KA, KF);
-    const int na = world == 1 ? 1 : slab_active_groups(nx, world, KA), tiles = KA / 16;
-    if (ngroups) *ngroups = na;
-    if (cols2) for (int g = 0; g < 2; ++g) cols2[g] = g < na ? 16 * (tiles / na + (g < tiles % na ? 1 : 0)) : 0;
+    if (int rc = check_geometry("fb_slab_col_groups", nx, ny, world)) return rc;
+    const SlabLayout L = slab_layout(nx, ny, world);
+    if (ngroups) *ngroups = L.nact;
+    if (cols2) for (int g = 0; g < 2; ++g) cols2[g] = L.cols[g];
     return FB_OK;
 }
 
@@ -146,13 +125,9 @@ extern "C" int fb_slab_create(fb_slab **out, int nx, int ny, float lx, float ly,
     for (hipEvent_t *e : evs)
         if (hipEventCreateWithFlags(e, hipEventDisableTiming) != hipSuccess) return bail(fail(FB_EHIP, "fb_slab_create: cannot create events"));
     if ((rc = model_create_impl(&s->m, s->c, nu, dt, true))) return bail(rc);
-    slab_plan(nx, ny, world, &s->nfg, &s->nch);
-    s->ncg = s->c->nact;
-    if (s->ncg > 1) s->nfg = 1;
-    // Nothing to overlap when a stage has one field group and one row chunk (small slabs): the exchanges then go on the compute
-    // stream, in order, and the stage has no cross-stream hand-overs (each costs the GPU ~10-15 us of idling; tools/slab_local_time.py:
-    // rank-local 4096^2 step on 8 ranks 0.47 -> 0.3x ms).  FB_SLAB_TWO_STREAMS=1 keeps the separate communication stream.
-    if (s->nfg == 1 && s->nch == 1 && s->ncg == 1 && !getenv("FB_SLAB_TWO_STREAMS")) {
+    const SlabLayout L = slab_layout(nx, ny, world);
+    s->nfg = L.nfg; s->nch = L.nch; s->ncg = s->c->nact;
+    if (!L.two_streams) {                                  // the exchanges go on the compute stream
         hipStreamDestroy(s->comm);
         s->comm = s->comp;
     }
@@ -382,7 +357,7 @@ static int slab_stage_groups(fb_slab *s, int stage)
     const int rows = c->XL / s->nch;
     // row pass (main.cpp:154-237, y part) in row chunks; each chunk's tendency rows leave, group by group, while the next chunk is computed
     for (int h = 0; h < s->nch; ++h) {
-        if ((rc = launch_row<ROW_FUSED>(c, fused_row_args(m, h * rows, rows)))) return rc;
+        if ((rc = launch_fused_row(m, h * rows, rows))) return rc;
         if ((rc = slab_after(s->comm, s->comp, s->ev_r[h]))) return rc;
         for (int g = 0; g < s->ncg; ++g) {
             const size_t nc = c->grp[g].ncols, fld = (size_t)c->XL * nc;
@@ -441,7 +416,7 @@ static int slab_stage(fb_slab *s, int stage)
     // row pass (main.cpp:154-237, y part) in row chunks; each chunk's tendency rows leave while the next chunk is computed
     const int rows = c->XL / s->nch;
     for (int h = 0; h < s->nch; ++h) {
-        if ((rc = launch_row<ROW_FUSED>(c, fused_row_args(m, h * rows, rows)))) return rc;
+        if ((rc = launch_fused_row(m, h * rows, rows))) return rc;
         if (c->world > 1) {
             if ((rc = slab_after(s->comm, s->comp, s->ev_r[h]))) return rc;
             if (h == 0 && s->comm != s->comp) HIPCHK(hipStreamWaitEvent(s->comm, s->ev_fwd_done, 0));    // the previous forward pass is done with t_recv

@@ -1,6 +1,7 @@
 // fftbaro.hip -- C ABI (include/fftbaro.h) of the MI355X-native barotropic-vorticity engine.
 // Host side: context/plan/tables, launch logic, model state machine.  Kernels: fb_kernels.h.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -76,6 +77,23 @@ struct ColGroup {
     int nct_active;             // 16-column tiles that contain at least one unmasked ky
 };
 
+// The kernel of the fused row pass (the FWD / INV passes always run the generic one).  RK_ROWH2 is a model's, not a context's:
+// it comes with the x pass XP_FULL2 (launch_fused_row).
+enum RowKernel {
+    RK_GENERIC,                 // k_row<ny> (Stockham) or k_row3<ny/3>
+    RK_ROWQ,                    // ny = 4096: k_rowq, one real row per 4-wave workgroup
+    RK_ROW8,                    // ny = 4096: k_row8, two rows per 512-thread workgroup (FB_ROWQ=0)
+    RK_ROWH_8192,               // k_rowh<1>
+    RK_ROWH_16384,              // k_rowh<2>
+    RK_ROWH2,                   // ny = nx = 8192 on one GPU: k_rowh2, the last radix-2 step of the x transform fused in
+};
+// The x pass of a model's RK stage.  The value is k_col_full's nsub (nx / 4096).
+enum XPass {
+    XP_COLS = 0,                // the three column kernels: forward strided sub-pass, k_col_mid, backward strided sub-pass
+    XP_FULL1 = 1,               // nx = 4096: k_col_full<., 1>
+    XP_FULL2 = 2,               // nx = 8192: k_col_full<., 2>, with the row pass through k_rowh2
+};
+
 struct fb_ctx {
     int world, rank;            // slab decomposition: this process owns x rows [rank*XL, (rank+1)*XL)
     int XL;
@@ -83,16 +101,15 @@ struct fb_ctx {
     int KA, KF, katot;          // world > 1: columns per rank of the active (all groups together) / frozen slabs, katot = world*KA
     int nx, ny, hy, P;          // P = grp[0].ncols: pitch of the private layouts on one GPU
     int N1, N2;                 // nx = N1*N2
+    int jmax;                   // first ky with ky^2 >= gws: that column and all beyond are masked (fftwfop.cpp:57-61)
     float lx, ly;
     hipStream_t stream;
+    RowKernel row;              // the fused row pass (choose_row_kernel)
     // device tables
     float *d_gx; double *d_kx2; float *d_gy; double *d_ky2; double gws;
     cf *d_tw_n1, *d_tw_n2, *d_tw_big, *d_tw_row_bwd, *d_tw_row_fwd, *d_tw_256;
-    cf *d_tw_row3;              // W_ny^j for ny = 3*M (row pass = radix 3 x three length-M transforms) and ny = 4096 (k_row8), else NULL
-    bool use_row8;              // fused row pass of ny = 4096 through k_row8 (FB_NO_ROW8=1: the Stockham kernel)
-    int rowh_v;                 // fused row pass of ny = 8192 (1) / 16384 (2) through k_rowh (FB_NO_ROWH=1: 0 = the Stockham kernel)
+    cf *d_tw_row3;              // W_ny^j for k_row3 (ny = 3*M) and the row kernels other than RK_GENERIC, else NULL
     cf *d_tw_4096;              // W_4096^j for k_rowh's sub-transforms
-    bool use_rowq;              // fused row pass of ny = 4096 through k_rowq (one real row per 4-wave workgroup; FB_ROWQ=0: k_row8)
     cf *d_tw_2048;              // k_rowq's per-thread twiddle table (make_rowq_table)
     // the environment switches ("Switches"), read once by read_switches() when the context is created
     bool rowq_off, no_row8, no_rowh;                  // FB_ROWQ=0, FB_NO_ROW8, FB_NO_ROWH
@@ -210,8 +227,8 @@ template <typename T> static int upload(T **dptr, const std::vector<T> &h)
 
 static int autotune_pitch(fb_ctx *c);
 
-// The engine's environment switches, read here once per context; nothing else in this file but slab_active_groups (which
-// slab_plan also calls without a context) reads the environment.
+// The engine's environment switches, read here once per context; nothing else in this file but slab_layout (which the
+// host-side plan functions also call without a context) reads the environment.
 static void read_switches(fb_ctx *c)
 {
     auto set = [](const char *name) { return getenv(name) != nullptr; };
@@ -233,30 +250,67 @@ extern "C" int fb_create(fb_ctx **out, int nx, int ny, float lx, float ly) { ret
 
 static int round16(int v) { return (v + 15) / 16 * 16; }
 
-// columns per rank of the active and frozen slabs (must match slab.py: slab_geometry)
-static void slab_split(int ny, double gws, int world, int &jmax, int &KA, int &KF)
+// The slab layout of an nx x ny grid on `world` ranks and the schedule of its multi-GPU stage (fb_slab_driver.h; must match
+// slab.py).  Also defined on one rank, where fb_create_slab replaces the column split by the pitch.  The only reader of the
+// FB_SLAB_* switches.
+struct SlabLayout {
+    double gws;                 // dealiasing radius^2
+    int jmax;                   // first ky with ky^2 >= gws: that column and all beyond are masked (fftwfop.cpp:57-61)
+    int XL, KA, KF;             // rows per rank; columns per rank of the active and the frozen slabs
+    int nact, cols[2];          // active column groups of a rank (1 or 2) and their columns (cols[1] = 0 with one group)
+    int nfg, nch;               // field groups of the derivative exchange (1, 2 or 4), row chunks of the tendency exchange (1..8)
+    bool two_streams;           // the exchanges go on a communication stream of their own
+};
+
+static SlabLayout slab_layout(int nx, int ny, int world)
 {
+    SlabLayout L;
+    const int dxw = (int)ceil(((double)(float)nx) / 3.0), dyw = (int)ceil(((double)(float)ny) / 3.0);   // fftwfop.cpp:11-12
+    L.gws = (double)(float)((double)dxw * dxw + (double)dyw * dyw);                                    // :57
     const int hy = ny / 2 + 1;
-    jmax = 0;                                              // first ky with ky^2 >= gws: that column and all beyond are masked (fftwfop.cpp:57-61)
-    while (jmax < hy && (double)jmax * (double)jmax < gws) ++jmax;
-    KA = round16((jmax + world - 1) / world);
-    const int nf = hy - world * KA;
-    KF = nf > 0 ? round16((nf + world - 1) / world) : 0;
+    L.jmax = 0;
+    while (L.jmax < hy && (double)L.jmax * (double)L.jmax < L.gws) ++L.jmax;
+    L.XL = nx / world;
+    L.KA = round16((L.jmax + world - 1) / world);
+    const int nf = hy - world * L.KA;
+    L.KF = nf > 0 ? round16((nf + world - 1) / world) : 0;
+    // How many column groups the ACTIVE columns of a rank are cut into (fb_slab_driver.h: with two, a stage's forward x pass,
+    // update and backward x pass start on the first group while the second group's tendency is still on the links, and the first
+    // group's derivative fields leave while the second group is computed).  Worth it where one group's column work hides a
+    // collective's latency several times over: ~17.5 passes over nx*KA complex at ~5 TB/s.  FB_SLAB_COL_GROUPS=1|2 overrides.
+    L.nact = 1;
+    if (world > 1 && L.KA >= 32) {
+        const double col_us = 17.5 * (double)nx * L.KA * 8.0 / 5e6;
+        if (col_us >= 100.0) L.nact = 2;
+        if (const char *e = getenv("FB_SLAB_COL_GROUPS")) { const int v = atoi(e); if (v == 1 || v == 2) L.nact = v; }
+    }
+    const int tiles = L.KA / 16;                           // whole 16-column tiles, the first group takes the odd one
+    for (int g = 0; g < 2; ++g) L.cols[g] = g < L.nact ? 16 * (tiles / L.nact + (g < tiles % L.nact ? 1 : 0)) : 0;
+    // Pipelining a transpose against the pass that feeds it hides that pass's time, minus one more collective's latency per
+    // extra piece (tens of microseconds for a grouped RCCL send/recv).  So the derivative exchange is cut by fields only where one
+    // field's backward sub-pass (2 * nx * KA * 8 bytes at ~5 TB/s) is worth an operation, and the tendency exchange by row chunks
+    // only where half the row pass (5 * XL * (ny/2+1) * 8 bytes at ~4 TB/s) is.
+    const double bwd_us = 2.0 * nx * L.KA * 8.0 / 5e6, row_us = 5.0 * L.XL * (ny / 2 + 1) * 8.0 / 4e6;
+    L.nfg = world == 1 ? 1 : (bwd_us >= 20.0 ? 4 : (bwd_us >= 10.0 ? 2 : 1));
+    L.nch = world == 1 ? 1 : (row_us >= 100.0 ? 2 : 1);
+    if (const char *e = getenv("FB_SLAB_FIELD_GROUPS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) L.nfg = v; }
+    if (const char *e = getenv("FB_SLAB_ROW_CHUNKS")) { const int v = atoi(e); if (v >= 1 && v <= 8) L.nch = v; }
+    while (L.nch > 1 && ((L.XL / L.nch) & 1 || L.XL % L.nch)) L.nch >>= 1;     // chunks are whole row pairs
+    if (L.nact > 1) L.nfg = 1;                             // pipelined by column groups instead: a group's four fields leave together
+    // Nothing to overlap when a stage has one field group and one row chunk (small slabs): the exchanges then go on the compute
+    // stream, in order, and the stage has no cross-stream hand-overs (each costs the GPU ~10-15 us of idling; tools/slab_local_time.py:
+    // rank-local 4096^2 step on 8 ranks 0.47 -> 0.3x ms).  FB_SLAB_TWO_STREAMS=1 keeps the separate communication stream.
+    L.two_streams = L.nfg > 1 || L.nch > 1 || L.nact > 1 || getenv("FB_SLAB_TWO_STREAMS");
+    return L;
 }
 
-// How many column groups the ACTIVE columns of a rank are cut into (fb_slab_driver.h: with two, a stage's forward x pass,
-// update and backward x pass start on the first group while the second group's tendency is still on the links, and the first
-// group's derivative fields leave while the second group is computed).  Worth it where one group's column work hides a
-// collective's latency several times over: ~17.5 passes over nx*KA complex at ~5 TB/s.  FB_SLAB_COL_GROUPS=1|2 overrides.
-static int slab_active_groups(int nx, int world, int KA)
+// the kernel of the context's fused row pass; a model with the x pass XP_FULL2 runs k_rowh2 instead (launch_fused_row)
+static RowKernel choose_row_kernel(const fb_ctx *c)
 {
-    int na = 1;
-    if (world > 1 && KA >= 32) {
-        const double col_us = 17.5 * (double)nx * KA * 8.0 / 5e6;
-        if (col_us >= 100.0) na = 2;
-        if (const char *e = getenv("FB_SLAB_COL_GROUPS")) { const int v = atoi(e); if (v == 1 || v == 2) na = v; }
-    }
-    return na;
+    if (c->ny == 4096 && !c->no_row8) return c->rowq_off ? RK_ROW8 : RK_ROWQ;
+    if (c->ny == 8192 && !c->no_rowh) return RK_ROWH_8192;
+    if (c->ny == 16384 && !c->no_rowh) return RK_ROWH_16384;
+    return RK_GENERIC;
 }
 
 extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, int rank, int world)
@@ -282,10 +336,8 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
     // ---- coefficient tables: fftwfop.cpp:5-79 ----
     const float TWOPI = (float)(acosf(-1.0f) * 2.0f);                  // fftwfop.hpp:7
     const int hx = nx / 2 + 1;
-    const int dxw = (int)ceil(((double)(float)nx) / 3.0), dyw = (int)ceil(((double)(float)ny) / 3.0);   // :11-12
-    c->gws = (double)(float)((double)dxw * dxw + (double)dyw * dyw);              // :57
-    int jmax = 0;
-    slab_split(ny, c->gws, world, jmax, c->KA, c->KF);
+    const SlabLayout L = slab_layout(nx, ny, world);
+    c->gws = L.gws; c->jmax = L.jmax;
     int Ptot;                                              // table length: every global ky a local column can map to
     if (world == 1) {
         c->P = round16(c->hy);
@@ -294,16 +346,11 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
         c->KA = c->P; c->KF = 0; c->katot = c->P;
         Ptot = c->P + 96;                                  // room for the pitch candidates of autotune_pitch()
     } else {
+        c->KA = L.KA; c->KF = L.KF;
         c->katot = world * c->KA;
-        c->nact = slab_active_groups(nx, world, c->KA);
+        c->nact = L.nact;
         c->ngroups = c->nact + (c->KF > 0 ? 1 : 0);
-        const int tiles = c->KA / 16;
-        int off = 0;
-        for (int g = 0; g < c->nact; ++g) {                // whole 16-column tiles, the first group takes the odd one
-            const int nc = 16 * (tiles / c->nact + (g < tiles % c->nact ? 1 : 0));
-            c->grp[g] = ColGroup{nc, rank * c->KA + off, 0};
-            off += nc;
-        }
+        for (int g = 0; g < c->nact; ++g) c->grp[g] = ColGroup{L.cols[g], rank * c->KA + (g ? L.cols[0] : 0), 0};
         if (c->KF > 0) c->grp[c->nact] = ColGroup{c->KF, c->katot + rank * c->KF, 0};
         c->P = c->grp[0].ncols;
         Ptot = c->katot + world * c->KF + 16;
@@ -325,12 +372,11 @@ extern "C" int fb_create_slab(fb_ctx **out, int nx, int ny, float lx, float ly, 
         (rc = upload(&c->d_tw_row_fwd, make_row_table(ny % 3 ? ny : ny / 3, plan_radices_rt(ny % 3 ? ny : ny / 3, true))))) {
         fb_destroy(c); return rc;
     }
-    if ((ny % 3 == 0 || ny >= 4096) && (rc = upload(&c->d_tw_row3, make_root_table(ny)))) { fb_destroy(c); return rc; }   // 4096: k_row8's W_ny^j; 8192, 16384: k_rowh's
-    c->use_row8 = ny == 4096 && !c->no_row8;
-    c->rowh_v = (ny == 8192 || ny == 16384) && !c->no_rowh ? ny / 8192 : 0;
-    if (c->rowh_v && (rc = upload(&c->d_tw_4096, make_root_table(4096)))) { fb_destroy(c); return rc; }
-    c->use_rowq = c->use_row8 && !c->rowq_off;
-    if (c->use_rowq && (rc = upload(&c->d_tw_2048, make_rowq_table()))) { fb_destroy(c); return rc; }
+    c->row = choose_row_kernel(c);
+    // W_ny^j: k_row3, k_row8 and k_rowh read it.  k_rowq does not, but the table stays, so that the 4096^2 path allocates as it was measured.
+    if ((ny % 3 == 0 || c->row != RK_GENERIC) && (rc = upload(&c->d_tw_row3, make_root_table(ny)))) { fb_destroy(c); return rc; }
+    if ((c->row == RK_ROWH_8192 || c->row == RK_ROWH_16384) && (rc = upload(&c->d_tw_4096, make_root_table(4096)))) { fb_destroy(c); return rc; }
+    if (c->row == RK_ROWQ && (rc = upload(&c->d_tw_2048, make_rowq_table()))) { fb_destroy(c); return rc; }
     hipDeviceProp_t prop;
     if (hipGetDevice(&c->dev) != hipSuccess || hipGetDeviceProperties(&prop, c->dev) != hipSuccess) {
         fb_destroy(c); return fail(FB_EHIP, "fb_create: cannot query the device");
@@ -554,94 +600,60 @@ static int set_max_lds(const fb_ctx *c, const void *fn, size_t bytes)
     return FB_OK;
 }
 
+// Launch of a kernel with more dynamic LDS than the default limit.  The attribute is set on the kernel's first launch on a
+// device, and hipFuncSetAttribute must not run inside a stream capture: fb_model_step captures a step only after an eager one
+// (its warm-up step) has launched every kernel of the step, and the pitch probe and the PRIME launch of k_col_full run eagerly too.
+template <typename K, typename... A> static int launch_lds(const fb_ctx *c, K kern, int grid, int block, size_t lds, const A &...args)
+{
+    int rc = set_max_lds(c, (const void *)kern, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, c->stream, args...);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
 template <int N, int MODE> static int launch_row_t(fb_ctx *c, const RowArgs &a)
 {
     using C = RowCfg<N>;
-    const int npairs = a.nx / 2;
     constexpr int ppw = (C::PAIR2 && MODE == ROW_FUSED) ? C::G / 2 : C::G;      // row pairs per workgroup (fb_kernels.h, RowCfg)
-    int grid = (npairs + ppw - 1) / ppw;
-    const int cap = c->max_wg / 2;            // persistent-style grid: a few workgroups per CU, each loops over row pairs
-    if (grid > cap) grid = cap;
-    const bool slab = c->world > 1;
-    auto kern = slab ? k_row<N, MODE, true> : k_row<N, MODE, false>;
-    int rc = set_max_lds(c, (const void *)kern, C::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, c->stream, a);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    // persistent-style grid: a few workgroups per CU, each loops over row pairs
+    const int grid = std::min((a.nx / 2 + ppw - 1) / ppw, c->max_wg / 2);
+    return launch_lds(c, c->world > 1 ? k_row<N, MODE, true> : k_row<N, MODE, false>, grid, C::THREADS, C::LDS_BYTES, a);
 }
 
 template <int M, int MODE> static int launch_row3_t(fb_ctx *c, const RowArgs &a)
 {
     using C = Row3Cfg<M>;
-    const int npairs = a.nx / 2;
     constexpr int ppw = (C::TWO && MODE == ROW_FUSED) ? 1 : C::GP;     // row pairs per workgroup (fb_row3.h)
-    int grid = (npairs + ppw - 1) / ppw;
-    if (grid > c->max_wg) grid = c->max_wg;
-    const bool slab = c->world > 1;
-    auto kern = slab ? k_row3<M, MODE, true> : k_row3<M, MODE, false>;
-    int rc = set_max_lds(c, (const void *)kern, C::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(C::THREADS), C::LDS_BYTES, c->stream, a, (const cf *)c->d_tw_row3);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    const int grid = std::min((a.nx / 2 + ppw - 1) / ppw, c->max_wg);
+    return launch_lds(c, c->world > 1 ? k_row3<M, MODE, true> : k_row3<M, MODE, false>, grid, C::THREADS, C::LDS_BYTES, a, (const cf *)c->d_tw_row3);
 }
 
-static int launch_row8(fb_ctx *c, const RowArgs &a)
-{
-    const int npairs = a.nx / 2;
-    int grid = npairs, cap = c->max_wg / 4;   // two resident workgroups per CU, each loops over row pairs
-    if (grid > cap) grid = cap;
-    auto kern = c->world > 1 ? k_row8<true> : k_row8<false>;
-    int rc = set_max_lds(c, (const void *)kern, Row8::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), Row8::LDS_BYTES, c->stream, a, (const cf *)c->d_tw_row3);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-template <int V> static int launch_rowh(fb_ctx *c, const RowArgs &a)
-{
-    int grid = a.nx, cap = c->max_wg / (4 * V);   // resident workgroups: two per CU at ny = 8192, one at 16384; each loops over rows
-    if (grid > cap) grid = cap;
-    auto kern = c->world > 1 ? k_rowh<V, true> : k_rowh<V, false>;
-    int rc = set_max_lds(c, (const void *)kern, RowH<V>::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), RowH<V>::LDS_BYTES, c->stream, a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int launch_rowq(fb_ctx *c, const RowArgs &a)
-{
-    // one workgroup per row, four resident per CU: measured 0.076-0.078 ms per launch at 4096^2 against 0.081-0.084 with a persistent
-    // grid of 1024 looping over rows (the dispatcher's refill keeps the four contexts of a CU out of step; the prologue is cheap)
-    auto kern = c->world > 1 ? k_rowq<true, false> : a.prescaled ? k_rowq<false, true> : k_rowq<false, false>;
-    int rc = set_max_lds(c, (const void *)kern, RowQ::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(a.nx), dim3(256), RowQ::LDS_BYTES, c->stream, a, (const float4 *)c->d_tw_2048);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int launch_rowh2(fb_ctx *c, const RowArgs &a)
-{
-    int grid = a.nx, cap = c->max_wg / 8;         // one 1024-thread workgroup per CU, each loops over x2
-    if (grid > cap) grid = cap;
-    int rc = set_max_lds(c, (const void *)k_rowh2, RowH2::LDS_BYTES);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_rowh2, dim3(grid), dim3(1024), RowH2::LDS_BYTES, c->stream, a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-template <int MODE> static int launch_row(fb_ctx *c, const RowArgs &a)
+// k: the fused row kernel (ROW_FUSED only; the FWD / INV passes run the generic kernel for ny)
+template <int MODE> static int launch_row(fb_ctx *c, RowArgs a, RowKernel k = RK_GENERIC)
 {
     if (a.nx <= 0) return FB_OK;
-    if (MODE == ROW_FUSED && c->use_rowq) return launch_rowq(c, a);
-    if (MODE == ROW_FUSED && c->use_row8 && a.nx >= 2) return launch_row8(c, a);
-    if (MODE == ROW_FUSED && c->rowh_v == 1) return launch_rowh<1>(c, a);
-    if (MODE == ROW_FUSED && c->rowh_v == 2) return launch_rowh<2>(c, a);
+    const bool slab = c->world > 1;
+    if (MODE == ROW_FUSED) switch (k) {
+    case RK_ROWQ:
+        // one workgroup per row, four resident per CU: measured 0.076-0.078 ms per launch at 4096^2 against 0.081-0.084 with a persistent
+        // grid of 1024 looping over rows (the dispatcher's refill keeps the four contexts of a CU out of step; the prologue is cheap)
+        return launch_lds(c, slab ? k_rowq<true, false> : a.prescaled ? k_rowq<false, true> : k_rowq<false, false>, a.nx, 256, RowQ::LDS_BYTES,
+                          a, (const float4 *)c->d_tw_2048);
+    case RK_ROW8:                                          // two resident workgroups per CU, each loops over row pairs
+        if (a.nx < 2) break;
+        return launch_lds(c, slab ? k_row8<true> : k_row8<false>, std::min(a.nx / 2, c->max_wg / 4), 512, Row8::LDS_BYTES, a, (const cf *)c->d_tw_row3);
+    case RK_ROWH_8192:                                     // resident workgroups: two per CU at ny = 8192, one at 16384; each loops over rows
+        return launch_lds(c, slab ? k_rowh<1, true> : k_rowh<1, false>, std::min(a.nx, c->max_wg / 4), 512, RowH<1>::LDS_BYTES,
+                          a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3);
+    case RK_ROWH_16384:
+        return launch_lds(c, slab ? k_rowh<2, true> : k_rowh<2, false>, std::min(a.nx, c->max_wg / 8), 512, RowH<2>::LDS_BYTES,
+                          a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3);
+    case RK_ROWH2:                                         // one 1024-thread workgroup per CU, each loops over x2 and produces the rows x2, x2 + 4096
+        a.nx = 4096; a.sub_rows = 4096; a.tw_x = c->d_tw_big;
+        return launch_lds(c, k_rowh2, std::min(a.nx, c->max_wg / 8), 1024, RowH2::LDS_BYTES, a, (const cf *)c->d_tw_4096, (const cf *)c->d_tw_row3);
+    case RK_GENERIC: break;
+    }
     switch (c->ny) {
     case 192: return launch_row3_t<64, MODE>(c, a);
     case 384: return launch_row3_t<128, MODE>(c, a);
@@ -749,14 +761,33 @@ static size_t priv_elems(const fb_ctx *c) { return grp_elems(c, c->grp[0]); }   
 // tiles of every group that hold at least one column inside the dealiasing circle (the rest is frozen forever)
 static void finish_groups(fb_ctx *c)
 {
-    int jmax = 0;                                          // first ky with ky^2 >= gws (fftwfop.cpp:57-61)
-    while (jmax < c->hy && (double)jmax * (double)jmax < c->gws) ++jmax;
     for (int g = 0; g < c->ngroups; ++g) {
         ColGroup &G = c->grp[g];
-        const int act = (jmax - G.ky0 + 15) / 16;
+        const int act = (c->jmax - G.ky0 + 15) / 16;
         G.nct_active = act < 0 ? 0 : (act > G.ncols / 16 ? G.ncols / 16 : act);
         if (c->no_column_skip) G.nct_active = G.ncols / 16;
     }
+}
+
+// The x pass of a model on this context that is stepped by fb_model_step (a model driven phase by phase, fb_slab_*, always
+// takes XP_COLS).  The single-pass x transform (fb_col_full.h) applies on one GPU with a frozen Nyquist column and whole 8-column
+// tiles, at nx = 4096 (0.177 ms per stage against 0.21 ms for the three column kernels) and at nx = ny = 8192 with k_rowh
+// (FB_NO_ROWH=1 switches it off there too).  FB_FULL_PASS=0 keeps the three column kernels.
+static XPass choose_xpass(const fb_ctx *c)
+{
+    if (c->world != 1 || !c->nyq_frozen || ((c->ny / 2) % 8) != 0 || c->full_pass_off) return XP_COLS;
+    if (c->nx == 4096) return XP_FULL1;
+    if (c->nx == 8192 && c->row == RK_ROWH_8192) return XP_FULL2;
+    return XP_COLS;
+}
+
+// k_col_full<a.stage, a.nsub>: stage 0..3 forward x transform of the tendency + RK update + derivatives, 4 PRIME (fb_col_full.h)
+static int launch_full(const fb_ctx *c, const FullArgs &a)
+{
+    using K = void (*)(FullArgs);
+    static const K ks[2][5] = {{k_col_full<0, 1>, k_col_full<1, 1>, k_col_full<2, 1>, k_col_full<3, 1>, k_col_full<4, 1>},
+                               {k_col_full<0, 2>, k_col_full<1, 2>, k_col_full<2, 2>, k_col_full<3, 2>, k_col_full<4, 2>}};
+    return launch_lds(c, ks[a.nsub - 1][a.stage], a.nsub * (a.stage == 4 ? a.ntiles + 1 : a.ntiles), CF_THREADS, CF_LDS_BYTES, a);
 }
 
 // The strided x sub-pass reads rows N2*P*8 bytes apart; how well that stride spreads over the HBM channels
@@ -764,22 +795,13 @@ static void finish_groups(fb_ctx *c)
 // backward strided pass of four fields: 4096^2: P = 2064 0.0955 ms, 2080 0.084 ms; 8192^2: P = 4112 0.393 ms,
 // 4128 0.586 ms).  So on large single-GPU grids the pitch is chosen by timing that pass for a few candidates.
 // Results do not depend on the pitch (pad columns are zero and every pass is linear).
-// 0: the model's x pass will be the three column kernels; 1 / 2: the single-pass k_col_full with nx = 4096 / 8192 (fb_col_full.h)
-static int full_pass_nsub(const fb_ctx *c)
-{
-    if (c->world != 1 || !c->nyq_frozen || ((c->ny / 2) % 8) != 0 || c->full_pass_off) return 0;
-    if (c->nx == 4096) return 1;
-    if (c->nx == 8192 && c->rowh_v == 1) return 2;
-    return 0;
-}
-
 static int autotune_pitch(fb_ctx *c)
 {
     finish_groups(c);
     if (c->world != 1 || c->no_pitch_tune) return FB_OK;
     if ((size_t)c->nx * c->P * sizeof(cf) < ((size_t)32 << 20)) return FB_OK;      // cache-resident grids: nothing to gain
-    const int nsub = full_pass_nsub(c);
-    const int P0 = c->P, NC = nsub ? 7 : 4;                                        // create_impl leaves room for P0 + 96
+    const XPass xp = choose_xpass(c);
+    const int P0 = c->P, NC = xp != XP_COLS ? 7 : 4;                               // create_impl leaves room for P0 + 96
     constexpr int PITCH_HEADROOM = 96, RULE_EXTRA = 32;                            // the coefficient tables hold P0 + PITCH_HEADROOM columns
     static_assert(RULE_EXTRA <= PITCH_HEADROOM && 16 * (7 - 1) <= PITCH_HEADROOM, "pitch candidates must fit the table head-room of create_impl");
     if ((int)c->h_gy.size() < P0 + PITCH_HEADROOM) return fail(FB_EINVAL, "autotune_pitch: coefficient tables shorter than the pitch candidates");
@@ -788,7 +810,7 @@ static int autotune_pitch(fb_ctx *c)
     hipDeviceProp_t prop;
     int dev = 0;
     const bool is_gfx950 = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-    if (nsub && is_gfx950 && !c->pitch_tune) {
+    if (xp != XP_COLS && is_gfx950 && !c->pitch_tune) {
         // single-pass x transform: a fixed rule.  tools/pitch_scan.sh on three boxes: round16(ny/2 + 1) is the slowest pitch at
         // 4096^2 (k_col_full 0.1525-0.1556 ms against 0.148-0.152 for every other candidate) and, with + 16, at 8192^2 (0.75 / 0.79 ms
         // against 0.65-0.69 for + 32, + 64, + 96 and 0.69-0.72 for + 48, + 80).  The probe below (FB_PITCH_TUNE=1) sees the same
@@ -803,28 +825,21 @@ static int autotune_pitch(fb_ctx *c)
     // a stage-1 launch of k_col_full (tendency in, three state arrays, 64-byte row segments of four derivative fields out, rows
     // P*8 bytes apart) on zeroed buffers.  tools/pitch_scan.sh: the step time follows this probe; PRIME launches with two
     // repetitions per candidate (the first version) did not resolve the 2-4 % between pitches and often kept the worst one.
-    const int nbuf = nsub ? 9 : 1;           // k_col_full: Tin, 4 x W4, Z0, Zc, Acc, Zout
+    const int nbuf = xp != XP_COLS ? 9 : 1;  // k_col_full: Tin, 4 x W4, Z0, Zc, Acc, Zout
     cf *buf = nullptr;
     if (hipMalloc((void **)&buf, maxe * nbuf * sizeof(cf)) != hipSuccess) { hipGetLastError(); return FB_OK; }
     hipMemsetAsync(buf, 0, maxe * nbuf * sizeof(cf), c->stream);
-    if (nsub) {
-        const void *fn = nsub == 1 ? (const void *)k_col_full<1, 1> : (const void *)k_col_full<1, 2>;
-        if (set_max_lds(c, fn, CF_LDS_BYTES)) { hipFree(buf); return FB_OK; }
-    }
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     auto probe = [&](int P) -> int {
         ColGroup G = c->grp[0]; G.ncols = P;
-        if (!nsub) return launch_col_strided<+1>(c, G, buf, 1, 0);
+        if (xp == XP_COLS) return launch_col_strided<+1>(c, G, buf, 1, 0);
         FullArgs a; memset(&a, 0, sizeof(a));
         a.Tin = buf; a.W4 = buf + maxe; a.Zbase = buf + 5 * maxe; a.Zcur = buf + 6 * maxe; a.Acc = buf + 7 * maxe; a.Zout = buf + 8 * maxe;
         a.fstride = (long)c->nx * P; a.P = P; a.ntiles = (c->ny / 2) / 8;
-        a.ntiles_run = a.ntiles; a.nsub = nsub; a.stage = 1; a.nu = 0.f; a.dt = 0.f; a.coef = make_coef(c); a.tw256 = c->d_tw_256;
-        a.tw4096 = nsub == 1 ? c->d_tw_big : c->d_tw_4096; a.sub_rows = 4096;
-        const dim3 g(nsub * a.ntiles), b(CF_THREADS);
-        if (nsub == 1) hipLaunchKernelGGL((k_col_full<1, 1>), g, b, CF_LDS_BYTES, c->stream, a);
-        else hipLaunchKernelGGL((k_col_full<1, 2>), g, b, CF_LDS_BYTES, c->stream, a);
-        return hipGetLastError() == hipSuccess ? FB_OK : FB_EHIP;
+        a.ntiles_run = a.ntiles; a.nsub = xp; a.stage = 1; a.nu = 0.f; a.dt = 0.f; a.coef = make_coef(c); a.tw256 = c->d_tw_256;
+        a.tw4096 = xp == XP_FULL1 ? c->d_tw_big : c->d_tw_4096; a.sub_rows = 4096;
+        return launch_full(c, a);
     };
     const bool verbose = c->tune_verbose;
     // the device needs ~25 ms of this load to reach full speed: run the probe that long before timing it
@@ -979,10 +994,7 @@ struct fb_model {
     float nu, dt;
     GroupBufs gb[3];
     bool phase_flow;                 // driven phase by phase (fb_slab_*): always the three-kernel column path
-    // single-pass x-transform path (fb_col_full.h): ZA/ZB/ACC then use that kernel's private layout; nsub = nx/4096
-    // (2: the remaining radix-2 step of the x transform is fused into the row pass, k_rowh2)
-    bool full;
-    int nsub;
+    XPass xpass;                     // XP_FULL1/2 (fb_col_full.h): ZA/ZB/ACC then use k_col_full's private layout
     bool prescale;                   // k_col_full writes the derivative fields times 1/GRIDS and k_rowq<false, true> does not normalise (4096^2 on one GPU)
     // hipGraph replay of one RK4 step (launch-bound small grids): captured lazily on a non-null stream,
     // dropped whenever something baked into the kernel arguments changes (source pointer, stream)
@@ -1004,23 +1016,14 @@ static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool
     fb_model *m = new fb_model();
     memset(m, 0, sizeof(*m));
     m->c = c; m->nu = nu; m->dt = dt; m->phase_flow = phase_flow;
-    // single-pass x transform (fb_col_full.h) where it applies: one GPU, nx = 4096, frozen Nyquist column, whole
-    // 8-column tiles.  0.177 ms per stage against 0.21 ms for the three column kernels; FB_FULL_PASS=0 keeps the latter.
-    m->nsub = phase_flow ? 0 : full_pass_nsub(c);
-    m->full = m->nsub != 0;
-    m->prescale = m->full && c->world == 1 && c->use_rowq && !c->no_prescale;      // use_rowq: ny == 4096, so GRIDS = nx * ny is a power of two
+    m->xpass = phase_flow ? XP_COLS : choose_xpass(c);
+    m->prescale = m->xpass != XP_COLS && c->world == 1 && c->row == RK_ROWQ && !c->no_prescale;   // k_rowq: ny == 4096, so GRIDS = nx * ny is a power of two
     int rc = FB_OK;
     auto alloc0 = [&](cf **p, size_t elems) {              // zero-initialised device array (pad columns stay zero: every pass is linear)
         if (rc || elems == 0) return;
         if (hipMalloc((void **)p, elems * sizeof(cf)) != hipSuccess) { rc = fail(FB_ENOMEM, "model allocation failed"); return; }
         if (hipMemsetAsync(*p, 0, elems * sizeof(cf), c->stream) != hipSuccess) rc = fail(FB_EHIP, "hipMemsetAsync failed");
     };
-    if (m->full) {
-        const void *fns[10] = {(const void *)k_col_full<0, 1>, (const void *)k_col_full<1, 1>, (const void *)k_col_full<2, 1>, (const void *)k_col_full<3, 1>,
-                               (const void *)k_col_full<4, 1>, (const void *)k_col_full<0, 2>, (const void *)k_col_full<1, 2>, (const void *)k_col_full<2, 2>,
-                               (const void *)k_col_full<3, 2>, (const void *)k_col_full<4, 2>};
-        for (int st = 0; st < 10 && !rc; ++st) rc = set_max_lds(c, fns[st], CF_LDS_BYTES);
-    }
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t n = grp_elems(c, c->grp[g]);
         GroupBufs &B = m->gb[g];
@@ -1076,7 +1079,6 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
 static MidArgs mid_args(fb_model *m, int g, int stage);
 static int full_import_state(fb_model *m, cf *spec3);
 static int full_export_state(fb_model *m, cf *dst);
-static int launch_rowh2(fb_ctx *c, const RowArgs &a);
 
 extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort)
 {
@@ -1089,7 +1091,7 @@ extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort)
     m->primed = 0;
     int rc = r2c_private(c, d_vort, dst);                   // main.cpp:256
     if (rc) return rc;
-    if (m->full) return full_import_state(m, dst);
+    if (m->xpass != XP_COLS) return full_import_state(m, dst);
     return state_convert(c, c->grp[0], dst, m->gb[0].ZA, true);
 }
 
@@ -1105,19 +1107,15 @@ extern "C" int fb_model_set_source(fb_model *m, const float *d_src)
     if (!m->src && hipMalloc((void **)&m->src, n) != hipSuccess) { m->src = nullptr; return fail(FB_ENOMEM, "source allocation failed"); }
     hipLaunchKernelGGL(k_src_row_flags, dim3(c->XL), dim3(256), 0, c->stream, d_src, m->src_nz, c->ny);
     HIPCHK(hipGetLastError());
-    if (c->use_rowq) {                                            // k_rowq reads vort_src in its own physical-space order
-        hipLaunchKernelGGL(k_rowq_permute_src, dim3(grid_for(c, (size_t)c->XL * c->ny / 2)), dim3(256), 0, c->stream, d_src, m->src, c->XL);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
+    // k_rowq and k_rowh read vort_src in their own physical-space order (so does k_rowh2, on an RK_ROWH_8192 context)
+    const dim3 grid(grid_for(c, (size_t)c->XL * c->ny / 2)), blk(256);
+    switch (c->row) {
+    case RK_ROWQ: hipLaunchKernelGGL(k_rowq_permute_src, grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
+    case RK_ROWH_8192: hipLaunchKernelGGL((k_rowh_permute_src<1>), grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
+    case RK_ROWH_16384: hipLaunchKernelGGL((k_rowh_permute_src<2>), grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
+    default: HIPCHK(hipMemcpyAsync(m->src, d_src, n, hipMemcpyDeviceToDevice, c->stream)); return FB_OK;
     }
-    if (c->rowh_v) {                                              // k_rowh reads vort_src in its own physical-space order
-        const size_t pairs = (size_t)c->XL * c->ny / 2;
-        if (c->rowh_v == 1) hipLaunchKernelGGL((k_rowh_permute_src<1>), dim3(grid_for(c, pairs)), dim3(256), 0, c->stream, d_src, m->src, c->XL);
-        else hipLaunchKernelGGL((k_rowh_permute_src<2>), dim3(grid_for(c, pairs)), dim3(256), 0, c->stream, d_src, m->src, c->XL);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
-    }
-    HIPCHK(hipMemcpyAsync(m->src, d_src, n, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipGetLastError());
     return FB_OK;
 }
 
@@ -1134,8 +1132,22 @@ static MidArgs mid_args(fb_model *m, int g, int stage)
     return a;
 }
 
-
-static int launch_col_full(fb_model *m, int stage);
+// stage 0..3: forward x transform of the tendency + RK update + derivatives; stage 4: PRIME (derivatives of vort_c only)
+static int launch_col_full(fb_model *m, int stage)
+{
+    fb_ctx *c = m->c;
+    const GroupBufs &B = m->gb[0];
+    FullArgs a;
+    a.Tin = B.t_recv; a.Zbase = B.ZA; a.Zcur = B.ZB; a.Acc = B.ACC; a.Zout = B.ZA; a.W4 = B.w4_send;
+    a.fstride = (long)priv_elems(c); a.P = c->P; a.ntiles = (c->ny / 2) / 8; a.stage = stage; a.nu = m->nu; a.dt = m->dt;
+    a.nsub = m->xpass; a.sub_rows = 4096;
+    a.wscale = m->prescale ? 1.0f / (float)((size_t)c->nx * c->ny) : 1.0f;
+    a.ntiles_run = c->grp[0].nct_active * 2 < a.ntiles ? c->grp[0].nct_active * 2 : a.ntiles;   // 16-column tiles -> 8-column tiles
+    if (c->full_noskip) a.ntiles_run = a.ntiles;
+    if (stage == 4) a.ntiles_run = a.ntiles + 1;
+    a.coef = make_coef(c); a.tw256 = c->d_tw_256; a.tw4096 = m->xpass == XP_FULL1 ? c->d_tw_big : c->d_tw_4096;
+    return launch_full(c, a);
+}
 
 // full-path model: vort_c arrives in the 3-pass layout in `spec3`: move it into k_col_full's layout (every column, the
 // frozen ky = ny/2 one included) and run the PRIME launch, which leaves the four derivative fields of every column in W4
@@ -1143,7 +1155,7 @@ static int full_import_state(fb_model *m, cf *spec3)
 {
     fb_ctx *c = m->c;
     const int ntiles = (c->ny / 2) / 8;
-    hipLaunchKernelGGL((k_full_relayout<true>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)spec3, m->gb[0].ZA, c->P, c->N1, c->N2, ntiles, m->nsub, c->hy);
+    hipLaunchKernelGGL((k_full_relayout<true>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)spec3, m->gb[0].ZA, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy);
     HIPCHK(hipGetLastError());
     int rc = launch_col_full(m, 4);
     if (rc) return rc;
@@ -1157,36 +1169,7 @@ static int full_export_state(fb_model *m, cf *dst)
     fb_ctx *c = m->c;
     HIPCHK(hipMemsetAsync(dst, 0, priv_elems(c) * sizeof(cf), c->stream));
     const int ntiles = (c->ny / 2) / 8;
-    hipLaunchKernelGGL((k_full_relayout<false>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)m->gb[0].ZA, dst, c->P, c->N1, c->N2, ntiles, m->nsub, c->hy);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-// stage 0..3: forward x transform of the tendency + RK update + derivatives; stage 4: PRIME (derivatives of vort_c only)
-static int launch_col_full(fb_model *m, int stage)
-{
-    fb_ctx *c = m->c;
-    const GroupBufs &B = m->gb[0];
-    FullArgs a;
-    a.Tin = B.t_recv; a.Zbase = B.ZA; a.Zcur = B.ZB; a.Acc = B.ACC; a.Zout = B.ZA; a.W4 = B.w4_send;
-    a.fstride = (long)priv_elems(c); a.P = c->P; a.ntiles = (c->ny / 2) / 8; a.stage = stage; a.nu = m->nu; a.dt = m->dt;
-    a.nsub = m->nsub; a.sub_rows = 4096;
-    a.wscale = m->prescale ? 1.0f / (float)((size_t)c->nx * c->ny) : 1.0f;
-    a.ntiles_run = c->grp[0].nct_active * 2 < a.ntiles ? c->grp[0].nct_active * 2 : a.ntiles;   // 16-column tiles -> 8-column tiles
-    if (c->full_noskip) a.ntiles_run = a.ntiles;
-    if (stage == 4) a.ntiles_run = a.ntiles + 1;
-    a.coef = make_coef(c); a.tw256 = c->d_tw_256; a.tw4096 = m->nsub == 1 ? c->d_tw_big : c->d_tw_4096;
-    const dim3 g(m->nsub * (stage == 4 ? a.ntiles + 1 : a.ntiles)), b(CF_THREADS);
-#define FB_LAUNCH_FULL(ST) do { if (m->nsub == 1) hipLaunchKernelGGL((k_col_full<ST, 1>), g, b, CF_LDS_BYTES, c->stream, a); \
-                                else hipLaunchKernelGGL((k_col_full<ST, 2>), g, b, CF_LDS_BYTES, c->stream, a); } while (0)
-    switch (stage) {
-    case 0: FB_LAUNCH_FULL(0); break;
-    case 1: FB_LAUNCH_FULL(1); break;
-    case 2: FB_LAUNCH_FULL(2); break;
-    case 3: FB_LAUNCH_FULL(3); break;
-    default: FB_LAUNCH_FULL(4); break;
-    }
-#undef FB_LAUNCH_FULL
+    hipLaunchKernelGGL((k_full_relayout<false>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)m->gb[0].ZA, dst, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy);
     HIPCHK(hipGetLastError());
     return FB_OK;
 }
@@ -1214,7 +1197,8 @@ static int model_col_bwd_active(fb_model *m, int f0 = 0, int f1 = 4, int g = 0)
     const ColGroup &G = c->grp[g];
     return launch_col_strided<+1>(c, G, m->gb[g].w4_send + (size_t)f0 * w4_fstride(c, G), f1 - f0, w4_fstride(c, G), rowmap_w4(c, G), 0, G.nct_active);
 }
-static RowArgs fused_row_args(fb_model *m, int x0, int nrows)
+// row pass of an RK stage on the local rows [x0, x0 + nrows); the x pass XP_FULL2 comes with the row kernel k_rowh2
+static int launch_fused_row(fb_model *m, int x0, int nrows)
 {
     fb_ctx *c = m->c;
     RowArgs a = row_args_base(c);
@@ -1224,7 +1208,7 @@ static RowArgs fused_row_args(fb_model *m, int x0, int nrows)
         a.M = view_slab(c, w4, 4); a.T = view_slab(c, ts, 1); a.t_frozen = 0;
     }
     a.src = m->src; a.src_nz = m->src_nz; a.scale = 1.0f / (float)((size_t)c->nx * c->ny); a.x0 = x0; a.nx = nrows; a.prescaled = m->prescale ? 1 : 0;
-    return a;
+    return launch_row<ROW_FUSED>(c, a, m->xpass == XP_FULL2 ? RK_ROWH2 : c->row);
 }
 // forward x pass of the tendency + RK stage update + derivatives of the new stage state (three-kernel path)
 static int model_col_fwd(fb_model *m, int stage, int g = 0)
@@ -1254,22 +1238,18 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
     if (c->world != 1 || m->phase_flow) return fail(FB_EINVAL, "fb_model_step on a slab model: drive it with fb_slab_step");
     int rc;
     if (nsteps == 0) return FB_OK;
-    if (m->full && !m->primed) return fail(FB_EINVAL, "fb_model_step: set the state first");
+    if (m->xpass != XP_COLS && !m->primed) return fail(FB_EINVAL, "fb_model_step: set the state first");
     if (!m->primed && (rc = model_prime(m))) return rc;
-    if (m->primed == 1 && !m->full) { if ((rc = model_col_bwd_active(m))) return rc; m->primed = 2; }
+    if (m->primed == 1 && m->xpass == XP_COLS) { if ((rc = model_col_bwd_active(m))) return rc; m->primed = 2; }
     const ColGroup &G = c->grp[0];
     GroupBufs &B = m->gb[0];
     for (int s = 0; s < nsteps; ++s) {
         for (int k = 0; k < 4; ++k) {
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
-            RowArgs a = fused_row_args(m, 0, c->XL);
             PROF_BEGIN(1);
-            if (m->full && m->nsub == 2) {                // one workgroup per x2 produces the rows x2 and x2 + 4096 (k_rowh2)
-                a.nx = 4096; a.sub_rows = 4096; a.tw_x = c->d_tw_big;
-                if ((rc = launch_rowh2(c, a))) return rc;
-            } else if ((rc = launch_row<ROW_FUSED>(c, a))) return rc;
+            if ((rc = launch_fused_row(m, 0, c->XL))) return rc;
             PROF_END(1);
-            if (m->full) {                        // two launches per stage: row pass, single-pass x transform
+            if (m->xpass != XP_COLS) {                        // two launches per stage: row pass, single-pass x transform
                 PROF_BEGIN(3);
                 if ((rc = launch_col_full(m, k))) return rc;
                 PROF_END(3);
@@ -1369,7 +1349,7 @@ extern "C" int fb_model_get_spectrum(fb_model *m, float *d_spec)
     NEED_SINGLE(m->c);
     int rc;
     if ((rc = ensure_scratch(m->c))) return rc;
-    if (m->full) { if ((rc = full_export_state(m, m->c->d_scratch))) return rc; }
+    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, m->c->d_scratch))) return rc; }
     else if ((rc = state_convert(m->c, m->c->grp[0], m->gb[0].ZA, m->c->d_scratch, false))) return rc;
     return relayout(m->c, m->c->d_scratch, (cf *)d_spec, false);
 }
@@ -1382,7 +1362,7 @@ extern "C" int fb_model_set_spectrum(fb_model *m, const float *d_spec)
     m->warmed = false;
     int rc = relayout(m->c, (const cf *)d_spec, m->gb[0].ZB, true);
     if (rc) return rc;
-    if (m->full) return full_import_state(m, m->gb[0].ZB);
+    if (m->xpass != XP_COLS) return full_import_state(m, m->gb[0].ZB);
     return state_convert(m->c, m->c->grp[0], m->gb[0].ZB, m->gb[0].ZA, true);
 }
 
@@ -1394,7 +1374,7 @@ extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
     int rc;
     if ((rc = ensure_scratch(c))) return rc;
     // copy of vort_c (main.cpp:273), c2r, normalise (main.cpp:275)
-    if (m->full) { if ((rc = full_export_state(m, c->d_scratch))) return rc; }
+    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, c->d_scratch))) return rc; }
     else if ((rc = state_convert(c, c->grp[0], m->gb[0].ZA, c->d_scratch, false))) return rc;
     return c2r_private(c, c->d_scratch, d_vort, 1.0f / (float)((size_t)c->nx * c->ny));
 }

@@ -45,7 +45,7 @@ def slab_geometry(nx, ny, world):
 
 def slab_col_groups(nx, ny, world):
     """Columns per rank of the active column groups (one, or two where a stage is pipelined by column groups) -- mirrors
-    slab_active_groups() / fb_slab_col_groups in the engine.  A rank's active slab [rank*KA, (rank+1)*KA) is cut locally: its
+    slab_layout() / fb_slab_col_groups in the engine.  A rank's active slab [rank*KA, (rank+1)*KA) is cut locally: its
     first n_0 columns are group 0, the rest group 1."""
     import os
     _, ka, _ = slab_geometry(nx, ny, world)
