@@ -230,6 +230,78 @@ def test_engine_slab_many_steps_stay_in_step(n, world, steps, env):
     assert np.array_equal(got.view(np.uint32), ref.vort().cpu().numpy().view(np.uint32))
 
 
+_EXCHANGE_LOG = r'''
+import ctypes as C, json, sys
+sys.path.insert(0, %(root)r)
+import torch
+from importlib import import_module
+B = import_module("xlab-fftbarotropic_amd.binding")
+L = B.lib()
+n, world, log, h = %(n)d, %(world)d, [], C.c_void_p()
+B.check(L.fb_slab_create(C.byref(h), n, n, 6e5, 6e5, 6.5, 3.0, 0, world))
+cb = B.ALLTOALL_FN(lambda user, send, recv, stride, offset, count, stream: log.append((stride, offset, count)) or 0)    # moves nothing
+B.check(L.fb_slab_connect_callback(h, cb, None))
+rows = torch.zeros((n // world, n), dtype=torch.float32, device="cuda")
+logs = []
+for call in (lambda: L.fb_slab_set_vort_local(h, C.c_void_p(rows.data_ptr())), lambda: L.fb_slab_step(h, 1), lambda: L.fb_slab_step(h, 1),
+             lambda: L.fb_slab_get_vort_local(h, C.c_void_p(rows.data_ptr()))):
+    B.check(call())
+    logs.append(log[:])
+    del log[:]
+B.check(L.fb_slab_synchronize(h))
+L.fb_slab_destroy(h)
+print(json.dumps(logs))
+'''
+
+
+@pytest.mark.parametrize("n,world,env,plan", [(256, 2, {}, (1, 1, 1)),
+                                              (1024, 4, {"FB_SLAB_COL_GROUPS": "2"}, (2, 1, 1)),
+                                              (512, 2, {"FB_SLAB_COL_GROUPS": "2", "FB_SLAB_ROW_CHUNKS": "4"}, (2, 1, 4)),
+                                              (1024, 2, {"FB_SLAB_FIELD_GROUPS": "4", "FB_SLAB_ROW_CHUNKS": "4"}, (1, 4, 4))])
+def test_engine_slab_exchanges_follow_the_plan(monkeypatch, n, world, env, plan):
+    """The C++ driver issues the exchanges of the plan it reports (slab.plan), in the order the CPU rehearsal (SlabModel) issues them:
+    rank 0 of a `world`-rank model in a child process of its own, with a callback transport that moves nothing and records each
+    exchange's (stride, offset, count) in floats, against SlabModel over a backend that computes nothing, for set_vort_local, the
+    first step (priming, the column-group prologue), the second step (4 stages of plan.ops) and get_vort_local."""
+    import json
+    import subprocess
+    import sys
+    S = _slab()
+    for k in [k for k in os.environ if k.startswith("FB_SLAB_")]:
+        monkeypatch.delenv(k)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    p = S.plan(n, n, world)
+    assert (len(p.col_groups), p.field_groups, p.row_chunks) == plan
+
+    class NoCompute:
+        """SlabModel backend that computes nothing: only the order of the exchanges is of interest"""
+        def __init__(self):
+            self.XL, self.KA, self.KF = p.XL, p.KA, p.KF
+            self.ncols = p.col_groups + ([p.KF] if p.KF else [])
+            self.w4_send = self.w4_recv = self.t_send = self.t_recv = [None] * len(self.ncols)
+
+        def __getattr__(self, name):
+            return lambda *args: None
+
+    class Recorder(S.SlabModel):
+        def _xchg(self, recv, send, stride, offset, count):
+            log.append([2 * stride, 2 * offset, 2 * count])                    # complex elements -> the callback's floats
+    log, want = [], []
+    m = Recorder(n, n, rank=0, world=world, backend=NoCompute())
+    for call in (lambda: m.set_vort_local(np.zeros((p.XL, n))), lambda: m.step(1), lambda: m.step(1), m.vort_local):
+        call()
+        want.append(log[:])
+        del log[:]
+    assert want[2] and all(want)
+    res = subprocess.run([sys.executable, "-c", _EXCHANGE_LOG % {"root": ROOT, "n": n, "world": world}], stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, text=True, timeout=300, env=dict(os.environ))
+    assert res.returncode == 0, res.stderr[-2000:]
+    got = json.loads(res.stdout.strip().splitlines()[-1])
+    for what, g, w in zip(("set_vort_local", "first step", "second step", "get_vort_local"), got, want):
+        assert g == w, what
+
+
 def test_transport_selftests():
     """fb_slab_transport_selftest through the in-process hub (4 ranks) and through RCCL with world = 1 and the own block
     routed through grouped ncclSend/ncclRecv (FB_RCCL_SELF=1): library load, ncclCommInitRank, the grouped call path."""

@@ -3,6 +3,7 @@
 The HIP kernels cannot run here; the compute backend is the fp64 numpy test double
 (tests/slab_numpy_backend.py) that obeys the same buffer-layout contract, so what is under test
 is xlab-fftbarotropic_amd/slab.py: buffer geometry, who sends what to whom, phase order."""
+import math
 import os
 import socket
 import sys
@@ -25,7 +26,7 @@ def _free_port():
     return p
 
 
-def _worker(rank, world, port, n, steps, with_src, out_path, env=None):
+def _worker(rank, world, port, n, steps, with_src, out_path, env):
     os.environ.update(env or {})
     for p in (ROOT, HERE, os.path.join(ROOT, "oracle")):
         if p not in sys.path:
@@ -60,69 +61,109 @@ def _worker(rank, world, port, n, steps, with_src, out_path, env=None):
         want = slab.local_rows(ref.vort(), rank, world)
         err0 = float(np.abs(back0 - slab.local_rows(v0, rank, world)).max())
         err = R.rel_l2(rows, want)
-        np.save(out_path % rank, np.array([err0, err]))
+        np.save(out_path % rank, np.array([err0, err, m.nact, m.field_groups, m.row_chunks]))
     finally:
         dist.destroy_process_group()
 
 
+# (column groups, field groups, row chunks) of each case's plan, keyed by (world, n, switches): no case passes on another plan by accident
+_REHEARSAL_PLANS = {(2, 64, ""): (1, 1, 1), (4, 64, ""): (1, 1, 1), (2, 256, ""): (1, 1, 1),
+                    (2, 256, "FB_SLAB_COL_GROUPS=2"): (2, 1, 1),
+                    (4, 128, "FB_SLAB_COL_GROUPS=2"): (1, 1, 1),                            # KA = 16 < 32: one column group all the same
+                    (2, 256, "FB_SLAB_FIELD_GROUPS=4 FB_SLAB_ROW_CHUNKS=4"): (1, 4, 4),
+                    (4, 128, "FB_SLAB_FIELD_GROUPS=2 FB_SLAB_ROW_CHUNKS=2"): (1, 2, 2),
+                    (2, 256, "FB_SLAB_COL_GROUPS=2 FB_SLAB_ROW_CHUNKS=4"): (2, 1, 4)}
+
+
 @pytest.mark.parametrize("world,n,steps,with_src,env", [(2, 64, 3, False, None), (2, 64, 2, True, None), (4, 64, 2, False, None), (2, 256, 1, True, None),
                                                           (2, 256, 2, True, {"FB_SLAB_COL_GROUPS": "2"}),      # the stage pipelined by column groups
-                                                          (4, 128, 2, False, {"FB_SLAB_COL_GROUPS": "2"})])
+                                                          (4, 128, 2, False, {"FB_SLAB_COL_GROUPS": "2"}),
+                                                          (2, 256, 2, True, {"FB_SLAB_FIELD_GROUPS": "4", "FB_SLAB_ROW_CHUNKS": "4"}),
+                                                          (4, 128, 2, False, {"FB_SLAB_FIELD_GROUPS": "2", "FB_SLAB_ROW_CHUNKS": "2"}),
+                                                          (2, 256, 2, False, {"FB_SLAB_COL_GROUPS": "2", "FB_SLAB_ROW_CHUNKS": "4"})])
 def test_slab_exchange_matches_single_process(tmp_path, world, n, steps, with_src, env):
     port = _free_port()
     out = str(tmp_path / "err_%d.npy")
     mp.spawn(_worker, args=(world, port, n, steps, with_src, out, env), nprocs=world, join=True)
+    plan = _REHEARSAL_PLANS[(world, n, " ".join("%s=%s" % kv for kv in sorted((env or {}).items())))]
     for r in range(world):
-        err0, err = np.load(out % r)
+        err0, err, *got = np.load(out % r)
+        assert tuple(got) == plan, "rank %d ran the plan %s" % (r, got)
         assert err0 < 1e-12, "c2r(r2c(x)) across the transposes, rank %d" % r
         assert err < 1e-10, "rank %d: rel L2 %g" % (r, err)
 
 
-def test_slab_geometry_plan_and_world1():
-    """Host logic of the decomposition, no GPU: slab.py's geometry and per-stage schedule against the engine's own
-    (fb_slab_geometry / fb_slab_plan in libfftbaro.so), the even split of the ACTIVE columns, and world == 1."""
-    import ctypes as C
+def _geometry(nx, ny, world):
+    """(XL rows, KA active columns, KF frozen columns) per rank, restated from the reference's dealiasing (fftwfop.cpp:11-12,57): the
+    first ky with ky^2 >= gws and every one beyond are masked; the active and the frozen columns are cut into whole 16-column tiles."""
+    round16 = lambda v: (v + 15) // 16 * 16
+    hy = ny // 2 + 1
+    dxw, dyw = math.ceil(float(np.float32(nx)) / 3.0), math.ceil(float(np.float32(ny)) / 3.0)
+    gws = float(np.float32(float(dxw) ** 2 + float(dyw) ** 2))
+    jmax = 0
+    while jmax < hy and float(jmax) * float(jmax) < gws:
+        jmax += 1
+    ka = round16((jmax + world - 1) // world)
+    nf = hy - world * ka
+    return nx // world, ka, round16((nf + world - 1) // world) if nf > 0 else 0
+
+
+# BASELINE configs 4 and 5, the headline grid on 1..8 ranks, a 3*2^k grid and a small one whose active slabs cover everything:
+# the engine's (column groups, field groups, row chunks, one stage's operations) with no switch set
+_PLANS = {
+    (8192, 8192, 4): ([496, 480], 1, 1, [(3, 0), (4, 0), (5, 0), (6, 0), (2, 0), (5, 1), (6, 1), (2, 1)]),
+    (16384, 16384, 8): ([496, 480], 1, 2, [(3, 0), (4, 0), (3, 1), (4, 1), (5, 0), (6, 0), (2, 0), (5, 1), (6, 1), (2, 1)]),
+    (4096, 4096, 1): ([1936], 1, 1, [(1, 0), (3, 0), (5, 0)]),
+    (4096, 4096, 2): ([496, 480], 1, 1, [(3, 0), (4, 0), (5, 0), (6, 0), (2, 0), (5, 1), (6, 1), (2, 1)]),
+    (4096, 4096, 4): ([496], 1, 1, [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0)]),
+    (4096, 4096, 8): ([256], 1, 1, [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0)]),
+    (768, 768, 4): ([96], 1, 1, [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0)]),
+    (64, 64, 8): ([16], 1, 1, [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0)]),
+    (256, 1024, 2): ([192], 1, 1, [(1, 0), (2, 0), (3, 0), (4, 0), (5, 0)]),
+}
+
+
+def test_engine_slab_plan_and_world1(monkeypatch):
+    """Host logic of the decomposition, no GPU: the engine's geometry (fb_slab_geometry, through slab.plan) against the dealiasing
+    formula, its column groups and per-stage schedule against the table above, the even split of the ACTIVE columns, and world == 1."""
     for p in (ROOT, HERE):
         if p not in sys.path:
             sys.path.insert(0, p)
     from importlib import import_module
     import ref_numpy as R
-    import xlab_fftbarotropic_amd as X
     from slab_numpy_backend import NumpyBackend
     slab = import_module("xlab-fftbarotropic_amd.slab")
-    L = X.lib()
-    # BASELINE configs 4 and 5, the headline grid on 2..8 ranks, a 3*2^k grid and a small one whose active slabs cover everything
-    cases = [(8192, 8192, 4), (16384, 16384, 8), (4096, 4096, 1), (4096, 4096, 2), (4096, 4096, 4), (4096, 4096, 8), (768, 768, 4), (64, 64, 8), (256, 1024, 2)]
-    for nx, ny, w in cases:
-        xl, ka, kf = C.c_int(), C.c_int(), C.c_int()
-        assert L.fb_slab_geometry(nx, ny, w, C.byref(xl), C.byref(ka), C.byref(kf)) == 0
-        assert (xl.value, ka.value, kf.value) == slab.slab_geometry(nx, ny, w), (nx, ny, w)
-        fg, ch, ops = slab.engine_plan(nx, ny, w)
-        assert (fg, ch) == slab.stage_plan(nx, ny, w) and ops == slab.stage_schedule(nx, ny, w), (nx, ny, w)
-        ng, cols = C.c_int(), (C.c_int * 2)()
-        assert L.fb_slab_col_groups(nx, ny, w, C.byref(ng), cols) == 0
-        groups = slab.slab_col_groups(nx, ny, w)
-        assert [cols[g] for g in range(ng.value)] == groups and sum(groups) == ka.value and all(g % 16 == 0 and g > 0 for g in groups), (nx, ny, w)
+    B = import_module("xlab-fftbarotropic_amd.binding")
+    for env in [k for k in os.environ if k.startswith("FB_SLAB_")]:
+        monkeypatch.delenv(env)                                                # the table is the plan with no switch set
+    for (nx, ny, w), (groups, fg, ch, ops) in _PLANS.items():
+        p = slab.plan(nx, ny, w)
+        assert (p.XL, p.KA, p.KF) == _geometry(nx, ny, w), (nx, ny, w)
+        assert (p.col_groups, p.field_groups, p.row_chunks, p.ops) == (groups, fg, ch, ops), (nx, ny, w)
+        assert sum(groups) == p.KA and all(g % 16 == 0 and g > 0 for g in groups), (nx, ny, w)
         hy = ny // 2 + 1
-        assert w * ka.value + w * kf.value >= hy and ka.value % 16 == 0 and kf.value % 16 == 0
+        assert w * p.KA + w * p.KF >= hy and p.KA % 16 == 0 and p.KF % 16 == 0
         # every column inside the dealiasing circle lies in an active slab, and the last rank is not idle:
         jmax = int(np.ceil(np.sqrt(2.0) * np.ceil(ny / 3.0))) if nx == ny else None
         if jmax is not None:
-            assert w * ka.value >= jmax - 1
+            assert w * p.KA >= jmax - 1
             if jmax >= 16 * w:                                                 # (slabs are whole 16-column tiles)
-                assert (w - 1) * ka.value < jmax                               # active columns reach into the last rank's slab
-    assert slab.slab_geometry(8192, 8192, 4) == (2048, 976, 64)
-    assert slab.slab_geometry(16384, 16384, 8) == (2048, 976, 64)
-    assert slab.slab_geometry(4096, 4096, 8) == (512, 256, 16)
+                assert (w - 1) * p.KA < jmax                                   # active columns reach into the last rank's slab
+    assert slab.plan(8192, 8192, 4)[:3] == (2048, 976, 64)
+    assert slab.plan(16384, 16384, 8)[:3] == (2048, 976, 64)
+    assert slab.plan(4096, 4096, 8)[:3] == (512, 256, 16)
     # configs 4 and 5 and the headline grid on two ranks are pipelined by column groups (a group's four fields leave together);
     # smaller slabs keep one group and cut the derivative exchange by fields where that pays
-    assert slab.slab_col_groups(8192, 8192, 4) == [496, 480] and slab.slab_col_groups(16384, 16384, 8) == [496, 480]
-    assert slab.slab_col_groups(4096, 4096, 2) == [496, 480] and slab.slab_col_groups(4096, 4096, 4) == [496] and slab.slab_col_groups(4096, 4096, 8) == [256]
-    assert slab.stage_plan(8192, 8192, 4) == (1, 1) and slab.stage_plan(16384, 16384, 8) == (1, 2)
-    assert slab.stage_plan(4096, 4096, 2) == (1, 1) and slab.stage_plan(4096, 4096, 4) == (1, 1) and slab.stage_plan(4096, 4096, 8) == (1, 1) and slab.stage_plan(4096, 4096, 1) == (1, 1)
-    assert [k for k, _ in slab.stage_schedule(16384, 16384, 8)] == [3, 4, 3, 4, 5, 6, 2, 5, 6, 2]
-    assert L.fb_slab_plan(1000, 1000, 2, None, None, None, 0) == 0             # unsupported grid
-    n = 32
+    plan = lambda n, w: slab.plan(n, n, w)
+    assert plan(8192, 4).col_groups == [496, 480] and plan(16384, 8).col_groups == [496, 480]
+    assert plan(4096, 2).col_groups == [496, 480] and plan(4096, 4).col_groups == [496] and plan(4096, 8).col_groups == [256]
+    assert plan(8192, 4)[4:6] == (1, 1) and plan(16384, 8)[4:6] == (1, 2)
+    assert plan(4096, 2)[4:6] == (1, 1) and plan(4096, 4)[4:6] == (1, 1) and plan(4096, 8)[4:6] == (1, 1) and plan(4096, 1)[4:6] == (1, 1)
+    assert [k for k, _ in plan(16384, 8).ops] == [3, 4, 3, 4, 5, 6, 2, 5, 6, 2]
+    assert B.lib().fb_slab_plan(1000, 1000, 2, None, None, None, 0) == 0       # unsupported grid
+    with pytest.raises(B.FftBaroError):
+        slab.plan(1000, 1000, 2)
+    n = 64
     rng = np.random.default_rng(0)
     v0 = 1e-3 * rng.standard_normal((n, n))
     be = NumpyBackend(n, n, 6e5, 6e5, 6.5, 3.0, 0, 1)

@@ -37,7 +37,7 @@ struct fb_slab {
 
 // ---- schedule (host logic, no GPU needed): how finely one stage's two transposes are pipelined ----
 #define FB_OP_COL_BWD   1       /* arg = field group */
-#define FB_OP_XCHG_W4   2       /* arg = field group */
+#define FB_OP_XCHG_W4   2       /* arg = field group (column group when the stage is pipelined by column groups) */
 #define FB_OP_ROW       3       /* arg = row chunk   */
 #define FB_OP_XCHG_T    4       /* arg = row chunk   */
 #define FB_OP_COL_FWD   5       /* arg = column group (0 unless the stage is pipelined by column groups) */
@@ -246,6 +246,20 @@ static int slab_xchg(fb_slab *s, const cf *send, cf *recv, size_t stride, size_t
     ++s->step_ops;
     return s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * stride, 2 * offset, 2 * count, s->comm);
 }
+// every group's whole tendency-sized buffer through the transport (to_cols: t_send -> t_recv, rows -> columns; else the
+// reverse), behind the compute stream's work so far and ahead of what it does next
+static int slab_transpose_all(fb_slab *s, bool to_cols)
+{
+    fb_ctx *c = s->c; fb_model *m = s->m;
+    int rc;
+    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
+        cf *send = to_cols ? m->gb[g].t_send : m->gb[g].t_recv, *recv = to_cols ? m->gb[g].t_recv : m->gb[g].t_send;
+        if ((rc = slab_xchg(s, send, recv, blk, 0, blk))) return rc;
+    }
+    return slab_after(s->comp, s->comm, s->ev_misc[1]);
+}
 #define SLAB_READY(s) do { if (!(s)) return fail(FB_EINVAL, "slab NULL"); if (!(s)->connected) return fail(FB_EINVAL, "slab model is not connected to a transport (fb_slab_connect_*)"); } while (0)
 
 // ---- state in / out ----
@@ -260,13 +274,7 @@ extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
     a.rin = d_rows;
     const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
     a.T = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
-    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
-    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = slab_xchg(s, m->gb[g].t_send, m->gb[g].t_recv, blk, 0, blk))) return rc;
-    }
-    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    if ((rc = launch_row<ROW_FWD>(c, a)) || (rc = slab_transpose_all(s, true))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
         const ColGroup &G = c->grp[g];
         if ((rc = launch_col_strided<-1>(c, G, m->gb[g].t_recv, 1, 0)) || (rc = launch_col_block<-1>(c, G, m->gb[g].t_recv, 1, 0))) return rc;
@@ -300,12 +308,7 @@ static int slab_c2r_of_state(fb_slab *s, int what, float scale, float *d_rows)
         HIPCHK(hipGetLastError());
         if ((rc = launch_col_block<+1>(c, G, w, 1, 0)) || (rc = launch_col_strided<+1>(c, G, w, 1, 0))) return rc;   // natural [x][ncols] == [dst][XL][ncols]
     }
-    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = slab_xchg(s, m->gb[g].t_recv, m->gb[g].t_send, blk, 0, blk))) return rc;
-    }
-    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    if ((rc = slab_transpose_all(s, false))) return rc;
     RowArgs a = row_args_base(c);
     const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
     a.M = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
@@ -348,6 +351,17 @@ static int slab_prime(fb_slab *s)
     return FB_OK;
 }
 
+// backward x pass of column group g's four derivative fields on its active tiles, then their exchange (columns -> rows)
+static int slab_group_bwd_send(fb_slab *s, int g)
+{
+    fb_ctx *c = s->c; fb_model *m = s->m;
+    const size_t fld = (size_t)c->XL * c->grp[g].ncols;
+    int rc;
+    if ((rc = model_col_bwd_active(m, 0, 4, g))) return rc;
+    if ((rc = slab_after(s->comm, s->comp, s->ev_f[g]))) return rc;
+    return slab_xchg(s, m->gb[g].w4_send, m->gb[g].w4_recv, 4 * fld, 0, 4 * fld);
+}
+
 // Pipelined by column groups (ncg == 2).  On entry the derivative fields of every group are complete in w4_recv (m->primed == 2:
 // slab_groups_prologue after priming, or the previous stage).
 static int slab_stage_groups(fb_slab *s, int stage)
@@ -368,12 +382,8 @@ static int slab_stage_groups(fb_slab *s, int stage)
     // per column group: forward x pass, viscosity, mask, RK stage update, derivatives of the new stage state, backward x pass
     // (main.cpp:148,179-212,237-251,296-312); the group's four fields leave while the next group is computed
     for (int g = 0; g < s->ncg; ++g) {
-        const size_t fld = (size_t)c->XL * c->grp[g].ncols;
         HIPCHK(hipStreamWaitEvent(s->comp, s->ev_tg[g], 0));
-        if ((rc = model_col_fwd(m, stage, g))) return rc;
-        if ((rc = model_col_bwd_active(m, 0, 4, g))) return rc;
-        if ((rc = slab_after(s->comm, s->comp, s->ev_f[g]))) return rc;
-        if ((rc = slab_xchg(s, m->gb[g].w4_send, m->gb[g].w4_recv, 4 * fld, 0, 4 * fld))) return rc;
+        if ((rc = model_col_fwd(m, stage, g)) || (rc = slab_group_bwd_send(s, g))) return rc;
     }
     m->primed = 2;
     return slab_after(s->comp, s->comm, s->ev_w4);          // the next row pass (or a record pass) reads w4_recv
@@ -381,15 +391,10 @@ static int slab_stage_groups(fb_slab *s, int stage)
 // after priming: backward x pass on the active tiles of every group and the first exchange of the derivative fields
 static int slab_groups_prologue(fb_slab *s)
 {
-    fb_ctx *c = s->c; fb_model *m = s->m;
     int rc;
-    for (int g = 0; g < s->ncg; ++g) {
-        const size_t fld = (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = model_col_bwd_active(m, 0, 4, g))) return rc;
-        if ((rc = slab_after(s->comm, s->comp, s->ev_f[g]))) return rc;
-        if ((rc = slab_xchg(s, m->gb[g].w4_send, m->gb[g].w4_recv, 4 * fld, 0, 4 * fld))) return rc;
-    }
-    m->primed = 2;
+    for (int g = 0; g < s->ncg; ++g)
+        if ((rc = slab_group_bwd_send(s, g))) return rc;
+    s->m->primed = 2;
     return slab_after(s->comp, s->comm, s->ev_w4);
 }
 

@@ -250,8 +250,8 @@ extern "C" int fb_create(fb_ctx **out, int nx, int ny, float lx, float ly) { ret
 
 static int round16(int v) { return (v + 15) / 16 * 16; }
 
-// The slab layout of an nx x ny grid on `world` ranks and the schedule of its multi-GPU stage (fb_slab_driver.h; must match
-// slab.py).  Also defined on one rank, where fb_create_slab replaces the column split by the pitch.  The only reader of the
+// The slab layout of an nx x ny grid on `world` ranks and the schedule of its multi-GPU stage (fb_slab_driver.h).  Also
+// defined on one rank, where fb_create_slab replaces the column split by the pitch.  The only reader of the
 // FB_SLAB_* switches.
 struct SlabLayout {
     double gws;                 // dealiasing radius^2

@@ -13,86 +13,46 @@ Two drivers with one schedule:
     (RCCL unique id over torch.distributed; the in-process hub; a gloo callback for rehearsals on one GPU).
   * `SlabModel(backend=...)` -- the same schedule spelled in Python over a pluggable compute backend, so that the
     exchange logic (who sends which block to whom, in which order) runs on CPU under gloo with the numpy test double of
-    tests/slab_numpy_backend.py.  `stage_schedule()` is checked against the engine's `fb_slab_plan`.
+    tests/slab_numpy_backend.py.  Its layout and stage schedule are the engine's own (`plan()`: fb_slab_geometry,
+    fb_slab_col_groups, fb_slab_plan), so the rehearsal follows the engine's slab switches (Switches) through it.
 There is no fallback from one to the other.
 """
+import collections
 import ctypes as C
-import math
 
 import numpy as np
 
 OP_COL_BWD, OP_XCHG_W4, OP_ROW, OP_XCHG_T, OP_COL_FWD, OP_COL_ALL_BWD = 1, 2, 3, 4, 5, 6
 
 
-def _round16(v):
-    return (v + 15) // 16 * 16
+Plan = collections.namedtuple("Plan", "XL KA KF col_groups field_groups row_chunks ops")
+
+
+def plan(nx, ny, world):
+    """The engine's slab layout and stage schedule of an nx x ny grid on `world` ranks (fb_slab_geometry, fb_slab_col_groups,
+    fb_slab_plan: host logic, no GPU needed; the engine's slab switches act through them).  XL rows, KA active and KF frozen columns
+    per rank; col_groups: the columns of each active column group (two where a stage is pipelined by column groups; a rank's active
+    slab [rank*KA, (rank+1)*KA) is cut locally, group 0 its first columns); ops: one RK stage in issue order, as (kind, argument)
+    with the meanings of FB_OP_* in csrc/fb_slab_driver.h.  Raises FftBaroError on a geometry the engine refuses."""
+    from . import binding as B
+    L = B.lib()
+    xl, ka, kf = C.c_int(), C.c_int(), C.c_int()
+    B.check(L.fb_slab_geometry(nx, ny, world, C.byref(xl), C.byref(ka), C.byref(kf)))
+    ng, cols = C.c_int(), (C.c_int * 2)()
+    B.check(L.fb_slab_col_groups(nx, ny, world, C.byref(ng), cols))
+    fg, ch, ops = C.c_int(), C.c_int(), (C.c_int * 64)()
+    n = L.fb_slab_plan(nx, ny, world, C.byref(fg), C.byref(ch), ops, 64)
+    return Plan(xl.value, ka.value, kf.value, cols[:ng.value], fg.value, ch.value, [(ops[i] // 16, ops[i] % 16) for i in range(n)])
 
 
 def slab_geometry(nx, ny, world):
-    """(XL rows, KA active columns, KF frozen columns) per rank -- must match slab_split() in csrc/fftbaro.hip
-    (tests/test_slab_cpu.py compares with fb_slab_geometry)."""
-    hy = ny // 2 + 1
-    dxw, dyw = math.ceil(float(np.float32(nx)) / 3.0), math.ceil(float(np.float32(ny)) / 3.0)
-    gws = float(np.float32(float(dxw) ** 2 + float(dyw) ** 2))                 # fftwfop.cpp:57
-    jmax = 0
-    while jmax < hy and float(jmax) * float(jmax) < gws:
-        jmax += 1
-    ka = _round16((jmax + world - 1) // world)
-    nf = hy - world * ka
-    kf = _round16((nf + world - 1) // world) if nf > 0 else 0
-    return nx // world, ka, kf
+    """(XL rows, KA active columns, KF frozen columns) per rank: the first three fields of plan()."""
+    return tuple(plan(nx, ny, world)[:3])
 
 
 def slab_col_groups(nx, ny, world):
-    """Columns per rank of the active column groups (one, or two where a stage is pipelined by column groups) -- mirrors
-    slab_layout() / fb_slab_col_groups in the engine.  A rank's active slab [rank*KA, (rank+1)*KA) is cut locally: its
-    first n_0 columns are group 0, the rest group 1."""
-    import os
-    _, ka, _ = slab_geometry(nx, ny, world)
-    na = 1
-    if world > 1 and ka >= 32:
-        if 17.5 * nx * ka * 8.0 / 5e6 >= 100.0:              # one rank's column work of a stage, microseconds at ~5 TB/s
-            na = 2
-        if os.environ.get("FB_SLAB_COL_GROUPS") in ("1", "2"):
-            na = int(os.environ["FB_SLAB_COL_GROUPS"])
-    tiles = ka // 16
-    return [16 * (tiles // na + (1 if g < tiles % na else 0)) for g in range(na)]
-
-
-def stage_plan(nx, ny, world):
-    """(field groups, row chunks) of one RK stage's two transposes -- mirrors slab_plan() in csrc/fb_slab_driver.h."""
-    xl, ka, _ = slab_geometry(nx, ny, world)
-    bwd_us, row_us = 2.0 * nx * ka * 8.0 / 5e6, 5.0 * xl * (ny // 2 + 1) * 8.0 / 4e6      # one field's backward sub-pass, the row pass
-    fg = 1 if world == 1 else (4 if bwd_us >= 20.0 else (2 if bwd_us >= 10.0 else 1))
-    ch = 1 if world == 1 else (2 if row_us >= 100.0 else 1)
-    while ch > 1 and ((xl // ch) & 1 or xl % ch):
-        ch >>= 1
-    if len(slab_col_groups(nx, ny, world)) > 1:
-        fg = 1                                               # pipelined by column groups: a group's four fields leave together
-    return fg, ch
-
-
-def stage_schedule(nx, ny, world):
-    """Operations of one RK stage in issue order, as (kind, argument) -- mirrors fb_slab_plan."""
-    fg, ch = stage_plan(nx, ny, world)
-    ops = []
-    ncg = len(slab_col_groups(nx, ny, world))
-    if ncg > 1:                                              # arguments of OP_XCHG_W4 / OP_COL_*: the column group
-        for h in range(ch):
-            ops += [(OP_ROW, h), (OP_XCHG_T, h)]
-        for g in range(ncg):
-            ops += [(OP_COL_FWD, g), (OP_COL_ALL_BWD, g), (OP_XCHG_W4, g)]
-        return ops
-    for g in range(fg):
-        ops.append((OP_COL_BWD, g))
-        if world > 1:
-            ops.append((OP_XCHG_W4, g))
-    for h in range(ch):
-        ops.append((OP_ROW, h))
-        if world > 1:
-            ops.append((OP_XCHG_T, h))
-    ops.append((OP_COL_FWD, 0))
-    return ops
+    """Columns per rank of each active column group: plan().col_groups."""
+    return plan(nx, ny, world).col_groups
 
 
 LINK_GBS = 60.0         # assumed xGMI rate per direction and peer (7 links x ~153 GB/s bidirectional per GPU: <= 77 GB/s one way)
@@ -110,21 +70,18 @@ def predicted_step_ms(nx, ny, world, local_ms_per_step=None):
                    x pass + update (10.2/22.5), the first field group's backward sub-pass (7.3/22.5 / groups) and the first row chunk
         stage    = t_link + exposed;  step = 4 stages.
     Returns (ms per step, dict of the terms)."""
-    xl, ka, _ = slab_geometry(nx, ny, world)
-    fg, ch = stage_plan(nx, ny, world)
-    ncg = len(slab_col_groups(nx, ny, world))
-    hy = ny // 2 + 1
+    p = plan(nx, ny, world)
     if local_ms_per_step is None:
-        local = 22.4 * 8.0 * nx * _round16(hy) / world / 5e12 * 1e3
+        local = 22.4 * 8.0 * nx * ((ny // 2 + 1 + 15) // 16 * 16) / world / 5e12 * 1e3    # the single-GPU pitch
     else:
         local = local_ms_per_step / 4.0
     if world == 1:
         return 4.0 * local, {"t_link_ms": 0.0, "local_ms": local, "exposed_ms": local}
-    t_link = 5.0 * xl * ka * 8.0 / (LINK_GBS * 1e9) * 1e3 + 2 * GROUP_LATENCY_MS
-    if ncg > 1:
-        exposed = local * (5.0 / 22.5) / ch
+    t_link = 5.0 * p.XL * p.KA * 8.0 / (LINK_GBS * 1e9) * 1e3 + 2 * GROUP_LATENCY_MS
+    if len(p.col_groups) > 1:
+        exposed = local * (5.0 / 22.5) / p.row_chunks
     else:
-        exposed = local * (10.2 / 22.5 + 7.3 / 22.5 / fg + 5.0 / 22.5 / ch)
+        exposed = local * (10.2 / 22.5 + 7.3 / 22.5 / p.field_groups + 5.0 / 22.5 / p.row_chunks)
     return 4.0 * (t_link + exposed), {"t_link_ms_per_stage": t_link, "local_ms_per_stage": local, "exposed_ms_per_stage": exposed,
                                       "link_GBs_assumed": LINK_GBS, "group_latency_ms_assumed": GROUP_LATENCY_MS,
                                       "local_from": "measured (null transport)" if local_ms_per_step is not None else "22.4 C / world at 5 TB/s"}
@@ -165,10 +122,7 @@ class EngineSlab:
         v = [C.c_int() for _ in range(7)]
         B.check(self.L.fb_slab_info(self._h, *[C.byref(x) for x in v]))
         self.XL, self.KA, self.KF, self.kyA0, self.kyF0, self.field_groups, self.row_chunks = [x.value for x in v]
-        assert world == 1 or (self.XL, self.KA, self.KF) == slab_geometry(nx, ny, world)      # one rank: one group of all columns at the engine's pitch
-        ng, cols = C.c_int(), (C.c_int * 2)()
-        B.check(self.L.fb_slab_col_groups(nx, ny, world, C.byref(ng), cols))
-        self.col_groups = [cols[g] for g in range(ng.value)]                                  # 2 entries: the stage is pipelined by column groups
+        self.col_groups = slab_col_groups(nx, ny, world)                                      # 2 entries: the stage is pipelined by column groups
         self._cb = None
         self.transport = "none"
         if world > 1:
@@ -347,15 +301,6 @@ def local_hub_destroy(hub):
     B.lib().fb_local_hub_destroy(C.c_void_p(hub))
 
 
-def engine_plan(nx, ny, world):
-    """(field groups, row chunks, [(kind, argument), ...]) as the engine reports them (fb_slab_plan; no GPU needed)."""
-    from . import binding as B
-    fg, ch = C.c_int(), C.c_int()
-    ops = (C.c_int * 64)()
-    n = B.lib().fb_slab_plan(nx, ny, world, C.byref(fg), C.byref(ch), ops, 64)
-    return fg.value, ch.value, [(ops[i] // 16, ops[i] % 16) for i in range(n)]
-
-
 # ---------------------------------------------------------------------------------------------------------------
 # the same schedule in Python over a pluggable compute backend (CPU rehearsal of the exchange logic)
 # ---------------------------------------------------------------------------------------------------------------
@@ -393,13 +338,14 @@ class SlabModel:
             import torch.distributed as dist
         self.dist = dist
         self.be = backend
-        self.XL, self.KA, self.KF = slab_geometry(nx, ny, world)
+        self.plan = plan(nx, ny, world)
+        self.XL, self.KA, self.KF = self.plan.XL, self.plan.KA, self.plan.KF
         assert (self.be.XL, self.be.KA, self.be.KF) == (self.XL, self.KA, self.KF)
-        self.field_groups, self.row_chunks = stage_plan(nx, ny, world)
-        self.cols = slab_col_groups(nx, ny, world) + ([self.KF] if self.KF else [])     # columns per rank of every group, the engine's order
-        self.nact = len(self.cols) - (1 if self.KF else 0)
+        self.field_groups, self.row_chunks = self.plan.field_groups, self.plan.row_chunks
+        self.cols = self.plan.col_groups + ([self.KF] if self.KF else [])             # columns per rank of every group, the engine's order
+        self.nact = len(self.plan.col_groups)
         assert list(self.be.ncols) == self.cols
-        self.primed = 0
+        self.primed = False
 
     def _xchg(self, recv, send, stride, offset, count):
         if self.world > 1:
@@ -413,7 +359,7 @@ class SlabModel:
         for g, n in enumerate(self.cols):
             self._xchg(be.t_recv[g], be.t_send[g], self.XL * n, 0, self.XL * n)
         be.r2c_cols()
-        self.primed = 0
+        self.primed = False
 
     def set_source_local(self, src_rows):
         self.be.set_source(src_rows)
@@ -425,6 +371,29 @@ class SlabModel:
             self._xchg(be.t_send[g], be.t_recv[g], self.XL * n, 0, self.XL * n)
         return be.c2r_rows()
 
+    def _op(self, kind, arg, stage=None):
+        """One operation of the engine's stage schedule (FB_OP_* in csrc/fb_slab_driver.h)."""
+        be, rows = self.be, self.XL // self.row_chunks
+        fields = lambda fgrp: (4 * fgrp // self.field_groups, 4 * (fgrp + 1) // self.field_groups)
+        if kind == OP_COL_BWD:                                                    # arg: the field group
+            be.col_bwd(*fields(arg), 0)
+        elif kind == OP_COL_ALL_BWD:                                              # arg: the column group
+            be.col_bwd(0, 4, arg)
+        elif kind == OP_XCHG_W4:                                                  # arg: the column group if there are two, else the field group
+            g, (f0, f1) = (arg, (0, 4)) if self.nact > 1 else (0, fields(arg))
+            fld = self.XL * self.cols[g]
+            self._xchg(be.w4_recv[g], be.w4_send[g], 4 * fld, f0 * fld, (f1 - f0) * fld)
+        elif kind == OP_ROW:                                                      # arg: the row chunk
+            be.row(arg * rows, rows)
+        elif kind == OP_XCHG_T:                                                   # arg: the row chunk, of every active column group
+            for g in range(self.nact):
+                nc = self.cols[g]
+                self._xchg(be.t_recv[g], be.t_send[g], self.XL * nc, arg * rows * nc, rows * nc)
+        elif kind == OP_COL_FWD:                                                  # arg: the column group
+            be.col_fwd(stage, arg)
+        else:
+            raise ValueError("unknown stage operation %d" % kind)
+
     def step(self, n=1):
         be = self.be
         if n <= 0:
@@ -432,44 +401,17 @@ class SlabModel:
         if not self.primed:
             be.prime()                                                            # derivatives of every column; frozen ones final
             if self.KF:
-                gf = self.nact
-                self._xchg(be.w4_recv[gf], be.w4_send[gf], 4 * self.XL * self.KF, 0, 4 * self.XL * self.KF)
-            self.primed = 1
-        if self.nact > 1 and self.primed == 1:                                    # slab_groups_prologue
-            for g in range(self.nact):
-                be.col_bwd(0, 4, g)
-                self._xchg(be.w4_recv[g], be.w4_send[g], 4 * self.XL * self.cols[g], 0, 4 * self.XL * self.cols[g])
-            self.primed = 2
-        rows = self.XL // self.row_chunks
+                fld = self.XL * self.KF
+                self._xchg(be.w4_recv[self.nact], be.w4_send[self.nact], 4 * fld, 0, 4 * fld)
+            if self.nact > 1:                                                     # slab_groups_prologue: every group's derivatives leave
+                for g in range(self.nact):
+                    self._op(OP_COL_ALL_BWD, g)
+                    self._op(OP_XCHG_W4, g)
+            self.primed = True
         for _ in range(n):
             for k in range(4):                                                    # main.cpp:288-317
-                for kind, arg in stage_schedule(self.nx, self.ny, self.world):
-                    if self.nact > 1:                                             # pipelined by column groups: arg of the column operations = the group
-                        if kind == OP_ROW:
-                            be.row(arg * rows, rows)
-                        elif kind == OP_XCHG_T:
-                            for g in range(self.nact):
-                                nc = self.cols[g]
-                                self._xchg(be.t_recv[g], be.t_send[g], self.XL * nc, arg * rows * nc, rows * nc)
-                        elif kind == OP_COL_FWD:
-                            be.col_fwd(k, arg)
-                        elif kind == OP_COL_ALL_BWD:
-                            be.col_bwd(0, 4, arg)
-                        else:
-                            self._xchg(be.w4_recv[arg], be.w4_send[arg], 4 * self.XL * self.cols[arg], 0, 4 * self.XL * self.cols[arg])
-                        continue
-                    fld = self.XL * self.cols[0]
-                    if kind == OP_COL_BWD:
-                        be.col_bwd(4 * arg // self.field_groups, 4 * (arg + 1) // self.field_groups, 0)
-                    elif kind == OP_XCHG_W4:
-                        f0, f1 = 4 * arg // self.field_groups, 4 * (arg + 1) // self.field_groups
-                        self._xchg(be.w4_recv[0], be.w4_send[0], 4 * fld, f0 * fld, (f1 - f0) * fld)
-                    elif kind == OP_ROW:
-                        be.row(arg * rows, rows)
-                    elif kind == OP_XCHG_T:
-                        self._xchg(be.t_recv[0], be.t_send[0], fld, arg * rows * self.cols[0], rows * self.cols[0])
-                    else:
-                        be.col_fwd(k, 0)
+                for kind, arg in self.plan.ops:
+                    self._op(kind, arg, k)
 
     def close(self):
         self.be.close()
