@@ -153,6 +153,16 @@ int fb_model_use_graph(fb_model *m, int enable);
 int fb_model_get_vort(fb_model *m, float *d_vort_real);
 /* stage-0 record dumps psi, u, v (any may be NULL)   main.cpp:181-222 */
 int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v);
+/* Okubo-Weiss record output (no reference counterpart; its README names the filamentation time, Rozoff et al. 2006), device
+ * [nx][ny] outputs, either may be NULL (both NULL: FB_EINVAL).  From psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117) and the
+ * velocity u = -dpsi/dy, v = dpsi/dx of fb_model_get_diag:
+ *   W = S1^2 + S2^2 - zeta^2 = 4 (psi_xy^2 - psi_xx psi_yy)  [s^-2],  S1 = u_x - v_y, S2 = v_x + u_y, zeta = v_x - u_y
+ *   tau_fil = 2 / sqrt(W) [s] where W > 0, +inf where W <= 0 (never NaN)
+ * Each second derivative is gradx/grady applied twice to psi_c, c2r'd and divided by GRIDS; every column takes part, the frozen
+ * ones beyond the dealiasing circle too.  zeta here is the vorticity of (u, v): it lacks the domain-mean mode that the vorticity
+ * record carries (a periodic psi has no mean, and a mean rotation is no strain).  Enqueued on the context stream, no
+ * synchronisation; uses record buffers of its own (allocated on first use) and leaves the state and a captured step untouched. */
+int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -206,6 +216,8 @@ int fb_slab_set_source_local(fb_slab *s, const float *d_rows);
 int fb_slab_get_vort_local(fb_slab *s, float *d_rows);
 /* the stage-0 record dumps psi, u, v (main.cpp:181-222) on this rank's rows; any may be NULL */
 int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v);
+/* fb_model_get_okubo_weiss on this rank's rows [XL][ny] (either may be NULL, not both); collective: every rank calls it */
+int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -132,6 +132,32 @@ __global__ void __launch_bounds__(256) k_psi_private(SpecCoef c, cf *__restrict_
     }
 }
 
+// record path of the Okubo-Weiss output: the second derivatives of psi_c = invertLaplacian(vort_c) from one column group's state
+// (3-pass private layout in `zin`, local column j holds ky = ky0 + j, as k_psi_private) into the fields 0, 1, 2 of `z`, fstride
+// apart: psi_xx = gradx(gradx(psi_c)), psi_yy = grady(grady(psi_c)), psi_xy = gradx(grady(psi_c)); pad columns zero.  Every
+// column takes part, the frozen ones too (their modes are not zero).  zin may be field 0 of z: each element is read before it is
+// written, by the same thread.  Same float32 forms as k_spec_op (no contraction).
+__global__ void __launch_bounds__(256) k_ow_spec(SpecCoef c, const cf *zin, cf *z, long fstride, int P, int N1, int N2, int ky0)
+{
+#pragma clang fp contract(off)
+    const size_t total = (size_t)c.nx * P;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)(idx / P), col = (int)(idx - (size_t)row * P);
+        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d, j = ky0 + col;
+        cf a = zin[idx], xx = cf_make(0.f, 0.f), yy = xx, xy = xx;
+        if (j < c.hy) {
+            const float li = (i == 0 && j == 0) ? 1.0f : coef_lap(c, i, j);           // fftwfop.cpp:42-43,112-117
+            a = cf_make(a.x / li, a.y / li);
+            const float kx = c.gx[i], ky = c.gy[j];
+            const cf ax = cf_make(-a.y * kx, a.x * kx), ay = cf_make(-a.y * ky, a.x * ky);   // fftwfop.cpp:87-103
+            xx = cf_make(-ax.y * kx, ax.x * kx);
+            yy = cf_make(-ay.y * ky, ay.x * ky);
+            xy = cf_make(-ay.y * kx, ay.x * kx);
+        }
+        z[idx] = xx; z[idx + fstride] = yy; z[idx + 2 * fstride] = xy;
+    }
+}
+
 // State arrays (vort_c0, stage state, RK accumulator) are touched by k_col_mid only, so they live
 // in that kernel's register order ("tile-major"): tile (cb, ct) = N2 rows x 16 columns is contiguous,
 //   complex index = ((tile*(NLB/2) + e/2)*64 + lane)*2 + (e & 1),   e = 8 s + q  <->  row d = h + 4 s + R1 q,
@@ -155,7 +181,17 @@ __global__ void __launch_bounds__(256) k_state_relayout(const cf *__restrict__ i
 // -------------------------------------------------------------------------------------------
 // row pass (y direction), T = N/16 threads per transform, G = max(1, 256/T) row pairs per WG
 // -------------------------------------------------------------------------------------------
-enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2 };
+enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2, ROW_OW = 3 };
+
+// ROW_OW epilogue at one point: Okubo-Weiss parameter W = S1^2 + S2^2 - zeta^2 = 4 (psi_xy^2 - psi_xx psi_yy) and filamentation time
+// tau_fil = 2 / sqrt(W) where W > 0, +inf elsewhere (Rozoff et al. 2006), from the normalised second derivatives of psi
+FB_DEV void ow_point(float pxx, float pyy, float pxy, float *w_out, float *tau_out, size_t i)
+{
+#pragma clang fp contract(off)
+    const float w = 4.0f * (pxy * pxy - pxx * pyy);
+    if (w_out) w_out[i] = w;
+    if (tau_out) tau_out[i] = w > 0.0f ? 2.0f / sqrtf(w) : __builtin_inff();
+}
 
 // A mixed-space array as the row pass sees it: element (field, row, k), k = global ky in [0, ny/2].
 // One GPU: one segment of pitch ka.  Multi-GPU exchange buffers: the row is cut into ky slabs of `ka` columns (the ACTIVE
@@ -178,8 +214,8 @@ struct RowArgs {
     int t_frozen;           // multi-GPU: 1 = also store the frozen columns of T (FWD: the state); FUSED: 0, their tendency is masked
     const float *src;       // vort_src (real [x][y]) or NULL                       (FUSED)
     const int *src_nz;      // per local row: 1 = the row of vort_src holds a non-zero value; rows of zeros are not read (x + 0 == x)
-    const float *rin;       // real input  [x][y]                                   (FWD)
-    float *rout;            // real output [x][y]                                   (INV)
+    const float *rin;       // real input  [x][y]                                   (FWD; OW: the tau_fil output or NULL, see row_rout2)
+    float *rout;            // real output [x][y]                                   (INV; OW: W, or NULL)
     int x0, nx;             // local rows [x0, x0 + nx), nx even (a row chunk of the pipelined multi-GPU step, else everything)
     float scale;            // 1/GRIDS (FUSED) ; 1/GRIDS or 1 (INV)
     int prescaled;          // FUSED, k_rowq on one GPU: the four fields arrive multiplied by 1/GRIDS already (FullArgs::wscale)
@@ -188,6 +224,10 @@ struct RowArgs {
     long sub_rows;
     const cf *tw_x;
 };
+
+// ROW_OW's second real output travels in `rin`, which no other field of that mode needs: a field of its own would change RowArgs,
+// and with it the code of every existing row kernel instance
+FB_DEV float *row_rout2(const RowArgs &a) { return const_cast<float *>(a.rin); }
 
 // one workgroup per row of vort_src: does the row hold anything but zeros?  (The FIFO producer's cake covers a tenth of the rows,
 // and its "switch off" input is a field of zeros, vort_src_input.cpp:46,52-55: such rows cost the row pass no traffic.)
@@ -248,7 +288,9 @@ template <bool SLAB> FB_DEV bool row_keep(const RowView &v, int t_frozen, int k)
 // Hermitian-extend two half-spectrum rows A,B into Z = A_ext + i B_ext, straight into the first
 // backward stage's registers (SURVEY note N2: imaginary parts at k=0 and k=N/2 are ignored).
 // Thread t owns positions t + i*T: for i < 8 that is k itself, for i >= 8 the mirror of N - pos.
-template <int N, bool SLAB>
+// TAG = 1: ROW_OW's own instance.  Where one mode alone calls an instance with constant fields, the compiler specialises the
+// instance for them, and a caller with other fields would change the code of that mode's kernels.
+template <int N, bool SLAB, int TAG = 0>
 FB_DEV void row_load_pair(cf *reg, int t, const RowView &v, int fA, int fB, int rowA, int rowB)
 {
     constexpr int T = N / 16, R0 = RowTw<N, false>::radix(0);
@@ -499,7 +541,7 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
             else rowfft<N, true>(lds, launder(t), twf_own, reg);
             if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the next pair's first rows have landed
             row_store_pair<N, SLAB>(lds, launder(t), reg, valid, a.T, a.t_frozen, x0, x1);
-        } else {
+        } else if (MODE == ROW_INV) {
             row_load_pair<N, SLAB>(reg, launder(t), a.M, 0, 0, x0, x1);
             rowfft<N, false>(lds, launder(t), twb, reg);
             if (valid) {
@@ -508,6 +550,25 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
                     const int y = t_it + ord_i<RL>(e) * T;
                     a.rout[(size_t)x0 * N + y] = reg[e].x * a.scale;
                     a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
+                }
+            }
+        } else {
+            // ROW_OW: fields psi_xx, psi_yy, psi_xy.  psi_xy of both rows in one transform, then psi_xx and psi_yy of each row in one
+            // (three transforms per row pair), W and tau_fil in registers
+            float xy0[16], xy1[16];
+            row_load_pair<N, SLAB, 1>(reg, launder(t), a.M, 2, 2, x0, x1);
+            rowfft<N, false>(lds, launder(t), twb, reg);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { xy0[e] = reg[e].x * a.scale; xy1[e] = reg[e].y * a.scale; }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int x = x0 + r;
+                row_load_pair<N, SLAB, 1>(reg, launder(t), a.M, 0, 1, x, x);
+                rowfft<N, false>(lds, launder(t), twb, reg);
+                if (valid) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        ow_point(reg[e].x * a.scale, reg[e].y * a.scale, r ? xy1[e] : xy0[e], a.rout, row_rout2(a), (size_t)x * N + t_it + ord_i<RL>(e) * T);
                 }
             }
         }

@@ -68,8 +68,8 @@ FB_DEV void row3_load_lds(cf *reg, int r, int t, const cf *sa, const cf *sb, con
     }
 }
 
-// Hermitian-extended packed spectrum value Z[k], 0 <= k < N, of the two half-spectrum rows A, B
-template <int N, bool SLAB>
+// Hermitian-extended packed spectrum value Z[k], 0 <= k < N, of the two half-spectrum rows A, B (TAG: as row_load_pair's)
+template <int N, bool SLAB, int TAG = 0>
 FB_DEV cf row3_z(const RowView &v, int fA, int fB, int rowA, int rowB, int k)
 {
     const bool mirror = 2 * k > N;
@@ -80,16 +80,16 @@ FB_DEV cf row3_z(const RowView &v, int fA, int fB, int rowA, int rowB, int k)
 }
 
 // backward input of sub-transform r: radix-3 over the spectrum thirds + twiddle, into the first stage's registers
-template <int M, bool SLAB>
+template <int M, bool SLAB, int TAG = 0>
 FB_DEV void row3_load(cf *reg, int r, int t, const RowView &v, int fA, int fB, int rowA, int rowB, const cf *__restrict__ twN)
 {
     constexpr int N = 3 * M, T = M / 16, R0 = RowTw<M, false>::radix(0);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
         const int p0 = t + ord_i<R0>(e) * T;
-        cf z0 = row3_z<N, SLAB>(v, fA, fB, rowA, rowB, p0);
-        cf z1 = row3_z<N, SLAB>(v, fA, fB, rowA, rowB, p0 + M);
-        cf z2 = row3_z<N, SLAB>(v, fA, fB, rowA, rowB, p0 + 2 * M);
+        cf z0 = row3_z<N, SLAB, TAG>(v, fA, fB, rowA, rowB, p0);
+        cf z1 = row3_z<N, SLAB, TAG>(v, fA, fB, rowA, rowB, p0 + M);
+        cf z2 = row3_z<N, SLAB, TAG>(v, fA, fB, rowA, rowB, p0 + 2 * M);
         fft3<+1>(z0, z1, z2);                                   // z_r = sum_j Z[p0 + M j] exp(+2 pi i r j / 3)
         const cf g = r == 0 ? z0 : (r == 1 ? z1 : z2);
         reg[e] = r == 0 ? g : cmulc(g, twN[r * p0]);            // * W_N^{-r p0}
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
             if constexpr (C::SHARE) row_fft<M, true>(lds, launder(t), reinterpret_cast<const RowTwSrc<M, true, true> &>(twb), reg);
             else row_fft<M, true>(lds, launder(t), twf_own, reg);
             row3_store<M, SLAB>(lds_pair, r, launder(t), reg, valid, a.T, a.t_frozen, x0, x1, twN);
-        } else {
+        } else if (MODE == ROW_INV) {
             row3_load<M, SLAB>(reg, r, launder(t), a.M, 0, 0, x0, x1, twN);
             row_fft<M, false>(lds, launder(t), twb, reg);
             if (valid) {
@@ -241,6 +241,25 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
                     const int y = 3 * (tl + ord_i<RL>(e) * T) + r;
                     a.rout[(size_t)x0 * N + y] = reg[e].x * a.scale;
                     a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
+                }
+            }
+        } else {
+            // ROW_OW (as k_row): psi_xy of both rows in one transform, psi_xx and psi_yy of each row in one, W and tau_fil in registers
+            float xy0[16], xy1[16];
+            row3_load<M, SLAB, 1>(reg, r, launder(t), a.M, 2, 2, x0, x1, twN);
+            row_fft<M, false>(lds, launder(t), twb, reg);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { xy0[e] = reg[e].x * a.scale; xy1[e] = reg[e].y * a.scale; }
+#pragma unroll 1
+            for (int rr = 0; rr < 2; ++rr) {
+                const int x = x0 + rr;
+                row3_load<M, SLAB, 1>(reg, r, launder(t), a.M, 0, 1, x, x, twN);
+                row_fft<M, false>(lds, launder(t), twb, reg);
+                if (valid) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        ow_point(reg[e].x * a.scale, reg[e].y * a.scale, rr ? xy1[e] : xy0[e], a.rout, row_rout2(a),
+                                 (size_t)x * N + 3 * (tl + ord_i<RL>(e) * T) + r);
                 }
             }
         }

@@ -335,6 +335,40 @@ extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, floa
     return FB_OK;
 }
 
+// Okubo-Weiss parameter and filamentation time on this rank's rows (either may be NULL): per column group the three second
+// derivatives of psi through the backward x pass, ONE all-to-all of all three in the reverse roles, the row pass with the
+// Okubo-Weiss epilogue.  The record buffers are the model's own (ow_work, ow_send), never the step's.
+extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
+{
+    SLAB_READY(s);
+    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
+    fb_ctx *c = s->c; fb_model *m = s->m;
+    int rc;
+    for (int g = 0; g < c->ngroups; ++g)
+        if ((rc = ow_group_cols(m, g))) return rc;
+    if (c->world == 1) return ow_rows(c, view_single(c, m->ow_work[0], (long)priv_elems(c)), d_w_rows, d_tau_rows);
+    // [3][nx][ncols] == [3][dst][XL][ncols] -> [dst][3][XL][ncols]: each peer's three blocks contiguous
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
+        if (blk == 0) continue;
+        if (!m->ow_send[g] && hipMalloc((void **)&m->ow_send[g], 3 * grp_elems(c, c->grp[g]) * sizeof(cf)) != hipSuccess) {
+            m->ow_send[g] = nullptr;
+            return fail(FB_ENOMEM, "record-path allocation failed");
+        }
+        for (int f = 0; f < 3; ++f)
+            HIPCHK(hipMemcpy2DAsync(m->ow_send[g] + f * blk, 3 * blk * sizeof(cf), m->ow_work[g] + f * c->world * blk, blk * sizeof(cf),
+                                    blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t blk = 3 * (size_t)c->XL * c->grp[g].ncols;
+        if ((rc = slab_xchg(s, m->ow_send[g], m->ow_work[g], blk, 0, blk))) return rc;
+    }
+    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    const cf *w[3] = {m->ow_work[0], m->ow_work[1], m->ow_work[2]};
+    return ow_rows(c, view_slab(c, w, 3), d_w_rows, d_tau_rows);
+}
+
 // ---- the step ----
 static int slab_prime(fb_slab *s)
 {

@@ -47,7 +47,7 @@ extern "C" const char *fb_strerror(int s)
 }
 extern "C" const char *fb_last_error(void) { return g_last_error.c_str(); }
 extern "C" void fb_internal_set_error(const char *msg) { g_last_error = msg ? msg : ""; }   // fb_fieldio.cpp, fb_slab_comm.cpp
-extern "C" int fb_version(void) { return 200; }
+extern "C" int fb_version(void) { return 201; }
 extern "C" int fb_device_count(int *count)
 {
     if (!count) return fail(FB_EINVAL, "fb_device_count: NULL");
@@ -1004,6 +1004,10 @@ struct fb_model {
     float *src;                      // vort_src (this rank's rows) or NULL (== zeros)
     int *src_nz;                     // per row of src: 1 = holds a non-zero value (k_src_row_flags)
     cf *nat[3];                      // natural-layout temporaries for the record path (lazy)
+    // the Okubo-Weiss record path (lazy, never read by the step): per column group, the three fields psi_xx, psi_yy, psi_xy
+    // [3][nx][ncols] in ow_work through the x pass; multi-GPU: then copied to ow_send as [dst][3][XL][ncols] and exchanged back into
+    // ow_work as [src][3][XL][ncols], the layout of view_slab
+    cf *ow_work[3], *ow_send[3];
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
     // tiles only (the backward strided pass on the active tiles comes next); 2: finished on every tile (ready for the row pass)
     int primed;
@@ -1059,6 +1063,8 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->src) hipFree(m->src);
     if (m->src_nz) hipFree(m->src_nz);
     for (auto p : m->nat) if (p) hipFree(p);
+    for (auto p : m->ow_work) if (p) hipFree(p);
+    for (auto p : m->ow_send) if (p) hipFree(p);
     delete m;
     return FB_OK;
 }
@@ -1399,6 +1405,44 @@ extern "C" int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d
         if ((rc = fb_gradx(c, psi, tmp)) || (rc = fb_c2r(c, tmp, d_v, 1))) return rc;                                 // :212-214
     }
     return FB_OK;
+}
+
+// ---- Okubo-Weiss record path (fb_model_get_okubo_weiss, fb_slab_get_okubo_weiss_local) ----
+// group g's three second-derivative fields of psi, [3][nx][ncols] in the model's own record buffer, through the backward x pass
+static int ow_group_cols(fb_model *m, int g)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[g];
+    const size_t n = grp_elems(c, G);
+    if (n == 0) return FB_OK;
+    if (!m->ow_work[g] && hipMalloc((void **)&m->ow_work[g], 3 * n * sizeof(cf)) != hipSuccess) { m->ow_work[g] = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+    cf *z = m->ow_work[g];
+    int rc;
+    // copy of vort_c in the 3-pass layout into field 0, then the three fields from it in place
+    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, z))) return rc; }
+    else if ((rc = state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
+    hipLaunchKernelGGL(k_ow_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, make_coef(c), (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+    HIPCHK(hipGetLastError());
+    if ((rc = launch_col_block<+1>(c, G, z, 3, (long)n))) return rc;
+    return launch_col_strided<+1>(c, G, z, 3, (long)n);
+}
+// the row pass with the Okubo-Weiss epilogue over the three fields in view M
+static int ow_rows(fb_ctx *c, const RowView &M, float *d_w, float *d_tau)
+{
+    RowArgs a = row_args_base(c);
+    a.M = M; a.rout = d_w; a.rin = d_tau;             // (ROW_OW: rin carries the second output, fb_kernels.h row_rout2)
+    a.scale = 1.0f / (float)((size_t)c->nx * c->ny);
+    return launch_row<ROW_OW>(c, a);
+}
+
+extern "C" int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau)
+{
+    if (!m || (!d_w && !d_tau)) return fail(FB_EINVAL, "fb_model_get_okubo_weiss: NULL");
+    fb_ctx *c = m->c;
+    NEED_SINGLE(c);
+    int rc;
+    if ((rc = ow_group_cols(m, 0))) return rc;
+    return ow_rows(c, view_single(c, m->ow_work[0], (long)priv_elems(c)), d_w, d_tau);
 }
 
 #include "fb_slab_driver.h"

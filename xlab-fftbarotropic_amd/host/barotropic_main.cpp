@@ -22,6 +22,8 @@
 // FIFO source is read per rank from "<fifo>.<rank>" (vort_src_input.out --world P --rank r produces that rank's rows).
 // --ranks-as-threads runs all P ranks as threads of ONE process on ONE GPU through the in-process transport: the
 // rehearsal of the multi-rank host logic.
+// --dump-okubo-weiss (no reference counterpart) adds okubo_weiss_step_N.bin and tau_fil_step_N.bin to every record, after v (and
+// dvortdt) in ./log, on one GPU and with --world P.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -58,6 +60,7 @@ struct Config {
     bool timing = true;                                                            // the [timing] summary on stderr (--no-timing: off)
     int record_buffers = 0;                                                        // sets of pinned record buffers: 0 = by size (two while a set is <= 1 GiB), 1, 2
     bool dump_grad = false, dump_dvortdt = false;                                  // the OUTPUT_GRAD_VORT / OUTPUT_DVORTDT blocks of main.cpp:156-162,170-176,229-235 as run-time options
+    bool dump_ow = false;                                                          // Okubo-Weiss parameter and filamentation time (no reference counterpart)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -200,7 +203,7 @@ struct RecordWriter {
     std::thread th; std::mutex mu; std::condition_variable cv;
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
-    void *e_copy[2] = {nullptr, nullptr}; float *h[2][7] = {{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};
+    void *e_copy[2] = {nullptr, nullptr}; float *h[2][9] = {};
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src)
     std::vector<std::pair<const char *, int> > items;
     SourceFeed *feed = nullptr;                                                        // vort_src as of the record step is held until written
@@ -273,6 +276,7 @@ struct Engine {
     // the optional stage-0 dumps of getDvortdt(debug) (main.cpp:156-162,170-176,229-235): dvortdx, dvortdy and
     // dvortdt = -u dvortdx - v dvortdy + vort_src of the CURRENT state (u, v as get() returned them; src NULL = zeros); any output may be NULL
     virtual void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src) = 0;
+    virtual void get_okubo_weiss(float *d_w, float *d_tau) = 0;                       // --dump-okubo-weiss, on the compute stream
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -313,6 +317,7 @@ struct SingleEngine : Engine {
         must(fb_grady(fop, d_spec, d_tmp), "grady"); must(fb_c2r(fop, d_tmp, gy, 1), "c2r");          // main.cpp:165,168
         if (d_dzdt) must(fb_jacobian(fop, d_u, d_v, gx, gy, d_src, d_dzdt), "jacobian");               // main.cpp:225-227
     }
+    void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_model_get_okubo_weiss(model, d_w, d_tau), "fb_model_get_okubo_weiss"); }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -348,6 +353,7 @@ struct SlabEngine : Engine {
     {
         std::fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); std::exit(2);      // (refused in main() already)
     }
+    void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_slab_get_okubo_weiss_local(sl, d_w, d_tau), "fb_slab_get_okubo_weiss_local"); }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -360,24 +366,27 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     void *copy = nullptr, *e_rec = nullptr, *e_h2d = nullptr, *e_src = nullptr;
     must(fb_stream_create(&copy), "stream");
     for (void **e : {&e_rec, &e_h2d, &e_src}) must(fb_event_create(e), "event");
-    // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt)
-    const bool use[7] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt};
-    float *d_in = nullptr, *d_out[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt);
+    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss)
+    constexpr int NB = 9;
+    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow};
+    float *d_in = nullptr, *d_out[NB] = {};
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
-    for (int i = 0; i < 7; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
+    for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
 
     RecordWriter writer;
     size_t set_bytes = 0;
-    for (int i = 0; i < 7; ++i) if (use[i]) set_bytes += floats * sizeof(float);
+    for (int i = 0; i < NB; ++i) if (use[i]) set_bytes += floats * sizeof(float);
     writer.nsets = cfg.record_buffers == 1 || cfg.record_buffers == 2 ? cfg.record_buffers : (set_bytes <= ((size_t)1 << 30) ? 2 : 1);
     for (int b = 0; b < writer.nsets; ++b) {
         must(fb_event_create(&writer.e_copy[b]), "event");
-        for (int i = 0; i < 7; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
+        for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
     writer.items.push_back({"psi", 1}); writer.items.push_back({"u", 2}); writer.items.push_back({"v", 3});   // main.cpp:181-222
     if (cfg.dump_dvortdt) writer.items.push_back({"dvortdt", 6});                      // main.cpp:229-235
+    if (cfg.dump_ow) { writer.items.push_back({"okubo_weiss", 7}); writer.items.push_back({"tau_fil", 8}); }
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -447,10 +456,11 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 eng->get_debug(d_out[4], d_out[5], d_out[6], d_out[2], d_out[3], feed.cur >= 0 ? d_in : nullptr);
                 eng->record(e_src);                                                    // d_in may be overwritten behind this
             }
+            if (cfg.dump_ow) eng->get_okubo_weiss(d_out[7], d_out[8]);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
-            for (int i = 0; i < 7; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
+            for (int i = 0; i < NB; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -511,7 +521,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     }
     if (feed_done) delete feedp;
     fb_free(d_in); for (auto p : d_out) if (p) fb_free(p);
-    for (int b = 0; b < 2; ++b) { for (int i = 0; i < 7; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]); if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]); }
+    for (int b = 0; b < 2; ++b) { for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]); if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]); }
     delete eng;
     for (void *e : {e_rec, e_h2d, e_src}) fb_event_destroy(e);
     fb_stream_destroy(copy);
@@ -526,7 +536,7 @@ int main(int argc, char *args[])
                                     {"world", 1, 0, 9}, {"rank", 1, 0, 10}, {"comm-file", 1, 0, 11}, {"ranks-as-threads", 0, 0, 12},
                                     {"launch-token", 1, 0, 13}, {"comm-max-age", 1, 0, 14}, {"comm-timeout", 1, 0, 15}, {"fifo-fanout", 0, 0, 16},
                                     {"no-timing", 0, 0, 17}, {"dump-grad-vort", 0, 0, 18}, {"dump-dvortdt", 0, 0, 19}, {"record-buffers", 1, 0, 20},
-                                    {0, 0, 0, 0}};
+                                    {"dump-okubo-weiss", 0, 0, 21}, {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
         switch (opt) {
@@ -555,6 +565,7 @@ int main(int argc, char *args[])
         case 18: cfg.dump_grad = true; break;            // main.cpp:156-162,170-176 (#ifdef OUTPUT_GRAD_VORT; configuration.hpp:4-5 defines only OUTPUT_PSI and OUTPUT_WIND)
         case 19: cfg.dump_dvortdt = true; break;
         case 20: cfg.record_buffers = atoi(optarg); break;         // main.cpp:229-235 (#ifdef OUTPUT_DVORTDT)
+        case 21: cfg.dump_ow = true; break;              // okubo_weiss_step_N.bin, tau_fil_step_N.bin (also with --world P)
         }
     }
     if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || (cfg.world > 1 && !cfg.threads && cfg.comm_file.empty()) ||

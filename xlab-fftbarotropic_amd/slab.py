@@ -251,6 +251,14 @@ class EngineSlab:
         self.synchronize()
         return psi, u, v
 
+    def okubo_weiss_local(self):
+        """This rank's rows of the Okubo-Weiss parameter and the filamentation time (fb_slab_get_okubo_weiss_local).  Collective."""
+        t = self.torch
+        w, tau = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2))
+        self.B.check(self.L.fb_slab_get_okubo_weiss_local(self._h, C.c_void_p(w.data_ptr()), C.c_void_p(tau.data_ptr())))
+        self.synchronize()
+        return w, tau
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
