@@ -163,6 +163,21 @@ int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v);
  * record carries (a periodic psi has no mean, and a mean rotation is no strain).  Enqueued on the context stream, no
  * synchronisation; uses record buffers of its own (allocated on first use) and leaves the state and a captured step untouched. */
 int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau);
+/* Effective eddy diffusivity (Nakamura 1996; Hendricks and Schubert 2009; no reference counterpart, its README names the output)
+ * with the vorticity as the tracer and kappa = nu.  zeta is the vorticity record (fb_model_get_vort, bit for bit), g = zeta_x^2 +
+ * zeta_y^2 with zeta_x = c2r(gradx(vort_c))/GRIDS, zeta_y = c2r(grady(vort_c))/GRIDS (every column), in float32.  Bins: qmin, qmax =
+ * float32 min / max of zeta; point -> b = floor(((double)q - qmin) * ((double)nbins / ((double)qmax - qmin))) clamped to
+ * [0, nbins-1] (all in bin 0 when qmax == qmin).  d_table: device float64 [nbins][9], one row per bin, dQ = (qmax - qmin)/nbins,
+ * dx = Lx/nx, dy = Ly/ny:
+ *   0 Q_lo = qmin + b dQ   1 Q_hi = qmin + (b+1) dQ   2 n_b (points)   3 A_b = n_b dx dy [m^2]
+ *   4 A_ge = sum over b' >= b of A_b' (area where zeta >= Q_lo, summed from the top bin down)   5 S_b = dx dy sum_bin g [s^-2]
+ *   6 Le^2 = S_b A_b / dQ^2 [m^2] (0 where n_b = 0 or dQ = 0)   7 r_e = sqrt((A_ge - A_b/2)/pi) [m]
+ *   8 K_eff = nu Le^2 / (4 pi^2 r_e^2) [m^2 s^-1] (0 where Le^2 = 0 or r_e = 0)
+ * Area counts from the top (a cyclone); for other geometries renormalise Le^2 with a minimum length of your own.  d_zeta, d_grad2:
+ * optional device [nx][ny] outputs of zeta and g (NULL: record buffers of the model's own).  nbins in [2, 4096], else FB_EINVAL, as
+ * for a NULL model or table (checked before any HIP call).  Enqueued on the context stream, no synchronisation; leaves the state
+ * and a captured step untouched. */
+int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -218,6 +233,10 @@ int fb_slab_get_vort_local(fb_slab *s, float *d_rows);
 int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v);
 /* fb_model_get_okubo_weiss on this rank's rows [XL][ny] (either may be NULL, not both); collective: every rank calls it */
 int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows);
+/* fb_model_get_eddy_diffusivity of the whole domain: d_zeta_rows, d_grad2_rows are this rank's rows [XL][ny] (optional), d_table
+ * the full table, on every rank (the ranks' ranges and histograms are all-gathered through the transport, summed in rank order);
+ * collective: every rank calls it */
+int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -80,6 +80,7 @@ def lib():
     L.fb_model_get_vort.argtypes = [vp, fp]
     L.fb_model_get_diag.argtypes = [vp, fp, fp, fp]
     L.fb_model_get_okubo_weiss.argtypes = [vp, fp, fp]
+    L.fb_model_get_eddy_diffusivity.argtypes = [vp, ip, vp, fp, fp]
     L.fb_model_get_spectrum.argtypes = [vp, fp]
     L.fb_model_set_spectrum.argtypes = [vp, fp]
     L.fb_model_info.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
@@ -101,6 +102,7 @@ def lib():
     L.fb_slab_get_vort_local.argtypes = [vp, fp]
     L.fb_slab_get_diag_local.argtypes = [vp, fp, fp, fp]
     L.fb_slab_get_okubo_weiss_local.argtypes = [vp, fp, fp]
+    L.fb_slab_get_eddy_diffusivity.argtypes = [vp, ip, vp, fp, fp]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -121,11 +123,11 @@ EXPORTS = [
     "fb_gradx", "fb_grady", "fb_laplacian", "fb_invert_laplacian", "fb_dealiase", "fb_r2c", "fb_c2r",
     "fb_backward_normalize", "fb_negate", "fb_jacobian", "fb_spec_axpy", "fb_spec_evolve", "fb_spec_rk4_combine",
     "fb_model_create", "fb_model_destroy", "fb_model_set_vort", "fb_model_set_source", "fb_model_step",
-    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
+    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
     "fb_model_time_steps", "fb_model_profile_steps", "fb_write_field", "fb_read_field", "fb_make_field", "fb_make_source_kuo2004",
     "fb_create_slab", "fb_slab_unique_id", "fb_slab_create", "fb_slab_destroy", "fb_slab_connect_rccl", "fb_local_hub_create",
     "fb_local_hub_destroy", "fb_slab_connect_local", "fb_slab_connect_callback", "fb_slab_set_vort_local", "fb_slab_set_source_local",
-    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
+    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
@@ -135,6 +137,10 @@ def check(status):
     if status != 0:
         L = lib()
         raise FftBaroError("%s: %s" % (L.fb_strerror(status).decode(), L.fb_last_error().decode()))
+
+
+# the columns of the effective eddy diffusivity table (fb_model_get_eddy_diffusivity, include/fftbaro.h), one row per bin of zeta
+EDDY_DIFFUSIVITY_COLUMNS = ("Q_lo", "Q_hi", "n", "A", "A_ge", "S", "Le2", "r_e", "K_eff")
 
 
 def _torch():
@@ -329,6 +335,15 @@ class Model:
         w, tau = self.fop.empty_real(), self.fop.empty_real()
         check(lib().fb_model_get_okubo_weiss(self._h, _ptr(w), _ptr(tau)))
         return w, tau
+
+    def eddy_diffusivity(self, nbins=256, fields=False):
+        """The effective eddy diffusivity table, float64 [nbins, 9] (columns EDDY_DIFFUSIVITY_COLUMNS), of the vorticity binned in
+        nbins contour intervals; with fields=True also (zeta, grad2): the vorticity and |grad zeta|^2, [nx, ny] tensors."""
+        t = self.torch
+        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
+        zeta, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
+        check(lib().fb_model_get_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(zeta) if fields else None, _ptr(g) if fields else None))
+        return (table, zeta, g) if fields else table
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

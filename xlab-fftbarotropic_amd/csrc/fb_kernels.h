@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(256) k_state_relayout(const cf *__restrict__ i
 // -------------------------------------------------------------------------------------------
 // row pass (y direction), T = N/16 threads per transform, G = max(1, 256/T) row pairs per WG
 // -------------------------------------------------------------------------------------------
-enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2, ROW_OW = 3 };
+enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2, ROW_OW = 3, ROW_KEFF = 4 };
 
 // ROW_OW epilogue at one point: Okubo-Weiss parameter W = S1^2 + S2^2 - zeta^2 = 4 (psi_xy^2 - psi_xx psi_yy) and filamentation time
 // tau_fil = 2 / sqrt(W) where W > 0, +inf elsewhere (Rozoff et al. 2006), from the normalised second derivatives of psi
@@ -191,6 +191,13 @@ FB_DEV void ow_point(float pxx, float pyy, float pxy, float *w_out, float *tau_o
     const float w = 4.0f * (pxy * pxy - pxx * pyy);
     if (w_out) w_out[i] = w;
     if (tau_out) tau_out[i] = w > 0.0f ? 2.0f / sqrtf(w) : __builtin_inff();
+}
+
+// ROW_KEFF epilogue at one point: |grad zeta|^2 = zeta_x^2 + zeta_y^2 from the normalised gradient (no contraction, as ow_point)
+FB_DEV void keff_grad2_point(float zx, float zy, float *g_out, size_t i)
+{
+#pragma clang fp contract(off)
+    g_out[i] = zx * zx + zy * zy;
 }
 
 // A mixed-space array as the row pass sees it: element (field, row, k), k = global ky in [0, ny/2].
@@ -214,8 +221,8 @@ struct RowArgs {
     int t_frozen;           // multi-GPU: 1 = also store the frozen columns of T (FWD: the state); FUSED: 0, their tendency is masked
     const float *src;       // vort_src (real [x][y]) or NULL                       (FUSED)
     const int *src_nz;      // per local row: 1 = the row of vort_src holds a non-zero value; rows of zeros are not read (x + 0 == x)
-    const float *rin;       // real input  [x][y]                                   (FWD; OW: the tau_fil output or NULL, see row_rout2)
-    float *rout;            // real output [x][y]                                   (INV; OW: W, or NULL)
+    const float *rin;       // real input  [x][y]                                   (FWD; OW: the tau_fil output or NULL; KEFF: |grad zeta|^2; see row_rout2)
+    float *rout;            // real output [x][y]                                   (INV; OW: W, or NULL; KEFF: zeta)
     int x0, nx;             // local rows [x0, x0 + nx), nx even (a row chunk of the pipelined multi-GPU step, else everything)
     float scale;            // 1/GRIDS (FUSED) ; 1/GRIDS or 1 (INV)
     int prescaled;          // FUSED, k_rowq on one GPU: the four fields arrive multiplied by 1/GRIDS already (FullArgs::wscale)
@@ -225,7 +232,7 @@ struct RowArgs {
     const cf *tw_x;
 };
 
-// ROW_OW's second real output travels in `rin`, which no other field of that mode needs: a field of its own would change RowArgs,
+// ROW_OW's (and ROW_KEFF's) second real output travels in `rin`, which no other field of that mode needs: a field of its own would change RowArgs,
 // and with it the code of every existing row kernel instance
 FB_DEV float *row_rout2(const RowArgs &a) { return const_cast<float *>(a.rin); }
 
@@ -288,7 +295,7 @@ template <bool SLAB> FB_DEV bool row_keep(const RowView &v, int t_frozen, int k)
 // Hermitian-extend two half-spectrum rows A,B into Z = A_ext + i B_ext, straight into the first
 // backward stage's registers (SURVEY note N2: imaginary parts at k=0 and k=N/2 are ignored).
 // Thread t owns positions t + i*T: for i < 8 that is k itself, for i >= 8 the mirror of N - pos.
-// TAG = 1: ROW_OW's own instance.  Where one mode alone calls an instance with constant fields, the compiler specialises the
+// TAG = 1: ROW_OW's own instance, TAG = 2: ROW_KEFF's.  Where one mode alone calls an instance with constant fields, the compiler specialises the
 // instance for them, and a caller with other fields would change the code of that mode's kernels.
 template <int N, bool SLAB, int TAG = 0>
 FB_DEV void row_load_pair(cf *reg, int t, const RowView &v, int fA, int fB, int rowA, int rowB)
@@ -552,7 +559,7 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
                     a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
                 }
             }
-        } else {
+        } else if (MODE == ROW_OW) {
             // ROW_OW: fields psi_xx, psi_yy, psi_xy.  psi_xy of both rows in one transform, then psi_xx and psi_yy of each row in one
             // (three transforms per row pair), W and tau_fil in registers
             float xy0[16], xy1[16];
@@ -569,6 +576,30 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
                         ow_point(reg[e].x * a.scale, reg[e].y * a.scale, r ? xy1[e] : xy0[e], a.rout, row_rout2(a), (size_t)x * N + t_it + ord_i<RL>(e) * T);
+                }
+            }
+        } else {
+            // ROW_KEFF: fields zeta, zeta_x, zeta_y.  zeta of rows x0, x1 in one transform packed as ROW_INV packs them (so that it
+            // equals the vorticity record bit for bit), then zeta_x and zeta_y of each row in one; zeta and |grad zeta|^2 stored
+            row_load_pair<N, SLAB, 2>(reg, launder(t), a.M, 0, 0, x0, x1);
+            rowfft<N, false>(lds, launder(t), twb, reg);
+            if (valid) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int y = t_it + ord_i<RL>(e) * T;
+                    a.rout[(size_t)x0 * N + y] = reg[e].x * a.scale;
+                    a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int x = x0 + r;
+                row_load_pair<N, SLAB, 2>(reg, launder(t), a.M, 1, 2, x, x);
+                rowfft<N, false>(lds, launder(t), twb, reg);
+                if (valid) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        keff_grad2_point(reg[e].x * a.scale, reg[e].y * a.scale, row_rout2(a), (size_t)x * N + t_it + ord_i<RL>(e) * T);
                 }
             }
         }

@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
                     a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
                 }
             }
-        } else {
+        } else if (MODE == ROW_OW) {
             // ROW_OW (as k_row): psi_xy of both rows in one transform, psi_xx and psi_yy of each row in one, W and tau_fil in registers
             float xy0[16], xy1[16];
             row3_load<M, SLAB, 1>(reg, r, launder(t), a.M, 2, 2, x0, x1, twN);
@@ -260,6 +260,29 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
                     for (int e = 0; e < 16; ++e)
                         ow_point(reg[e].x * a.scale, reg[e].y * a.scale, rr ? xy1[e] : xy0[e], a.rout, row_rout2(a),
                                  (size_t)x * N + 3 * (tl + ord_i<RL>(e) * T) + r);
+                }
+            }
+        } else {
+            // ROW_KEFF (as k_row): zeta of both rows in one transform packed as ROW_INV, zeta_x and zeta_y of each row in one
+            row3_load<M, SLAB, 2>(reg, r, launder(t), a.M, 0, 0, x0, x1, twN);
+            row_fft<M, false>(lds, launder(t), twb, reg);
+            if (valid) {
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const int y = 3 * (tl + ord_i<RL>(e) * T) + r;
+                    a.rout[(size_t)x0 * N + y] = reg[e].x * a.scale;
+                    a.rout[(size_t)x1 * N + y] = reg[e].y * a.scale;
+                }
+            }
+#pragma unroll 1
+            for (int rr = 0; rr < 2; ++rr) {
+                const int x = x0 + rr;
+                row3_load<M, SLAB, 2>(reg, r, launder(t), a.M, 1, 2, x, x, twN);
+                row_fft<M, false>(lds, launder(t), twb, reg);
+                if (valid) {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        keff_grad2_point(reg[e].x * a.scale, reg[e].y * a.scale, row_rout2(a), (size_t)x * N + 3 * (tl + ord_i<RL>(e) * T) + r);
                 }
             }
         }

@@ -335,18 +335,16 @@ extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, floa
     return FB_OK;
 }
 
-// Okubo-Weiss parameter and filamentation time on this rank's rows (either may be NULL): per column group the three second
-// derivatives of psi through the backward x pass, ONE all-to-all of all three in the reverse roles, the row pass with the
-// Okubo-Weiss epilogue.  The record buffers are the model's own (ow_work, ow_send), never the step's.
-extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
+// The three record-path fields of this rank's rows (keff: zeta, zeta_x, zeta_y; else the second derivatives of psi): per column
+// group through the backward x pass, then ONE all-to-all of all three in the reverse roles; *M: the row pass's view of them.  The
+// record buffers are the model's own (ow_work, ow_send), never the step's.
+static int slab_rec3_fields(fb_slab *s, bool keff, RowView *M)
 {
-    SLAB_READY(s);
-    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
     fb_ctx *c = s->c; fb_model *m = s->m;
     int rc;
     for (int g = 0; g < c->ngroups; ++g)
-        if ((rc = ow_group_cols(m, g))) return rc;
-    if (c->world == 1) return ow_rows(c, view_single(c, m->ow_work[0], (long)priv_elems(c)), d_w_rows, d_tau_rows);
+        if ((rc = ow_group_cols(m, g, keff))) return rc;
+    if (c->world == 1) { *M = view_single(c, m->ow_work[0], (long)priv_elems(c)); return FB_OK; }
     // [3][nx][ncols] == [3][dst][XL][ncols] -> [dst][3][XL][ncols]: each peer's three blocks contiguous
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t blk = (size_t)c->XL * c->grp[g].ncols;
@@ -366,7 +364,35 @@ extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float 
     }
     if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
     const cf *w[3] = {m->ow_work[0], m->ow_work[1], m->ow_work[2]};
-    return ow_rows(c, view_slab(c, w, 3), d_w_rows, d_tau_rows);
+    *M = view_slab(c, w, 3);
+    return FB_OK;
+}
+
+// Okubo-Weiss parameter and filamentation time on this rank's rows (either may be NULL): the three second derivatives of psi
+// (slab_rec3_fields), the row pass with the Okubo-Weiss epilogue.
+extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
+{
+    SLAB_READY(s);
+    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
+    RowView M;
+    int rc;
+    if ((rc = slab_rec3_fields(s, false, &M))) return rc;
+    return ow_rows(s->c, M, d_w_rows, d_tau_rows);
+}
+
+// Effective eddy diffusivity table (fb_model_get_eddy_diffusivity), collective: zeta, zeta_x, zeta_y (slab_rec3_fields), the row
+// pass with the ROW_KEFF epilogue into this rank's rows of zeta and |grad zeta|^2, then the contour-area histogram of those rows
+// with the ranks' (min, max) and histograms all-gathered through the transport (keff_finish): every rank gets the whole table.
+extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows)
+{
+    SLAB_READY(s);
+    int rc;
+    if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
+    if ((rc = keff_outputs(s->m, d_zeta_rows, d_grad2_rows))) return rc;
+    RowView M;
+    if ((rc = slab_rec3_fields(s, true, &M))) return rc;
+    if ((rc = keff_rows(s->c, M, d_zeta_rows, d_grad2_rows))) return rc;
+    return keff_finish(s->m, s, nbins, d_zeta_rows, d_grad2_rows, d_table);
 }
 
 // ---- the step ----

@@ -24,6 +24,9 @@
 // rehearsal of the multi-rank host logic.
 // --dump-okubo-weiss (no reference counterpart) adds okubo_weiss_step_N.bin and tau_fil_step_N.bin to every record, after v (and
 // dvortdt) in ./log, on one GPU and with --world P.
+// --dump-eddy-diffusivity [--keff-bins N] (no reference counterpart, N in [2, 4096], default 256) adds eddy_diffusivity_step_N.bin to
+// every record: the effective eddy diffusivity table of fb_model_get_eddy_diffusivity, raw little-endian float64 [N][9], the last
+// file of a record in ./log (after v, dvortdt or tau_fil); on one GPU and with --world P, where rank 0 alone writes it.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -61,6 +64,7 @@ struct Config {
     int record_buffers = 0;                                                        // sets of pinned record buffers: 0 = by size (two while a set is <= 1 GiB), 1, 2
     bool dump_grad = false, dump_dvortdt = false;                                  // the OUTPUT_GRAD_VORT / OUTPUT_DVORTDT blocks of main.cpp:156-162,170-176,229-235 as run-time options
     bool dump_ow = false;                                                          // Okubo-Weiss parameter and filamentation time (no reference counterpart)
+    bool dump_keff = false; int keff_bins = 256;                                   // effective eddy diffusivity table and its number of bins (no reference counterpart)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -204,7 +208,10 @@ struct RecordWriter {
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
     void *e_copy[2] = {nullptr, nullptr}; float *h[2][9] = {};
-    // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src)
+    double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
+    enum { KEFF_TABLE = -2 };
+    // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
+    // KEFF_TABLE = the eddy diffusivity table: one whole file, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
     SourceFeed *feed = nullptr;                                                        // vort_src as of the record step is held until written
     std::string output; FILE *log_fd = nullptr; size_t floats = 0;
@@ -226,6 +233,16 @@ struct RecordWriter {
             char fn[1024];
             for (size_t i = 0; i < items.size(); ++i) {                                // main.cpp:268-278, :156-235
                 snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), items[i].first, job.step);
+                if (items[i].second == KEFF_TABLE) {
+                    if (!lead) continue;
+                    FILE *f = fopen(fn, "wb");
+                    if (!f || fwrite(ht[job.set], 1, table_bytes, f) != table_bytes) { perror("Write field."); std::exit(1); }
+                    fclose(f);
+                    if (!whole) fprintf(stderr, "Output %s\n", fn);
+                    fprintf(log_fd, "%s\n", fn); fflush(log_fd);
+                    bytes += table_bytes;
+                    continue;
+                }
                 const float *data = items[i].second < 0 ? job.src : h[job.set][items[i].second];
                 if (whole) must(fb_write_field(fn, data, floats), "writeField");
                 else {
@@ -242,7 +259,7 @@ struct RecordWriter {
             const double this_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
             busy_s += this_s;
             if (this_s > slowest_s) slowest_s = this_s;
-            bytes += items.size() * floats * sizeof(float);
+            for (const auto &it : items) if (it.second != KEFF_TABLE) bytes += floats * sizeof(float);
             lk.lock();
             writing = false;
             set_free[job.set] = true;
@@ -277,6 +294,7 @@ struct Engine {
     // dvortdt = -u dvortdx - v dvortdy + vort_src of the CURRENT state (u, v as get() returned them; src NULL = zeros); any output may be NULL
     virtual void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src) = 0;
     virtual void get_okubo_weiss(float *d_w, float *d_tau) = 0;                       // --dump-okubo-weiss, on the compute stream
+    virtual void get_eddy_diffusivity(int nbins, double *d_table) = 0;                // --dump-eddy-diffusivity, on the compute stream (collective)
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -318,6 +336,10 @@ struct SingleEngine : Engine {
         if (d_dzdt) must(fb_jacobian(fop, d_u, d_v, gx, gy, d_src, d_dzdt), "jacobian");               // main.cpp:225-227
     }
     void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_model_get_okubo_weiss(model, d_w, d_tau), "fb_model_get_okubo_weiss"); }
+    void get_eddy_diffusivity(int nbins, double *d_table) override
+    {
+        must(fb_model_get_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_eddy_diffusivity");
+    }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -354,6 +376,10 @@ struct SlabEngine : Engine {
         std::fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); std::exit(2);      // (refused in main() already)
     }
     void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_slab_get_okubo_weiss_local(sl, d_w, d_tau), "fb_slab_get_okubo_weiss_local"); }
+    void get_eddy_diffusivity(int nbins, double *d_table) override
+    {
+        must(fb_slab_get_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_eddy_diffusivity");
+    }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -373,6 +399,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     float *d_in = nullptr, *d_out[NB] = {};
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
     for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
+    // the eddy diffusivity table (--dump-eddy-diffusivity): every rank computes it (collective), the lead rank copies it out and writes it
+    const size_t table_bytes = cfg.dump_keff ? (size_t)cfg.keff_bins * 9 * sizeof(double) : 0;
+    double *d_table = nullptr;
+    if (cfg.dump_keff) must(fb_malloc((void **)&d_table, table_bytes), "fb_malloc");
 
     RecordWriter writer;
     size_t set_bytes = 0;
@@ -381,12 +411,15 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     for (int b = 0; b < writer.nsets; ++b) {
         must(fb_event_create(&writer.e_copy[b]), "event");
         for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
+        if (cfg.dump_keff && lead) must(fb_malloc_host((void **)&writer.ht[b], table_bytes), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
     writer.items.push_back({"psi", 1}); writer.items.push_back({"u", 2}); writer.items.push_back({"v", 3});   // main.cpp:181-222
     if (cfg.dump_dvortdt) writer.items.push_back({"dvortdt", 6});                      // main.cpp:229-235
     if (cfg.dump_ow) { writer.items.push_back({"okubo_weiss", 7}); writer.items.push_back({"tau_fil", 8}); }
+    if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
+    writer.table_bytes = table_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -457,10 +490,12 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 eng->record(e_src);                                                    // d_in may be overwritten behind this
             }
             if (cfg.dump_ow) eng->get_okubo_weiss(d_out[7], d_out[8]);
+            if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
             for (int i = 0; i < NB; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
+            if (writer.ht[set]) must(fb_memcpy_d2h_async(copy, writer.ht[set], d_table, table_bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -521,7 +556,12 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     }
     if (feed_done) delete feedp;
     fb_free(d_in); for (auto p : d_out) if (p) fb_free(p);
-    for (int b = 0; b < 2; ++b) { for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]); if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]); }
+    if (d_table) fb_free(d_table);
+    for (int b = 0; b < 2; ++b) {
+        for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
+        if (writer.ht[b]) fb_free_host(writer.ht[b]);
+        if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
+    }
     delete eng;
     for (void *e : {e_rec, e_h2d, e_src}) fb_event_destroy(e);
     fb_stream_destroy(copy);
@@ -536,7 +576,7 @@ int main(int argc, char *args[])
                                     {"world", 1, 0, 9}, {"rank", 1, 0, 10}, {"comm-file", 1, 0, 11}, {"ranks-as-threads", 0, 0, 12},
                                     {"launch-token", 1, 0, 13}, {"comm-max-age", 1, 0, 14}, {"comm-timeout", 1, 0, 15}, {"fifo-fanout", 0, 0, 16},
                                     {"no-timing", 0, 0, 17}, {"dump-grad-vort", 0, 0, 18}, {"dump-dvortdt", 0, 0, 19}, {"record-buffers", 1, 0, 20},
-                                    {"dump-okubo-weiss", 0, 0, 21}, {0, 0, 0, 0}};
+                                    {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23}, {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
         switch (opt) {
@@ -566,6 +606,14 @@ int main(int argc, char *args[])
         case 19: cfg.dump_dvortdt = true; break;
         case 20: cfg.record_buffers = atoi(optarg); break;         // main.cpp:229-235 (#ifdef OUTPUT_DVORTDT)
         case 21: cfg.dump_ow = true; break;              // okubo_weiss_step_N.bin, tau_fil_step_N.bin (also with --world P)
+        case 22: cfg.dump_keff = true; break;            // eddy_diffusivity_step_N.bin (also with --world P)
+        case 23: {
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (!*optarg || *end || v < 2 || v > 4096) { fprintf(stderr, "--keff-bins: an integer in [2, 4096]\n"); return 2; }
+            cfg.keff_bins = (int)v;
+            break;
+        }
         }
     }
     if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || (cfg.world > 1 && !cfg.threads && cfg.comm_file.empty()) ||

@@ -259,6 +259,17 @@ class EngineSlab:
         self.synchronize()
         return w, tau
 
+    def eddy_diffusivity(self, nbins=256, fields=False):
+        """The effective eddy diffusivity table of the whole domain, float64 [nbins, 9] (fb_slab_get_eddy_diffusivity), the same on
+        every rank; with fields=True also this rank's rows (zeta, grad2), [XL, ny].  Collective."""
+        t = self.torch
+        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
+        zeta, g = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2)) if fields else (None, None)
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        self.B.check(self.L.fb_slab_get_eddy_diffusivity(self._h, nbins, ptr(table), ptr(zeta), ptr(g)))
+        self.synchronize()
+        return (table, zeta, g) if fields else table
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
