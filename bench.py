@@ -8,20 +8,27 @@
 One "step" = one RK4 step (4 stages = 16 c2r + 4 r2c 2-D FFTs + all pointwise work of
 main.cpp:286-317) of the synthetic workload below, state resident in HBM.  Prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set-up, spin-up, the W warm-up and the K timed steps, --dump-outputs if given,
+and the line.  Everything else the benchmark measures runs only with `--full`, after the timed steps: at N=1 the per-kernel timing
+pass and the roofline figures, the `driver` leg and the `cpu_baseline` leg; at N>1 the local-passes run behind
+`local_passes_ms_per_step` and `predicted`, the same-grid single-GPU rate and `configs_run`.  (The N>1 transport self-test stays in
+every run: it is also the transport's first use, so the links are set up before anything is timed.)
+
 Workload at N=1: BASELINE.json configs[2] -- 4096x4096 Kuo2004 initial field, fp32,
 dt = 3*1024/4096 s (the reference's dt=3 s is unstable above N~2300).
 For N>1 the same grid is split into x-row / ky-column slabs (strong scaling; the engine drives the
 RCCL all-to-all transposes itself, csrc/fb_slab_driver.h), see DESIGN.md section 6.  The N>1 line also carries: `rccl_ranks`
-(ncclCommCount as every rank's communicator reports it), `devices` (HIP ordinals), `predicted` (the model of DESIGN.md section 6
-beside the measured `value`), `one_gpu_same_grid_steps_per_s` / `vs_1gpu_same_grid` (rank 0 alone on the same grid in the same job)
-and `configs_run`: at N = 4 also 8192^2 gaussian (BASELINE configs[3]), at N = 8 also 16384^2 source-forced (configs[4]), each with
-its own single-GPU rate.  At N=1 a `driver` leg times the C++ drop-in driver itself (1000 steps, record_step 100).
+(ncclCommCount as every rank's communicator reports it) and `devices` (HIP ordinals); with --full also `predicted` (the model of
+DESIGN.md section 6 beside the measured `value`), `one_gpu_same_grid_steps_per_s` / `vs_1gpu_same_grid` (rank 0 alone on the same
+grid in the same job) and `configs_run`: at N = 4 also 8192^2 gaussian (BASELINE configs[3]), at N = 8 also 16384^2 source-forced
+(configs[4]), each with its own single-GPU rate.  At N=1 --full adds a `driver` leg that times the C++ drop-in driver itself (1000
+steps, record_step 100).
 
 `--steps K` is the number of timed steps and `ms_per_step` the time of one of them.  At N=1, `--dump-outputs DIR` writes the
 vorticity field the last timed step left (W + K steps from the initial field) to DIR as .npy files, so that two builds can be
 compared output for output on identical inputs.
 
-Roofline conventions: `roofline.achieved` uses the contract's algorithmic bytes (SURVEY.md
+Roofline conventions (--full): `roofline.achieved` uses the contract's algorithmic bytes (SURVEY.md
 8(d): 8 N^2 per 1-D pass over a field, 320 N^2 per step); next to it the line carries the bytes the kernels really
 move (`traffic`, from the committed rocprofv3 PMC passes), `traffic_frac` = those bytes / launch time / peak, and at
 step level `tight_frac` against the fully fused lower bound of 256 N^2.
@@ -157,15 +164,19 @@ def parse_args(argv=None):
                                                   "16384 kuo2004 + source; smaller grids elliptic)")
     ap.add_argument("--source", type=int, default=None, help="1: the source-forced variant (main-shallow-water.cpp:277-338) with the FIFO "
                                                              "producer's cake switched on; default: on for --grid 16384 (BASELINE configs[4])")
-    ap.add_argument("--cpu-steps", type=int, default=5, help="oracle steps for the 1-core cpu_baseline leg (0 = skip cpu_baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: at N=1 the per-kernel timing pass "
+                         "(roofline, kernels_*), the driver leg and cpu_baseline; at N>1 the local-passes run and predicted, the same-grid "
+                         "single-GPU rate and configs_run")
+    ap.add_argument("--cpu-steps", type=int, default=5, help="--full: oracle steps for the 1-core cpu_baseline leg (0 = skip cpu_baseline)")
     ap.add_argument("--spinup-steps", type=int, default=None,
                     help="untimed device spin-up before the warm-up: this many steps, then the state is reset (default: ~30 ms worth; 0 = none)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--also-grid", default="auto",
-                    help="N>1: further grids run in the same job as `configs_run` (comma separated; 'auto' = 8192 at N=4 -- BASELINE configs[3] -- "
+                    help="N>1 with --full: further grids run in the same job as `configs_run` (comma separated; 'auto' = 8192 at N=4 -- BASELINE configs[3] -- "
                          "and 16384 at N=8 -- configs[4]; 'none' = only --grid)")
     ap.add_argument("--driver-steps", type=int, default=None,
-                    help="N=1: the `driver` leg -- the C++ drop-in driver (host/barotropic_main.out) on the same workload for this many steps with "
+                    help="N=1 with --full: the `driver` leg -- the C++ drop-in driver (host/barotropic_main.out) on the same workload for this many steps with "
                          "record_step 100 (configuration.hpp:34-36), records into a temporary directory (default: 1000 at the default grid, else 0 = off)")
     ap.add_argument("--launch-timeout", type=float, default=540.0,
                     help="N>1 started from a plain shell: seconds before the child job (its whole process group) is ended; the headline line rank 0 has "
@@ -365,6 +376,11 @@ def slab_run(X, torch, dist, slab, args, n, kind, with_source, dt, rank, world):
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     model.close()
+    out = {"steps_per_s": K / elapsed, "ms_per_step": 1e3 * elapsed / K, "spinup_steps": spinup, "slab": info,
+           "rccl_ranks": rccl_ranks, "devices": [d["hip_device"] for d in every],
+           "rccl": {"comm_ranks": counts, "comm_rank": [d["comm_rank"] for d in every], "comm_device": [d["comm_device"] for d in every]}}
+    if not args.full:
+        return out
     # how much of that is local work: the same schedule with a transport that moves nothing (fields are garbage, timing is not)
     m0 = slab.EngineSlab(n, n, dt=dt, rank=rank, world=world, transport="null", dist=dist)
     m0.set_vort_local(v0_local)
@@ -381,13 +397,11 @@ def slab_run(X, torch, dist, slab, args, n, kind, with_source, dt, rank, world):
     m0.close()
     del v0_local, src_local
     pred_ms, terms = slab.predicted_step_ms(n, n, world, local_ms)
-    return {"steps_per_s": K / elapsed, "ms_per_step": 1e3 * elapsed / K, "spinup_steps": spinup, "slab": info,
-            "local_passes_ms_per_step": local_ms,          # the step with exchanges that move nothing: what is left is the links
-            "rccl_ranks": rccl_ranks, "devices": [d["hip_device"] for d in every],
-            "rccl": {"comm_ranks": counts, "comm_rank": [d["comm_rank"] for d in every], "comm_device": [d["comm_device"] for d in every]},
-            "predicted": dict({"steps_per_s": 1e3 / pred_ms, "what": "DESIGN.md section 6 model (slab.predicted_step_ms): stage = link time of "
-                               "5 fields x XL x KA complex per peer at an ASSUMED rate + the local work no transfer hides; not a measurement"},
-                              **terms)}
+    out["local_passes_ms_per_step"] = local_ms              # the step with exchanges that move nothing: what is left is the links
+    out["predicted"] = dict({"steps_per_s": 1e3 / pred_ms, "what": "DESIGN.md section 6 model (slab.predicted_step_ms): stage = link time of "
+                             "5 fields x XL x KA complex per peer at an ASSUMED rate + the local work no transfer hides; not a measurement"},
+                            **terms)
+    return out
 
 
 def one_gpu_same_grid(X, torch, dist, args, n, kind, with_source, dt, rank):
@@ -458,6 +472,38 @@ def driver_leg(X, n, kind, with_source, dt, steps, record_step=100):
         shutil.rmtree(d, ignore_errors=True)
 
 
+def kernel_figures(torch, model, n, K, steps_per_s):
+    """--full, N=1: per-kernel HIP-event timing over a second pass of the same K steps (events on the launch stream), and the
+    line's roofline and per-kernel figures made from it and from the committed PMC summary of the grid."""
+    prof = model.profile_steps(K)
+    torch.cuda.synchronize()
+    if prof["k_col_strided_bwd4"][1] == 0 and prof["k_col_strided_fwd1"][1] == 0:     # single-pass x transform in use
+        prof = {"k_row_fused": prof["k_row_fused"], "k_col_full": prof["k_col_mid"]}
+    per = {k: (ms / max(cnt, 1)) for k, (ms, cnt) in prof.items()}
+    tot = {k: ms for k, (ms, cnt) in prof.items()}
+    dom = max(tot, key=tot.get)
+    pmc_path, pmc = pmc_profile(n)
+    traffic = {k: pmc_traffic(pmc, k) for k in per}
+    ach = ALG_N2[dom] * n * n / (per[dom] * 1e-3) / 1e9
+    fig = {"roofline": {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS, "traffic": traffic[dom],
+                        "traffic_frac": (traffic[dom] / (per[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic[dom] else None,
+                        # provenance of `traffic`: NOT measured by this run (PMC passes need their own rocprofv3 runs)
+                        "traffic_source": ({"file": pmc_path, "commit": pmc.get("commit"), "command": pmc.get("command")} if pmc else None),
+                        "avg_launch_ms": per[dom], "alg_bytes_per_launch": ALG_N2[dom] * n * n}}
+    fig["kernels_ms_per_launch"] = per
+    fig["kernels_ms_per_step"] = {k: v / K for k, v in tot.items()}
+    # credit-based and counter-based rates side by side: the contract's 8 N^2-per-pass credit counts the row pass's
+    # traffic twice (it reads 4 C and writes 1 C for 40 N^2 of credit), the counter bytes are what really crosses the fabric
+    fig["kernels_GBs"] = {k: {"credit": ALG_N2[k] * n * n / (per[k] * 1e-3) / 1e9,
+                              "traffic": (traffic[k] / (per[k] * 1e-3) / 1e9) if traffic[k] else None} for k in per}
+    if all(traffic.values()):
+        per_step = sum(traffic[k] * (prof[k][1] / K) for k in per)
+        fig["traffic_bytes_per_step"] = per_step
+        fig["traffic_frac"] = per_step * steps_per_s / 1e9 / HBM_PEAK_GBS
+    return fig
+
+
 def dump_outputs(d, vort):
     """--dump-outputs: the vorticity field after the last timed step as d/vort.npy (float32) and the indices of its rows as
     d/vort_rows.npy (float64).  Above DUMP_FIELD_BYTES the rows are a sample fixed by the grid alone (seed 0, ascending), so that two
@@ -518,32 +564,34 @@ def main():
         out = base_line(r["steps_per_s"], r["ms_per_step"], r["spinup_steps"])
         out["config"]["slab"] = r["slab"]
         for k in ("local_passes_ms_per_step", "rccl_ranks", "devices", "rccl", "predicted"):
-            out[k] = r[k]
+            if k in r:                                           # the first and the last only with --full
+                out[k] = r[k]
         leave = os.environ.get("FB_BENCH_LINE_FILE")
         if rank == 0 and leave:                                  # a later failure must not cost the headline figure (self_launch reads this)
             with open(leave, "w") as f:
                 json.dump(out, f)
-        one = one_gpu_same_grid(X, torch, dist, args, n, kind, with_source, dt, rank)
-        out["one_gpu_same_grid_steps_per_s"] = one               # rank 0 alone, the fused single-GPU model, same grid, same job
-        out["vs_1gpu_same_grid"] = (r["steps_per_s"] / one) if one else None
-        # the workloads BASELINE names for this many GPUs, in the same job: configs[3] at N = 4, configs[4] at N = 8
-        also = {"auto": {4: [8192], 8: [16384]}.get(world, []), "none": []}.get(args.also_grid)
-        if also is None:
-            also = [int(g) for g in args.also_grid.split(",") if g]
-        out["configs_run"] = []
-        for g in also:
-            gk, gs, gdt = workload_of(g)
-            rg = slab_run(X, torch, dist, slab, args, g, gk, gs, gdt, rank, world)
-            og = one_gpu_same_grid(X, torch, dist, args, g, gk, gs, gdt, rank)
-            out["configs_run"].append({
-                "workload": workload_text(g, gk, gs, gdt), "grid": [g, g], "source": gs, "value": rg["steps_per_s"], "unit": "steps/s",
-                "ms_per_step": rg["ms_per_step"], "steps": K, "warmup": W, "spinup_steps": rg["spinup_steps"],
-                "local_passes_ms_per_step": rg["local_passes_ms_per_step"], "predicted": rg["predicted"], "slab": rg["slab"],
-                "rccl_ranks": rg["rccl_ranks"], "one_gpu_same_grid_steps_per_s": og, "vs_1gpu_same_grid": (rg["steps_per_s"] / og) if og else None,
-                "step_roofline_frac": 320.0 * g * g * rg["steps_per_s"] / 1e9 / (HBM_PEAK_GBS * world)})
-            if rank == 0 and leave:
-                with open(leave, "w") as f:
-                    json.dump(out, f)
+        if args.full:
+            one = one_gpu_same_grid(X, torch, dist, args, n, kind, with_source, dt, rank)
+            out["one_gpu_same_grid_steps_per_s"] = one               # rank 0 alone, the fused single-GPU model, same grid, same job
+            out["vs_1gpu_same_grid"] = (r["steps_per_s"] / one) if one else None
+            # the workloads BASELINE names for this many GPUs, in the same job: configs[3] at N = 4, configs[4] at N = 8
+            also = {"auto": {4: [8192], 8: [16384]}.get(world, []), "none": []}.get(args.also_grid)
+            if also is None:
+                also = [int(g) for g in args.also_grid.split(",") if g]
+            out["configs_run"] = []
+            for g in also:
+                gk, gs, gdt = workload_of(g)
+                rg = slab_run(X, torch, dist, slab, args, g, gk, gs, gdt, rank, world)
+                og = one_gpu_same_grid(X, torch, dist, args, g, gk, gs, gdt, rank)
+                out["configs_run"].append({
+                    "workload": workload_text(g, gk, gs, gdt), "grid": [g, g], "source": gs, "value": rg["steps_per_s"], "unit": "steps/s",
+                    "ms_per_step": rg["ms_per_step"], "steps": K, "warmup": W, "spinup_steps": rg["spinup_steps"],
+                    "local_passes_ms_per_step": rg["local_passes_ms_per_step"], "predicted": rg["predicted"], "slab": rg["slab"],
+                    "rccl_ranks": rg["rccl_ranks"], "one_gpu_same_grid_steps_per_s": og, "vs_1gpu_same_grid": (rg["steps_per_s"] / og) if og else None,
+                    "step_roofline_frac": 320.0 * g * g * rg["steps_per_s"] / 1e9 / (HBM_PEAK_GBS * world)})
+                if rank == 0 and leave:
+                    with open(leave, "w") as f:
+                        json.dump(out, f)
         if rank == 0:
             print(json.dumps(out), flush=True)
         dist.barrier()
@@ -553,46 +601,21 @@ def main():
     model, elapsed, spinup = single_gpu_run(X, torch, n, kind, with_source, dt, K, W, args.spinup_steps)
     out = base_line(K / elapsed, 1e3 * elapsed / K, spinup)
     steps_per_s = K / elapsed
-    if args.dump_outputs:                   # before the profiling pass below steps the model on
+    if args.dump_outputs:                   # before the profiling pass of --full steps the model on
         out["dumped_outputs"] = {"dir": args.dump_outputs, "after_steps": W + K,
                                  "files": dump_outputs(args.dump_outputs, model.vort().cpu().numpy())}
 
-    # per-kernel HIP-event timing over a second pass of the same K steps (events on the launch stream)
-    prof = model.profile_steps(K)
-    torch.cuda.synchronize()
-    if prof["k_col_strided_bwd4"][1] == 0 and prof["k_col_strided_fwd1"][1] == 0:     # single-pass x transform in use
-        prof = {"k_row_fused": prof["k_row_fused"], "k_col_full": prof["k_col_mid"]}
-    per = {k: (ms / max(cnt, 1)) for k, (ms, cnt) in prof.items()}
-    tot = {k: ms for k, (ms, cnt) in prof.items()}
-    dom = max(tot, key=tot.get)
-    pmc_path, pmc = pmc_profile(n)
-    traffic = {k: pmc_traffic(pmc, k) for k in per}
-    ach = ALG_N2[dom] * n * n / (per[dom] * 1e-3) / 1e9
-    out["roofline"] = {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                       "frac": ach / HBM_PEAK_GBS, "traffic": traffic[dom],
-                       "traffic_frac": (traffic[dom] / (per[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic[dom] else None,
-                       # provenance of `traffic`: NOT measured by this run (PMC passes need their own rocprofv3 runs)
-                       "traffic_source": ({"file": pmc_path, "commit": pmc.get("commit"), "command": pmc.get("command")} if pmc else None),
-                       "avg_launch_ms": per[dom], "alg_bytes_per_launch": ALG_N2[dom] * n * n}
-    out["kernels_ms_per_launch"] = per
-    out["kernels_ms_per_step"] = {k: v / K for k, v in tot.items()}
-    # credit-based and counter-based rates side by side: the contract's 8 N^2-per-pass credit counts the row pass's
-    # traffic twice (it reads 4 C and writes 1 C for 40 N^2 of credit), the counter bytes are what really crosses the fabric
-    out["kernels_GBs"] = {k: {"credit": ALG_N2[k] * n * n / (per[k] * 1e-3) / 1e9,
-                              "traffic": (traffic[k] / (per[k] * 1e-3) / 1e9) if traffic[k] else None} for k in per}
-    if all(traffic.values()):
-        per_step = sum(traffic[k] * (prof[k][1] / K) for k in per)
-        out["traffic_bytes_per_step"] = per_step
-        out["traffic_frac"] = per_step * steps_per_s / 1e9 / HBM_PEAK_GBS
-    del model
-    torch.cuda.empty_cache()
-    dsteps = args.driver_steps if args.driver_steps is not None else (1000 if (n == 4096 and not with_source) else 0)
-    if dsteps > 0:
-        out["driver"] = driver_leg(X, n, kind, with_source, dt, dsteps)
-        if "driver_steps_per_s" in out["driver"]:
-            out["driver"]["vs_value"] = out["driver"]["driver_steps_per_s"] / steps_per_s
-    if args.cpu_steps > 0:
-        out["cpu_baseline"] = cpu_baseline(n, dt, kind, args.cpu_steps, with_source)
+    if args.full:
+        out.update(kernel_figures(torch, model, n, K, steps_per_s))
+        del model
+        torch.cuda.empty_cache()
+        dsteps = args.driver_steps if args.driver_steps is not None else (1000 if (n == 4096 and not with_source) else 0)
+        if dsteps > 0:
+            out["driver"] = driver_leg(X, n, kind, with_source, dt, dsteps)
+            if "driver_steps_per_s" in out["driver"]:
+                out["driver"]["vs_value"] = out["driver"]["driver_steps_per_s"] / steps_per_s
+        if args.cpu_steps > 0:
+            out["cpu_baseline"] = cpu_baseline(n, dt, kind, args.cpu_steps, with_source)
     print(json.dumps(out))
 
 

@@ -19,6 +19,13 @@ def test_steps_and_dump_arguments():
             bench.parse_args(bad)
 
 
+def test_full_is_off_by_default():
+    assert bench.parse_args([]).full is False
+    assert bench.parse_args(["--full"]).full is True
+    a = bench.parse_args(["--gpus", "2", "--full", "--also-grid", "256"])
+    assert (a.gpus, a.full, a.also_grid) == (2, True, "256")
+
+
 @pytest.mark.parametrize("n", [256, 4096, 8192])
 def test_dump_outputs_is_bounded_and_repeatable(tmp_path, n):
     v = np.random.default_rng(n).standard_normal((n, n), dtype=np.float32)

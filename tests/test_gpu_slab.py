@@ -393,12 +393,32 @@ def test_bench_starts_its_own_ranks_from_a_plain_shell(tmp_path):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--grid", "512", "--steps", "3", "--warmup", "1",
-           "--cpu-steps", "0", "--also-grid", "256"]
+           "--cpu-steps", "0", "--also-grid", "256", "--full"]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and lines[0].startswith("{")                         # stdout is the line and nothing else
     _bench_line_checks(json.loads(lines[0]))
+
+
+def test_bench_plain_multi_gpu_line_is_the_headline_run_only(tmp_path):
+    """Without --full the N > 1 line is the headline run alone: no local-passes run, no prediction, no same-grid single-GPU run and no
+    further grids, whatever --also-grid says; the transport self-test before the timed steps stays."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--grid", "256", "--steps", "3", "--warmup", "1",
+           "--also-grid", "256"]
+    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env, cwd=str(tmp_path))
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and lines[0].startswith("{")
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["value"] > 0 and d["steps"] == 3 and d["config"]["parallelism"] == "slab2"
+    assert d["devices"] == [0, 0] and d["rccl_ranks"] is None and d["config"]["slab"]["transport_selftest"] == "ok"
+    gone = ("local_passes_ms_per_step", "predicted", "one_gpu_same_grid_steps_per_s", "vs_1gpu_same_grid", "configs_run")
+    assert not [k for k in gone if k in d], d
 
 
 def test_engine_slab_two_processes_gloo_matches_single(tmp_path):
