@@ -162,7 +162,9 @@ def test_record_has_no_side_effects():
     assert np.array_equal(_bits(wg), _bits(w0))
 
 
-def _slab_ow(n, world, steps, v0, env):
+def _slab_run(n, world, steps, v0, env, run):
+    """`world` EngineSlab ranks as threads over local_hub: set v0, step `steps`, then run(m) -> a tuple of this rank's row tensors;
+    the tuple's entries, rows of every rank stacked"""
     import threading
     S = _slab()
     hub = S.local_hub(world)
@@ -174,8 +176,7 @@ def _slab_ow(n, world, steps, v0, env):
             try:
                 m.set_vort_local(S.local_rows(v0, r, world))
                 m.step(steps)
-                w, tau = m.okubo_weiss_local()
-                out[r] = (w.cpu().numpy(), tau.cpu().numpy())
+                out[r] = [t.cpu().numpy() for t in run(m)]
             finally:
                 m.close()
         except BaseException as e:                                          # noqa: BLE001 -- re-raised below
@@ -198,21 +199,56 @@ def _slab_ow(n, world, steps, v0, env):
     for e in errs:
         if e is not None:
             raise e
-    return np.concatenate([o[0] for o in out]), np.concatenate([o[1] for o in out])
+    return [np.concatenate([o[i] for o in out]) for i in range(len(out[0]))]
 
 
 @pytest.mark.parametrize("world,n,env", [(2, 256, {}), (4, 768, {}), (8, 512, {"FB_SLAB_COL_GROUPS": "2"}),
-                                         (4, 1024, {"FB_SLAB_COL_GROUPS": "2"}), (2, 512, {"FB_SLAB_FIELD_GROUPS": "2"})])
+                                         (4, 1024, {"FB_SLAB_COL_GROUPS": "2"}), (2, 512, {"FB_SLAB_FIELD_GROUPS": "2"}), (1, 256, {})])
 def test_slab_equals_single_gpu_bitwise(world, n, env):
+    """The slab's records (ranks as threads) against the one-GPU model's, bit for bit: Okubo-Weiss, vorticity, psi, u, v"""
     import xlab_fftbarotropic_amd as X
     v0 = X.make_field("kuo2004", n)
     ref = X.Model(n, n)
     ref.set_vort(v0)
     ref.step(3)
-    want_w, want_tau = _ow(ref)
-    w, tau = _slab_ow(n, world, 3, v0, env)
-    assert np.array_equal(_bits(w), _bits(want_w))
-    assert np.array_equal(_bits(tau), _bits(want_tau))
+    want = [t.cpu().numpy() for t in ref.okubo_weiss() + (ref.vort(),) + ref.diag()]
+    got = _slab_run(n, world, 3, v0, env, lambda m: m.okubo_weiss_local() + (m.vort_local(),) + m.diag_local())
+    for name, a, b in zip(("W", "tau", "vort", "psi", "u", "v"), got, want):
+        assert np.array_equal(_bits(a), _bits(b)), name
+
+
+@pytest.mark.parametrize("n", [4096, 8192])
+def test_record_has_no_side_effects_full_pass(n):
+    """Records between steps leave the step untouched on the single-pass x transform: k_col_full with k_rowq and its prescale
+    (4096^2) and with k_rowh2 (8192^2): step k, every record, step k again == 2k plain steps, bit for bit"""
+    import xlab_fftbarotropic_amd as X
+    v0 = X.make_field("kuo2004", n)
+    ref = X.Model(n, n, dt=3.0 * 1024 / n)
+    ref.set_vort(v0)
+    ref.step(6)
+    want = ref.vort().cpu().numpy()
+    ref.close()
+    m = X.Model(n, n, dt=3.0 * 1024 / n)
+    m.set_vort(v0)
+    m.step(3)
+    m.vort(), m.diag(), m.okubo_weiss(), m.eddy_diffusivity(fields=True)
+    m.step(3)
+    assert np.array_equal(_bits(m.vort().cpu().numpy()), _bits(want))
+
+
+def test_slab_record_has_no_side_effects():
+    """The same on a 4-rank slab (ranks as threads): step k, every record, step k again == 2k plain steps, bit for bit"""
+    import xlab_fftbarotropic_amd as X
+    n, world = 512, 4
+    v0 = X.make_field("kuo2004", n)
+    want = _slab_run(n, world, 6, v0, {}, lambda m: (m.vort_local(),))[0]
+
+    def records_then_step(m):
+        m.vort_local(), m.diag_local(), m.okubo_weiss_local(), m.eddy_diffusivity(fields=True)
+        m.step(3)
+        return (m.vort_local(),)
+    got = _slab_run(n, world, 3, v0, {}, records_then_step)[0]
+    assert np.array_equal(_bits(got), _bits(want))
 
 
 def test_driver_dump_okubo_weiss(tmp_path):

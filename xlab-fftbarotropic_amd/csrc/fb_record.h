@@ -1,0 +1,274 @@
+// fb_record.h -- state in and the record outputs of a model (included by fftbaro.hip after fb_slab_driver.h; C ABI: include/fftbaro.h).
+//
+// One layer serves the one-GPU model (fb_model_*, s == NULL) and a rank of a slab (fb_slab_*, this rank's rows).  A record is, per
+// column group: the export of vort_c into the model's record workspace, the spectral kernel of its kind (none for the vorticity;
+// k_psi_private for psi, u, v; k_ow_spec; k_keff_spec), the backward x pass; on a slab of several ranks one all-to-all per group in
+// the reverse roles; then the row pass with the kind's epilogue.  The record buffers are the model's own (rec_work, rec_send): a record
+// never writes the step's buffers (ZA, ZB, ACC, w4_*, t_*).
+#pragma once
+
+// ---- state in (fb_model_set_vort, fb_slab_set_vort_local) ----
+// readField + fftwf_execute(p_fwd_vort), main.cpp:143-144,256: y transform of the local rows into t_send -> transpose (slab) -> x
+// transform of the local columns in t_recv -> the state's layout.  One GPU: t_send == t_recv.
+static int state_in(fb_model *m, fb_slab *s, const float *d_rows)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    m->warmed = false;                                      // the next fb_model_step starts with an eager (priming) step
+    m->primed = 0;
+    if (!s) HIPCHK(hipMemsetAsync(m->gb[0].t_send, 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
+    RowArgs a = row_args_base(c);
+    a.rin = d_rows;
+    const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
+    a.T = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
+    if ((rc = launch_row<ROW_FWD>(c, a)) || (s && (rc = slab_transpose_all(s)))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        cf *t = m->gb[g].t_recv;
+        if ((rc = launch_col_strided<-1>(c, G, t, 1, 0)) || (rc = launch_col_block<-1>(c, G, t, 1, 0))) return rc;
+        if ((rc = m->xpass != XP_COLS ? full_import_state(m, t) : state_convert(c, G, t, m->gb[g].ZA, true))) return rc;
+    }
+    return FB_OK;
+}
+
+extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort)
+{
+    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_set_vort: NULL");
+    NEED_SINGLE(m->c);
+    return state_in(m, nullptr, d_vort);
+}
+
+extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
+{
+    SLAB_READY(s);
+    if (!d_rows) return fail(FB_EINVAL, "fb_slab_set_vort_local: NULL");
+    return state_in(s->m, s, d_rows);
+}
+
+// ---- the record layer ----
+enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF };
+
+static int rec_alloc(cf **p, size_t elems)
+{
+    if (!*p && hipMalloc((void **)p, elems * sizeof(cf)) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+    return FB_OK;
+}
+
+// The record fields of `kind` (one, or three for REC_OW / REC_KEFF) of every column group through the backward x pass in
+// rec_work[g] ([3][nx][ncols_g], field 0 for one field), and on a slab of several ranks their exchange; *M: the row pass's view.
+static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
+{
+    fb_ctx *c = m->c;
+    const int nf = kind >= REC_OW ? 3 : 1;
+    const bool xchg = s && c->world > 1;
+    int rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        if ((rc = rec_alloc(&m->rec_work[g], 3 * n)) || (xchg && (rc = rec_alloc(&m->rec_send[g], 3 * n)))) return rc;
+        cf *z = m->rec_work[g];
+        // copy of vort_c in the 3-pass layout into field 0 (main.cpp:273), then the kind's fields from it in place
+        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
+        const SpecCoef k = make_coef(c);
+        const dim3 grid(grid_for(c, n)), blk(256);
+        switch (kind) {
+        case REC_VORT: break;
+        case REC_PSI: hipLaunchKernelGGL((k_psi_private<0>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
+        case REC_U: hipLaunchKernelGGL((k_psi_private<1>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
+        case REC_V: hipLaunchKernelGGL((k_psi_private<2>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
+        case REC_OW: hipLaunchKernelGGL(k_ow_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
+        case REC_KEFF: hipLaunchKernelGGL(k_keff_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
+        }
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_col_block<+1>(c, G, z, nf, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, nf, (long)n))) return rc;
+    }
+    if (!xchg) { *M = view_single(c, m->rec_work[0], (long)priv_elems(c)); return FB_OK; }
+    // [nf][nx][ncols] == [nf][dst][XL][ncols].  Three fields are regrouped into rec_send as [dst][3][XL][ncols] (each peer's blocks
+    // contiguous) and come back into rec_work as [src][3][XL][ncols]; one field leaves rec_work as it is and arrives in rec_send.
+    for (int g = 0; g < c->ngroups && nf > 1; ++g) {
+        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
+        for (int f = 0; f < 3 && blk; ++f)
+            HIPCHK(hipMemcpy2DAsync(m->rec_send[g] + f * blk, 3 * blk * sizeof(cf), m->rec_work[g] + f * c->world * blk, blk * sizeof(cf),
+                                    blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
+    }
+    cf *const *send = nf > 1 ? m->rec_send : m->rec_work, *const *recv = nf > 1 ? m->rec_work : m->rec_send;
+    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t blk = nf * (size_t)c->XL * c->grp[g].ncols;
+        if ((rc = slab_xchg(s, send[g], recv[g], blk, 0, blk))) return rc;
+    }
+    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    const cf *v[3] = {recv[0], recv[1], recv[2]};
+    *M = view_slab(c, v, nf);
+    return FB_OK;
+}
+
+// One record into the rows of this rank (one GPU: every row), normalised by 1/GRIDS: REC_VORT, REC_PSI, REC_U, REC_V into out0;
+// REC_OW: W into out0 and tau_fil into out1 (either may be NULL); REC_KEFF: zeta into out0 and |grad zeta|^2 into out1.
+static int record(fb_model *m, fb_slab *s, RecKind kind, float *out0, float *out1 = nullptr)
+{
+    fb_ctx *c = m->c;
+    RowArgs a = row_args_base(c);
+    int rc;
+    if ((rc = record_fields(m, s, kind, &a.M))) return rc;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    a.scale = kind == REC_U ? -g : g;                   // u = -dpsi/dy: normalise, then negate (SURVEY note N3): (x * g) * -1 == x * (-g) exactly
+    a.rout = out0; a.rin = out1;                        // (ROW_OW, ROW_KEFF: rin carries the second output, fb_kernels.h row_rout2)
+    if (kind == REC_OW) return launch_row<ROW_OW>(c, a);
+    if (kind == REC_KEFF) return launch_row<ROW_KEFF>(c, a);
+    return launch_row<ROW_INV>(c, a);
+}
+
+// the stage-0 record dumps of main.cpp:181-222 (any may be NULL): psi, u = -dpsi/dy, v = dpsi/dx
+static int record_diag(fb_model *m, fb_slab *s, float *d_psi, float *d_u, float *d_v)
+{
+    float *out[3] = {d_psi, d_u, d_v};
+    int rc;
+    for (int k = 0; k < 3; ++k)
+        if (out[k] && (rc = record(m, s, (RecKind)(REC_PSI + k), out[k]))) return rc;
+    return FB_OK;
+}
+
+// ---- effective eddy diffusivity: zeta and |grad zeta|^2 (REC_KEFF), then the table ----
+static int keff_check(const char *fn, const double *d_table, int nbins)
+{
+    if (!d_table) return fail(FB_EINVAL, std::string(fn) + ": NULL table");
+    if (nbins < 2 || nbins > 4096) return fail(FB_EINVAL, std::string(fn) + ": nbins outside [2, 4096]");
+    return FB_OK;
+}
+
+// zeta and |grad zeta|^2 of this rank's rows -> the table [nbins][9] (fb_keff.h), on every rank.  One reduction buffer, f64 parts first:
+//   sum_part [nwg][nbins], hist_send [world][nbins][2], hist_recv [world][nbins][2] (f64); cnt_part [nwg][nbins] (u32);
+//   mm_part [nmm][2], mm_send [world][2], mm_recv [world][2] (f32).
+// One GPU (s == NULL or world 1): the rank's results are written straight to the receive buffers.  A slab: two small all-gathers
+// through the transport's all-to-all (each rank sends the same block to every peer), behind the compute stream's work.
+static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table)
+{
+    fb_ctx *c = m->c;
+    const int world = c->world;
+    const size_t n = (size_t)c->XL * c->ny;
+    const bool v4 = (((size_t)zeta | (size_t)grad2) & 15) == 0;          // n is a multiple of 4 (ny >= 64)
+    const int nmm = grid_for(c, v4 ? n / 4 : n);
+    // histogram workgroups: at least 32 Ki points each; the partials stay within ~12 MiB at 4096 bins
+    const int cap = std::min(1024, std::max(256, (1 << 20) / nbins));
+    const int nwg = (int)std::max<size_t>(1, std::min<size_t>((size_t)cap, (n + 32767) / 32768));
+    const size_t nh = (size_t)nbins * 2;
+    const size_t o_hsend = (size_t)nwg * nbins * sizeof(double), o_hrecv = o_hsend + (world > 1 ? world * nh * sizeof(double) : 0);
+    const size_t o_cnt = o_hrecv + world * nh * sizeof(double), o_mm = o_cnt + (size_t)nwg * nbins * sizeof(unsigned);
+    const size_t o_mmsend = o_mm + 2 * (size_t)nmm * sizeof(float), o_mmrecv = o_mmsend + 2 * (size_t)world * sizeof(float);
+    const size_t bytes = o_mmrecv + 2 * (size_t)world * sizeof(float);
+    if (!m->keff_red || m->keff_red_cap < bytes) {
+        if (m->keff_red) { HIPCHK(hipFree(m->keff_red)); m->keff_red = nullptr; m->keff_red_cap = 0; }      // (hipFree waits for the device)
+        if (hipMalloc(&m->keff_red, bytes) != hipSuccess) { m->keff_red = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+        m->keff_red_cap = bytes;
+    }
+    char *base = (char *)m->keff_red;
+    double *sum_part = (double *)base, *hsend = (double *)(base + o_hsend), *hrecv = (double *)(base + o_hrecv);
+    unsigned *cnt_part = (unsigned *)(base + o_cnt);
+    float *mm_part = (float *)(base + o_mm), *mmsend = (float *)(base + o_mmsend), *mmrecv = (float *)(base + o_mmrecv);
+    const bool xchg = s && world > 1;
+    int rc;
+    auto gather = [&](const float *send, float *recv, size_t count) -> int {
+        int r;
+        if ((r = slab_after(s->comm, s->comp, s->ev_misc[0]))) return r;
+        if ((r = s->tp.alltoall(s->tp.self, send, recv, count, 0, count, s->comm))) return r;
+        return slab_after(s->comp, s->comm, s->ev_misc[1]);
+    };
+    if (v4) hipLaunchKernelGGL((k_keff_minmax<true>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
+    else hipLaunchKernelGGL((k_keff_minmax<false>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_keff_minmax_final, dim3(1), dim3(256), 0, c->stream, (const float *)mm_part, nmm, xchg ? mmsend : mmrecv, xchg ? world : 1);
+    HIPCHK(hipGetLastError());
+    if (xchg && (rc = gather(mmsend, mmrecv, 2))) return rc;
+    // dynamic LDS: 12 B per bin (histogram), 16 B per bin (table); the attribute once per kernel and device, for 4096 bins
+    if ((rc = set_max_lds(c, (const void *)k_keff_hist<true>, 4096 * 12)) || (rc = set_max_lds(c, (const void *)k_keff_hist<false>, 4096 * 12)) ||
+        (rc = set_max_lds(c, (const void *)k_keff_table, 4096 * 16)))
+        return rc;
+    if (v4) hipLaunchKernelGGL((k_keff_hist<true>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
+    else hipLaunchKernelGGL((k_keff_hist<false>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_keff_reduce, dim3((nbins + KEFF_RB - 1) / KEFF_RB), dim3(256), 0, c->stream, (const unsigned *)cnt_part, (const double *)sum_part, nwg, nbins,
+                       xchg ? hsend : hrecv, xchg ? world : 1, nh);
+    HIPCHK(hipGetLastError());
+    if (xchg && (rc = gather((const float *)hsend, (float *)hrecv, 2 * nh))) return rc;
+    hipLaunchKernelGGL(k_keff_table, dim3(1), dim3(256), (size_t)nbins * 16, c->stream, (const double *)hrecv, world, (const float *)mmrecv, nbins,
+                       (double)c->lx / c->nx, (double)c->ly / c->ny, (double)m->nu, d_table);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+// the row pass's outputs: the caller's, or the model's own buffers (keff_fields [2][XL][ny]) for those the caller does not want
+static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, float *zeta, float *grad2)
+{
+    const size_t n = (size_t)m->c->XL * m->c->ny;
+    if ((!zeta || !grad2) && !m->keff_fields && hipMalloc((void **)&m->keff_fields, 2 * n * sizeof(float)) != hipSuccess) {
+        m->keff_fields = nullptr;
+        return fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    if (!zeta) zeta = m->keff_fields;
+    if (!grad2) grad2 = m->keff_fields + n;
+    int rc;
+    if ((rc = record(m, s, REC_KEFF, zeta, grad2))) return rc;
+    return keff_finish(m, s, nbins, zeta, grad2, d_table);
+}
+
+// ---- the entry points ----
+extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
+{
+    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_get_vort: NULL");
+    NEED_SINGLE(m->c);
+    return record(m, nullptr, REC_VORT, d_vort);            // main.cpp:273-275
+}
+
+extern "C" int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v)
+{
+    if (!m) return fail(FB_EINVAL, "model NULL");
+    NEED_SINGLE(m->c);
+    return record_diag(m, nullptr, d_psi, d_u, d_v);
+}
+
+extern "C" int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau)
+{
+    if (!m || (!d_w && !d_tau)) return fail(FB_EINVAL, "fb_model_get_okubo_weiss: NULL");
+    NEED_SINGLE(m->c);
+    return record(m, nullptr, REC_OW, d_w, d_tau);
+}
+
+extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_get_eddy_diffusivity: NULL model");
+    int rc;
+    if ((rc = keff_check("fb_model_get_eddy_diffusivity", d_table, nbins))) return rc;
+    NEED_SINGLE(m->c);
+    return record_keff(m, nullptr, nbins, d_table, d_zeta, d_grad2);
+}
+
+extern "C" int fb_slab_get_vort_local(fb_slab *s, float *d_rows)
+{
+    SLAB_READY(s);
+    if (!d_rows) return fail(FB_EINVAL, "fb_slab_get_vort_local: NULL");
+    return record(s->m, s, REC_VORT, d_rows);
+}
+
+extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v)
+{
+    SLAB_READY(s);
+    return record_diag(s->m, s, d_psi, d_u, d_v);
+}
+
+extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
+{
+    SLAB_READY(s);
+    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
+    return record(s->m, s, REC_OW, d_w_rows, d_tau_rows);
+}
+
+// collective: the ranks' (min, max) and histograms are all-gathered through the transport (keff_finish), every rank gets the whole table
+extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows)
+{
+    SLAB_READY(s);
+    int rc;
+    if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
+    return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows);
+}

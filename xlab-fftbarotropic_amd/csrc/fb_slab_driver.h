@@ -246,153 +246,26 @@ static int slab_xchg(fb_slab *s, const cf *send, cf *recv, size_t stride, size_t
     ++s->step_ops;
     return s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * stride, 2 * offset, 2 * count, s->comm);
 }
-// every group's whole tendency-sized buffer through the transport (to_cols: t_send -> t_recv, rows -> columns; else the
-// reverse), behind the compute stream's work so far and ahead of what it does next
-static int slab_transpose_all(fb_slab *s, bool to_cols)
+// every group's whole t_send through the transport into t_recv (rows -> columns), behind the compute stream's work so far and
+// ahead of what it does next
+static int slab_transpose_all(fb_slab *s)
 {
     fb_ctx *c = s->c; fb_model *m = s->m;
     int rc;
     if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        cf *send = to_cols ? m->gb[g].t_send : m->gb[g].t_recv, *recv = to_cols ? m->gb[g].t_recv : m->gb[g].t_send;
-        if ((rc = slab_xchg(s, send, recv, blk, 0, blk))) return rc;
+        if ((rc = slab_xchg(s, m->gb[g].t_send, m->gb[g].t_recv, blk, 0, blk))) return rc;
     }
     return slab_after(s->comp, s->comm, s->ev_misc[1]);
 }
 #define SLAB_READY(s) do { if (!(s)) return fail(FB_EINVAL, "slab NULL"); if (!(s)->connected) return fail(FB_EINVAL, "slab model is not connected to a transport (fb_slab_connect_*)"); } while (0)
 
-// ---- state in / out ----
-extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
-{
-    SLAB_READY(s);
-    if (!d_rows) return fail(FB_EINVAL, "fb_slab_set_vort_local: NULL");
-    fb_ctx *c = s->c; fb_model *m = s->m;
-    int rc;
-    // readField + fftwf_execute(p_fwd_vort), main.cpp:143-144,256: y transform of the local rows -> transpose -> x transform of the local columns
-    RowArgs a = row_args_base(c);
-    a.rin = d_rows;
-    const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
-    a.T = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
-    if ((rc = launch_row<ROW_FWD>(c, a)) || (rc = slab_transpose_all(s, true))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        if ((rc = launch_col_strided<-1>(c, G, m->gb[g].t_recv, 1, 0)) || (rc = launch_col_block<-1>(c, G, m->gb[g].t_recv, 1, 0))) return rc;
-        if ((rc = state_convert(c, G, m->gb[g].t_recv, m->gb[g].ZA, true))) return rc;
-    }
-    m->primed = 0;
-    return FB_OK;
-}
-
+// ---- the source (state in and the record outputs: fb_record.h) ----
 extern "C" int fb_slab_set_source_local(fb_slab *s, const float *d_rows)
 {
     if (!s) return fail(FB_EINVAL, "slab NULL");
     return fb_model_set_source(s->m, d_rows);               // this rank's [XL][ny] rows of vort_src (main-shallow-water.cpp:304), NULL = zeros
-}
-
-// spectral field (a function of vort_c, selected by `what`) -> this rank's rows of the physical field * scale:
-// x transform of the local columns -> transpose in the reverse roles -> y transform of the local rows
-static int slab_c2r_of_state(fb_slab *s, int what, float scale, float *d_rows)
-{
-    fb_ctx *c = s->c; fb_model *m = s->m;
-    int rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        cf *w = m->gb[g].t_recv;
-        if ((rc = state_convert(c, G, m->gb[g].ZA, w, false))) return rc;           // copy of vort_c (main.cpp:273)
-        const size_t total = grp_elems(c, G);
-        const dim3 grid(grid_for(c, total)), blk(256);
-        if (what == 1) hipLaunchKernelGGL((k_psi_private<0>), grid, blk, 0, c->stream, make_coef(c), w, G.ncols, c->N1, c->N2, G.ky0);
-        else if (what == 2) hipLaunchKernelGGL((k_psi_private<1>), grid, blk, 0, c->stream, make_coef(c), w, G.ncols, c->N1, c->N2, G.ky0);
-        else if (what == 3) hipLaunchKernelGGL((k_psi_private<2>), grid, blk, 0, c->stream, make_coef(c), w, G.ncols, c->N1, c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
-        if ((rc = launch_col_block<+1>(c, G, w, 1, 0)) || (rc = launch_col_strided<+1>(c, G, w, 1, 0))) return rc;   // natural [x][ncols] == [dst][XL][ncols]
-    }
-    if ((rc = slab_transpose_all(s, false))) return rc;
-    RowArgs a = row_args_base(c);
-    const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
-    a.M = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
-    a.rout = d_rows; a.scale = scale;
-    return launch_row<ROW_INV>(c, a);
-}
-
-extern "C" int fb_slab_get_vort_local(fb_slab *s, float *d_rows)
-{
-    SLAB_READY(s);
-    if (!d_rows) return fail(FB_EINVAL, "fb_slab_get_vort_local: NULL");
-    return slab_c2r_of_state(s, 0, 1.0f / (float)((size_t)s->c->nx * s->c->ny), d_rows);      // record path, main.cpp:273-281
-}
-
-// the stage-0 record dumps of main.cpp:181-222 on this rank's rows (any may be NULL): psi, u = -dpsi/dy, v = dpsi/dx
-extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v)
-{
-    SLAB_READY(s);
-    const float g = 1.0f / (float)((size_t)s->c->nx * s->c->ny);
-    int rc;
-    if (d_psi && (rc = slab_c2r_of_state(s, 1, g, d_psi))) return rc;
-    if (d_u && (rc = slab_c2r_of_state(s, 2, -g, d_u))) return rc;                  // normalise, then negate (SURVEY note N3): (x * g) * -1 == x * (-g) exactly
-    if (d_v && (rc = slab_c2r_of_state(s, 3, g, d_v))) return rc;
-    return FB_OK;
-}
-
-// The three record-path fields of this rank's rows (keff: zeta, zeta_x, zeta_y; else the second derivatives of psi): per column
-// group through the backward x pass, then ONE all-to-all of all three in the reverse roles; *M: the row pass's view of them.  The
-// record buffers are the model's own (ow_work, ow_send), never the step's.
-static int slab_rec3_fields(fb_slab *s, bool keff, RowView *M)
-{
-    fb_ctx *c = s->c; fb_model *m = s->m;
-    int rc;
-    for (int g = 0; g < c->ngroups; ++g)
-        if ((rc = ow_group_cols(m, g, keff))) return rc;
-    if (c->world == 1) { *M = view_single(c, m->ow_work[0], (long)priv_elems(c)); return FB_OK; }
-    // [3][nx][ncols] == [3][dst][XL][ncols] -> [dst][3][XL][ncols]: each peer's three blocks contiguous
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        if (blk == 0) continue;
-        if (!m->ow_send[g] && hipMalloc((void **)&m->ow_send[g], 3 * grp_elems(c, c->grp[g]) * sizeof(cf)) != hipSuccess) {
-            m->ow_send[g] = nullptr;
-            return fail(FB_ENOMEM, "record-path allocation failed");
-        }
-        for (int f = 0; f < 3; ++f)
-            HIPCHK(hipMemcpy2DAsync(m->ow_send[g] + f * blk, 3 * blk * sizeof(cf), m->ow_work[g] + f * c->world * blk, blk * sizeof(cf),
-                                    blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
-    }
-    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t blk = 3 * (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = slab_xchg(s, m->ow_send[g], m->ow_work[g], blk, 0, blk))) return rc;
-    }
-    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    const cf *w[3] = {m->ow_work[0], m->ow_work[1], m->ow_work[2]};
-    *M = view_slab(c, w, 3);
-    return FB_OK;
-}
-
-// Okubo-Weiss parameter and filamentation time on this rank's rows (either may be NULL): the three second derivatives of psi
-// (slab_rec3_fields), the row pass with the Okubo-Weiss epilogue.
-extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
-{
-    SLAB_READY(s);
-    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
-    RowView M;
-    int rc;
-    if ((rc = slab_rec3_fields(s, false, &M))) return rc;
-    return ow_rows(s->c, M, d_w_rows, d_tau_rows);
-}
-
-// Effective eddy diffusivity table (fb_model_get_eddy_diffusivity), collective: zeta, zeta_x, zeta_y (slab_rec3_fields), the row
-// pass with the ROW_KEFF epilogue into this rank's rows of zeta and |grad zeta|^2, then the contour-area histogram of those rows
-// with the ranks' (min, max) and histograms all-gathered through the transport (keff_finish): every rank gets the whole table.
-extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows)
-{
-    SLAB_READY(s);
-    int rc;
-    if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
-    if ((rc = keff_outputs(s->m, d_zeta_rows, d_grad2_rows))) return rc;
-    RowView M;
-    if ((rc = slab_rec3_fields(s, true, &M))) return rc;
-    if ((rc = keff_rows(s->c, M, d_zeta_rows, d_grad2_rows))) return rc;
-    return keff_finish(s->m, s, nbins, d_zeta_rows, d_grad2_rows, d_table);
 }
 
 // ---- the step ----

@@ -1004,14 +1004,12 @@ struct fb_model {
     const float *graph_src; hipStream_t graph_stream;
     float *src;                      // vort_src (this rank's rows) or NULL (== zeros)
     int *src_nz;                     // per row of src: 1 = holds a non-zero value (k_src_row_flags)
-    cf *nat[3];                      // natural-layout temporaries for the record path (lazy)
-    // the Okubo-Weiss record path (lazy, never read by the step): per column group, the three fields psi_xx, psi_yy, psi_xy
-    // [3][nx][ncols] in ow_work through the x pass; multi-GPU: then copied to ow_send as [dst][3][XL][ncols] and exchanged back into
-    // ow_work as [src][3][XL][ncols], the layout of view_slab
-    cf *ow_work[3], *ow_send[3];
-    // the eddy-diffusivity record path (lazy, never read by the step) shares ow_work / ow_send for its three spectral fields, and
-    // adds zeta and |grad zeta|^2 ([2][XL][ny], for a caller who passes no outputs of their own) and the reduction buffers (grown
-    // to the largest request)
+    // the record workspace (fb_record.h; lazy, never read by the step): per column group, a record's one or three fields
+    // [3][nx][ncols] in rec_work through the x pass; multi-GPU: exchanged into rec_send (one field) or regrouped into rec_send as
+    // [dst][3][XL][ncols] and exchanged back into rec_work as [src][3][XL][ncols] (three), the layout of view_slab
+    cf *rec_work[3], *rec_send[3];
+    // the eddy-diffusivity record adds zeta and |grad zeta|^2 ([2][XL][ny], for a caller who passes no outputs of their own) and
+    // the reduction buffers (grown to the largest request)
     float *keff_fields;
     void *keff_red; size_t keff_red_cap;
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
@@ -1068,9 +1066,8 @@ extern "C" int fb_model_destroy(fb_model *m)
     model_drop_graph(m);
     if (m->src) hipFree(m->src);
     if (m->src_nz) hipFree(m->src_nz);
-    for (auto p : m->nat) if (p) hipFree(p);
-    for (auto p : m->ow_work) if (p) hipFree(p);
-    for (auto p : m->ow_send) if (p) hipFree(p);
+    for (auto p : m->rec_work) if (p) hipFree(p);
+    for (auto p : m->rec_send) if (p) hipFree(p);
     if (m->keff_fields) hipFree(m->keff_fields);
     if (m->keff_red) hipFree(m->keff_red);
     delete m;
@@ -1088,25 +1085,6 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;
     return FB_OK;
-}
-
-static MidArgs mid_args(fb_model *m, int g, int stage);
-static int full_import_state(fb_model *m, cf *spec3);
-static int full_export_state(fb_model *m, cf *dst);
-
-extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort)
-{
-    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_set_vort: NULL");
-    fb_ctx *c = m->c;
-    NEED_SINGLE(c);
-    m->warmed = false;                                      // the next fb_model_step starts with an eager (priming) step
-    cf *dst = m->gb[0].ZB;                                  // 3-pass row layout in ZB (stage scratch), then into ZA's layout
-    HIPCHK(hipMemsetAsync(dst, 0, priv_elems(c) * sizeof(cf), c->stream));
-    m->primed = 0;
-    int rc = r2c_private(c, d_vort, dst);                   // main.cpp:256
-    if (rc) return rc;
-    if (m->xpass != XP_COLS) return full_import_state(m, dst);
-    return state_convert(c, c->grp[0], dst, m->gb[0].ZA, true);
 }
 
 extern "C" int fb_model_set_source(fb_model *m, const float *d_src)
@@ -1380,185 +1358,7 @@ extern "C" int fb_model_set_spectrum(fb_model *m, const float *d_spec)
     return state_convert(m->c, m->c->grp[0], m->gb[0].ZB, m->gb[0].ZA, true);
 }
 
-extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
-{
-    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_get_vort: NULL");
-    fb_ctx *c = m->c;
-    NEED_SINGLE(c);
-    int rc;
-    if ((rc = ensure_scratch(c))) return rc;
-    // copy of vort_c (main.cpp:273), c2r, normalise (main.cpp:275)
-    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, c->d_scratch))) return rc; }
-    else if ((rc = state_convert(c, c->grp[0], m->gb[0].ZA, c->d_scratch, false))) return rc;
-    return c2r_private(c, c->d_scratch, d_vort, 1.0f / (float)((size_t)c->nx * c->ny));
-}
-
-extern "C" int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v)
-{
-    if (!m) return fail(FB_EINVAL, "model NULL");
-    fb_ctx *c = m->c;
-    NEED_SINGLE(c);
-    const size_t n = (size_t)c->nx * c->hy * sizeof(cf);
-    for (auto &p : m->nat)
-        if (!p && hipMalloc((void **)&p, n) != hipSuccess) return fail(FB_ENOMEM, "record-path allocation failed");
-    int rc;
-    float *vc = (float *)m->nat[0], *psi = (float *)m->nat[1], *tmp = (float *)m->nat[2];
-    if ((rc = fb_model_get_spectrum(m, vc))) return rc;
-    if ((rc = fb_invert_laplacian(c, vc, psi))) return rc;                       // main.cpp:179
-    if (d_psi && (rc = fb_c2r(c, psi, d_psi, 1))) return rc;                     // :185-188
-    if (d_u) {
-        if ((rc = fb_grady(c, psi, tmp)) || (rc = fb_c2r(c, tmp, d_u, 1)) || (rc = fb_negate(c, d_u))) return rc;   // :198-201
-    }
-    if (d_v) {
-        if ((rc = fb_gradx(c, psi, tmp)) || (rc = fb_c2r(c, tmp, d_v, 1))) return rc;                                 // :212-214
-    }
-    return FB_OK;
-}
-
-// ---- Okubo-Weiss record path (fb_model_get_okubo_weiss, fb_slab_get_okubo_weiss_local) ----
-// group g's three second-derivative fields of psi (keff: zeta, zeta_x, zeta_y, for the eddy diffusivity), [3][nx][ncols] in the
-// model's own record buffer, through the backward x pass
-static int ow_group_cols(fb_model *m, int g, bool keff = false)
-{
-    fb_ctx *c = m->c;
-    const ColGroup &G = c->grp[g];
-    const size_t n = grp_elems(c, G);
-    if (n == 0) return FB_OK;
-    if (!m->ow_work[g] && hipMalloc((void **)&m->ow_work[g], 3 * n * sizeof(cf)) != hipSuccess) { m->ow_work[g] = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
-    cf *z = m->ow_work[g];
-    int rc;
-    // copy of vort_c in the 3-pass layout into field 0, then the three fields from it in place
-    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, z))) return rc; }
-    else if ((rc = state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
-    if (keff) hipLaunchKernelGGL(k_keff_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, make_coef(c), (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-    else hipLaunchKernelGGL(k_ow_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, make_coef(c), (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-    HIPCHK(hipGetLastError());
-    if ((rc = launch_col_block<+1>(c, G, z, 3, (long)n))) return rc;
-    return launch_col_strided<+1>(c, G, z, 3, (long)n);
-}
-// the row pass with the Okubo-Weiss epilogue over the three fields in view M
-static int ow_rows(fb_ctx *c, const RowView &M, float *d_w, float *d_tau)
-{
-    RowArgs a = row_args_base(c);
-    a.M = M; a.rout = d_w; a.rin = d_tau;             // (ROW_OW: rin carries the second output, fb_kernels.h row_rout2)
-    a.scale = 1.0f / (float)((size_t)c->nx * c->ny);
-    return launch_row<ROW_OW>(c, a);
-}
-
-extern "C" int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau)
-{
-    if (!m || (!d_w && !d_tau)) return fail(FB_EINVAL, "fb_model_get_okubo_weiss: NULL");
-    fb_ctx *c = m->c;
-    NEED_SINGLE(c);
-    int rc;
-    if ((rc = ow_group_cols(m, 0))) return rc;
-    return ow_rows(c, view_single(c, m->ow_work[0], (long)priv_elems(c)), d_w, d_tau);
-}
-
-// ---- effective eddy diffusivity record path (fb_model_get_eddy_diffusivity, fb_slab_get_eddy_diffusivity) ----
-// the row pass with the ROW_KEFF epilogue over the three fields zeta, zeta_x, zeta_y in view M: zeta and |grad zeta|^2, normalised
-static int keff_rows(fb_ctx *c, const RowView &M, float *d_zeta, float *d_grad2)
-{
-    RowArgs a = row_args_base(c);
-    a.M = M; a.rout = d_zeta; a.rin = d_grad2;        // (ROW_KEFF: rin carries the second output, fb_kernels.h row_rout2)
-    a.scale = 1.0f / (float)((size_t)c->nx * c->ny);
-    return launch_row<ROW_KEFF>(c, a);
-}
-// outputs of the row pass: the caller's, or the model's own record buffers
-static int keff_outputs(fb_model *m, float *&zeta, float *&grad2)
-{
-    const size_t n = (size_t)m->c->XL * m->c->ny;
-    if (zeta && grad2) return FB_OK;
-    if (!m->keff_fields && hipMalloc((void **)&m->keff_fields, 2 * n * sizeof(float)) != hipSuccess) {
-        m->keff_fields = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
-    }
-    if (!zeta) zeta = m->keff_fields;
-    if (!grad2) grad2 = m->keff_fields + n;
-    return FB_OK;
-}
-static int keff_check(const char *fn, const double *d_table, int nbins)
-{
-    if (!d_table) return fail(FB_EINVAL, std::string(fn) + ": NULL table");
-    if (nbins < 2 || nbins > 4096) return fail(FB_EINVAL, std::string(fn) + ": nbins outside [2, 4096]");
-    return FB_OK;
-}
-struct fb_slab;
-static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table);
-
-extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_get_eddy_diffusivity: NULL model");
-    int rc;
-    if ((rc = keff_check("fb_model_get_eddy_diffusivity", d_table, nbins))) return rc;
-    fb_ctx *c = m->c;
-    NEED_SINGLE(c);
-    if ((rc = keff_outputs(m, d_zeta, d_grad2))) return rc;
-    if ((rc = ow_group_cols(m, 0, true))) return rc;
-    if ((rc = keff_rows(c, view_single(c, m->ow_work[0], (long)priv_elems(c)), d_zeta, d_grad2))) return rc;
-    return keff_finish(m, nullptr, nbins, d_zeta, d_grad2, d_table);
-}
-
 #include "fb_slab_driver.h"
-
-// zeta and |grad zeta|^2 of this rank's rows -> the table [nbins][9] (fb_keff.h), on every rank.  One reduction buffer, f64 parts first:
-//   sum_part [nwg][nbins], hist_send [world][nbins][2], hist_recv [world][nbins][2] (f64); cnt_part [nwg][nbins] (u32);
-//   mm_part [nmm][2], mm_send [world][2], mm_recv [world][2] (f32).
-// One GPU (s == NULL or world 1): the rank's results are written straight to the receive buffers.  A slab: two small all-gathers
-// through the transport's all-to-all (each rank sends the same block to every peer), behind the compute stream's work.
-static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table)
-{
-    fb_ctx *c = m->c;
-    const int world = c->world;
-    const size_t n = (size_t)c->XL * c->ny;
-    const bool v4 = (((size_t)zeta | (size_t)grad2) & 15) == 0;          // n is a multiple of 4 (ny >= 64)
-    const int nmm = grid_for(c, v4 ? n / 4 : n);
-    // histogram workgroups: at least 32 Ki points each; the partials stay within ~12 MiB at 4096 bins
-    const int cap = std::min(1024, std::max(256, (1 << 20) / nbins));
-    const int nwg = (int)std::max<size_t>(1, std::min<size_t>((size_t)cap, (n + 32767) / 32768));
-    const size_t nh = (size_t)nbins * 2;
-    const size_t o_hsend = (size_t)nwg * nbins * sizeof(double), o_hrecv = o_hsend + (world > 1 ? world * nh * sizeof(double) : 0);
-    const size_t o_cnt = o_hrecv + world * nh * sizeof(double), o_mm = o_cnt + (size_t)nwg * nbins * sizeof(unsigned);
-    const size_t o_mmsend = o_mm + 2 * (size_t)nmm * sizeof(float), o_mmrecv = o_mmsend + 2 * (size_t)world * sizeof(float);
-    const size_t bytes = o_mmrecv + 2 * (size_t)world * sizeof(float);
-    if (!m->keff_red || m->keff_red_cap < bytes) {
-        if (m->keff_red) { HIPCHK(hipFree(m->keff_red)); m->keff_red = nullptr; m->keff_red_cap = 0; }      // (hipFree waits for the device)
-        if (hipMalloc(&m->keff_red, bytes) != hipSuccess) { m->keff_red = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
-        m->keff_red_cap = bytes;
-    }
-    char *base = (char *)m->keff_red;
-    double *sum_part = (double *)base, *hsend = (double *)(base + o_hsend), *hrecv = (double *)(base + o_hrecv);
-    unsigned *cnt_part = (unsigned *)(base + o_cnt);
-    float *mm_part = (float *)(base + o_mm), *mmsend = (float *)(base + o_mmsend), *mmrecv = (float *)(base + o_mmrecv);
-    const bool xchg = s && world > 1;
-    int rc;
-    auto gather = [&](const float *send, float *recv, size_t count) -> int {
-        int r;
-        if ((r = slab_after(s->comm, s->comp, s->ev_misc[0]))) return r;
-        if ((r = s->tp.alltoall(s->tp.self, send, recv, count, 0, count, s->comm))) return r;
-        return slab_after(s->comp, s->comm, s->ev_misc[1]);
-    };
-    if (v4) hipLaunchKernelGGL((k_keff_minmax<true>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
-    else hipLaunchKernelGGL((k_keff_minmax<false>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_keff_minmax_final, dim3(1), dim3(256), 0, c->stream, (const float *)mm_part, nmm, xchg ? mmsend : mmrecv, xchg ? world : 1);
-    HIPCHK(hipGetLastError());
-    if (xchg && (rc = gather(mmsend, mmrecv, 2))) return rc;
-    // dynamic LDS: 12 B per bin (histogram), 16 B per bin (table); the attribute once per kernel and device, for 4096 bins
-    if ((rc = set_max_lds(c, (const void *)k_keff_hist<true>, 4096 * 12)) || (rc = set_max_lds(c, (const void *)k_keff_hist<false>, 4096 * 12)) ||
-        (rc = set_max_lds(c, (const void *)k_keff_table, 4096 * 16)))
-        return rc;
-    if (v4) hipLaunchKernelGGL((k_keff_hist<true>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
-    else hipLaunchKernelGGL((k_keff_hist<false>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_keff_reduce, dim3((nbins + KEFF_RB - 1) / KEFF_RB), dim3(256), 0, c->stream, (const unsigned *)cnt_part, (const double *)sum_part, nwg, nbins,
-                       xchg ? hsend : hrecv, xchg ? world : 1, nh);
-    HIPCHK(hipGetLastError());
-    if (xchg && (rc = gather((const float *)hsend, (float *)hrecv, 2 * nh))) return rc;
-    hipLaunchKernelGGL(k_keff_table, dim3(1), dim3(256), (size_t)nbins * 16, c->stream, (const double *)hrecv, world, (const float *)mmrecv, nbins,
-                       (double)c->lx / c->nx, (double)c->ly / c->ny, (double)m->nu, d_table);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
+#include "fb_record.h"
 
 // field I/O (fb_write_field / fb_read_field, writeField / readField): fb_fieldio.cpp
