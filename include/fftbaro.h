@@ -178,6 +178,18 @@ int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau);
  * for a NULL model or table (checked before any HIP call).  Enqueued on the context stream, no synchronisation; leaves the state
  * and a captured step untouched. */
 int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2);
+/* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
+ * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
+ * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
+ *   pxx_c, pyy_c, pxy_c = dealiase(gradx(gradx psi_c)), dealiase(grady(grady psi_c)), dealiase(gradx(grady psi_c))      (:139-150)
+ *   curv = (c2r(pxx_c) g) (c2r(pyy_c) g) - (c2r(pxy_c) g)^2, the two products rounded, then the difference               (:153-159)
+ *   q_c = rho * (f * (laplacian_coe psi_c) + (L_c + L_c)),  L_c = r2c(curv)                                              (:161-169)
+ *   p = c2r(invertLaplacian(q_c)) g                                                                                      (:171-172)
+ *   p -= p[ref_x + nx * ref_y]: the reference's flat index into the [nx][ny] field, kept as it is (:182-185; -x, -y of :71-79);
+ *   the stored value at that index is exactly 0.  rho, f: configuration.hpp:10-11 (1.0, 1e-5).
+ * FB_EINVAL (before any HIP call) for a NULL model or output, a negative ref_x / ref_y or a flat index >= nx * ny.  Enqueued on the
+ * context stream, no synchronisation, no host round trip; uses the record buffers and leaves the state and a captured step untouched. */
+int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -237,6 +249,9 @@ int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows
  * the full table, on every rank (the ranks' ranges and histograms are all-gathered through the transport, summed in rank order);
  * collective: every rank calls it */
 int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows);
+/* fb_model_get_pressure on this rank's rows [XL][ny], bit for bit (the reference point is a point of the whole domain: its owner's
+ * value reaches every rank through the transport); collective: every rank calls it */
+int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int ref_y, float *d_pres_rows);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

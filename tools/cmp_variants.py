@@ -2,7 +2,8 @@
 """Bitwise comparison of two library builds on a noisy 4096^2 (or given) state:
 tools/cmp_variants.py <alt.so|-> [n=4096] [steps=3] [--records] [KEY=VAL ...]
 Runs each build in its own process (FFTBARO_LIB; "-" = the in-tree library both times) and compares vort / spectrum bit for bit; with
---records also diag (psi, u, v), okubo_weiss (W, tau) and eddy_diffusivity (zeta, grad2 and the table), where columns 5-8 of the table
+--records also diag (psi, u, v), okubo_weiss (W, tau), pressure (pres, reference point (3, 5); only when both builds export
+fb_model_get_pressure) and eddy_diffusivity (zeta, grad2 and the table), where columns 5-8 of the table
 are f64 sums in the order of LDS atomics and are compared to rounding (relative 1e-9).  Whole fields are compared by sha256, so 16384^2
 fits.  KEY=VAL pairs are set in the environment of the second run only (run-time switches)."""
 import os, subprocess, sys, tempfile
@@ -24,6 +25,8 @@ if records:
     out["W"], out["tau"] = m.okubo_weiss()
     table, out["zeta"], out["grad2"] = m.eddy_diffusivity(fields=True)
     res["table"] = table.cpu().numpy()
+    if hasattr(X.lib(), "fb_model_get_pressure"):
+        out["pres"] = m.pressure(ref=(3, 5))
 for k, t in out.items():
     a = np.ascontiguousarray(t.cpu().numpy())
     res[k] = np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype=np.uint8)
@@ -46,7 +49,10 @@ with tempfile.TemporaryDirectory() as d:
         o = os.path.join(d, tag + ".npz")
         subprocess.check_call([sys.executable, "-c", CHILD, str(n), str(steps), o, "1" if records else "0"], env=e)
         outs.append(np.load(o))
-    for k in ("vort", "spec") + (("psi", "u", "v", "W", "tau", "zeta", "grad2") if records else ()):
+    has_pres = records and all("pres" in o.files for o in outs)
+    if records and not has_pres:
+        print("pres not compared: a build does not export fb_model_get_pressure")
+    for k in ("vort", "spec") + (("psi", "u", "v", "W", "tau", "zeta", "grad2") if records else ()) + (("pres",) if has_pres else ()):
         same = np.array_equal(outs[0][k], outs[1][k])
         a, b = outs[0][k + "_sample"], outs[1][k + "_sample"]
         print(k, "bitwise equal" if same else "DIFFERENT: max abs diff on a sample %g" % np.abs(a - b).max())

@@ -103,6 +103,10 @@ def lib():
     L.fb_slab_get_diag_local.argtypes = [vp, fp, fp, fp]
     L.fb_slab_get_okubo_weiss_local.argtypes = [vp, fp, fp]
     L.fb_slab_get_eddy_diffusivity.argtypes = [vp, ip, vp, fp, fp]
+    # (an older build chosen through FFTBARO_LIB for an A/B run lacks the pressure record: calling it there is an AttributeError)
+    for n in ("fb_model_get_pressure", "fb_slab_get_pressure_local"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, C.c_float, C.c_float, ip, ip, fp]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -123,11 +127,11 @@ EXPORTS = [
     "fb_gradx", "fb_grady", "fb_laplacian", "fb_invert_laplacian", "fb_dealiase", "fb_r2c", "fb_c2r",
     "fb_backward_normalize", "fb_negate", "fb_jacobian", "fb_spec_axpy", "fb_spec_evolve", "fb_spec_rk4_combine",
     "fb_model_create", "fb_model_destroy", "fb_model_set_vort", "fb_model_set_source", "fb_model_step",
-    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
+    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_pressure", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
     "fb_model_time_steps", "fb_model_profile_steps", "fb_write_field", "fb_read_field", "fb_make_field", "fb_make_source_kuo2004",
     "fb_create_slab", "fb_slab_unique_id", "fb_slab_create", "fb_slab_destroy", "fb_slab_connect_rccl", "fb_local_hub_create",
     "fb_local_hub_destroy", "fb_slab_connect_local", "fb_slab_connect_callback", "fb_slab_set_vort_local", "fb_slab_set_source_local",
-    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
+    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
@@ -344,6 +348,13 @@ class Model:
         zeta, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
         check(lib().fb_model_get_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(zeta) if fields else None, _ptr(g) if fields else None))
         return (table, zeta, g) if fields else table
+
+    def pressure(self, rho=1.0, f=1e-5, ref=(0, 0)):
+        """The nonlinear-balance pressure of the current state (invert_pres.cpp:135-185), an [nx, ny] tensor, minus its value at the
+        reference point ref = (ref_x, ref_y): the element ref_x + nx * ref_y of the flattened field, as the reference indexes it."""
+        out = self.fop.empty_real()
+        check(lib().fb_model_get_pressure(self._h, rho, f, int(ref[0]), int(ref[1]), _ptr(out)))
+        return out
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

@@ -158,6 +158,82 @@ __global__ void __launch_bounds__(256) k_ow_spec(SpecCoef c, const cf *zin, cf *
     }
 }
 
+// record path of the balanced pressure (invert_pres.cpp:135-185 with psi_c = invertLaplacian(vort_c)): the second derivatives of
+// psi_c as k_ow_spec forms them, each then multiplied by the dealiasing mask (invert_pres.cpp:139-150: chained first derivatives,
+// then fop.dealiase), into the fields 0, 1, 2 of `z`: psi_xx, psi_yy, psi_xy; pad columns zero.  zin may be field 0 of z (each
+// element is read before it is written, by the same thread).  Same float32 forms as k_spec_op (no contraction).
+__global__ void __launch_bounds__(256) k_pres_spec(SpecCoef c, const cf *zin, cf *z, long fstride, int P, int N1, int N2, int ky0)
+{
+#pragma clang fp contract(off)
+    const size_t total = (size_t)c.nx * P;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)(idx / P), col = (int)(idx - (size_t)row * P);
+        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d, j = ky0 + col;
+        cf a = zin[idx], xx = cf_make(0.f, 0.f), yy = xx, xy = xx;
+        if (j < c.hy) {
+            const float li = (i == 0 && j == 0) ? 1.0f : coef_lap(c, i, j);           // fftwfop.cpp:42-43,112-117
+            a = cf_make(a.x / li, a.y / li);
+            const float kx = c.gx[i], ky = c.gy[j], mk = coef_mask(c, i, j);
+            const cf ax = cf_make(-a.y * kx, a.x * kx), ay = cf_make(-a.y * ky, a.x * ky);   // fftwfop.cpp:87-103
+            xx = cf_make(-ax.y * kx, ax.x * kx);
+            yy = cf_make(-ay.y * ky, ay.x * ky);
+            xy = cf_make(-ay.y * kx, ay.x * kx);
+            xx = cf_make(xx.x * mk, xx.y * mk);                                       // fftwfop.cpp:119-124
+            yy = cf_make(yy.x * mk, yy.y * mk);
+            xy = cf_make(xy.x * mk, xy.y * mk);
+        }
+        z[idx] = xx; z[idx + fstride] = yy; z[idx + 2 * fstride] = xy;
+    }
+}
+
+// record path of the balanced pressure, the solve (invert_pres.cpp:164-171): `l` holds L_c = r2c(psi_xx psi_yy - psi_xy^2) and `zin`
+// the state vort_c of the same column group (both in the 3-pass private layout); in place on `l`
+//   t = laplacian_coe * psi_c,  a = f * t,  b = L + L,  q = rho * (a + b),  l = q / laplacian_coe_inverse
+// (the float32 bits of fb_laplacian, fb_spec_evolve(L, L, 1), fb_spec_axpy(., t, f), fb_invert_laplacian); pad columns zero.
+__global__ void __launch_bounds__(256) k_pres_solve(SpecCoef c, const cf *__restrict__ zin, cf *__restrict__ l, float rho, float f, int P, int N1, int N2,
+                                                    int ky0)
+{
+#pragma clang fp contract(off)
+    const size_t total = (size_t)c.nx * P;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)(idx / P), col = (int)(idx - (size_t)row * P);
+        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d, j = ky0 + col;
+        if (j >= c.hy) { l[idx] = cf_make(0.f, 0.f); continue; }                      // pad columns
+        const float lap = coef_lap(c, i, j), li = (i == 0 && j == 0) ? 1.0f : lap;   // fftwfop.cpp:42-45
+        const cf v = zin[idx], L = l[idx];
+        const cf psi = cf_make(v.x / li, v.y / li);                                   // fftwfop.cpp:112-117
+        const cf t = cf_make(psi.x * lap, psi.y * lap);                               // fftwfop.cpp:105-110
+        const float ax = t.x * f, ay = t.y * f, bx = L.x + L.x, by = L.y + L.y;
+        const float qx = rho * (bx + ax), qy = rho * (by + ay);
+        l[idx] = cf_make(qx / li, qy / li);
+    }
+}
+
+// reference point of the pressure record (invert_pres.cpp:182-185).  k_pres_ref: the owner of the point copies p[at] into each of
+// the `world` one-float blocks of `dst` (one per peer of the all-to-all that follows; one GPU: the block the subtraction reads);
+// a rank that does not own the point passes at < 0 and sends zeros.  k_pres_sub: p[i] -= *ref over this rank's rows.
+__global__ void k_pres_ref(const float *__restrict__ p, long at, float *__restrict__ dst, int world)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < world) dst[i] = at >= 0 ? p[at] : 0.0f;
+}
+template <bool V4>
+__global__ void __launch_bounds__(256) k_pres_sub(float *__restrict__ p, size_t n, const float *__restrict__ ref)
+{
+    const float r = *ref;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    if (V4) {
+        float4 *p4 = reinterpret_cast<float4 *>(p);
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += stride) {
+            float4 v = p4[i];
+            v.x -= r; v.y -= r; v.z -= r; v.w -= r;
+            p4[i] = v;
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] -= r;
+    }
+}
+
 // State arrays (vort_c0, stage state, RK accumulator) are touched by k_col_mid only, so they live
 // in that kernel's register order ("tile-major"): tile (cb, ct) = N2 rows x 16 columns is contiguous,
 //   complex index = ((tile*(NLB/2) + e/2)*64 + lane)*2 + (e & 1),   e = 8 s + q  <->  row d = h + 4 s + R1 q,
@@ -181,7 +257,16 @@ __global__ void __launch_bounds__(256) k_state_relayout(const cf *__restrict__ i
 // -------------------------------------------------------------------------------------------
 // row pass (y direction), T = N/16 threads per transform, G = max(1, 256/T) row pairs per WG
 // -------------------------------------------------------------------------------------------
-enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2, ROW_OW = 3, ROW_KEFF = 4 };
+enum { ROW_FUSED = 0, ROW_INV = 1, ROW_FWD = 2, ROW_OW = 3, ROW_KEFF = 4, ROW_PRES = 5 };
+
+// ROW_PRES product at one point: psi_xx psi_yy - psi_xy^2 from the normalised second derivatives of psi (invert_pres.cpp:159; the
+// two products rounded separately, then the difference: no contraction, as ow_point)
+FB_DEV float pres_curv_point(float pxx, float pyy, float pxy)
+{
+#pragma clang fp contract(off)
+    const float a = pxx * pyy, b = pxy * pxy;
+    return a - b;
+}
 
 // ROW_OW epilogue at one point: Okubo-Weiss parameter W = S1^2 + S2^2 - zeta^2 = 4 (psi_xy^2 - psi_xx psi_yy) and filamentation time
 // tau_fil = 2 / sqrt(W) where W > 0, +inf elsewhere (Rozoff et al. 2006), from the normalised second derivatives of psi
@@ -216,8 +301,8 @@ struct RowView {
     unsigned magA, magF;
 };
 struct RowArgs {
-    RowView M;              // mixed-space inputs                                   (FUSED: 4 fields, INV: 1)
-    RowView T;              // mixed-space output                                   (FUSED, FWD)
+    RowView M;              // mixed-space inputs                                   (FUSED: 4 fields, INV: 1, OW / KEFF / PRES: 3)
+    RowView T;              // mixed-space output                                   (FUSED, FWD, PRES)
     int t_frozen;           // multi-GPU: 1 = also store the frozen columns of T (FWD: the state); FUSED: 0, their tendency is masked
     const float *src;       // vort_src (real [x][y]) or NULL                       (FUSED)
     const int *src_nz;      // per local row: 1 = the row of vort_src holds a non-zero value; rows of zeros are not read (x + 0 == x)
@@ -295,7 +380,7 @@ template <bool SLAB> FB_DEV bool row_keep(const RowView &v, int t_frozen, int k)
 // Hermitian-extend two half-spectrum rows A,B into Z = A_ext + i B_ext, straight into the first
 // backward stage's registers (SURVEY note N2: imaginary parts at k=0 and k=N/2 are ignored).
 // Thread t owns positions t + i*T: for i < 8 that is k itself, for i >= 8 the mirror of N - pos.
-// TAG = 1: ROW_OW's own instance, TAG = 2: ROW_KEFF's.  Where one mode alone calls an instance with constant fields, the compiler specialises the
+// TAG = 1: ROW_OW's own instance, TAG = 2: ROW_KEFF's, TAG = 3: ROW_PRES's.  Where one mode alone calls an instance with constant fields, the compiler specialises the
 // instance for them, and a caller with other fields would change the code of that mode's kernels.
 template <int N, bool SLAB, int TAG = 0>
 FB_DEV void row_load_pair(cf *reg, int t, const RowView &v, int fA, int fB, int rowA, int rowB)
@@ -541,9 +626,30 @@ __global__ void __launch_bounds__(RowCfg<N>::THREADS, RowCfg<N>::MIN_WAVES) k_ro
                 const int y = t_it + ord_i<RL>(e) * T;
                 reg[e] = cf_make(a.rin[(size_t)x0 * N + y], a.rin[(size_t)x1 * N + y]);
             }
+        } else if (MODE == ROW_PRES) {
+            // ROW_PRES: fields psi_xx, psi_yy, psi_xy (masked), packed as ROW_OW packs them: psi_xy of both rows in one transform, then
+            // psi_xx and psi_yy of each row in one; the product psi_xx psi_yy - psi_xy^2 of row x0 becomes the real part and that of row
+            // x1 the imaginary part of the forward transform's input, as ROW_FUSED hands over the tendency (complete after r == 1)
+            float xy0[16], xy1[16], t0[16];
+            row_load_pair<N, SLAB, 3>(reg, launder(t), a.M, 2, 2, x0, x1);
+            rowfft<N, false>(lds, launder(t), twb, reg);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { xy0[e] = reg[e].x * a.scale; xy1[e] = reg[e].y * a.scale; t0[e] = 0.f; }
+#pragma unroll 1
+            for (int r = 0; r < 2; ++r) {
+                const int x = x0 + r;
+                row_load_pair<N, SLAB, 3>(reg, launder(t), a.M, 0, 1, x, x);
+                rowfft<N, false>(lds, launder(t), twb, reg);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float val = pres_curv_point(reg[e].x * a.scale, reg[e].y * a.scale, r ? xy1[e] : xy0[e]);
+                    reg[e] = cf_make(t0[e], val);
+                    t0[e] = val;
+                }
+            }
         }
 
-        if (MODE == ROW_FUSED || MODE == ROW_FWD) {
+        if (MODE == ROW_FUSED || MODE == ROW_FWD || MODE == ROW_PRES) {
             if constexpr (SHARE) rowfft<N, true>(lds, launder(t), reinterpret_cast<const RowTwSrc<N, true, true> &>(twb), reg);   // main.cpp:237 (y part)
             else rowfft<N, true>(lds, launder(t), twf_own, reg);
             if (DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the next pair's first rows have landed

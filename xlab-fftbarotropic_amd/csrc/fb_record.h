@@ -2,8 +2,8 @@
 //
 // One layer serves the one-GPU model (fb_model_*, s == NULL) and a rank of a slab (fb_slab_*, this rank's rows).  A record is, per
 // column group: the export of vort_c into the model's record workspace, the spectral kernel of its kind (none for the vorticity;
-// k_psi_private for psi, u, v; k_ow_spec; k_keff_spec), the backward x pass; on a slab of several ranks one all-to-all per group in
-// the reverse roles; then the row pass with the kind's epilogue.  The record buffers are the model's own (rec_work, rec_send): a record
+// k_psi_private for psi, u, v; k_ow_spec; k_keff_spec; k_pres_spec), the backward x pass; on a slab of several ranks one all-to-all per group in
+// the reverse roles; then the row pass with the kind's epilogue (the pressure goes on from there: record_pres).  The record buffers are the model's own (rec_work, rec_send): a record
 // never writes the step's buffers (ZA, ZB, ACC, w4_*, t_*).
 #pragma once
 
@@ -46,7 +46,7 @@ extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
 }
 
 // ---- the record layer ----
-enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF };
+enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF, REC_PRES };
 
 static int rec_alloc(cf **p, size_t elems)
 {
@@ -54,7 +54,34 @@ static int rec_alloc(cf **p, size_t elems)
     return FB_OK;
 }
 
-// The record fields of `kind` (one, or three for REC_OW / REC_KEFF) of every column group through the backward x pass in
+// nf fields (one or three) of every column group, through the backward x pass in rec_work[g], to the row pass: *M is its view.  One
+// GPU: rec_work itself.  A slab of several ranks: one all-to-all per group (columns -> rows).
+static int record_to_rows(fb_model *m, fb_slab *s, int nf, RowView *M)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if (!(s && c->world > 1)) { *M = view_single(c, m->rec_work[0], (long)priv_elems(c)); return FB_OK; }
+    // [nf][nx][ncols] == [nf][dst][XL][ncols].  Three fields are regrouped into rec_send as [dst][3][XL][ncols] (each peer's blocks
+    // contiguous) and come back into rec_work as [src][3][XL][ncols]; one field leaves rec_work as it is and arrives in rec_send.
+    for (int g = 0; g < c->ngroups && nf > 1; ++g) {
+        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
+        for (int f = 0; f < 3 && blk; ++f)
+            HIPCHK(hipMemcpy2DAsync(m->rec_send[g] + f * blk, 3 * blk * sizeof(cf), m->rec_work[g] + f * c->world * blk, blk * sizeof(cf),
+                                    blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
+    }
+    cf *const *send = nf > 1 ? m->rec_send : m->rec_work, *const *recv = nf > 1 ? m->rec_work : m->rec_send;
+    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t blk = nf * (size_t)c->XL * c->grp[g].ncols;
+        if ((rc = slab_xchg(s, send[g], recv[g], blk, 0, blk))) return rc;
+    }
+    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    const cf *v[3] = {recv[0], recv[1], recv[2]};
+    *M = view_slab(c, v, nf);
+    return FB_OK;
+}
+
+// The record fields of `kind` (one, or three for REC_OW / REC_KEFF / REC_PRES) of every column group through the backward x pass in
 // rec_work[g] ([3][nx][ncols_g], field 0 for one field), and on a slab of several ranks their exchange; *M: the row pass's view.
 static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
 {
@@ -79,29 +106,12 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
         case REC_V: hipLaunchKernelGGL((k_psi_private<2>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
         case REC_OW: hipLaunchKernelGGL(k_ow_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
         case REC_KEFF: hipLaunchKernelGGL(k_keff_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
+        case REC_PRES: hipLaunchKernelGGL(k_pres_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
         }
         HIPCHK(hipGetLastError());
         if ((rc = launch_col_block<+1>(c, G, z, nf, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, nf, (long)n))) return rc;
     }
-    if (!xchg) { *M = view_single(c, m->rec_work[0], (long)priv_elems(c)); return FB_OK; }
-    // [nf][nx][ncols] == [nf][dst][XL][ncols].  Three fields are regrouped into rec_send as [dst][3][XL][ncols] (each peer's blocks
-    // contiguous) and come back into rec_work as [src][3][XL][ncols]; one field leaves rec_work as it is and arrives in rec_send.
-    for (int g = 0; g < c->ngroups && nf > 1; ++g) {
-        const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        for (int f = 0; f < 3 && blk; ++f)
-            HIPCHK(hipMemcpy2DAsync(m->rec_send[g] + f * blk, 3 * blk * sizeof(cf), m->rec_work[g] + f * c->world * blk, blk * sizeof(cf),
-                                    blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
-    }
-    cf *const *send = nf > 1 ? m->rec_send : m->rec_work, *const *recv = nf > 1 ? m->rec_work : m->rec_send;
-    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t blk = nf * (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = slab_xchg(s, send[g], recv[g], blk, 0, blk))) return rc;
-    }
-    if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    const cf *v[3] = {recv[0], recv[1], recv[2]};
-    *M = view_slab(c, v, nf);
-    return FB_OK;
+    return record_to_rows(m, s, nf, M);
 }
 
 // One record into the rows of this rank (one GPU: every row), normalised by 1/GRIDS: REC_VORT, REC_PSI, REC_U, REC_V into out0;
@@ -213,6 +223,85 @@ static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, floa
     return keff_finish(m, s, nbins, zeta, grad2, d_table);
 }
 
+// ---- balanced pressure (REC_PRES): there and back ----
+// invert_pres.cpp:135-185 on the resident state.  Per column group k_pres_spec and the backward x pass of the three masked second
+// derivatives of psi (record_fields); the ROW_PRES row pass takes them to physical space, forms psi_xx psi_yy - psi_xy^2 in registers
+// and emits its forward y transform (one GPU: in place over field 0 of rec_work, each row pair reads its rows of all three fields
+// before it stores; a slab: into rec_send as [dst][XL][ncols], one all-to-all back into field 0 of rec_work = [nx][ncols]); the
+// forward x pass as state_in runs it; the state once more into field 1 (free by now) and k_pres_solve; then one field back as
+// every one-field record goes, and the reference point.
+static int pres_check(const char *fn, const fb_ctx *c, const float *out, int ref_x, int ref_y, long *flat)
+{
+    if (!out) return fail(FB_EINVAL, std::string(fn) + ": NULL output");
+    const long long at = (long long)ref_x + (long long)c->nx * ref_y;    // the reference's flat index (invert_pres.cpp:182), kept as it is
+    if (ref_x < 0 || ref_y < 0 || at >= (long long)c->nx * c->ny) return fail(FB_EINVAL, std::string(fn) + ": reference point outside the grid");
+    *flat = (long)at;
+    return FB_OK;
+}
+
+static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, float *out)
+{
+    fb_ctx *c = m->c;
+    const int world = c->world;
+    const bool xchg = s && world > 1;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    int rc;
+    if (!m->pres_ref && hipMalloc((void **)&m->pres_ref, 2 * (size_t)world * sizeof(float)) != hipSuccess) {
+        m->pres_ref = nullptr;
+        return fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    RowArgs a = row_args_base(c);
+    if ((rc = record_fields(m, s, REC_PRES, &a.M))) return rc;
+    const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
+    a.T = xchg ? view_slab(c, ts, 1) : view_single(c, m->rec_work[0], 0);
+    a.scale = g;
+    if ((rc = launch_row<ROW_PRES>(c, a))) return rc;
+    if (xchg) {                                             // rows -> columns, the tendency's direction
+        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+        for (int k = 0; k < c->ngroups; ++k) {
+            const size_t blk = (size_t)c->XL * c->grp[k].ncols;
+            if ((rc = slab_xchg(s, m->rec_send[k], m->rec_work[k], blk, 0, blk))) return rc;
+        }
+        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    }
+    const SpecCoef coef = make_coef(c);
+    for (int k = 0; k < c->ngroups; ++k) {
+        const ColGroup &G = c->grp[k];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        cf *z = m->rec_work[k];
+        if ((rc = launch_col_strided<-1>(c, G, z, 1, 0)) || (rc = launch_col_block<-1>(c, G, z, 1, 0))) return rc;
+        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z + n) : state_convert(c, G, m->gb[k].ZA, z + n, false))) return rc;
+        hipLaunchKernelGGL(k_pres_solve, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)(z + n), z, rho, f, G.ncols, c->N1, c->N2, G.ky0);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_col_block<+1>(c, G, z, 1, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 1, (long)n))) return rc;
+    }
+    RowArgs b = row_args_base(c);
+    if ((rc = record_to_rows(m, s, 1, &b.M))) return rc;
+    b.scale = g; b.rout = out;
+    if ((rc = launch_row<ROW_INV>(c, b))) return rc;
+    // the reference point: its owner's value to every rank (one float per peer through the transport's all-to-all, as keff_finish
+    // gathers), then p -= p_ref over this rank's rows
+    const size_t nloc = (size_t)c->XL * c->ny;
+    const int owner = (int)((size_t)flat / nloc);
+    float *ref_send = m->pres_ref, *ref_recv = m->pres_ref + world;
+    const long at = (!xchg || owner == c->rank) ? (long)((size_t)flat - (size_t)owner * nloc) : -1;
+    hipLaunchKernelGGL(k_pres_ref, dim3((world + 63) / 64), dim3(64), 0, c->stream, (const float *)out, at, xchg ? ref_send : ref_recv, xchg ? world : 1);
+    HIPCHK(hipGetLastError());
+    if (xchg) {
+        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+        if ((rc = s->tp.alltoall(s->tp.self, ref_send, ref_recv, 1, 0, 1, s->comm))) return rc;
+        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    }
+    const float *ref = ref_recv + (xchg ? owner : 0);
+    const bool v4 = ((size_t)out & 15) == 0;                // nloc is a multiple of 4 (ny >= 64)
+    const dim3 grid(grid_for(c, v4 ? nloc / 4 : nloc)), blk(256);
+    if (v4) hipLaunchKernelGGL((k_pres_sub<true>), grid, blk, 0, c->stream, out, nloc, ref);
+    else hipLaunchKernelGGL((k_pres_sub<false>), grid, blk, 0, c->stream, out, nloc, ref);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
 // ---- the entry points ----
 extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
 {
@@ -244,6 +333,16 @@ extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_t
     return record_keff(m, nullptr, nbins, d_table, d_zeta, d_grad2);
 }
 
+extern "C" int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_get_pressure: NULL model");
+    long flat = 0;
+    int rc;
+    if ((rc = pres_check("fb_model_get_pressure", m->c, d_pres, ref_x, ref_y, &flat))) return rc;
+    NEED_SINGLE(m->c);
+    return record_pres(m, nullptr, rho, f, flat, d_pres);   // invert_pres.cpp:135-185
+}
+
 extern "C" int fb_slab_get_vort_local(fb_slab *s, float *d_rows)
 {
     SLAB_READY(s);
@@ -262,6 +361,17 @@ extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float 
     SLAB_READY(s);
     if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
     return record(s->m, s, REC_OW, d_w_rows, d_tau_rows);
+}
+
+// collective: the reference point's value reaches every rank through the transport (record_pres)
+extern "C" int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int ref_y, float *d_pres_rows)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_get_pressure_local: NULL slab");
+    long flat = 0;
+    int rc;
+    if ((rc = pres_check("fb_slab_get_pressure_local", s->c, d_pres_rows, ref_x, ref_y, &flat))) return rc;
+    SLAB_READY(s);
+    return record_pres(s->m, s, rho, f, flat, d_pres_rows);
 }
 
 // collective: the ranks' (min, max) and histograms are all-gathered through the transport (keff_finish), every rank gets the whole table

@@ -227,8 +227,28 @@ __global__ void __launch_bounds__(Row3Cfg<M>::THREADS) k_row3(RowArgs a, const c
                 const int y = 3 * (tl + ord_i<RL>(e) * T) + r;
                 reg[e] = cf_make(a.rin[(size_t)x0 * N + y], a.rin[(size_t)x1 * N + y]);
             }
+        } else if (MODE == ROW_PRES) {
+            // ROW_PRES (as k_row): psi_xy of both rows in one transform, psi_xx and psi_yy of each row in one, the products of rows x0, x1
+            // as the real and imaginary parts of the forward transform's input
+            float xy0[16], xy1[16], t0[16];
+            row3_load<M, SLAB, 3>(reg, r, launder(t), a.M, 2, 2, x0, x1, twN);
+            row_fft<M, false>(lds, launder(t), twb, reg);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { xy0[e] = reg[e].x * a.scale; xy1[e] = reg[e].y * a.scale; t0[e] = 0.f; }
+#pragma unroll 1
+            for (int rr = 0; rr < 2; ++rr) {
+                const int x = x0 + rr;
+                row3_load<M, SLAB, 3>(reg, r, launder(t), a.M, 0, 1, x, x, twN);
+                row_fft<M, false>(lds, launder(t), twb, reg);
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const float val = pres_curv_point(reg[e].x * a.scale, reg[e].y * a.scale, rr ? xy1[e] : xy0[e]);
+                    reg[e] = cf_make(t0[e], val);
+                    t0[e] = val;
+                }
+            }
         }
-        if (MODE == ROW_FUSED || MODE == ROW_FWD) {
+        if (MODE == ROW_FUSED || MODE == ROW_FWD || MODE == ROW_PRES) {
             if constexpr (C::SHARE) row_fft<M, true>(lds, launder(t), reinterpret_cast<const RowTwSrc<M, true, true> &>(twb), reg);
             else row_fft<M, true>(lds, launder(t), twf_own, reg);
             row3_store<M, SLAB>(lds_pair, r, launder(t), reg, valid, a.T, a.t_frozen, x0, x1, twN);

@@ -1012,6 +1012,8 @@ struct fb_model {
     // the reduction buffers (grown to the largest request)
     float *keff_fields;
     void *keff_red; size_t keff_red_cap;
+    // the pressure record's reference-point value: [world] floats to send, [world] received (fb_record.h, record_pres)
+    float *pres_ref;
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
     // tiles only (the backward strided pass on the active tiles comes next); 2: finished on every tile (ready for the row pass)
     int primed;
@@ -1070,6 +1072,7 @@ extern "C" int fb_model_destroy(fb_model *m)
     for (auto p : m->rec_send) if (p) hipFree(p);
     if (m->keff_fields) hipFree(m->keff_fields);
     if (m->keff_red) hipFree(m->keff_red);
+    if (m->pres_ref) hipFree(m->pres_ref);
     delete m;
     return FB_OK;
 }

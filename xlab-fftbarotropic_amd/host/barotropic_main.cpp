@@ -26,7 +26,11 @@
 // dvortdt) in ./log, on one GPU and with --world P.
 // --dump-eddy-diffusivity [--keff-bins N] (no reference counterpart, N in [2, 4096], default 256) adds eddy_diffusivity_step_N.bin to
 // every record: the effective eddy diffusivity table of fb_model_get_eddy_diffusivity, raw little-endian float64 [N][9], the last
-// file of a record in ./log (after v, dvortdt or tau_fil); on one GPU and with --world P, where rank 0 alone writes it.
+// file of a record in ./log (after v, dvortdt, tau_fil or pres); on one GPU and with --world P, where rank 0 alone writes it.
+// --dump-pressure [--pres-rho R] [--pres-f F] [--pres-ref-x X] [--pres-ref-y Y] (defaults 1.0, 1e-5, 0, 0: configuration.hpp:10-11,
+// invert_pres.cpp:68-69) adds pres_step_N.bin to every record: the nonlinear-balance pressure that the reference's invert_pres.cpp
+// computes from psi_step_N.bin afterwards (:135-185), here from the resident state (fb_model_get_pressure), after tau_fil and before
+// eddy_diffusivity in ./log; on one GPU and with --world P.  A reference point outside the grid is refused (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -65,6 +69,8 @@ struct Config {
     bool dump_grad = false, dump_dvortdt = false;                                  // the OUTPUT_GRAD_VORT / OUTPUT_DVORTDT blocks of main.cpp:156-162,170-176,229-235 as run-time options
     bool dump_ow = false;                                                          // Okubo-Weiss parameter and filamentation time (no reference counterpart)
     bool dump_keff = false; int keff_bins = 256;                                   // effective eddy diffusivity table and its number of bins (no reference counterpart)
+    bool dump_pres = false; float pres_rho = 1.0f, pres_f = 1e-5f;                 // balanced pressure (invert_pres.cpp:135-185); rho, f: configuration.hpp:10-11
+    int pres_ref_x = 0, pres_ref_y = 0;                                            // its reference point (invert_pres.cpp:67-79)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -207,7 +213,7 @@ struct RecordWriter {
     std::thread th; std::mutex mu; std::condition_variable cv;
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
-    void *e_copy[2] = {nullptr, nullptr}; float *h[2][9] = {};
+    void *e_copy[2] = {nullptr, nullptr}; float *h[2][10] = {};
     double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
     enum { KEFF_TABLE = -2 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
@@ -295,6 +301,7 @@ struct Engine {
     virtual void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src) = 0;
     virtual void get_okubo_weiss(float *d_w, float *d_tau) = 0;                       // --dump-okubo-weiss, on the compute stream
     virtual void get_eddy_diffusivity(int nbins, double *d_table) = 0;                // --dump-eddy-diffusivity, on the compute stream (collective)
+    virtual void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) = 0;   // --dump-pressure, on the compute stream (collective)
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -340,6 +347,10 @@ struct SingleEngine : Engine {
     {
         must(fb_model_get_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_eddy_diffusivity");
     }
+    void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) override
+    {
+        must(fb_model_get_pressure(model, rho, f, ref_x, ref_y, d_pres), "fb_model_get_pressure");
+    }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -380,6 +391,10 @@ struct SlabEngine : Engine {
     {
         must(fb_slab_get_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_eddy_diffusivity");
     }
+    void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) override
+    {
+        must(fb_slab_get_pressure_local(sl, rho, f, ref_x, ref_y, d_pres), "fb_slab_get_pressure_local");
+    }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -393,9 +408,9 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     must(fb_stream_create(&copy), "stream");
     for (void **e : {&e_rec, &e_h2d, &e_src}) must(fb_event_create(e), "event");
     // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt);
-    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss)
-    constexpr int NB = 9;
-    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow};
+    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure)
+    constexpr int NB = 10;
+    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres};
     float *d_in = nullptr, *d_out[NB] = {};
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
     for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
@@ -418,6 +433,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     writer.items.push_back({"psi", 1}); writer.items.push_back({"u", 2}); writer.items.push_back({"v", 3});   // main.cpp:181-222
     if (cfg.dump_dvortdt) writer.items.push_back({"dvortdt", 6});                      // main.cpp:229-235
     if (cfg.dump_ow) { writer.items.push_back({"okubo_weiss", 7}); writer.items.push_back({"tau_fil", 8}); }
+    if (cfg.dump_pres) writer.items.push_back({"pres", 9});                            // invert_pres.cpp:187
     if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
     writer.table_bytes = table_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
@@ -490,6 +506,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 eng->record(e_src);                                                    // d_in may be overwritten behind this
             }
             if (cfg.dump_ow) eng->get_okubo_weiss(d_out[7], d_out[8]);
+            if (cfg.dump_pres) eng->get_pressure(cfg.pres_rho, cfg.pres_f, cfg.pres_ref_x, cfg.pres_ref_y, d_out[9]);
             if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
@@ -576,7 +593,9 @@ int main(int argc, char *args[])
                                     {"world", 1, 0, 9}, {"rank", 1, 0, 10}, {"comm-file", 1, 0, 11}, {"ranks-as-threads", 0, 0, 12},
                                     {"launch-token", 1, 0, 13}, {"comm-max-age", 1, 0, 14}, {"comm-timeout", 1, 0, 15}, {"fifo-fanout", 0, 0, 16},
                                     {"no-timing", 0, 0, 17}, {"dump-grad-vort", 0, 0, 18}, {"dump-dvortdt", 0, 0, 19}, {"record-buffers", 1, 0, 20},
-                                    {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23}, {0, 0, 0, 0}};
+                                    {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23},
+                                    {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
+                                    {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
         switch (opt) {
@@ -614,11 +633,25 @@ int main(int argc, char *args[])
             cfg.keff_bins = (int)v;
             break;
         }
+        case 24: cfg.dump_pres = true; break;            // pres_step_N.bin (also with --world P)
+        case 25: cfg.pres_rho = (float)atof(optarg); break;
+        case 26: cfg.pres_f = (float)atof(optarg); break;
+        case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (!*optarg || *end || v < 0 || v > 0x7fffffffL) { fprintf(stderr, "--pres-ref-x / --pres-ref-y: a non-negative integer\n"); return 2; }
+            (opt == 27 ? cfg.pres_ref_x : cfg.pres_ref_y) = (int)v;
+            break;
+        }
         }
     }
     if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || (cfg.world > 1 && !cfg.threads && cfg.comm_file.empty()) ||
         cfg.token.size() >= fbcomm::TOKEN_BYTES) {
         fprintf(stderr, "usage: ... --world P --rank r --comm-file FILE [--launch-token T]   (or --world P --ranks-as-threads)\n"); return 2;
+    }
+    // the reference's flat index ref_x + XPTS * ref_y (invert_pres.cpp:182) must name an element of the field
+    if ((long long)cfg.pres_ref_x + (long long)cfg.npts * cfg.pres_ref_y >= (long long)cfg.npts * cfg.npts) {
+        fprintf(stderr, "--pres-ref-x / --pres-ref-y: the reference point lies outside the %d x %d grid\n", cfg.npts, cfg.npts); return 2;
     }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
     if (cfg.total_steps < 0) cfg.total_steps = (int)(60 * 60 / cfg.dt);              // configuration.hpp:36

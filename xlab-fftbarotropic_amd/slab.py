@@ -270,6 +270,14 @@ class EngineSlab:
         self.synchronize()
         return (table, zeta, g) if fields else table
 
+    def pressure_local(self, rho=1.0, f=1e-5, ref=(0, 0)):
+        """This rank's rows of the nonlinear-balance pressure (fb_slab_get_pressure_local), minus its value at the reference point
+        ref = (ref_x, ref_y) of the whole domain (flat element ref_x + nx * ref_y).  Collective."""
+        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
+        self.B.check(self.L.fb_slab_get_pressure_local(self._h, rho, f, int(ref[0]), int(ref[1]), C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
