@@ -190,6 +190,25 @@ int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float
  * FB_EINVAL (before any HIP call) for a NULL model or output, a negative ref_x / ref_y or a flat index >= nx * ny.  Enqueued on the
  * context stream, no synchronisation, no host round trip; uses the record buffers and leaves the state and a captured step untouched. */
 int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres);
+/* Shell spectra and cascade fluxes of the current state (no reference counterpart): d_table is a device float64 [nshells][10], one row
+ * per wavenumber shell, nshells from fb_spectra_shells.  G = nx ny.  For a mode (i, j) of the half spectrum: i' = min(i, nx - i),
+ * kx = 2 pi i' / Lx, ky = 2 pi j / Ly, k^2 = kx^2 + ky^2 in float64 (2 pi = 6.283185307179586, Lx, Ly the context's float32 lengths
+ * widened); w = 1 for j = 0 and j = ny/2, else 2; M = the dealiasing mask (fftwfop.cpp:57-68); a = vort_c / G; n = M N / G with N the
+ * unnormalised r2c of J = -u zeta_x - v zeta_y, formed in float32 as a stage of the step forms it (main.cpp:151-227) WITHOUT vort_src
+ * and without the viscous term: the transfer is advective only, the forcing's input is not in the table.  Shells: dk = 2 pi /
+ * max(Lx, Ly), a mode belongs to shell b = floor(sqrt(k^2) / dk + 0.5); shell 0 holds the mean mode only.  Columns, every sum in
+ * float64 over all modes of the shell (the frozen ones beyond the mask included unless M appears):
+ *   0 k_lo = max(b - 0.5, 0) dk   1 k_hi = (b + 0.5) dk [rad m^-1]   2 n = sum w (modes of the full spectrum; sums to G)
+ *   3 E = sum w |a|^2 / (2 k^2) [m^2 s^-2] (0 for k = 0; sums to <u^2 + v^2>/2)   4 Z = sum w |a|^2 / 2 [s^-2] (sums to <zeta^2>/2)
+ *   5 T_E = sum w Re(conj(a) n) / k^2 [m^2 s^-3] (0 for k = 0)   6 T_Z = sum w Re(conj(a) n) [s^-3]
+ *   7 Pi_E = -sum_{b' <= b} T_E   8 Pi_Z = -sum_{b' <= b} T_Z (added from shell 0 upwards)   9 D_Z = sum M nu k^2 w |a|^2 [s^-3]
+ * so that d/dt sum Z = sum_b (T_Z - D_Z) for an unforced run.  The result repeats bit for bit from call to call on the same state.
+ * FB_EINVAL (before any HIP call) for a NULL model or table.  Enqueued on the context stream, no synchronisation, no host round trip;
+ * uses record buffers of the model's own (allocated on first use) and leaves the state, the step's buffers and a captured step untouched. */
+int fb_model_get_spectra(fb_model *m, double *d_table);
+/* host logic, no GPU needed: the number of shells, floor(sqrt((pi nx / Lx)^2 + (pi ny / Ly)^2) / dk + 0.5) + 1 (the corner mode lies in
+ * the last shell); FB_EINVAL for a NULL pointer, non-positive lengths or an unsupported size */
+int fb_spectra_shells(int nx, int ny, float lx, float ly, int *nshells);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -252,6 +271,10 @@ int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *
 /* fb_model_get_pressure on this rank's rows [XL][ny], bit for bit (the reference point is a point of the whole domain: its owner's
  * value reaches every rank through the transport); collective: every rank calls it */
 int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int ref_y, float *d_pres_rows);
+/* fb_model_get_spectra of the whole domain: the full table on every rank.  Each rank sums the modes of the ky columns it owns (active
+ * and frozen), the ranks' partial sums are all-gathered through the transport and added in rank order, the running sums of columns 7
+ * and 8 are taken after that; collective: every rank calls it */
+int fb_slab_get_spectra(fb_slab *s, double *d_table);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -107,6 +107,12 @@ def lib():
     for n in ("fb_model_get_pressure", "fb_slab_get_pressure_local"):
         if hasattr(L, n):
             getattr(L, n).argtypes = [vp, C.c_float, C.c_float, ip, ip, fp]
+    # (likewise the spectra record)
+    for n in ("fb_model_get_spectra", "fb_slab_get_spectra"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, vp]
+    if hasattr(L, "fb_spectra_shells"):
+        L.fb_spectra_shells.argtypes = [ip, ip, C.c_float, C.c_float, C.POINTER(ip)]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -127,11 +133,11 @@ EXPORTS = [
     "fb_gradx", "fb_grady", "fb_laplacian", "fb_invert_laplacian", "fb_dealiase", "fb_r2c", "fb_c2r",
     "fb_backward_normalize", "fb_negate", "fb_jacobian", "fb_spec_axpy", "fb_spec_evolve", "fb_spec_rk4_combine",
     "fb_model_create", "fb_model_destroy", "fb_model_set_vort", "fb_model_set_source", "fb_model_step",
-    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_pressure", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
+    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_pressure", "fb_model_get_spectra", "fb_spectra_shells", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
     "fb_model_time_steps", "fb_model_profile_steps", "fb_write_field", "fb_read_field", "fb_make_field", "fb_make_source_kuo2004",
     "fb_create_slab", "fb_slab_unique_id", "fb_slab_create", "fb_slab_destroy", "fb_slab_connect_rccl", "fb_local_hub_create",
     "fb_local_hub_destroy", "fb_slab_connect_local", "fb_slab_connect_callback", "fb_slab_set_vort_local", "fb_slab_set_source_local",
-    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
+    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_get_spectra", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
@@ -145,6 +151,16 @@ def check(status):
 
 # the columns of the effective eddy diffusivity table (fb_model_get_eddy_diffusivity, include/fftbaro.h), one row per bin of zeta
 EDDY_DIFFUSIVITY_COLUMNS = ("Q_lo", "Q_hi", "n", "A", "A_ge", "S", "Le2", "r_e", "K_eff")
+
+# the columns of the shell spectra table (fb_model_get_spectra, include/fftbaro.h), one row per wavenumber shell
+SPECTRA_COLUMNS = ("k_lo", "k_hi", "n", "E", "Z", "T_E", "T_Z", "Pi_E", "Pi_Z", "D_Z")
+
+
+def spectra_shells(nx, ny=None, Lx=600000.0, Ly=600000.0):
+    """The number of wavenumber shells (rows) of the spectra table of an nx x ny grid on an Lx x Ly domain; host logic, no GPU."""
+    n = C.c_int()
+    check(lib().fb_spectra_shells(nx, ny or nx, Lx, Ly, C.byref(n)))
+    return n.value
 
 
 def _torch():
@@ -274,6 +290,7 @@ class Model:
         self.fop = FftwfOperation(nx, ny, Lx, Ly)
         self.torch = self.fop.torch
         self.nx, self.ny, self.hy = nx, ny, ny // 2 + 1
+        self.Lx, self.Ly = Lx, Ly
         h = C.c_void_p()
         check(lib().fb_model_create(C.byref(h), self.fop._h, nu, dt))
         self._h = h
@@ -355,6 +372,14 @@ class Model:
         out = self.fop.empty_real()
         check(lib().fb_model_get_pressure(self._h, rho, f, int(ref[0]), int(ref[1]), _ptr(out)))
         return out
+
+    def spectra(self):
+        """The shell spectra and cascade fluxes of the current state, float64 [nshells, 10] (columns SPECTRA_COLUMNS): energy and
+        enstrophy spectra, advective transfers and fluxes, enstrophy dissipation per wavenumber shell."""
+        t = self.torch
+        table = t.empty((spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
+        check(lib().fb_model_get_spectra(self._h, _ptr(table)))
+        return table
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

@@ -2,8 +2,8 @@
 //
 // One layer serves the one-GPU model (fb_model_*, s == NULL) and a rank of a slab (fb_slab_*, this rank's rows).  A record is, per
 // column group: the export of vort_c into the model's record workspace, the spectral kernel of its kind (none for the vorticity;
-// k_psi_private for psi, u, v; k_ow_spec; k_keff_spec; k_pres_spec), the backward x pass; on a slab of several ranks one all-to-all per group in
-// the reverse roles; then the row pass with the kind's epilogue (the pressure goes on from there: record_pres).  The record buffers are the model's own (rec_work, rec_send): a record
+// k_psi_private for psi, u, v; k_ow_spec; k_keff_spec; k_pres_spec; k_spectra_deriv), the backward x pass; on a slab of several ranks one all-to-all per group in
+// the reverse roles; then the row pass with the kind's epilogue (the pressure and the spectra go on from there: record_pres, record_spectra).  The record buffers are the model's own (rec_work, rec_send): a record
 // never writes the step's buffers (ZA, ZB, ACC, w4_*, t_*).
 #pragma once
 
@@ -54,19 +54,19 @@ static int rec_alloc(cf **p, size_t elems)
     return FB_OK;
 }
 
-// nf fields (one or three) of every column group, through the backward x pass in rec_work[g], to the row pass: *M is its view.  One
+// nf fields (one, three, or four for the spectra) of every column group, through the backward x pass in rec_work[g], to the row pass: *M is its view.  One
 // GPU: rec_work itself.  A slab of several ranks: one all-to-all per group (columns -> rows).
 static int record_to_rows(fb_model *m, fb_slab *s, int nf, RowView *M)
 {
     fb_ctx *c = m->c;
     int rc;
     if (!(s && c->world > 1)) { *M = view_single(c, m->rec_work[0], (long)priv_elems(c)); return FB_OK; }
-    // [nf][nx][ncols] == [nf][dst][XL][ncols].  Three fields are regrouped into rec_send as [dst][3][XL][ncols] (each peer's blocks
-    // contiguous) and come back into rec_work as [src][3][XL][ncols]; one field leaves rec_work as it is and arrives in rec_send.
+    // [nf][nx][ncols] == [nf][dst][XL][ncols].  Several fields are regrouped into rec_send as [dst][nf][XL][ncols] (each peer's blocks
+    // contiguous) and come back into rec_work as [src][nf][XL][ncols]; one field leaves rec_work as it is and arrives in rec_send.
     for (int g = 0; g < c->ngroups && nf > 1; ++g) {
         const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        for (int f = 0; f < 3 && blk; ++f)
-            HIPCHK(hipMemcpy2DAsync(m->rec_send[g] + f * blk, 3 * blk * sizeof(cf), m->rec_work[g] + f * c->world * blk, blk * sizeof(cf),
+        for (int f = 0; f < nf && blk; ++f)
+            HIPCHK(hipMemcpy2DAsync(m->rec_send[g] + f * blk, nf * blk * sizeof(cf), m->rec_work[g] + f * c->world * blk, blk * sizeof(cf),
                                     blk * sizeof(cf), c->world, hipMemcpyDeviceToDevice, c->stream));
     }
     cf *const *send = nf > 1 ? m->rec_send : m->rec_work, *const *recv = nf > 1 ? m->rec_work : m->rec_send;
@@ -302,6 +302,109 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
     return FB_OK;
 }
 
+// ---- shell spectra and cascade fluxes: there and back, then the gather (fb_spectra.h) ----
+// The record workspace of this kind alone is larger than three fields: one GPU keeps the four derivative fields and N = r2c(J) side by
+// side (five fields; the state is exported once more over field 0 for the gather), a slab of several ranks four fields in rec_work
+// and in rec_send.  A workspace that another kind allocated first is replaced (hipFree waits for the device); the other kinds go on
+// using the larger one.
+static int rec_grow(cf **p, unsigned char *have, size_t n, int nf)
+{
+    if (*p && (*have ? *have : 3) >= nf) return FB_OK;
+    if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; *have = 0; }
+    if (hipMalloc((void **)p, nf * n * sizeof(cf)) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+    *have = (unsigned char)nf;
+    return FB_OK;
+}
+
+extern "C" int fb_spectra_shells(int nx, int ny, float lx, float ly, int *nshells)
+{
+    if (!nshells) return fail(FB_EINVAL, "fb_spectra_shells: NULL");
+    *nshells = 0;
+    if (!(lx > 0.f) || !(ly > 0.f)) return fail(FB_EINVAL, "fb_spectra_shells: Lx, Ly must be positive");
+    if (!fb_size_supported(nx, ny)) return fail(FB_EINVAL, "fb_spectra_shells: nx, ny must be powers of two in [64, 16384] or 3*2^k in [192, 3072]");
+    *nshells = spec_nshells(spec_grid(nx, ny, lx, ly));
+    return FB_OK;
+}
+
+// Per column group: the state into field 0 of rec_work, k_spectra_deriv, the backward x pass of the four fields (on a slab their
+// exchange); the step's fused row pass without a source (c2r of the four fields, J = -u zeta_x - v zeta_y, its forward y transform)
+// into the record workspace (one GPU: field 4 of rec_work; a slab: rec_send as [dst][XL][ncols] of the active groups, one all-to-all
+// back into field 0 of rec_work = [nx][ncols]); the forward x pass as state_in runs it; the state once more (one GPU: field 0, a
+// slab: field 1); k_spectra_gather over this rank's columns; on a slab the ranks' partial sums all-gathered as keff_finish gathers
+// its histograms; k_spectra_table.  spec_red: [world][nshells][6] to send (a slab of several ranks), [world][nshells][6] received.
+static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
+{
+    fb_ctx *c = m->c;
+    const int world = c->world;
+    const bool xchg = s && world > 1;
+    const SpecGrid sg = spec_grid(c->nx, c->ny, c->lx, c->ly);
+    const int nshells = spec_nshells(sg);
+    const size_t np = (size_t)nshells * SPEC_SUMS;
+    int rc;
+    if (!m->spec_red && hipMalloc((void **)&m->spec_red, (xchg ? 2 : 1) * (size_t)world * np * sizeof(double)) != hipSuccess) {
+        m->spec_red = nullptr;
+        return fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    const SpecCoef coef = make_coef(c);
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        if ((rc = rec_grow(&m->rec_work[g], &m->rec_work_nf[g], n, xchg ? 4 : 5)) || (xchg && (rc = rec_grow(&m->rec_send[g], &m->rec_send_nf[g], n, 4)))) return rc;
+        cf *z = m->rec_work[g];
+        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
+        hipLaunchKernelGGL(k_spectra_deriv, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+        HIPCHK(hipGetLastError());
+        if ((rc = launch_col_block<+1>(c, G, z, 4, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 4, (long)n))) return rc;
+    }
+    RowArgs a = row_args_base(c);
+    if ((rc = record_to_rows(m, s, 4, &a.M))) return rc;
+    const size_t n0 = priv_elems(c);
+    if (xchg) {
+        const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
+        a.T = view_slab(c, ts, 1);
+        a.t_frozen = 0;                                     // the frozen columns' transfer is masked: never read
+    } else {
+        HIPCHK(hipMemsetAsync(m->rec_work[0] + 4 * n0, 0, n0 * sizeof(cf), c->stream));       // pad columns zero
+        a.T = view_single(c, m->rec_work[0] + 4 * n0, 0);
+    }
+    a.scale = 1.0f / (float)((size_t)c->nx * c->ny);
+    if ((rc = launch_row<ROW_FUSED>(c, a, c->row))) return rc;             // main.cpp:151-227,237 without vort_src
+    if (xchg) {                                             // rows -> columns, the tendency's direction
+        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+        for (int k = 0; k < c->nact; ++k) {
+            const size_t blk = (size_t)c->XL * c->grp[k].ncols;
+            if ((rc = slab_xchg(s, m->rec_send[k], m->rec_work[k], blk, 0, blk))) return rc;
+        }
+        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    }
+    SpecGroups sgr;
+    memset(&sgr, 0, sizeof(sgr));
+    for (int k = 0; k < c->ngroups; ++k) {
+        const ColGroup &G = c->grp[k];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        const bool active = k < c->nact;
+        cf *nh = xchg ? m->rec_work[k] : m->rec_work[k] + 4 * n, *st = xchg ? m->rec_work[k] + n : m->rec_work[k];
+        if (active && ((rc = launch_col_strided<-1>(c, G, nh, 1, 0)) || (rc = launch_col_block<-1>(c, G, nh, 1, 0)))) return rc;
+        if ((rc = m->xpass != XP_COLS ? full_export_state(m, st) : state_convert(c, G, m->gb[k].ZA, st, false))) return rc;
+        const int q = sgr.ng++;
+        sgr.a[q] = st; sgr.nh[q] = active ? nh : nullptr; sgr.ncols[q] = G.ncols; sgr.ky0[q] = G.ky0;
+    }
+    double *send = (double *)m->spec_red, *recv = send + (xchg ? (size_t)world * np : 0);
+    hipLaunchKernelGGL(k_spectra_gather, dim3(nshells), dim3(256), 0, c->stream, sg, sgr, c->N1, c->N2, coef.gws_i, (double)m->nu, xchg ? send : recv,
+                       xchg ? world : 1, np);
+    HIPCHK(hipGetLastError());
+    if (xchg) {
+        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+        if ((rc = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * np, 0, 2 * np, s->comm))) return rc;
+        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    }
+    hipLaunchKernelGGL(k_spectra_table, dim3(1), dim3(256), 0, c->stream, (const double *)recv, xchg ? world : 1, nshells, sg.dk, d_table);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
 // ---- the entry points ----
 extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
 {
@@ -381,4 +484,21 @@ extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_tab
     int rc;
     if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
     return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows);
+}
+
+extern "C" int fb_model_get_spectra(fb_model *m, double *d_table)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_get_spectra: NULL model");
+    if (!d_table) return fail(FB_EINVAL, "fb_model_get_spectra: NULL table");
+    NEED_SINGLE(m->c);
+    return record_spectra(m, nullptr, d_table);
+}
+
+// collective: the ranks' partial sums are all-gathered through the transport (record_spectra), every rank gets the whole table
+extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL slab");
+    if (!d_table) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL table");
+    SLAB_READY(s);
+    return record_spectra(s->m, s, d_table);
 }

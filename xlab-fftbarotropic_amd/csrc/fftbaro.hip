@@ -15,6 +15,7 @@
 #include "../../include/fftbaro.h"
 #include "fb_kernels.h"
 #include "fb_keff.h"
+#include "fb_spectra.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1014,6 +1015,10 @@ struct fb_model {
     void *keff_red; size_t keff_red_cap;
     // the pressure record's reference-point value: [world] floats to send, [world] received (fb_record.h, record_pres)
     float *pres_ref;
+    // the spectra record: fields the record workspace holds where this kind has grown it (0: the three of the other kinds), and the
+    // shells' partial sums [world][nshells][6] to send and received (fb_record.h, record_spectra)
+    unsigned char rec_work_nf[3], rec_send_nf[3];
+    void *spec_red;
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
     // tiles only (the backward strided pass on the active tiles comes next); 2: finished on every tile (ready for the row pass)
     int primed;
@@ -1073,6 +1078,7 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->keff_fields) hipFree(m->keff_fields);
     if (m->keff_red) hipFree(m->keff_red);
     if (m->pres_ref) hipFree(m->pres_ref);
+    if (m->spec_red) hipFree(m->spec_red);
     delete m;
     return FB_OK;
 }

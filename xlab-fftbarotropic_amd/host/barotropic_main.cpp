@@ -31,6 +31,9 @@
 // invert_pres.cpp:68-69) adds pres_step_N.bin to every record: the nonlinear-balance pressure that the reference's invert_pres.cpp
 // computes from psi_step_N.bin afterwards (:135-185), here from the resident state (fb_model_get_pressure), after tau_fil and before
 // eddy_diffusivity in ./log; on one GPU and with --world P.  A reference point outside the grid is refused (exit status 2).
+// --dump-spectra (no reference counterpart) adds spectra_step_N.bin to every record: the shell spectra and cascade fluxes of
+// fb_model_get_spectra, raw little-endian float64 [nshells][10] (nshells from fb_spectra_shells), after pres and before eddy_diffusivity
+// in ./log; on one GPU and with --world P, where rank 0 alone writes it.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -71,6 +74,7 @@ struct Config {
     bool dump_keff = false; int keff_bins = 256;                                   // effective eddy diffusivity table and its number of bins (no reference counterpart)
     bool dump_pres = false; float pres_rho = 1.0f, pres_f = 1e-5f;                 // balanced pressure (invert_pres.cpp:135-185); rho, f: configuration.hpp:10-11
     int pres_ref_x = 0, pres_ref_y = 0;                                            // its reference point (invert_pres.cpp:67-79)
+    bool dump_spectra = false;                                                     // shell spectra and cascade fluxes (no reference counterpart)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -215,9 +219,10 @@ struct RecordWriter {
     int nsets = 1; bool set_free[2] = {true, true};
     void *e_copy[2] = {nullptr, nullptr}; float *h[2][10] = {};
     double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
-    enum { KEFF_TABLE = -2 };
+    double *hs[2] = {nullptr, nullptr}; size_t spectra_bytes = 0;                      // the spectra table (item buffer SPECTRA_TABLE), rank 0 only
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
-    // KEFF_TABLE = the eddy diffusivity table: one whole file, written by the lead rank alone)
+    // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
     SourceFeed *feed = nullptr;                                                        // vort_src as of the record step is held until written
     std::string output; FILE *log_fd = nullptr; size_t floats = 0;
@@ -239,14 +244,17 @@ struct RecordWriter {
             char fn[1024];
             for (size_t i = 0; i < items.size(); ++i) {                                // main.cpp:268-278, :156-235
                 snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), items[i].first, job.step);
-                if (items[i].second == KEFF_TABLE) {
+                if (items[i].second == KEFF_TABLE || items[i].second == SPECTRA_TABLE) {
                     if (!lead) continue;
+                    const bool keff = items[i].second == KEFF_TABLE;
+                    const double *tab = keff ? ht[job.set] : hs[job.set];
+                    const size_t tb = keff ? table_bytes : spectra_bytes;
                     FILE *f = fopen(fn, "wb");
-                    if (!f || fwrite(ht[job.set], 1, table_bytes, f) != table_bytes) { perror("Write field."); std::exit(1); }
+                    if (!f || fwrite(tab, 1, tb, f) != tb) { perror("Write field."); std::exit(1); }
                     fclose(f);
                     if (!whole) fprintf(stderr, "Output %s\n", fn);
                     fprintf(log_fd, "%s\n", fn); fflush(log_fd);
-                    bytes += table_bytes;
+                    bytes += tb;
                     continue;
                 }
                 const float *data = items[i].second < 0 ? job.src : h[job.set][items[i].second];
@@ -265,7 +273,7 @@ struct RecordWriter {
             const double this_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
             busy_s += this_s;
             if (this_s > slowest_s) slowest_s = this_s;
-            for (const auto &it : items) if (it.second != KEFF_TABLE) bytes += floats * sizeof(float);
+            for (const auto &it : items) if (it.second != KEFF_TABLE && it.second != SPECTRA_TABLE) bytes += floats * sizeof(float);
             lk.lock();
             writing = false;
             set_free[job.set] = true;
@@ -302,6 +310,7 @@ struct Engine {
     virtual void get_okubo_weiss(float *d_w, float *d_tau) = 0;                       // --dump-okubo-weiss, on the compute stream
     virtual void get_eddy_diffusivity(int nbins, double *d_table) = 0;                // --dump-eddy-diffusivity, on the compute stream (collective)
     virtual void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) = 0;   // --dump-pressure, on the compute stream (collective)
+    virtual void get_spectra(double *d_table) = 0;                                    // --dump-spectra, on the compute stream (collective)
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -351,6 +360,7 @@ struct SingleEngine : Engine {
     {
         must(fb_model_get_pressure(model, rho, f, ref_x, ref_y, d_pres), "fb_model_get_pressure");
     }
+    void get_spectra(double *d_table) override { must(fb_model_get_spectra(model, d_table), "fb_model_get_spectra"); }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -395,6 +405,7 @@ struct SlabEngine : Engine {
     {
         must(fb_slab_get_pressure_local(sl, rho, f, ref_x, ref_y, d_pres), "fb_slab_get_pressure_local");
     }
+    void get_spectra(double *d_table) override { must(fb_slab_get_spectra(sl, d_table), "fb_slab_get_spectra"); }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -418,6 +429,12 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t table_bytes = cfg.dump_keff ? (size_t)cfg.keff_bins * 9 * sizeof(double) : 0;
     double *d_table = nullptr;
     if (cfg.dump_keff) must(fb_malloc((void **)&d_table, table_bytes), "fb_malloc");
+    // the spectra table (--dump-spectra): likewise
+    int nshells = 0;
+    if (cfg.dump_spectra) must(fb_spectra_shells(N, N, cfg.LX, cfg.LY, &nshells), "fb_spectra_shells");
+    const size_t spectra_bytes = (size_t)nshells * 10 * sizeof(double);
+    double *d_spectra = nullptr;
+    if (cfg.dump_spectra) must(fb_malloc((void **)&d_spectra, spectra_bytes), "fb_malloc");
 
     RecordWriter writer;
     size_t set_bytes = 0;
@@ -427,6 +444,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         must(fb_event_create(&writer.e_copy[b]), "event");
         for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
         if (cfg.dump_keff && lead) must(fb_malloc_host((void **)&writer.ht[b], table_bytes), "fb_malloc_host");
+        if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
@@ -434,8 +452,9 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (cfg.dump_dvortdt) writer.items.push_back({"dvortdt", 6});                      // main.cpp:229-235
     if (cfg.dump_ow) { writer.items.push_back({"okubo_weiss", 7}); writer.items.push_back({"tau_fil", 8}); }
     if (cfg.dump_pres) writer.items.push_back({"pres", 9});                            // invert_pres.cpp:187
+    if (cfg.dump_spectra) writer.items.push_back({"spectra", RecordWriter::SPECTRA_TABLE});
     if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
-    writer.table_bytes = table_bytes;
+    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -507,12 +526,14 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             }
             if (cfg.dump_ow) eng->get_okubo_weiss(d_out[7], d_out[8]);
             if (cfg.dump_pres) eng->get_pressure(cfg.pres_rho, cfg.pres_f, cfg.pres_ref_x, cfg.pres_ref_y, d_out[9]);
+            if (cfg.dump_spectra) eng->get_spectra(d_spectra);
             if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
             for (int i = 0; i < NB; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
             if (writer.ht[set]) must(fb_memcpy_d2h_async(copy, writer.ht[set], d_table, table_bytes), "d2h");
+            if (writer.hs[set]) must(fb_memcpy_d2h_async(copy, writer.hs[set], d_spectra, spectra_bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -574,9 +595,11 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (feed_done) delete feedp;
     fb_free(d_in); for (auto p : d_out) if (p) fb_free(p);
     if (d_table) fb_free(d_table);
+    if (d_spectra) fb_free(d_spectra);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
+        if (writer.hs[b]) fb_free_host(writer.hs[b]);
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -595,6 +618,7 @@ int main(int argc, char *args[])
                                     {"no-timing", 0, 0, 17}, {"dump-grad-vort", 0, 0, 18}, {"dump-dvortdt", 0, 0, 19}, {"record-buffers", 1, 0, 20},
                                     {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23},
                                     {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
+                                    {"dump-spectra", 0, 0, 29},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -634,6 +658,7 @@ int main(int argc, char *args[])
             break;
         }
         case 24: cfg.dump_pres = true; break;            // pres_step_N.bin (also with --world P)
+        case 29: cfg.dump_spectra = true; break;         // spectra_step_N.bin (also with --world P)
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)

@@ -116,6 +116,7 @@ class EngineSlab:
         ny = ny or nx
         self.torch, self.B, self.L = torch, B, B.lib()
         self.nx, self.ny, self.rank, self.world, self.dist = nx, ny, rank, world, dist
+        self.Lx, self.Ly = Lx, Ly
         h = C.c_void_p()
         B.check(self.L.fb_slab_create(C.byref(h), nx, ny, Lx, Ly, nu, dt, rank, world))
         self._h = h
@@ -277,6 +278,16 @@ class EngineSlab:
         self.B.check(self.L.fb_slab_get_pressure_local(self._h, rho, f, int(ref[0]), int(ref[1]), C.c_void_p(out.data_ptr())))
         self.synchronize()
         return out
+
+    def spectra(self):
+        """The shell spectra and cascade fluxes of the whole domain, float64 [nshells, 10] (fb_slab_get_spectra; columns
+        binding.SPECTRA_COLUMNS), the same on every rank.  Collective."""
+        t = self.torch
+        table = t.empty((self.B.spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes the table on ITS stream
+        self.B.check(self.L.fb_slab_get_spectra(self._h, C.c_void_p(table.data_ptr())))
+        self.synchronize()
+        return table
 
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
