@@ -178,6 +178,24 @@ int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau);
  * for a NULL model or table (checked before any HIP call).  Enqueued on the context stream, no synchronisation; leaves the state
  * and a captured step untouched. */
 int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2);
+/* Passive tracer (no reference counterpart): a second real [nx][ny] field c with a diffusivity kappa >= 0 of its own, carried along
+ * by the model's flow.  fb_model_set_tracer takes the device field d_c_real in as fb_model_set_vort takes the vorticity (readField +
+ * r2c, main.cpp:143-144,256) and keeps it as a half spectrum c_c; from then on every step advances c_c by the RK4 step of
+ * main.cpp:288-317 beside vort_c, stage by stage: stage k uses psi_c = invertLaplacian(vort_c) of the vorticity's state of stage k,
+ * u = -psi_y, v = psi_x as the vorticity's own stage k forms them, and
+ *   tend_c = dealiase( r2c(-u c_x - v c_y) + kappa laplacian(c_c) ),  c_x = c2r(gradx c_c)/GRIDS, c_y = c2r(grady c_c)/GRIDS
+ * in float32 with the forms of main.cpp:225-227 (no source), :240-243 (kappa for NU), :246-251, :309-312.  Modes outside the
+ * dealiasing circle never change after fb_model_set_tracer, the mean mode is kept.  A tracer set to the vorticity with kappa = nu
+ * follows the vorticity.  One tracer per model; d_c_real == NULL removes it and frees its state.  The vorticity, its step and every
+ * other record are bit for bit what they are without a tracer; fb_model_set_vort leaves the tracer in place.  A captured step
+ * (fb_model_use_graph) is dropped and captured again with the tracer's stages.  fb_model_get_tracer: the tracer as fb_model_get_vort
+ * returns the vorticity.  fb_model_get_tracer_eddy_diffusivity: fb_model_get_eddy_diffusivity of the tracer, kappa in the place of
+ * nu in column 8 (d_c, d_grad2: optional outputs of c and |grad c|^2).  FB_EINVAL before any HIP call: NULL model, kappa negative
+ * or not finite, a get without a tracer set, and what fb_model_get_eddy_diffusivity rejects.  Enqueued on the context stream, no
+ * synchronisation. */
+int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa);   /* NULL: remove the tracer */
+int fb_model_get_tracer(fb_model *m, float *d_c_real);
+int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2);
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -275,6 +293,12 @@ int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int re
  * and frozen), the ranks' partial sums are all-gathered through the transport and added in rank order, the running sums of columns 7
  * and 8 are taken after that; collective: every rank calls it */
 int fb_slab_get_spectra(fb_slab *s, double *d_table);
+/* the passive tracer (fb_model_set_tracer) of a slab: this rank's rows [XL][ny] in and out, bit for bit what one GPU computes; the
+ * table is that of the whole domain, on every rank, as fb_slab_get_eddy_diffusivity gathers it; all three are collective.  The
+ * tracer's stages exchange their fields through the transport beside the step's own exchanges. */
+int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa);  /* NULL: remove the tracer */
+int fb_slab_get_tracer_local(fb_slab *s, float *d_rows);
+int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -113,6 +113,16 @@ def lib():
             getattr(L, n).argtypes = [vp, vp]
     if hasattr(L, "fb_spectra_shells"):
         L.fb_spectra_shells.argtypes = [ip, ip, C.c_float, C.c_float, C.POINTER(ip)]
+    # (likewise the passive tracer)
+    for n in ("fb_model_set_tracer", "fb_slab_set_tracer_local"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, fp, C.c_float]
+    for n in ("fb_model_get_tracer", "fb_slab_get_tracer_local"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, fp]
+    for n in ("fb_model_get_tracer_eddy_diffusivity", "fb_slab_get_tracer_eddy_diffusivity"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, ip, vp, fp, fp]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -139,6 +149,7 @@ EXPORTS = [
     "fb_local_hub_destroy", "fb_slab_connect_local", "fb_slab_connect_callback", "fb_slab_set_vort_local", "fb_slab_set_source_local",
     "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_get_spectra", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
+    "fb_model_set_tracer", "fb_model_get_tracer", "fb_model_get_tracer_eddy_diffusivity", "fb_slab_set_tracer_local", "fb_slab_get_tracer_local", "fb_slab_get_tracer_eddy_diffusivity",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
 
@@ -380,6 +391,25 @@ class Model:
         table = t.empty((spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
         check(lib().fb_model_get_spectra(self._h, _ptr(table)))
         return table
+
+    def set_tracer(self, c, kappa=0.0):
+        """Sets the passive tracer, an [nx, ny] field advected by the model's flow with the diffusivity kappa [m^2 s^-1] (it is stepped
+        beside the vorticity from now on); c=None removes it."""
+        if c is None:
+            check(lib().fb_model_set_tracer(self._h, None, 0.0))
+        else:
+            a = self._dev(c); check(lib().fb_model_set_tracer(self._h, _ptr(a), float(kappa))); self.fop.synchronize()
+
+    def tracer(self):
+        out = self.fop.empty_real(); check(lib().fb_model_get_tracer(self._h, _ptr(out))); return out
+
+    def tracer_eddy_diffusivity(self, nbins=256, fields=False):
+        """eddy_diffusivity() of the passive tracer, with its kappa in the place of nu; with fields=True also (c, |grad c|^2)."""
+        t = self.torch
+        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
+        c, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
+        check(lib().fb_model_get_tracer_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(c) if fields else None, _ptr(g) if fields else None))
+        return (table, c, g) if fields else table
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

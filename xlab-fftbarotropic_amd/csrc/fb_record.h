@@ -83,7 +83,8 @@ static int record_to_rows(fb_model *m, fb_slab *s, int nf, RowView *M)
 
 // The record fields of `kind` (one, or three for REC_OW / REC_KEFF / REC_PRES) of every column group through the backward x pass in
 // rec_work[g] ([3][nx][ncols_g], field 0 for one field), and on a slab of several ranks their exchange; *M: the row pass's view.
-static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
+// tr: the record is taken of the tracer (its base array, in the 3-pass layout already) in the place of the vorticity.
+static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, bool tr = false)
 {
     fb_ctx *c = m->c;
     const int nf = kind >= REC_OW ? 3 : 1;
@@ -96,7 +97,8 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
         if ((rc = rec_alloc(&m->rec_work[g], 3 * n)) || (xchg && (rc = rec_alloc(&m->rec_send[g], 3 * n)))) return rc;
         cf *z = m->rec_work[g];
         // copy of vort_c in the 3-pass layout into field 0 (main.cpp:273), then the kind's fields from it in place
-        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
+        if (tr) HIPCHK(hipMemcpyAsync(z, m->tr_c0[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        else if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
         const SpecCoef k = make_coef(c);
         const dim3 grid(grid_for(c, n)), blk(256);
         switch (kind) {
@@ -116,12 +118,12 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M)
 
 // One record into the rows of this rank (one GPU: every row), normalised by 1/GRIDS: REC_VORT, REC_PSI, REC_U, REC_V into out0;
 // REC_OW: W into out0 and tau_fil into out1 (either may be NULL); REC_KEFF: zeta into out0 and |grad zeta|^2 into out1.
-static int record(fb_model *m, fb_slab *s, RecKind kind, float *out0, float *out1 = nullptr)
+static int record(fb_model *m, fb_slab *s, RecKind kind, float *out0, float *out1 = nullptr, bool tr = false)
 {
     fb_ctx *c = m->c;
     RowArgs a = row_args_base(c);
     int rc;
-    if ((rc = record_fields(m, s, kind, &a.M))) return rc;
+    if ((rc = record_fields(m, s, kind, &a.M, tr))) return rc;
     const float g = 1.0f / (float)((size_t)c->nx * c->ny);
     a.scale = kind == REC_U ? -g : g;                   // u = -dpsi/dy: normalise, then negate (SURVEY note N3): (x * g) * -1 == x * (-g) exactly
     a.rout = out0; a.rin = out1;                        // (ROW_OW, ROW_KEFF: rin carries the second output, fb_kernels.h row_rout2)
@@ -153,7 +155,7 @@ static int keff_check(const char *fn, const double *d_table, int nbins)
 //   mm_part [nmm][2], mm_send [world][2], mm_recv [world][2] (f32).
 // One GPU (s == NULL or world 1): the rank's results are written straight to the receive buffers.  A slab: two small all-gathers
 // through the transport's all-to-all (each rank sends the same block to every peer), behind the compute stream's work.
-static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table)
+static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table, double kappa)
 {
     fb_ctx *c = m->c;
     const int world = c->world;
@@ -203,13 +205,14 @@ static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, co
     HIPCHK(hipGetLastError());
     if (xchg && (rc = gather((const float *)hsend, (float *)hrecv, 2 * nh))) return rc;
     hipLaunchKernelGGL(k_keff_table, dim3(1), dim3(256), (size_t)nbins * 16, c->stream, (const double *)hrecv, world, (const float *)mmrecv, nbins,
-                       (double)c->lx / c->nx, (double)c->ly / c->ny, (double)m->nu, d_table);
+                       (double)c->lx / c->nx, (double)c->ly / c->ny, kappa, d_table);
     HIPCHK(hipGetLastError());
     return FB_OK;
 }
 
 // the row pass's outputs: the caller's, or the model's own buffers (keff_fields [2][XL][ny]) for those the caller does not want
-static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, float *zeta, float *grad2)
+// (tr: of the tracer, with its kappa where the table of the vorticity uses nu)
+static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, float *zeta, float *grad2, bool tr = false)
 {
     const size_t n = (size_t)m->c->XL * m->c->ny;
     if ((!zeta || !grad2) && !m->keff_fields && hipMalloc((void **)&m->keff_fields, 2 * n * sizeof(float)) != hipSuccess) {
@@ -219,8 +222,8 @@ static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, floa
     if (!zeta) zeta = m->keff_fields;
     if (!grad2) grad2 = m->keff_fields + n;
     int rc;
-    if ((rc = record(m, s, REC_KEFF, zeta, grad2))) return rc;
-    return keff_finish(m, s, nbins, zeta, grad2, d_table);
+    if ((rc = record(m, s, REC_KEFF, zeta, grad2, tr))) return rc;
+    return keff_finish(m, s, nbins, zeta, grad2, d_table, tr ? (double)m->kappa : (double)m->nu);
 }
 
 // ---- balanced pressure (REC_PRES): there and back ----
@@ -326,35 +329,43 @@ extern "C" int fb_spectra_shells(int nx, int ny, float lx, float ly, int *nshell
     return FB_OK;
 }
 
-// Per column group: the state into field 0 of rec_work, k_spectra_deriv, the backward x pass of the four fields (on a slab their
-// exchange); the step's fused row pass without a source (c2r of the four fields, J = -u zeta_x - v zeta_y, its forward y transform)
-// into the record workspace (one GPU: field 4 of rec_work; a slab: rec_send as [dst][XL][ncols] of the active groups, one all-to-all
-// back into field 0 of rec_work = [nx][ncols]); the forward x pass as state_in runs it; the state once more (one GPU: field 0, a
-// slab: field 1); k_spectra_gather over this rank's columns; on a slab the ranks' partial sums all-gathered as keff_finish gathers
-// its histograms; k_spectra_table.  spec_red: [world][nshells][6] to send (a slab of several ranks), [world][nshells][6] received.
-static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
+// The advective tendency r2c(-u a_x - v a_y) of a scalar exactly as a stage of the step forms it, through the record workspace.  Per
+// column group `fill(g, G, z, n)` writes the four derivative spectra a_x, a_y, grady psi, gradx psi into the fields 0..3 of rec_work
+// (the workspace is grown to what this path needs first); then the backward x pass of the four fields (on a slab their exchange);
+// the step's fused row pass without a source (c2r of the four fields, J = -u a_x - v a_y, its forward y transform) into the record
+// workspace (one GPU: field 4 of rec_work; a slab: rec_send as [dst][XL][ncols] of the active groups, one all-to-all back into
+// field 0 of rec_work = [nx][ncols]); the forward x pass of the active groups as state_in runs it.  advect_out(m, s, g): where group
+// g's result lies, in the 3-pass layout.  The groups of frozen columns get none: every mode of theirs is masked.
+static cf *advect_out(fb_model *m, fb_slab *s, int g)
+{
+    return s && m->c->world > 1 ? m->rec_work[g] : m->rec_work[g] + 4 * grp_elems(m->c, m->c->grp[g]);
+}
+
+static int advect_workspace(fb_model *m, fb_slab *s)
 {
     fb_ctx *c = m->c;
-    const int world = c->world;
-    const bool xchg = s && world > 1;
-    const SpecGrid sg = spec_grid(c->nx, c->ny, c->lx, c->ly);
-    const int nshells = spec_nshells(sg);
-    const size_t np = (size_t)nshells * SPEC_SUMS;
+    const bool xchg = s && c->world > 1;
     int rc;
-    if (!m->spec_red && hipMalloc((void **)&m->spec_red, (xchg ? 2 : 1) * (size_t)world * np * sizeof(double)) != hipSuccess) {
-        m->spec_red = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t n = grp_elems(c, c->grp[g]);
+        if (n == 0) continue;
+        if ((rc = rec_grow(&m->rec_work[g], &m->rec_work_nf[g], n, xchg ? 4 : 5)) || (xchg && (rc = rec_grow(&m->rec_send[g], &m->rec_send_nf[g], n, 4)))) return rc;
     }
-    const SpecCoef coef = make_coef(c);
+    return FB_OK;
+}
+
+template <class Fill> static int record_advect(fb_model *m, fb_slab *s, Fill fill)
+{
+    fb_ctx *c = m->c;
+    const bool xchg = s && c->world > 1;
+    int rc;
+    if ((rc = advect_workspace(m, s))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
         const ColGroup &G = c->grp[g];
         const size_t n = grp_elems(c, G);
         if (n == 0) continue;
-        if ((rc = rec_grow(&m->rec_work[g], &m->rec_work_nf[g], n, xchg ? 4 : 5)) || (xchg && (rc = rec_grow(&m->rec_send[g], &m->rec_send_nf[g], n, 4)))) return rc;
         cf *z = m->rec_work[g];
-        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
-        hipLaunchKernelGGL(k_spectra_deriv, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
+        if ((rc = fill(g, G, z, n))) return rc;
         if ((rc = launch_col_block<+1>(c, G, z, 4, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 4, (long)n))) return rc;
     }
     RowArgs a = row_args_base(c);
@@ -378,6 +389,41 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
         }
         if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
     }
+    for (int k = 0; k < c->nact; ++k) {
+        const ColGroup &G = c->grp[k];
+        if (grp_elems(c, G) == 0) continue;
+        cf *nh = advect_out(m, s, k);
+        if ((rc = launch_col_strided<-1>(c, G, nh, 1, 0)) || (rc = launch_col_block<-1>(c, G, nh, 1, 0))) return rc;
+    }
+    return FB_OK;
+}
+
+// record_advect of the vorticity itself (per column group: the state into field 0 of rec_work, k_spectra_deriv); the state once more
+// (one GPU: field 0, a slab: field 1); k_spectra_gather over this rank's columns; on a slab the ranks' partial sums all-gathered as
+// keff_finish gathers its histograms; k_spectra_table.  spec_red: [world][nshells][6] to send (a slab of several ranks),
+// [world][nshells][6] received.
+static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
+{
+    fb_ctx *c = m->c;
+    const int world = c->world;
+    const bool xchg = s && world > 1;
+    const SpecGrid sg = spec_grid(c->nx, c->ny, c->lx, c->ly);
+    const int nshells = spec_nshells(sg);
+    const size_t np = (size_t)nshells * SPEC_SUMS;
+    int rc;
+    if (!m->spec_red && hipMalloc((void **)&m->spec_red, (xchg ? 2 : 1) * (size_t)world * np * sizeof(double)) != hipSuccess) {
+        m->spec_red = nullptr;
+        return fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    const SpecCoef coef = make_coef(c);
+    auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
+        int r;
+        if ((r = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return r;
+        hipLaunchKernelGGL(k_spectra_deriv, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+        HIPCHK(hipGetLastError());
+        return FB_OK;
+    };
+    if ((rc = record_advect(m, s, fill))) return rc;
     SpecGroups sgr;
     memset(&sgr, 0, sizeof(sgr));
     for (int k = 0; k < c->ngroups; ++k) {
@@ -385,8 +431,7 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
         const size_t n = grp_elems(c, G);
         if (n == 0) continue;
         const bool active = k < c->nact;
-        cf *nh = xchg ? m->rec_work[k] : m->rec_work[k] + 4 * n, *st = xchg ? m->rec_work[k] + n : m->rec_work[k];
-        if (active && ((rc = launch_col_strided<-1>(c, G, nh, 1, 0)) || (rc = launch_col_block<-1>(c, G, nh, 1, 0)))) return rc;
+        cf *nh = advect_out(m, s, k), *st = xchg ? m->rec_work[k] + n : m->rec_work[k];
         if ((rc = m->xpass != XP_COLS ? full_export_state(m, st) : state_convert(c, G, m->gb[k].ZA, st, false))) return rc;
         const int q = sgr.ng++;
         sgr.a[q] = st; sgr.nh[q] = active ? nh : nullptr; sgr.ncols[q] = G.ncols; sgr.ky0[q] = G.ky0;
@@ -501,4 +546,181 @@ extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table)
     if (!d_table) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL table");
     SLAB_READY(s);
     return record_spectra(s->m, s, d_table);
+}
+
+// ---- the passive tracer (kernels: fb_tracer.h) ----
+static void tracer_free(fb_model *m)
+{
+    for (int g = 0; g < 3; ++g) {
+        cf **arr[] = {&m->tr_c0[g], &m->tr_c1[g], &m->tr_acc[g]};
+        for (cf **p : arr) if (*p) { hipFree(*p); *p = nullptr; }
+    }
+    m->tracer = false;
+}
+
+// One RK stage of the tracer, at the top of the step's stage `stage`: the vorticity's state of this stage is vort_c0 (ZA) at stage 0
+// and the stage state ZB afterwards (k_col_mid and k_col_full store it at every stage below 3), the tracer's likewise.  Launches per
+// column group: k_tracer_vstate (where the state arrays are not in the 3-pass layout), k_tracer_deriv; record_advect; per group of
+// active columns k_tracer_update.  On a slab the exchanges are record_advect's, on the streams and events the records use.
+static int tracer_stage(fb_model *m, fb_slab *s, int stage)
+{
+    fb_ctx *c = m->c;
+    const SpecCoef coef = make_coef(c);
+    int rc;
+    auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
+        const bool staged = stage > 0 && g < c->nact;       // the frozen columns' state is the base at every stage
+        const cf *v0 = m->gb[g].ZA, *v1 = staged ? m->gb[g].ZB : m->gb[g].ZA;
+        cf *vx = z + 2 * n;                                  // field 2: read by k_tracer_deriv before it writes grady psi there
+        if (m->xpass != XP_COLS) {
+            hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, v0, v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
+            v0 = v1 = vx;
+        } else if (state_tm(c)) {
+            hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, vx, G.ncols, c->N1, c->N2, G.ky0);
+            v0 = v1 = vx;
+        }
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_tracer_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, v0, v1, (const cf *)m->tr_c0[g],
+                           (const cf *)(staged ? m->tr_c1[g] : m->tr_c0[g]), z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+        HIPCHK(hipGetLastError());
+        return FB_OK;
+    };
+    if ((rc = record_advect(m, s, fill))) return rc;
+    for (int g = 0; g < c->nact; ++g) {
+        const ColGroup &G = c->grp[g];
+        const int ncr = 16 * G.nct_active;
+        if (grp_elems(c, G) == 0 || ncr == 0) continue;
+        const dim3 grid(grid_for(c, (size_t)c->nx * ncr / 2)), blk(256);
+        const cf *jh = advect_out(m, s, g);
+        cf *c0 = m->tr_c0[g], *c1 = m->tr_c1[g], *ac = m->tr_acc[g];
+        switch (stage) {
+        case 0: hipLaunchKernelGGL((k_tracer_update<0>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        case 1: hipLaunchKernelGGL((k_tracer_update<1>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        case 2: hipLaunchKernelGGL((k_tracer_update<2>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        default: hipLaunchKernelGGL((k_tracer_update<3>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return FB_OK;
+}
+
+// readField + r2c of the tracer as state_in takes the vorticity (ROW_FWD, the transpose on a slab, the forward x pass), through the
+// record workspace into the tracer's base arrays; d_rows == NULL removes the tracer.  The vorticity, its derivative fields and
+// `primed` stay as they are.  The captured step is dropped and the next fb_model_step starts with an eager step, which launches every
+// kernel of the longer step once before it is captured (launch_lds).
+static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
+{
+    fb_ctx *c = m->c;
+    const bool xchg = s && c->world > 1;
+    int rc;
+    model_drop_graph(m);
+    m->warmed = false;
+    if (!d_rows) {
+        if (m->tracer) HIPCHK(hipStreamSynchronize(c->stream));
+        tracer_free(m);
+        return FB_OK;
+    }
+    if ((rc = advect_workspace(m, s))) return rc;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t n = grp_elems(c, c->grp[g]);
+        if (n == 0) continue;
+        if ((rc = rec_alloc(&m->tr_c0[g], n)) || (g < c->nact && ((rc = rec_alloc(&m->tr_c1[g], n)) || (rc = rec_alloc(&m->tr_acc[g], n))))) {
+            tracer_free(m);
+            return rc;
+        }
+        if (g < c->nact) {                                  // pad columns and the columns beyond the last active tile stay zero
+            HIPCHK(hipMemsetAsync(m->tr_c1[g], 0, n * sizeof(cf), c->stream));
+            HIPCHK(hipMemsetAsync(m->tr_acc[g], 0, n * sizeof(cf), c->stream));
+        }
+    }
+    RowArgs a = row_args_base(c);
+    a.rin = d_rows;
+    if (xchg) {
+        const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
+        a.T = view_slab(c, ts, 1);
+    } else {
+        HIPCHK(hipMemsetAsync(m->rec_work[0], 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
+        a.T = view_single(c, m->rec_work[0], 0);
+    }
+    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+    if (xchg) {
+        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+        for (int g = 0; g < c->ngroups; ++g) {
+            const size_t blk = (size_t)c->XL * c->grp[g].ncols;
+            if ((rc = slab_xchg(s, m->rec_send[g], m->rec_work[g], blk, 0, blk))) return rc;
+        }
+        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
+    }
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        cf *t = m->rec_work[g];
+        if ((rc = launch_col_strided<-1>(c, G, t, 1, 0)) || (rc = launch_col_block<-1>(c, G, t, 1, 0))) return rc;
+        HIPCHK(hipMemcpyAsync(m->tr_c0[g], t, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+    }
+    m->kappa = kappa;
+    m->tracer = true;
+    return FB_OK;
+}
+
+static int kappa_check(const char *fn, float kappa)
+{
+    if (!(kappa >= 0.0f) || !std::isfinite(kappa)) return fail(FB_EINVAL, std::string(fn) + ": kappa must be finite and >= 0");
+    return FB_OK;
+}
+
+extern "C" int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_set_tracer: NULL model");
+    int rc;
+    if ((rc = kappa_check("fb_model_set_tracer", kappa))) return rc;
+    NEED_SINGLE(m->c);
+    return tracer_in(m, nullptr, d_c_real, kappa);
+}
+
+extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real)
+{
+    if (!m || !d_c_real) return fail(FB_EINVAL, "fb_model_get_tracer: NULL");
+    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer: no tracer is set");
+    NEED_SINGLE(m->c);
+    return record(m, nullptr, REC_VORT, d_c_real, nullptr, true);
+}
+
+extern "C" int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: NULL model");
+    int rc;
+    if ((rc = keff_check("fb_model_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
+    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: no tracer is set");
+    NEED_SINGLE(m->c);
+    return record_keff(m, nullptr, nbins, d_table, d_c, d_grad2, true);
+}
+
+// collective on a slab of several ranks, as fb_slab_set_vort_local
+extern "C" int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_set_tracer_local: NULL slab");
+    int rc;
+    if ((rc = kappa_check("fb_slab_set_tracer_local", kappa))) return rc;
+    SLAB_READY(s);
+    return tracer_in(s->m, s, d_rows, kappa);
+}
+
+extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows)
+{
+    if (!s || !d_rows) return fail(FB_EINVAL, "fb_slab_get_tracer_local: NULL");
+    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_local: no tracer is set");
+    SLAB_READY(s);
+    return record(s->m, s, REC_VORT, d_rows, nullptr, true);
+}
+
+// collective, as fb_slab_get_eddy_diffusivity
+extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: NULL slab");
+    int rc;
+    if ((rc = keff_check("fb_slab_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
+    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: no tracer is set");
+    SLAB_READY(s);
+    return record_keff(s->m, s, nbins, d_table, d_c_rows, d_grad2_rows, true);
 }

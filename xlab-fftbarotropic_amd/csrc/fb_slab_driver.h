@@ -382,8 +382,10 @@ extern "C" int fb_slab_step(fb_slab *s, int nsteps)
     }
     if (s->ncg > 1 && s->m->primed == 1 && (rc = slab_groups_prologue(s))) return rc;
     for (int n = 0; n < nsteps; ++n)
-        for (int k = 0; k < 4; ++k)                         // main.cpp:288-317
+        for (int k = 0; k < 4; ++k) {                       // main.cpp:288-317
+            if (s->m->tracer && (rc = tracer_stage(s->m, s, k))) return rc;
             if ((rc = slab_stage(s, k))) return rc;
+        }
     return FB_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "fb_kernels.h"
 #include "fb_keff.h"
 #include "fb_spectra.h"
+#include "fb_tracer.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1022,6 +1023,12 @@ struct fb_model {
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
     // tiles only (the backward strided pass on the active tiles comes next); 2: finished on every tile (ready for the row pass)
     int primed;
+    // the passive tracer (fb_tracer.h; host side in fb_record.h): per column group in the 3-pass layout [nx][ncols] the base c_c, and
+    // for the groups of active columns the stage state and the RK accumulator; NULL without a tracer.  Never in the record workspace:
+    // a record taken between two steps overwrites that.
+    cf *tr_c0[3], *tr_c1[3], *tr_acc[3];
+    float kappa;
+    bool tracer, graph_tracer;       // a tracer is set; the captured step holds the tracer's stages
 };
 
 static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool phase_flow)
@@ -1060,6 +1067,8 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
 }
 
 static void model_drop_graph(fb_model *m);
+static void tracer_free(fb_model *m);
+static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_record.h
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1079,6 +1088,7 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->keff_red) hipFree(m->keff_red);
     if (m->pres_ref) hipFree(m->pres_ref);
     if (m->spec_red) hipFree(m->spec_red);
+    tracer_free(m);
     delete m;
     return FB_OK;
 }
@@ -1090,6 +1100,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
     if (hbm) {
         size_t n = m->src ? (size_t)c->XL * c->ny * 4 : 0;
         for (int g = 0; g < c->ngroups; ++g) n += (c->world > 1 ? (g < c->nact ? 13 : 11) : 8) * grp_elems(c, c->grp[g]) * sizeof(cf);
+        for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
         *hbm = n;
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;
@@ -1246,6 +1257,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
     GroupBufs &B = m->gb[0];
     for (int s = 0; s < nsteps; ++s) {
         for (int k = 0; k < 4; ++k) {
+            if (m->tracer && (rc = tracer_stage(m, nullptr, k))) return rc;       // the tracer's stage k, from the state this stage starts from
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
             PROF_BEGIN(1);
             if ((rc = launch_fused_row(m, 0, c->XL))) return rc;
@@ -1293,7 +1305,7 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
     if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
     int rc;
     if (!m->warmed) { if ((rc = model_step_impl(m, 1, nullptr))) return rc; m->warmed = true; --nsteps; }
-    if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream)) model_drop_graph(m);
+    if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream || m->graph_tracer != m->tracer)) model_drop_graph(m);
     if (!m->graph_exec) {
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -1304,7 +1316,7 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
         e = hipGraphInstantiate(&m->graph_exec, g, nullptr, nullptr, 0);
         hipGraphDestroy(g);
         HIPCHK(e);
-        m->graph_src = m->src; m->graph_stream = c->stream;
+        m->graph_src = m->src; m->graph_stream = c->stream; m->graph_tracer = m->tracer;
         // the captured step has NOT executed: replay it below like the others
     }
     for (int s = 0; s < nsteps; ++s) HIPCHK(hipGraphLaunch(m->graph_exec, c->stream));

@@ -34,6 +34,11 @@
 // --dump-spectra (no reference counterpart) adds spectra_step_N.bin to every record: the shell spectra and cascade fluxes of
 // fb_model_get_spectra, raw little-endian float64 [nshells][10] (nshells from fb_spectra_shells), after pres and before eddy_diffusivity
 // in ./log; on one GPU and with --world P, where rank 0 alone writes it.
+// --tracer FILE [--tracer-kappa K] (no reference counterpart, K >= 0, default 0) reads FILE from the input directory as the initial
+// field is read and sets it as the model's passive tracer (fb_model_set_tracer) with the diffusivity K; every record gains
+// tracer_step_N.bin, the last field file of a record in ./log, and with --dump-eddy-diffusivity tracer_eddy_diffusivity_step_N.bin
+// after it (fb_model_get_tracer_eddy_diffusivity, [N][9] float64 as eddy_diffusivity); on one GPU and with --world P, where rank 0
+// alone writes the table.
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -75,6 +80,7 @@ struct Config {
     bool dump_pres = false; float pres_rho = 1.0f, pres_f = 1e-5f;                 // balanced pressure (invert_pres.cpp:135-185); rho, f: configuration.hpp:10-11
     int pres_ref_x = 0, pres_ref_y = 0;                                            // its reference point (invert_pres.cpp:67-79)
     bool dump_spectra = false;                                                     // shell spectra and cascade fluxes (no reference counterpart)
+    std::string tracer_file; float tracer_kappa = 0.0f;                            // the passive tracer's initial field and diffusivity (no reference counterpart)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -217,10 +223,11 @@ struct RecordWriter {
     std::thread th; std::mutex mu; std::condition_variable cv;
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
-    void *e_copy[2] = {nullptr, nullptr}; float *h[2][10] = {};
+    void *e_copy[2] = {nullptr, nullptr}; float *h[2][11] = {};
     double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
     double *hs[2] = {nullptr, nullptr}; size_t spectra_bytes = 0;                      // the spectra table (item buffer SPECTRA_TABLE), rank 0 only
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3 };
+    double *hk[2] = {nullptr, nullptr};                                                // the tracer's eddy diffusivity table (item buffer TRACER_KEFF_TABLE, table_bytes), rank 0 only
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -244,10 +251,10 @@ struct RecordWriter {
             char fn[1024];
             for (size_t i = 0; i < items.size(); ++i) {                                // main.cpp:268-278, :156-235
                 snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), items[i].first, job.step);
-                if (items[i].second == KEFF_TABLE || items[i].second == SPECTRA_TABLE) {
+                if (items[i].second <= KEFF_TABLE) {
                     if (!lead) continue;
-                    const bool keff = items[i].second == KEFF_TABLE;
-                    const double *tab = keff ? ht[job.set] : hs[job.set];
+                    const bool keff = items[i].second != SPECTRA_TABLE;
+                    const double *tab = items[i].second == KEFF_TABLE ? ht[job.set] : keff ? hk[job.set] : hs[job.set];
                     const size_t tb = keff ? table_bytes : spectra_bytes;
                     FILE *f = fopen(fn, "wb");
                     if (!f || fwrite(tab, 1, tb, f) != tb) { perror("Write field."); std::exit(1); }
@@ -273,7 +280,7 @@ struct RecordWriter {
             const double this_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
             busy_s += this_s;
             if (this_s > slowest_s) slowest_s = this_s;
-            for (const auto &it : items) if (it.second != KEFF_TABLE && it.second != SPECTRA_TABLE) bytes += floats * sizeof(float);
+            for (const auto &it : items) if (it.second > KEFF_TABLE) bytes += floats * sizeof(float);
             lk.lock();
             writing = false;
             set_free[job.set] = true;
@@ -311,6 +318,9 @@ struct Engine {
     virtual void get_eddy_diffusivity(int nbins, double *d_table) = 0;                // --dump-eddy-diffusivity, on the compute stream (collective)
     virtual void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) = 0;   // --dump-pressure, on the compute stream (collective)
     virtual void get_spectra(double *d_table) = 0;                                    // --dump-spectra, on the compute stream (collective)
+    virtual void set_tracer(const float *d, float kappa) = 0;                         // --tracer (collective)
+    virtual void get_tracer(float *d) = 0;
+    virtual void get_tracer_eddy_diffusivity(int nbins, double *d_table) = 0;         // --tracer with --dump-eddy-diffusivity (collective)
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -361,6 +371,12 @@ struct SingleEngine : Engine {
         must(fb_model_get_pressure(model, rho, f, ref_x, ref_y, d_pres), "fb_model_get_pressure");
     }
     void get_spectra(double *d_table) override { must(fb_model_get_spectra(model, d_table), "fb_model_get_spectra"); }
+    void set_tracer(const float *d, float kappa) override { must(fb_model_set_tracer(model, d, kappa), "fb_model_set_tracer"); }
+    void get_tracer(float *d) override { must(fb_model_get_tracer(model, d), "fb_model_get_tracer"); }
+    void get_tracer_eddy_diffusivity(int nbins, double *d_table) override
+    {
+        must(fb_model_get_tracer_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_tracer_eddy_diffusivity");
+    }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -406,6 +422,12 @@ struct SlabEngine : Engine {
         must(fb_slab_get_pressure_local(sl, rho, f, ref_x, ref_y, d_pres), "fb_slab_get_pressure_local");
     }
     void get_spectra(double *d_table) override { must(fb_slab_get_spectra(sl, d_table), "fb_slab_get_spectra"); }
+    void set_tracer(const float *d, float kappa) override { must(fb_slab_set_tracer_local(sl, d, kappa), "fb_slab_set_tracer_local"); }
+    void get_tracer(float *d) override { must(fb_slab_get_tracer_local(sl, d), "fb_slab_get_tracer_local"); }
+    void get_tracer_eddy_diffusivity(int nbins, double *d_table) override
+    {
+        must(fb_slab_get_tracer_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_tracer_eddy_diffusivity");
+    }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -419,9 +441,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     must(fb_stream_create(&copy), "stream");
     for (void **e : {&e_rec, &e_h2d, &e_src}) must(fb_event_create(e), "event");
     // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt);
-    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure)
-    constexpr int NB = 10;
-    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres};
+    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure); 10 = tracer (--tracer)
+    constexpr int NB = 11;
+    const bool tracer = !cfg.tracer_file.empty();
+    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres, tracer};
     float *d_in = nullptr, *d_out[NB] = {};
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
     for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
@@ -429,6 +452,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t table_bytes = cfg.dump_keff ? (size_t)cfg.keff_bins * 9 * sizeof(double) : 0;
     double *d_table = nullptr;
     if (cfg.dump_keff) must(fb_malloc((void **)&d_table, table_bytes), "fb_malloc");
+    double *d_ttable = nullptr;                                                        // the tracer's table (--tracer with --dump-eddy-diffusivity)
+    if (cfg.dump_keff && tracer) must(fb_malloc((void **)&d_ttable, table_bytes), "fb_malloc");
     // the spectra table (--dump-spectra): likewise
     int nshells = 0;
     if (cfg.dump_spectra) must(fb_spectra_shells(N, N, cfg.LX, cfg.LY, &nshells), "fb_spectra_shells");
@@ -444,6 +469,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         must(fb_event_create(&writer.e_copy[b]), "event");
         for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
         if (cfg.dump_keff && lead) must(fb_malloc_host((void **)&writer.ht[b], table_bytes), "fb_malloc_host");
+        if (cfg.dump_keff && tracer && lead) must(fb_malloc_host((void **)&writer.hk[b], table_bytes), "fb_malloc_host");
         if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
@@ -454,6 +480,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (cfg.dump_pres) writer.items.push_back({"pres", 9});                            // invert_pres.cpp:187
     if (cfg.dump_spectra) writer.items.push_back({"spectra", RecordWriter::SPECTRA_TABLE});
     if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
+    if (tracer) writer.items.push_back({"tracer", 10});
+    if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
     writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
@@ -462,9 +490,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     std::vector<float> zeros(floats, 0.0f);                                            // vort_src before the first input (main.cpp:110 leaves it uninitialised)
     char filename[1024];
 
-    snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.init_file.c_str());
-    {   // readField (main.cpp:143-144) into a pinned buffer; a rank reads its rows of the file (fieldio.cpp:21-33 reads all of it)
-        float *h0 = writer.h[0][0];
+    // readField (main.cpp:143-144) into a pinned buffer and on into d_in; a rank reads its rows of the file (fieldio.cpp:21-33 reads all of it)
+    auto read_rows = [&](float *h0) {
         if (P == 1) must(fb_read_field(filename, h0, floats), "readField");
         else {
             const int fd = open(filename, O_RDONLY);
@@ -477,7 +504,9 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         must(fb_memcpy_h2d_async(copy, d_in, h0, floats * sizeof(float)), "h2d");
         must(fb_event_record(e_h2d, copy), "record");
         eng->wait(e_h2d);
-    }
+    };
+    snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.init_file.c_str());
+    read_rows(writer.h[0][0]);
     SourceFeed *feedp = new SourceFeed;
     SourceFeed &feed = *feedp;
     const std::string fifo = (P == 1 || cfg.vort_src_filename.empty()) ? cfg.vort_src_filename : cfg.vort_src_filename + "." + std::to_string(rank);
@@ -487,6 +516,14 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     eng->set_vort(d_in);                                                               // main.cpp:256
     eng->record(e_src);                                                                // d_in is free again behind this
     must(fb_event_synchronize(e_h2d), "sync");                                         // the pinned buffer goes back to the record path
+    if (tracer) {                                                                      // the tracer's field, as the initial field was read
+        snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.tracer_file.c_str());
+        must(fb_stream_wait_event(copy, e_src), "wait");                               // set_vort has read d_in
+        read_rows(writer.h[0][10]);
+        eng->set_tracer(d_in, cfg.tracer_kappa);
+        eng->record(e_src);
+        must(fb_event_synchronize(e_h2d), "sync");
+    }
 
     // [timing] ("add steps/s + GB/s summary"; the reference prints no timing, main.cpp:262-264).  The step loop is
     // never synchronised for it: time-stamped events on the compute stream bracket the stretches BETWEEN record steps -- a stretch ends
@@ -528,12 +565,15 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (cfg.dump_pres) eng->get_pressure(cfg.pres_rho, cfg.pres_f, cfg.pres_ref_x, cfg.pres_ref_y, d_out[9]);
             if (cfg.dump_spectra) eng->get_spectra(d_spectra);
             if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
+            if (tracer) eng->get_tracer(d_out[10]);
+            if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
             for (int i = 0; i < NB; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
             if (writer.ht[set]) must(fb_memcpy_d2h_async(copy, writer.ht[set], d_table, table_bytes), "d2h");
             if (writer.hs[set]) must(fb_memcpy_d2h_async(copy, writer.hs[set], d_spectra, spectra_bytes), "d2h");
+            if (writer.hk[set]) must(fb_memcpy_d2h_async(copy, writer.hk[set], d_ttable, table_bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -595,11 +635,13 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (feed_done) delete feedp;
     fb_free(d_in); for (auto p : d_out) if (p) fb_free(p);
     if (d_table) fb_free(d_table);
+    if (d_ttable) fb_free(d_ttable);
     if (d_spectra) fb_free(d_spectra);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
         if (writer.hs[b]) fb_free_host(writer.hs[b]);
+        if (writer.hk[b]) fb_free_host(writer.hk[b]);
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -618,7 +660,7 @@ int main(int argc, char *args[])
                                     {"no-timing", 0, 0, 17}, {"dump-grad-vort", 0, 0, 18}, {"dump-dvortdt", 0, 0, 19}, {"record-buffers", 1, 0, 20},
                                     {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23},
                                     {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
-                                    {"dump-spectra", 0, 0, 29},
+                                    {"dump-spectra", 0, 0, 29}, {"tracer", 1, 0, 30}, {"tracer-kappa", 1, 0, 31},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -659,6 +701,14 @@ int main(int argc, char *args[])
         }
         case 24: cfg.dump_pres = true; break;            // pres_step_N.bin (also with --world P)
         case 29: cfg.dump_spectra = true; break;         // spectra_step_N.bin (also with --world P)
+        case 30: cfg.tracer_file = optarg; break;       // tracer_step_N.bin (also with --world P)
+        case 31: {
+            char *end = nullptr;
+            const float v = strtof(optarg, &end);
+            if (!*optarg || *end || !(v >= 0.0f) || v > 3.0e38f) { fprintf(stderr, "--tracer-kappa: a finite number >= 0\n"); return 2; }
+            cfg.tracer_kappa = v;
+            break;
+        }
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)

@@ -289,6 +289,35 @@ class EngineSlab:
         self.synchronize()
         return table
 
+    def set_tracer_local(self, rows, kappa=0.0):
+        """This rank's rows of the passive tracer and its diffusivity (fb_slab_set_tracer_local); rows=None removes the tracer.
+        Collective."""
+        if rows is None:
+            self.B.check(self.L.fb_slab_set_tracer_local(self._h, None, 0.0))
+        else:
+            a = self._rows(rows)
+            self.B.check(self.L.fb_slab_set_tracer_local(self._h, C.c_void_p(a.data_ptr()), float(kappa)))
+        self.synchronize()
+
+    def tracer_local(self):
+        """This rank's rows of the passive tracer (fb_slab_get_tracer_local).  Collective."""
+        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
+        self.B.check(self.L.fb_slab_get_tracer_local(self._h, C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
+    def tracer_eddy_diffusivity(self, nbins=256, fields=False):
+        """eddy_diffusivity() of the passive tracer, with its kappa in the place of nu (fb_slab_get_tracer_eddy_diffusivity); with
+        fields=True also this rank's rows (c, |grad c|^2).  Collective."""
+        t = self.torch
+        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
+        c, g = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2)) if fields else (None, None)
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
+        t.cuda.current_stream().synchronize()                   # the engine writes the table on ITS stream
+        self.B.check(self.L.fb_slab_get_tracer_eddy_diffusivity(self._h, nbins, ptr(table), ptr(c), ptr(g)))
+        self.synchronize()
+        return (table, c, g) if fields else table
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
