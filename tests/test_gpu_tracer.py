@@ -266,7 +266,7 @@ def test_records_and_tracer_do_not_disturb_each_other():
     assert _same(_np(c.tracer()), before)
 
 
-def _slab_run(nx, ny, world, steps, v0, c0, kappa, env, nbins):
+def _slab_run(nx, ny, world, steps, v0, c0, kappa, env, nbins, src=None, **model_kw):
     import threading
     S = _slab()
     hub = S.local_hub(world)
@@ -274,9 +274,11 @@ def _slab_run(nx, ny, world, steps, v0, c0, kappa, env, nbins):
 
     def work(r):
         try:
-            m = S.EngineSlab(nx, ny, rank=r, world=world, transport=hub)
+            m = S.EngineSlab(nx, ny, rank=r, world=world, transport=hub, **model_kw)
             try:
                 m.set_vort_local(S.local_rows(v0, r, world))
+                if src is not None:
+                    m.set_source_local(S.local_rows(src, r, world))
                 m.set_tracer_local(S.local_rows(c0, r, world), kappa)
                 m.step(steps)
                 tr = m.tracer_local().cpu().numpy()
@@ -325,27 +327,41 @@ def _col_groups(nx, ny, world, env):
                 os.environ[k] = v
 
 
+# The cases of NOISY run the inputs of the tracer's path matrix (tracer_numpy.noisy_inputs: never-dealiased noise on both fields, a
+# vorticity source, the recipe's dt) in the place of Kuo2004 and the gaussian: 256^2 and 384 x 192 keep the state in the 3-pass layout
+# (N2 < 32; 384: N1 = 24), 128 x 4096 has k_rowq on every rank.
+NOISY = {(2, 256, 256), (4, 384, 192), (2, 128, 4096)}
+
+
 # groups: the plan each case gets.  The default plan has one active column group at every size here; the stage pipelined by column
 # groups (slab_stage_groups) is forced at 8192 x 256 on 2, 4 and 8 ranks.  8192 x 256 has frozen columns at every world size.
 @pytest.mark.parametrize("world,nx,ny,env,groups", [(2, 1024, 1024, {}, 1), (4, 1024, 1024, {}, 1), (8, 1024, 1024, {}, 1),
                                                     (2, 8192, 256, {}, 1), (4, 8192, 256, {}, 1), (8, 8192, 256, {}, 1),
                                                     (2, 8192, 256, {"FB_SLAB_COL_GROUPS": "2"}, 2), (4, 8192, 256, {"FB_SLAB_COL_GROUPS": "2"}, 2),
-                                                    (8, 8192, 256, {"FB_SLAB_COL_GROUPS": "2"}, 2)])
+                                                    (8, 8192, 256, {"FB_SLAB_COL_GROUPS": "2"}, 2),
+                                                    (2, 256, 256, {}, 1), (4, 384, 192, {}, 1), (2, 128, 4096, {}, 1)])
 def test_slab_equals_single_gpu(world, nx, ny, env, groups):
     """ranks as threads on one GPU: tracer_local() over the ranks equals the one-GPU tracer() bit for bit after 10 steps, so does the
     vorticity; the tracer's eddy diffusivity table has the one-GPU counts (columns 0-4) on every rank, columns 5-8 to 1e-9"""
     import xlab_fftbarotropic_amd as X
     assert _col_groups(nx, ny, world, env) == groups
-    v0 = X.make_field("kuo2004", nx, ny)
-    c0 = _offset_gaussian(nx, ny)
     nbins, kappa = 64, 20.0
-    one = X.Model(nx, ny)
+    if (world, nx, ny) in NOISY:
+        import tracer_numpy as T
+        v0, c0, src = T.noisy_inputs(nx, ny, 3e-2)
+        kw = {"nu": T.RECIPE_NU, "dt": T.recipe_dt(nx, ny)}
+    else:
+        v0, c0, src, kw = X.make_field("kuo2004", nx, ny), _offset_gaussian(nx, ny), None, {}
+    one = X.Model(nx, ny, **kw)
     one.set_vort(v0)
+    if src is not None:
+        one.set_source(src)
     one.set_tracer(c0, kappa=kappa)
     one.step(10)
     wt, wv, wk = _np(one.tracer()), _np(one.vort()), _np(one.tracer_eddy_diffusivity(nbins))
     one.close()
-    out = _slab_run(nx, ny, world, 10, v0, c0, kappa, env, nbins)
+    assert np.isfinite(wt).all() and not _same(wt, c0)
+    out = _slab_run(nx, ny, world, 10, v0, c0, kappa, env, nbins, src, **kw)
     tr = np.concatenate([o[0] for o in out], axis=0)
     vo = np.concatenate([o[1] for o in out], axis=0)
     again = np.concatenate([o[3] for o in out], axis=0)
