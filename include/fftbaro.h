@@ -227,6 +227,34 @@ int fb_model_get_spectra(fb_model *m, double *d_table);
 /* host logic, no GPU needed: the number of shells, floor(sqrt((pi nx / Lx)^2 + (pi ny / Ly)^2) / dk + 0.5) + 1 (the corner mode lies in
  * the last shell); FB_EINVAL for a NULL pointer, non-positive lengths or an unsupported size */
 int fb_spectra_shells(int nx, int ny, float lx, float ly, int *nshells);
+/* Azimuthal means about a vortex centre (no reference counterpart: it ships find_min, run by hand on a psi record).  The fields: zeta
+ * as fb_model_get_vort returns it, psi, u, v as fb_model_get_diag returns them, bit for bit; psi is formed for FB_CENTER_PSI_MIN only.
+ * d_center: four device doubles xc, yc, flat index, value.  FB_CENTER_FIXED: the caller's (xc, yc) with 0 <= xc < Lx, 0 <= yc < Ly,
+ * index -1, value 0.  FB_CENTER_PSI_MIN / FB_CENTER_VORT_MAX: the grid point of the smallest psi / largest zeta of the whole domain,
+ * ties to the smallest flat index ny i + j (np.argmin / np.argmax of the flattened [nx][ny] field); xc = i dx, yc = j dy, dx =
+ * (double)Lx / nx, dy = (double)Ly / ny (the context's float32 lengths widened), the value widened.  Per point (i, j), in float64
+ * without contraction: ddx = i dx - xc, minus Lx where ddx > Lx/2, plus Lx where ddx < -Lx/2 (the minimum image), ddy likewise;
+ * r2 = ddx^2 + ddy^2, r = sqrt(r2); the bin b is the integer with (b dr)^2 <= r2 < ((b + 1) dr)^2 (points with b >= nbins take no
+ * part); c1 = ddx / r, s1 = ddy / r (1, 0 at r2 = 0); v_r = u c1 + v s1, v_t = v c1 - u s1; c_m = c_{m-1} c1 - s_{m-1} s1,
+ * s_m = s_{m-1} c1 + c_{m-1} s1.  d_table: device float64 [nbins][12 + 2 nmodes], one row per radial bin, <.> the mean over its points:
+ *   0 r_lo = b dr   1 r_hi = (b + 1) dr [m]   2 n (points)   3 <r>   4 <zeta>   5 <v_t>   6 <v_r>   7 <zeta^2>   8 <v_t^2>   9 <v_r^2>
+ *   10 <v_r zeta>   11 Gamma = dx dy sum_{b' <= b} sum zeta [m^2 s^-1], the circulation inside r_hi, added from bin 0 upwards
+ *   12 + 2 (m - 1), 13 + 2 (m - 1): Re, Im of zeta_m = <zeta e^{-i m theta}> = (<zeta c_m>, -<zeta s_m>), m = 1 .. nmodes
+ * A row with n = 0 has zeros in columns 3-10 and from 12 on.  The eddy quantities are the caller's to form: eddy enstrophy
+ * <zeta^2> - <zeta>^2, eddy vorticity flux <v_r zeta> - <v_r><zeta>, amplitude of wavenumber m 2 |zeta_m| (the differences cancel;
+ * the table keeps the moments).  The counts are exact; the sums are added with float64 atomics and may differ in the last bits from
+ * call to call.  FB_EINVAL before any HIP call: a NULL model, table or centre; an unknown mode; a fixed centre outside the domain or
+ * not finite; nbins outside [2, 4096]; nmodes outside [0, 8]; dr not finite, dr < min(dx, dy), or nbins dr > min(Lx, Ly) / 2 (every
+ * circle lies whole inside the minimum-image cell).  Enqueued on the context stream, no synchronisation, no host round trip; uses
+ * record buffers of the model's own (allocated on first use: two real fields and table-sized reduction buffers) and leaves the
+ * state, the step's buffers, a tracer and a captured step untouched. */
+#define FB_CENTER_FIXED    0   /* the caller's (xc, yc)                                         */
+#define FB_CENTER_PSI_MIN  1   /* grid point of the smallest psi (cyclone's circulation centre) */
+#define FB_CENTER_VORT_MAX 2   /* grid point of the largest zeta                                */
+int fb_model_get_azimuthal(fb_model *m, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table,
+                           double *d_center);
+/* host logic, no GPU needed: the columns of the table, 12 + 2 nmodes; FB_EINVAL for nmodes outside [0, 8] or a NULL pointer */
+int fb_azimuthal_cols(int nmodes, int *ncols);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -293,6 +321,11 @@ int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int re
  * and frozen), the ranks' partial sums are all-gathered through the transport and added in rank order, the running sums of columns 7
  * and 8 are taken after that; collective: every rank calls it */
 int fb_slab_get_spectra(fb_slab *s, double *d_table);
+/* fb_model_get_azimuthal of the whole domain: the full table and the centre on every rank.  The ranks' centre candidates, then their
+ * sums over the rows they own, are all-gathered through the transport; the sums are added in rank order; collective: every rank
+ * calls it */
+int fb_slab_get_azimuthal(fb_slab *s, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table,
+                          double *d_center);
 /* the passive tracer (fb_model_set_tracer) of a slab: this rank's rows [XL][ny] in and out, bit for bit what one GPU computes; the
  * table is that of the whole domain, on every rank, as fb_slab_get_eddy_diffusivity gathers it; all three are collective.  The
  * tracer's stages exchange their fields through the transport beside the step's own exchanges. */

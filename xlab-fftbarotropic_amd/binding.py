@@ -123,6 +123,12 @@ def lib():
     for n in ("fb_model_get_tracer_eddy_diffusivity", "fb_slab_get_tracer_eddy_diffusivity"):
         if hasattr(L, n):
             getattr(L, n).argtypes = [vp, ip, vp, fp, fp]
+    # (likewise the azimuthal-mean record)
+    for n in ("fb_model_get_azimuthal", "fb_slab_get_azimuthal"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, ip, C.c_double, C.c_double, ip, C.c_double, ip, vp, vp]
+    if hasattr(L, "fb_azimuthal_cols"):
+        L.fb_azimuthal_cols.argtypes = [ip, C.POINTER(ip)]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -150,6 +156,7 @@ EXPORTS = [
     "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_get_spectra", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
     "fb_model_set_tracer", "fb_model_get_tracer", "fb_model_get_tracer_eddy_diffusivity", "fb_slab_set_tracer_local", "fb_slab_get_tracer_local", "fb_slab_get_tracer_eddy_diffusivity",
+    "fb_azimuthal_cols", "fb_model_get_azimuthal", "fb_slab_get_azimuthal",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
 
@@ -172,6 +179,38 @@ def spectra_shells(nx, ny=None, Lx=600000.0, Ly=600000.0):
     n = C.c_int()
     check(lib().fb_spectra_shells(nx, ny or nx, Lx, Ly, C.byref(n)))
     return n.value
+
+
+# the first twelve columns of the azimuthal-mean table (fb_model_get_azimuthal, include/fftbaro.h), one row per radial bin; then
+# Re, Im of the azimuthal Fourier coefficient of zeta for m = 1 .. nmodes
+AZIMUTHAL_COLUMNS = ("r_lo", "r_hi", "n", "r", "zeta", "v_t", "v_r", "zeta2", "v_t2", "v_r2", "v_r_zeta", "Gamma")
+CENTER_MODES = {"fixed": 0, "psi-min": 1, "vort-max": 2}
+
+
+def azimuthal_cols(nmodes):
+    """The number of columns of the azimuthal-mean table with nmodes azimuthal wavenumbers, 12 + 2 nmodes; host logic, no GPU."""
+    n = C.c_int()
+    check(lib().fb_azimuthal_cols(nmodes, C.byref(n)))
+    return n.value
+
+
+def azimuthal_args(nx, ny, Lx, Ly, center, nbins, dr):
+    """(mode, xc, yc, nbins, dr) of an azimuthal() call: center "psi-min" | "vort-max" | (xc, yc); the defaults dr = max(dx, dy) and
+    nbins = floor(min(Lx, Ly) / 2 / dr), at most 4096, with dx, dy from the float32 lengths as the engine takes them."""
+    lx, ly = float(np.float32(Lx)), float(np.float32(Ly))
+    if isinstance(center, str):
+        if center not in ("psi-min", "vort-max"):
+            raise ValueError("center: 'psi-min', 'vort-max' or (xc, yc)")
+        mode, xc, yc = CENTER_MODES[center], 0.0, 0.0
+    else:
+        mode, (xc, yc) = 0, center
+    if dr is None:
+        dr = max(lx / nx, ly / ny)
+    if nbins is None:
+        nbins = min(4096, int(np.floor(min(lx, ly) / 2 / dr))) if dr > 0 else 0
+        while nbins > 2 and nbins * dr > min(lx, ly) / 2:
+            nbins -= 1
+    return mode, float(xc), float(yc), int(nbins), float(dr)
 
 
 def _torch():
@@ -391,6 +430,20 @@ class Model:
         table = t.empty((spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
         check(lib().fb_model_get_spectra(self._h, _ptr(table)))
         return table
+
+    def azimuthal(self, center="psi-min", nbins=None, dr=None, nmodes=4):
+        """(table, center): the azimuthal means about a vortex centre (fb_model_get_azimuthal).  center: "psi-min" (grid point of the
+        smallest psi), "vort-max" (of the largest zeta) or a fixed (xc, yc) [m]; nbins radial bins of the width dr [m] (defaults:
+        dr = max(dx, dy), nbins = floor(min(Lx, Ly) / 2 / dr), at most 4096); table float64 [nbins, 12 + 2 nmodes] (columns
+        AZIMUTHAL_COLUMNS, then Re, Im of the azimuthal wavenumbers 1 .. nmodes of zeta), center float64 [4] = xc, yc, flat index,
+        value; both on the GPU."""
+        t = self.torch
+        mode, xc, yc, nbins, dr = azimuthal_args(self.nx, self.ny, self.Lx, self.Ly, center, nbins, dr)
+        table = t.empty((max(nbins, 0), 12 + 2 * max(int(nmodes), 0)), dtype=t.float64, device="cuda")
+        cen = t.empty(4, dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
+        check(lib().fb_model_get_azimuthal(self._h, mode, xc, yc, nbins, dr, int(nmodes), _ptr(table), _ptr(cen)))
+        return table, cen
 
     def set_tracer(self, c, kappa=0.0):
         """Sets the passive tracer, an [nx, ny] field advected by the model's flow with the diffusivity kappa [m^2 s^-1] (it is stepped

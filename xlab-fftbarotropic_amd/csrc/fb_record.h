@@ -226,6 +226,159 @@ static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, floa
     return keff_finish(m, s, nbins, zeta, grad2, d_table, tr ? (double)m->kappa : (double)m->nu);
 }
 
+// ---- azimuthal means about a vortex centre (fb_azim.h): psi or zeta for the centre, then zeta, u, v and the table ----
+extern "C" int fb_azimuthal_cols(int nmodes, int *ncols)
+{
+    if (!ncols) return fail(FB_EINVAL, "fb_azimuthal_cols: NULL");
+    *ncols = 0;
+    if (nmodes < 0 || nmodes > AZIM_MAX_MODES) return fail(FB_EINVAL, "fb_azimuthal_cols: nmodes outside [0, 8]");
+    *ncols = AZIM_BASE_COLS + 2 * nmodes;
+    return FB_OK;
+}
+
+static int azim_check(const char *fn, const fb_ctx *c, int mode, double xc, double yc, int nbins, double dr, int nmodes, const double *d_table,
+                      const double *d_center)
+{
+    const std::string f(fn);
+    if (!d_table || !d_center) return fail(FB_EINVAL, f + ": NULL table or centre");
+    if (mode != FB_CENTER_FIXED && mode != FB_CENTER_PSI_MIN && mode != FB_CENTER_VORT_MAX) return fail(FB_EINVAL, f + ": unknown centre mode");
+    const double lx = (double)c->lx, ly = (double)c->ly, dx = lx / c->nx, dy = ly / c->ny;
+    if (mode == FB_CENTER_FIXED && !(std::isfinite(xc) && std::isfinite(yc) && xc >= 0.0 && xc < lx && yc >= 0.0 && yc < ly))
+        return fail(FB_EINVAL, f + ": the fixed centre must be finite with 0 <= xc < Lx, 0 <= yc < Ly");
+    if (nbins < 2 || nbins > 4096) return fail(FB_EINVAL, f + ": nbins outside [2, 4096]");
+    if (nmodes < 0 || nmodes > AZIM_MAX_MODES) return fail(FB_EINVAL, f + ": nmodes outside [0, 8]");
+    if (!std::isfinite(dr)) return fail(FB_EINVAL, f + ": dr is not finite");
+    if (dr < std::min(dx, dy)) return fail(FB_EINVAL, f + ": dr below min(dx, dy)");
+    if ((double)nbins * dr > std::min(lx, ly) / 2) return fail(FB_EINVAL, f + ": nbins * dr beyond min(Lx, Ly) / 2 (the minimum-image cell)");
+    return FB_OK;
+}
+
+// the tile of k_azim_bin: of the shapes TX x TY = AZIM_TILE with TY = 4 .. 256 a divisor of ny, the one whose radii span the fewest
+// bins; W = that span + 3, capped by 64 KiB of LDS (beyond the cap k_azim_bin adds a point to the global sums directly)
+static void azim_tile(AzimGeo &g, int ns)
+{
+    int best = 0x7fffffff;
+    for (int ty = 4; ty <= 256 && ty <= g.ny; ty *= 2) {
+        if (g.ny % ty) continue;
+        const int tx = AZIM_TILE / ty;
+        const double span = std::hypot((tx - 1) * g.dx, (ty - 1) * g.dy) / g.dr;
+        const int need = span < 1.0e6 ? (int)span + 3 : 1000003;
+        if (need < best) { best = need; g.TX = tx; g.TY = ty; }
+    }
+    g.W = std::min(best, 65536 / (ns * (int)sizeof(double)));
+}
+
+template <int NM> static int azim_launch_bin(const fb_ctx *c, const AzimGeo &g, const float *zeta, const float *u, const float *v, const double *center, double *part)
+{
+    const int ns = AZIM_BASE_SUMS + 2 * NM, tiles = ((g.XL + g.TX - 1) / g.TX) * (g.ny / g.TY);
+    int rc;
+    if ((rc = set_max_lds(c, (const void *)k_azim_bin<NM>, 65536))) return rc;
+    hipLaunchKernelGGL((k_azim_bin<NM>), dim3(tiles), dim3(256), (size_t)g.W * ns * sizeof(double), c->stream, g, zeta, u, v, center, part);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+// The record's own buffers: azim_fields [2][XL][ny] (f32) and one reduction buffer, grown on demand:
+//   part_send [world][nbins][ns], part_recv [world][nbins][ns] (a slab of several ranks; else the one part), cand_send [world][4],
+//   cand_recv [world][4] (f64); pi [nparts] (i64); pk [nparts] (f32).
+// The fields: psi (FB_CENTER_PSI_MIN only) into field 1 and its argmin, or zeta into field 0 and its argmax; then zeta into field 0,
+// u into field 1, and v, the last record taken, into the record workspace where that record's row pass no longer reads or never
+// read: field 1 of rec_work on one GPU, the largest group's rec_work on a slab of several ranks (its one field has left for
+// rec_send by then).  On a slab two small all-gathers through the transport's all-to-all, as keff_finish: the ranks' candidates,
+// then their sums; a rank's global row is rank * XL + local row.
+static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
+{
+    fb_ctx *c = m->c;
+    const int world = c->world, ns = AZIM_BASE_SUMS + 2 * nmodes;
+    const bool xchg = s && world > 1;
+    const size_t n = (size_t)c->XL * c->ny, np = (size_t)nbins * ns;
+    const int nparts = grid_for(c, n);
+    int rc;
+    if (!m->azim_fields && hipMalloc((void **)&m->azim_fields, 2 * n * sizeof(float)) != hipSuccess) {
+        m->azim_fields = nullptr;
+        return fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    const size_t o_precv = (xchg ? world * np : 0) * sizeof(double), o_csend = o_precv + (xchg ? world : 1) * np * sizeof(double);
+    const size_t o_crecv = o_csend + (xchg ? world : 0) * AZIM_ARG_W * sizeof(double), o_pi = o_crecv + (size_t)world * AZIM_ARG_W * sizeof(double);
+    const size_t o_pk = o_pi + (size_t)nparts * sizeof(long long), bytes = o_pk + (size_t)nparts * sizeof(float);
+    if (!m->azim_red || m->azim_red_cap < bytes) {
+        if (m->azim_red) { HIPCHK(hipFree(m->azim_red)); m->azim_red = nullptr; m->azim_red_cap = 0; }      // (hipFree waits for the device)
+        if (hipMalloc(&m->azim_red, bytes) != hipSuccess) { m->azim_red = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+        m->azim_red_cap = bytes;
+    }
+    char *base = (char *)m->azim_red;
+    double *psend = (double *)base, *precv = (double *)(base + o_precv), *csend = (double *)(base + o_csend), *crecv = (double *)(base + o_crecv);
+    long long *pi = (long long *)(base + o_pi);
+    float *pk = (float *)(base + o_pk);
+    float *f0 = m->azim_fields, *f1 = m->azim_fields + n;
+    auto gather = [&](const double *send, double *recv, size_t count) -> int {
+        int r;
+        if ((r = slab_after(s->comm, s->comp, s->ev_misc[0]))) return r;
+        if ((r = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * count, 0, 2 * count, s->comm))) return r;
+        return slab_after(s->comp, s->comm, s->ev_misc[1]);
+    };
+    AzimGeo g;
+    g.lx = (double)c->lx; g.ly = (double)c->ly; g.dx = g.lx / c->nx; g.dy = g.ly / c->ny; g.dr = dr;
+    g.nbins = nbins; g.XL = c->XL; g.ny = c->ny; g.row0 = c->rank * c->XL;
+    azim_tile(g, ns);
+    // the centre
+    bool have_zeta = false;
+    if (mode == FB_CENTER_FIXED) {
+        hipLaunchKernelGGL(k_azim_center, dim3(1), dim3(64), 0, c->stream, (const double *)nullptr, world, xc, yc, c->ny, g.dx, g.dy, d_center);
+        HIPCHK(hipGetLastError());
+    } else {
+        const bool vmax = mode == FB_CENTER_VORT_MAX;
+        float *q = vmax ? f0 : f1;
+        if ((rc = record(m, s, vmax ? REC_VORT : REC_PSI, q))) return rc;
+        have_zeta = vmax;
+        if (vmax) hipLaunchKernelGGL((k_azim_arg<true>), dim3(nparts), dim3(256), 0, c->stream, (const float *)q, n, pk, pi);
+        else hipLaunchKernelGGL((k_azim_arg<false>), dim3(nparts), dim3(256), 0, c->stream, (const float *)q, n, pk, pi);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_azim_arg_final, dim3(1), dim3(256), 0, c->stream, (const float *)pk, (const long long *)pi, nparts, (const float *)q,
+                           (long long)c->rank * (long long)n, xchg ? csend : crecv, xchg ? world : 1);
+        HIPCHK(hipGetLastError());
+        if (xchg && (rc = gather(csend, crecv, AZIM_ARG_W))) return rc;
+        hipLaunchKernelGGL(k_azim_center, dim3(1), dim3(64), 0, c->stream, (const double *)crecv, world, 0.0, 0.0, c->ny, g.dx, g.dy, d_center);
+        HIPCHK(hipGetLastError());
+    }
+    // the fields
+    if (!have_zeta && (rc = record(m, s, REC_VORT, f0))) return rc;
+    if ((rc = record(m, s, REC_U, f1))) return rc;
+    float *f2 = nullptr;
+    if (!xchg) f2 = (float *)(m->rec_work[0] + priv_elems(c));
+    else {
+        size_t cap = 0;
+        for (int k = 0; k < c->ngroups; ++k) {
+            const size_t have = (size_t)(m->rec_work_nf[k] ? m->rec_work_nf[k] : 3) * grp_elems(c, c->grp[k]) * sizeof(cf);
+            if (m->rec_work[k] && have > cap) { cap = have; f2 = (float *)m->rec_work[k]; }
+        }
+        if (cap < n * sizeof(float)) return fail(FB_EUNSUPPORTED, "azimuthal record: the record workspace cannot hold a field of rows");
+    }
+    if ((rc = record(m, s, REC_V, f2))) return rc;
+    // the sums and the table
+    HIPCHK(hipMemsetAsync(psend, 0, np * sizeof(double), c->stream));
+    switch (nmodes) {
+    case 0: rc = azim_launch_bin<0>(c, g, f0, f1, f2, d_center, psend); break;
+    case 1: rc = azim_launch_bin<1>(c, g, f0, f1, f2, d_center, psend); break;
+    case 2: rc = azim_launch_bin<2>(c, g, f0, f1, f2, d_center, psend); break;
+    case 3: rc = azim_launch_bin<3>(c, g, f0, f1, f2, d_center, psend); break;
+    case 4: rc = azim_launch_bin<4>(c, g, f0, f1, f2, d_center, psend); break;
+    case 5: rc = azim_launch_bin<5>(c, g, f0, f1, f2, d_center, psend); break;
+    case 6: rc = azim_launch_bin<6>(c, g, f0, f1, f2, d_center, psend); break;
+    case 7: rc = azim_launch_bin<7>(c, g, f0, f1, f2, d_center, psend); break;
+    default: rc = azim_launch_bin<8>(c, g, f0, f1, f2, d_center, psend); break;
+    }
+    if (rc) return rc;
+    if (xchg) {                                             // one copy of this rank's sums per peer
+        for (int r = 1; r < world; ++r) HIPCHK(hipMemcpyAsync(psend + r * np, psend, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if ((rc = gather(psend, precv, np))) return rc;
+    }
+    hipLaunchKernelGGL(k_azim_table, dim3(1), dim3(256), (size_t)nbins * sizeof(double), c->stream, (const double *)precv, xchg ? world : 1, nbins, nmodes, dr,
+                       g.dx, g.dy, d_table);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
 // ---- balanced pressure (REC_PRES): there and back ----
 // invert_pres.cpp:135-185 on the resident state.  Per column group k_pres_spec and the backward x pass of the three masked second
 // derivatives of psi (record_fields); the ROW_PRES row pass takes them to physical space, forms psi_xx psi_yy - psi_xy^2 in registers
@@ -529,6 +682,26 @@ extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_tab
     int rc;
     if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
     return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows);
+}
+
+extern "C" int fb_model_get_azimuthal(fb_model *m, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_get_azimuthal: NULL model");
+    int rc;
+    if ((rc = azim_check("fb_model_get_azimuthal", m->c, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center))) return rc;
+    NEED_SINGLE(m->c);
+    return record_azimuthal(m, nullptr, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
+}
+
+// collective: the ranks' centre candidates and sums are all-gathered through the transport (record_azimuthal), every rank gets the
+// whole table and the centre
+extern "C" int fb_slab_get_azimuthal(fb_slab *s, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_get_azimuthal: NULL slab");
+    int rc;
+    if ((rc = azim_check("fb_slab_get_azimuthal", s->c, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center))) return rc;
+    SLAB_READY(s);
+    return record_azimuthal(s->m, s, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
 }
 
 extern "C" int fb_model_get_spectra(fb_model *m, double *d_table)

@@ -15,6 +15,7 @@
 #include "../../include/fftbaro.h"
 #include "fb_kernels.h"
 #include "fb_keff.h"
+#include "fb_azim.h"
 #include "fb_spectra.h"
 #include "fb_tracer.h"
 #include "fb_col_full.h"
@@ -1014,6 +1015,10 @@ struct fb_model {
     // the reduction buffers (grown to the largest request)
     float *keff_fields;
     void *keff_red; size_t keff_red_cap;
+    // the azimuthal-mean record adds zeta and u (or psi) ([2][XL][ny]; v goes to the record workspace) and its reduction buffer (grown
+    // to the largest request)
+    float *azim_fields;
+    void *azim_red; size_t azim_red_cap;
     // the pressure record's reference-point value: [world] floats to send, [world] received (fb_record.h, record_pres)
     float *pres_ref;
     // the spectra record: fields the record workspace holds where this kind has grown it (0: the three of the other kinds), and the
@@ -1086,6 +1091,8 @@ extern "C" int fb_model_destroy(fb_model *m)
     for (auto p : m->rec_send) if (p) hipFree(p);
     if (m->keff_fields) hipFree(m->keff_fields);
     if (m->keff_red) hipFree(m->keff_red);
+    if (m->azim_fields) hipFree(m->azim_fields);
+    if (m->azim_red) hipFree(m->azim_red);
     if (m->pres_ref) hipFree(m->pres_ref);
     if (m->spec_red) hipFree(m->spec_red);
     tracer_free(m);

@@ -39,6 +39,12 @@
 // tracer_step_N.bin, the last field file of a record in ./log, and with --dump-eddy-diffusivity tracer_eddy_diffusivity_step_N.bin
 // after it (fb_model_get_tracer_eddy_diffusivity, [N][9] float64 as eddy_diffusivity); on one GPU and with --world P, where rank 0
 // alone writes the table.
+// --dump-azimuthal [--azim-center psi-min|vort-max|X,Y] [--azim-bins N] [--azim-dr D] [--azim-modes M] (no reference counterpart; defaults
+// psi-min, D = max(dx, dy), N = floor(min(Lx, Ly) / 2 / D) at most 4096, M = 4) adds azimuthal_step_N.bin to every record: the
+// azimuthal-mean table of fb_model_get_azimuthal, raw little-endian float64 [N][12 + 2 M], and azimuthal_center_step_N.bin after it:
+// the four doubles xc, yc, flat index, value of the centre, so that the sequence over the records is the vortex track.  The last two
+// files of a record in ./log; on one GPU and with --world P, where rank 0 alone writes them.  Arguments that the C ABI would refuse
+// are refused here (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -81,6 +87,8 @@ struct Config {
     int pres_ref_x = 0, pres_ref_y = 0;                                            // its reference point (invert_pres.cpp:67-79)
     bool dump_spectra = false;                                                     // shell spectra and cascade fluxes (no reference counterpart)
     std::string tracer_file; float tracer_kappa = 0.0f;                            // the passive tracer's initial field and diffusivity (no reference counterpart)
+    bool dump_azim = false; int azim_mode = FB_CENTER_PSI_MIN; double azim_xc = 0.0, azim_yc = 0.0;   // azimuthal means about a vortex centre (no reference counterpart)
+    int azim_bins = 0, azim_modes = 4; double azim_dr = 0.0;                       // 0: the default number of bins / bin width
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -227,7 +235,9 @@ struct RecordWriter {
     double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
     double *hs[2] = {nullptr, nullptr}; size_t spectra_bytes = 0;                      // the spectra table (item buffer SPECTRA_TABLE), rank 0 only
     double *hk[2] = {nullptr, nullptr};                                                // the tracer's eddy diffusivity table (item buffer TRACER_KEFF_TABLE, table_bytes), rank 0 only
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4 };
+    double *ha[2] = {nullptr, nullptr}; size_t azim_bytes = 0;                         // the azimuthal-mean table (item buffer AZIM_TABLE), rank 0 only
+    double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -253,9 +263,14 @@ struct RecordWriter {
                 snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), items[i].first, job.step);
                 if (items[i].second <= KEFF_TABLE) {
                     if (!lead) continue;
-                    const bool keff = items[i].second != SPECTRA_TABLE;
-                    const double *tab = items[i].second == KEFF_TABLE ? ht[job.set] : keff ? hk[job.set] : hs[job.set];
-                    const size_t tb = keff ? table_bytes : spectra_bytes;
+                    const double *tab = nullptr; size_t tb = 0;
+                    switch (items[i].second) {
+                    case KEFF_TABLE: tab = ht[job.set]; tb = table_bytes; break;
+                    case TRACER_KEFF_TABLE: tab = hk[job.set]; tb = table_bytes; break;
+                    case SPECTRA_TABLE: tab = hs[job.set]; tb = spectra_bytes; break;
+                    case AZIM_TABLE: tab = ha[job.set]; tb = azim_bytes; break;
+                    default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
+                    }
                     FILE *f = fopen(fn, "wb");
                     if (!f || fwrite(tab, 1, tb, f) != tb) { perror("Write field."); std::exit(1); }
                     fclose(f);
@@ -321,6 +336,7 @@ struct Engine {
     virtual void set_tracer(const float *d, float kappa) = 0;                         // --tracer (collective)
     virtual void get_tracer(float *d) = 0;
     virtual void get_tracer_eddy_diffusivity(int nbins, double *d_table) = 0;         // --tracer with --dump-eddy-diffusivity (collective)
+    virtual void get_azimuthal(const Config &cfg, double *d_table, double *d_center) = 0;     // --dump-azimuthal, on the compute stream (collective)
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -377,6 +393,10 @@ struct SingleEngine : Engine {
     {
         must(fb_model_get_tracer_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_tracer_eddy_diffusivity");
     }
+    void get_azimuthal(const Config &cfg, double *d_table, double *d_center) override
+    {
+        must(fb_model_get_azimuthal(model, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_model_get_azimuthal");
+    }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -428,6 +448,10 @@ struct SlabEngine : Engine {
     {
         must(fb_slab_get_tracer_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_tracer_eddy_diffusivity");
     }
+    void get_azimuthal(const Config &cfg, double *d_table, double *d_center) override
+    {
+        must(fb_slab_get_azimuthal(sl, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_slab_get_azimuthal");
+    }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -460,6 +484,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t spectra_bytes = (size_t)nshells * 10 * sizeof(double);
     double *d_spectra = nullptr;
     if (cfg.dump_spectra) must(fb_malloc((void **)&d_spectra, spectra_bytes), "fb_malloc");
+    // the azimuthal-mean table and its centre (--dump-azimuthal): likewise
+    const size_t azim_bytes = cfg.dump_azim ? (size_t)cfg.azim_bins * (12 + 2 * cfg.azim_modes) * sizeof(double) : 0;
+    double *d_azim = nullptr, *d_azim_center = nullptr;
+    if (cfg.dump_azim) { must(fb_malloc((void **)&d_azim, azim_bytes), "fb_malloc"); must(fb_malloc((void **)&d_azim_center, 4 * sizeof(double)), "fb_malloc"); }
 
     RecordWriter writer;
     size_t set_bytes = 0;
@@ -471,6 +499,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (cfg.dump_keff && lead) must(fb_malloc_host((void **)&writer.ht[b], table_bytes), "fb_malloc_host");
         if (cfg.dump_keff && tracer && lead) must(fb_malloc_host((void **)&writer.hk[b], table_bytes), "fb_malloc_host");
         if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
+        if (cfg.dump_azim && lead) { must(fb_malloc_host((void **)&writer.ha[b], azim_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hc[b], 4 * sizeof(double)), "fb_malloc_host"); }
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
@@ -482,7 +511,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
     if (tracer) writer.items.push_back({"tracer", 10});
     if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
-    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes;
+    if (cfg.dump_azim) { writer.items.push_back({"azimuthal", RecordWriter::AZIM_TABLE}); writer.items.push_back({"azimuthal_center", RecordWriter::AZIM_CENTER}); }
+    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -567,6 +597,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
             if (tracer) eng->get_tracer(d_out[10]);
             if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
+            if (cfg.dump_azim) eng->get_azimuthal(cfg, d_azim, d_azim_center);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
@@ -574,6 +605,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (writer.ht[set]) must(fb_memcpy_d2h_async(copy, writer.ht[set], d_table, table_bytes), "d2h");
             if (writer.hs[set]) must(fb_memcpy_d2h_async(copy, writer.hs[set], d_spectra, spectra_bytes), "d2h");
             if (writer.hk[set]) must(fb_memcpy_d2h_async(copy, writer.hk[set], d_ttable, table_bytes), "d2h");
+            if (writer.ha[set]) must(fb_memcpy_d2h_async(copy, writer.ha[set], d_azim, azim_bytes), "d2h");
+            if (writer.hc[set]) must(fb_memcpy_d2h_async(copy, writer.hc[set], d_azim_center, 4 * sizeof(double)), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -637,11 +670,15 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (d_table) fb_free(d_table);
     if (d_ttable) fb_free(d_ttable);
     if (d_spectra) fb_free(d_spectra);
+    if (d_azim) fb_free(d_azim);
+    if (d_azim_center) fb_free(d_azim_center);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
         if (writer.hs[b]) fb_free_host(writer.hs[b]);
         if (writer.hk[b]) fb_free_host(writer.hk[b]);
+        if (writer.ha[b]) fb_free_host(writer.ha[b]);
+        if (writer.hc[b]) fb_free_host(writer.hc[b]);
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -661,6 +698,7 @@ int main(int argc, char *args[])
                                     {"dump-okubo-weiss", 0, 0, 21}, {"dump-eddy-diffusivity", 0, 0, 22}, {"keff-bins", 1, 0, 23},
                                     {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
                                     {"dump-spectra", 0, 0, 29}, {"tracer", 1, 0, 30}, {"tracer-kappa", 1, 0, 31},
+                                    {"dump-azimuthal", 0, 0, 32}, {"azim-center", 1, 0, 33}, {"azim-bins", 1, 0, 34}, {"azim-dr", 1, 0, 35}, {"azim-modes", 1, 0, 36},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -709,6 +747,34 @@ int main(int argc, char *args[])
             cfg.tracer_kappa = v;
             break;
         }
+        case 32: cfg.dump_azim = true; break;            // azimuthal_step_N.bin, azimuthal_center_step_N.bin (also with --world P)
+        case 33: {
+            const std::string a = optarg;
+            char *e1 = nullptr, *e2 = nullptr;
+            if (a == "psi-min") cfg.azim_mode = FB_CENTER_PSI_MIN;
+            else if (a == "vort-max") cfg.azim_mode = FB_CENTER_VORT_MAX;
+            else {
+                cfg.azim_mode = FB_CENTER_FIXED;
+                cfg.azim_xc = strtod(optarg, &e1);
+                if (e1 != optarg && *e1 == ',') cfg.azim_yc = strtod(e1 + 1, &e2);
+                if (!e2 || e2 == e1 + 1 || *e2) { fprintf(stderr, "--azim-center: psi-min, vort-max or X,Y\n"); return 2; }
+            }
+            break;
+        }
+        case 34: case 36: {
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (opt == 34 && (!*optarg || *end || v < 2 || v > 4096)) { fprintf(stderr, "--azim-bins: an integer in [2, 4096]\n"); return 2; }
+            if (opt == 36 && (!*optarg || *end || v < 0 || v > 8)) { fprintf(stderr, "--azim-modes: an integer in [0, 8]\n"); return 2; }
+            (opt == 34 ? cfg.azim_bins : cfg.azim_modes) = (int)v;
+            break;
+        }
+        case 35: {
+            char *end = nullptr;
+            cfg.azim_dr = strtod(optarg, &end);
+            if (!*optarg || *end || !(cfg.azim_dr > 0.0) || cfg.azim_dr > 1.0e300) { fprintf(stderr, "--azim-dr: a finite number > 0\n"); return 2; }
+            break;
+        }
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
@@ -727,6 +793,21 @@ int main(int argc, char *args[])
     // the reference's flat index ref_x + XPTS * ref_y (invert_pres.cpp:182) must name an element of the field
     if ((long long)cfg.pres_ref_x + (long long)cfg.npts * cfg.pres_ref_y >= (long long)cfg.npts * cfg.npts) {
         fprintf(stderr, "--pres-ref-x / --pres-ref-y: the reference point lies outside the %d x %d grid\n", cfg.npts, cfg.npts); return 2;
+    }
+    if (cfg.dump_azim) {                                                               // what fb_model_get_azimuthal would refuse, and the defaults
+        const double lx = (double)cfg.LX, ly = (double)cfg.LY, ddx = lx / cfg.npts, ddy = ly / cfg.npts, half = (lx < ly ? lx : ly) / 2;
+        if (!(ddx > 0.0) || !(ddy > 0.0)) { fprintf(stderr, "--dump-azimuthal: needs a positive domain and grid size\n"); return 2; }
+        if (cfg.azim_dr == 0.0) cfg.azim_dr = ddx > ddy ? ddx : ddy;
+        if (cfg.azim_bins == 0) {
+            const double q = half / cfg.azim_dr;
+            cfg.azim_bins = q >= 4096.0 ? 4096 : (int)q;
+            while (cfg.azim_bins > 2 && cfg.azim_bins * cfg.azim_dr > half) --cfg.azim_bins;
+        }
+        if (cfg.azim_dr < (ddx < ddy ? ddx : ddy)) { fprintf(stderr, "--azim-dr: below min(dx, dy)\n"); return 2; }
+        if (cfg.azim_bins < 2 || cfg.azim_bins * cfg.azim_dr > half) { fprintf(stderr, "--azim-bins / --azim-dr: need 2 <= bins and bins * dr <= min(Lx, Ly) / 2\n"); return 2; }
+        if (cfg.azim_mode == FB_CENTER_FIXED && !(cfg.azim_xc >= 0.0 && cfg.azim_xc < lx && cfg.azim_yc >= 0.0 && cfg.azim_yc < ly)) {
+            fprintf(stderr, "--azim-center: X,Y must lie inside the domain, 0 <= X < Lx and 0 <= Y < Ly\n"); return 2;
+        }
     }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
     if (cfg.total_steps < 0) cfg.total_steps = (int)(60 * 60 / cfg.dt);              // configuration.hpp:36

@@ -289,6 +289,18 @@ class EngineSlab:
         self.synchronize()
         return table
 
+    def azimuthal(self, center="psi-min", nbins=None, dr=None, nmodes=4):
+        """(table, center): the azimuthal means of the whole domain about a vortex centre (fb_slab_get_azimuthal; arguments and
+        columns as binding.Model.azimuthal), the same on every rank.  Collective."""
+        t = self.torch
+        mode, xc, yc, nbins, dr = self.B.azimuthal_args(self.nx, self.ny, self.Lx, self.Ly, center, nbins, dr)
+        table = t.empty((max(nbins, 0), 12 + 2 * max(int(nmodes), 0)), dtype=t.float64, device="cuda")
+        cen = t.empty(4, dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
+        self.B.check(self.L.fb_slab_get_azimuthal(self._h, mode, xc, yc, nbins, dr, int(nmodes), C.c_void_p(table.data_ptr()), C.c_void_p(cen.data_ptr())))
+        self.synchronize()
+        return table, cen
+
     def set_tracer_local(self, rows, kappa=0.0):
         """This rank's rows of the passive tracer and its diffusivity (fb_slab_set_tracer_local); rows=None removes the tracer.
         Collective."""
