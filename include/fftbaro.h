@@ -196,6 +196,31 @@ int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float
 int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa);   /* NULL: remove the tracer */
 int fb_model_get_tracer(fb_model *m, float *d_c_real);
 int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2);
+/* Lagrangian particles (no reference counterpart): n points (x, y) [m] on the doubly periodic domain, float64 and UNWRAPPED (a particle
+ * that leaves through one side keeps counting; positions are wrapped only where they index a field).  Grid point (i, j) of an
+ * [nx][ny] field lies at x = i dx, y = j dy, dx = (double)Lx / nx, dy = (double)Ly / ny (the context's float32 lengths, widened, as
+ * fb_model_get_azimuthal takes its centre).  From fb_model_set_particles on every step advances the particles by the RK4 step of
+ * main.cpp:288-317 beside vort_c, coupled stage by stage:
+ *   k1 = U_0(X0), k2 = U_1(X0 + dt/2 k1), k3 = U_2(X0 + dt/2 k2), k4 = U_3(X0 + dt k3), X <- X0 + dt/6 (k1 + 2 k2 + 2 k3 + k4)
+ * with U_s = (u, v) of the vorticity's state of stage s (vort_c0 at stage 0, the stage state afterwards: the state the tracer's
+ * stage s uses), two float32 [nx][ny] fields formed as fb_model_get_diag forms u and v, in its kernels and its rounding; everything
+ * from the interpolation on is float64.  The interpolation is the tensor product of 4-point cubic Lagrange polynomials: per axis
+ * s = x / dx, i0 = floor(s) (a 64-bit integer), t = s - i0, the rows (i0 - 1 .. i0 + 2) mod nx as a non-negative modulus (positions
+ * many domain lengths away, on either side, index correctly) with the weights
+ *   w(-1) = -t (t-1) (t-2) / 6,  w(0) = (t+1) (t-1) (t-2) / 2,  w(1) = -(t+1) t (t-2) / 2,  w(2) = (t+1) t (t-1) / 6,
+ * so that a particle on a grid point gets the grid value.  A position that is not finite reads nothing and stays NaN.
+ * fb_model_set_particles: d_xy device float64 [n][2], n in [1, 2^24]; d_xy == NULL (with n == 0) removes the particles and frees
+ * their state.  fb_model_get_particles: the unwrapped positions, [n][2].  fb_model_particle_count: n, 0 when none are set.
+ * fb_model_sample: the same interpolation of ANY device [nx][ny] float32 field (zeta, the tracer, W, the pressure ...) at any n
+ * positions d_xy [n][2] into d_out, float64 [n]; it needs no particles set and does not touch them.  The vorticity, a tracer and
+ * every record are bit for bit what they are without particles.  Setting or removing particles drops a captured step
+ * (fb_model_use_graph); it is captured again with the particles' stages.  FB_EINVAL before any HIP call: a NULL model, n outside
+ * [1, 2^24], NULL positions with n > 0, a NULL field or output, fb_model_get_particles without particles set.  Enqueued on the
+ * context stream, no synchronisation, no host round trip. */
+int fb_model_set_particles(fb_model *m, const double *d_xy, int n);        /* NULL: remove the particles */
+int fb_model_get_particles(fb_model *m, double *d_xy);
+int fb_model_particle_count(fb_model *m, int *n);
+int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out);
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -332,6 +357,13 @@ int fb_slab_get_azimuthal(fb_slab *s, int center_mode, double xc, double yc, int
 int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa);  /* NULL: remove the tracer */
 int fb_slab_get_tracer_local(fb_slab *s, float *d_rows);
 int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows);
+/* the Lagrangian particles (fb_model_set_particles) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
+ * world > 1 they return FB_EUNSUPPORTED: particles distributed over row slabs need neighbour halo rows that the all-to-all transport
+ * does not provide. */
+int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n);          /* NULL: remove the particles */
+int fb_slab_get_particles(fb_slab *s, double *d_xy);
+int fb_slab_particle_count(fb_slab *s, int *n);
+int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -129,6 +129,19 @@ def lib():
             getattr(L, n).argtypes = [vp, ip, C.c_double, C.c_double, ip, C.c_double, ip, vp, vp]
     if hasattr(L, "fb_azimuthal_cols"):
         L.fb_azimuthal_cols.argtypes = [ip, C.POINTER(ip)]
+    # (likewise the Lagrangian particles)
+    for n in ("fb_model_set_particles", "fb_slab_set_particles"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, vp, ip]
+    for n in ("fb_model_get_particles", "fb_slab_get_particles"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, vp]
+    for n in ("fb_model_particle_count", "fb_slab_particle_count"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, C.POINTER(ip)]
+    for n in ("fb_model_sample", "fb_slab_sample"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, fp, vp, ip, vp]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -157,6 +170,8 @@ EXPORTS = [
     "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
     "fb_model_set_tracer", "fb_model_get_tracer", "fb_model_get_tracer_eddy_diffusivity", "fb_slab_set_tracer_local", "fb_slab_get_tracer_local", "fb_slab_get_tracer_eddy_diffusivity",
     "fb_azimuthal_cols", "fb_model_get_azimuthal", "fb_slab_get_azimuthal",
+    "fb_model_set_particles", "fb_model_get_particles", "fb_model_particle_count", "fb_model_sample",
+    "fb_slab_set_particles", "fb_slab_get_particles", "fb_slab_particle_count", "fb_slab_sample",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
 
@@ -222,6 +237,29 @@ def _torch():
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+PARTICLES_MAX = 1 << 24
+
+
+def particles_dev(torch, xy):
+    """Particle positions, numpy or torch float64 [n, 2], as a contiguous tensor on the GPU that has landed there."""
+    if isinstance(xy, np.ndarray):
+        xy = torch.from_numpy(np.ascontiguousarray(xy, dtype=np.float64))
+    if xy.dtype != torch.float64 or xy.dim() != 2 or xy.shape[1] != 2:
+        raise ValueError("particle positions: float64 [n, 2]")
+    xy = xy.cuda().contiguous()
+    torch.cuda.current_stream().synchronize()                   # the engine reads them on ITS stream
+    return xy
+
+
+def wrap_positions(torch, xy, Lx, Ly):
+    """Unwrapped positions [n, 2] folded into [0, Lx) x [0, Ly), the float32 lengths widened as the engine takes them."""
+    out = torch.empty_like(xy)
+    for k, L in enumerate((float(np.float32(Lx)), float(np.float32(Ly)))):
+        r = torch.remainder(xy[:, k], L)
+        out[:, k] = torch.where(r >= L, torch.zeros_like(r), r)     # (a tiny negative position folds to L itself in rounding)
+    return out
 
 
 class FftwfOperation:
@@ -463,6 +501,42 @@ class Model:
         c, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
         check(lib().fb_model_get_tracer_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(c) if fields else None, _ptr(g) if fields else None))
         return (table, c, g) if fields else table
+
+    def set_particles(self, xy):
+        """Sets the Lagrangian particles, float64 [n, 2] positions (x, y) [m] (numpy or torch), advected by the model's flow from now
+        on with the RK4 scheme of the step itself; xy=None removes them."""
+        if xy is None:
+            check(lib().fb_model_set_particles(self._h, None, 0))
+        else:
+            a = particles_dev(self.torch, xy)
+            check(lib().fb_model_set_particles(self._h, _ptr(a), int(a.shape[0]))); self.fop.synchronize()
+
+    def particle_count(self):
+        n = C.c_int()
+        check(lib().fb_model_particle_count(self._h, C.byref(n)))
+        return n.value
+
+    def particles(self, wrap=False):
+        """The particles' positions, a float64 [n, 2] tensor: unwrapped (a particle that left through one side keeps counting), or with
+        wrap=True folded into [0, Lx) x [0, Ly)."""
+        t = self.torch
+        out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
+        check(lib().fb_model_get_particles(self._h, _ptr(out)))
+        self.fop.synchronize()
+        return wrap_positions(t, out, self.Lx, self.Ly) if wrap else out
+
+    def sample(self, field, xy=None):
+        """An [nx, ny] float32 field (numpy or torch: the vorticity, the tracer, W, the pressure ...) interpolated to the positions
+        xy, float64 [n, 2], or to the particles (xy=None), by the particles' cubic Lagrange scheme: a float64 [n] tensor."""
+        t = self.torch
+        f = self._dev(field)
+        a = self.particles() if xy is None else particles_dev(t, xy)
+        out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()
+        check(lib().fb_model_sample(self._h, _ptr(f), _ptr(a), int(a.shape[0]), _ptr(out)))
+        self.fop.synchronize()
+        return out
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

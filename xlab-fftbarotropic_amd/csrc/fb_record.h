@@ -897,3 +897,193 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
     SLAB_READY(s);
     return record_keff(s->m, s, nbins, d_table, d_c_rows, d_grad2_rows, true);
 }
+
+// ---- the Lagrangian particles (kernels: fb_particles.h) ----
+#define FB_PARTICLES_MAX (1 << 24)
+
+static void particles_free(fb_model *m)
+{
+    if (m->pt) { hipFree(m->pt); m->pt = nullptr; }
+    if (m->pt_uv) { hipFree(m->pt_uv); m->pt_uv = nullptr; }
+    m->pt_n = 0;
+}
+
+static PartGeo part_geo(const fb_ctx *c)
+{
+    PartGeo g;
+    g.dx = (double)c->lx / c->nx; g.dy = (double)c->ly / c->ny; g.nx = c->nx; g.ny = c->ny;
+    return g;
+}
+
+// One RK stage of the particles, at the top of the step's stage `stage`, where tracer_stage runs: before the step's own stage
+// overwrites ZB.  The vorticity's state of the stage (tracer_stage: ZA at stage 0, ZB afterwards, a masked mode from ZA) goes into
+// the 3-pass layout (k_tracer_vstate_* into field 1 of the record workspace where the state arrays are laid out otherwise; read in
+// place where they are not); k_particle_uv_spec leaves the spectra of u and v in the fields 0 and 1; the backward x pass of both and
+// one ROW_INV row pass each, with the scales of record(), into the particles' own real fields; k_particle_stage.  One GPU or a slab
+// of one rank: one column group, no exchange.
+static int particle_stage(fb_model *m, int stage)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
+    const SpecCoef coef = make_coef(c);
+    cf *z = m->rec_work[0];
+    const cf *v0 = m->gb[0].ZA, *v1 = stage > 0 ? m->gb[0].ZB : m->gb[0].ZA;
+    int rc;
+    if (m->xpass != XP_COLS) {
+        hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, v0, v1, z + n, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
+        v0 = v1 = z + n;
+    } else if (state_tm(c)) {
+        hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z + n, G.ncols, c->N1, c->N2, G.ky0);
+        v0 = v1 = z + n;
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_particle_uv_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+    HIPCHK(hipGetLastError());
+    if ((rc = launch_col_block<+1>(c, G, z, 2, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 2, (long)n))) return rc;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    RowArgs a = row_args_base(c);
+    a.M = view_single(c, z, (long)n); a.scale = -g; a.rout = m->pt_uv;                // u = -dpsi/dy (record(), REC_U)
+    if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+    a.M = view_single(c, z + n, (long)n); a.scale = g; a.rout = m->pt_uv + nr;        // v = dpsi/dx
+    if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+    const dim3 grid(grid_for(c, (size_t)m->pt_n)), blk(256);
+    const PartGeo pg = part_geo(c);
+    const float *u = m->pt_uv, *v = m->pt_uv + nr;
+    const double dt = (double)m->dt;
+    switch (stage) {
+    case 0: hipLaunchKernelGGL((k_particle_stage<0>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
+    case 1: hipLaunchKernelGGL((k_particle_stage<1>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
+    case 2: hipLaunchKernelGGL((k_particle_stage<2>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
+    default: hipLaunchKernelGGL((k_particle_stage<3>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
+    }
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+static int particles_check(const char *fn, const double *d_xy, int n)
+{
+    if (!d_xy) return n == 0 ? FB_OK : fail(FB_EINVAL, std::string(fn) + ": NULL positions with n > 0");
+    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
+    return FB_OK;
+}
+
+// The particles in (d_xy == NULL removes them).  The vorticity, a tracer and `primed` stay as they are.  As tracer_in: the captured
+// step is dropped and the next fb_model_step starts with an eager step before the longer step is captured.  The record workspace is
+// grown to its largest size first (advect_workspace), so that no later record replaces the buffer a captured step reads.
+static int particles_in(fb_model *m, fb_slab *s, const double *d_xy, int n)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    model_drop_graph(m);
+    m->warmed = false;
+    if (m->pt_n) HIPCHK(hipStreamSynchronize(c->stream));
+    particles_free(m);
+    if (!d_xy) return FB_OK;
+    if ((rc = advect_workspace(m, s))) return rc;
+    if (hipMalloc((void **)&m->pt, 6 * (size_t)n * sizeof(double)) != hipSuccess) { m->pt = nullptr; return fail(FB_ENOMEM, "particle allocation failed"); }
+    if (hipMalloc((void **)&m->pt_uv, 2 * (size_t)c->nx * c->ny * sizeof(float)) != hipSuccess) {
+        m->pt_uv = nullptr;
+        particles_free(m);
+        return fail(FB_ENOMEM, "particle allocation failed");
+    }
+    HIPCHK(hipMemsetAsync(m->pt, 0, 6 * (size_t)n * sizeof(double), c->stream));
+    hipLaunchKernelGGL(k_particle_unpack, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, d_xy, m->pt, m->pt + n, n);
+    HIPCHK(hipGetLastError());
+    m->pt_n = n;
+    return FB_OK;
+}
+
+static int particles_out(fb_model *m, double *d_xy)
+{
+    fb_ctx *c = m->c;
+    hipLaunchKernelGGL(k_particle_pack, dim3(grid_for(c, (size_t)m->pt_n)), dim3(256), 0, c->stream, (const double *)m->pt, (const double *)(m->pt + m->pt_n), d_xy, m->pt_n);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+static int sample_check(const char *fn, const float *d_field, const double *d_xy, int n, const double *d_out)
+{
+    if (!d_field || !d_xy || !d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL");
+    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
+    return FB_OK;
+}
+
+static int sample(fb_ctx *c, const float *d_field, const double *d_xy, int n, double *d_out)
+{
+    hipLaunchKernelGGL(k_sample, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, part_geo(c), d_field, d_xy, n, d_out);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+extern "C" int fb_model_set_particles(fb_model *m, const double *d_xy, int n)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_set_particles: NULL model");
+    int rc;
+    if ((rc = particles_check("fb_model_set_particles", d_xy, n))) return rc;
+    NEED_SINGLE(m->c);
+    if (m->phase_flow) return fail(FB_EINVAL, "fb_model_set_particles on a slab model: use fb_slab_set_particles");
+    return particles_in(m, nullptr, d_xy, n);
+}
+
+extern "C" int fb_model_get_particles(fb_model *m, double *d_xy)
+{
+    if (!m || !d_xy) return fail(FB_EINVAL, "fb_model_get_particles: NULL");
+    if (!m->pt_n) return fail(FB_EINVAL, "fb_model_get_particles: no particles are set");
+    return particles_out(m, d_xy);
+}
+
+extern "C" int fb_model_particle_count(fb_model *m, int *n)
+{
+    if (!m || !n) return fail(FB_EINVAL, "fb_model_particle_count: NULL");
+    *n = m->pt_n;
+    return FB_OK;
+}
+
+extern "C" int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out)
+{
+    if (!m) return fail(FB_EINVAL, "fb_model_sample: NULL model");
+    int rc;
+    if ((rc = sample_check("fb_model_sample", d_field, d_xy, n, d_out))) return rc;
+    NEED_SINGLE(m->c);
+    return sample(m->c, d_field, d_xy, n, d_out);
+}
+
+// a slab of one rank goes through the same code; particles distributed over row slabs would need neighbour halo rows that the
+// all-to-all transport does not provide
+#define SLAB_PARTICLES_ONE_RANK(s, fn) do { if ((s)->c->world > 1) return fail(FB_EUNSUPPORTED, std::string(fn) + ": particles are not supported on a slab of several ranks (world > 1)"); } while (0)
+
+extern "C" int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_set_particles: NULL slab");
+    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_set_particles");
+    int rc;
+    if ((rc = particles_check("fb_slab_set_particles", d_xy, n))) return rc;
+    SLAB_READY(s);
+    return particles_in(s->m, s, d_xy, n);
+}
+
+extern "C" int fb_slab_get_particles(fb_slab *s, double *d_xy)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_get_particles: NULL slab");
+    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_get_particles");
+    if (!d_xy) return fail(FB_EINVAL, "fb_slab_get_particles: NULL");
+    if (!s->m->pt_n) return fail(FB_EINVAL, "fb_slab_get_particles: no particles are set");
+    return particles_out(s->m, d_xy);
+}
+
+extern "C" int fb_slab_particle_count(fb_slab *s, int *n)
+{
+    if (!s || !n) return fail(FB_EINVAL, "fb_slab_particle_count: NULL");
+    *n = s->m->pt_n;
+    return FB_OK;
+}
+
+extern "C" int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out)
+{
+    if (!s) return fail(FB_EINVAL, "fb_slab_sample: NULL slab");
+    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_sample");
+    int rc;
+    if ((rc = sample_check("fb_slab_sample", d_field, d_xy, n, d_out))) return rc;
+    return sample(s->c, d_field, d_xy, n, d_out);
+}

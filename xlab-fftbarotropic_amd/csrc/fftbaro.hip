@@ -18,6 +18,7 @@
 #include "fb_azim.h"
 #include "fb_spectra.h"
 #include "fb_tracer.h"
+#include "fb_particles.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1034,6 +1035,10 @@ struct fb_model {
     cf *tr_c0[3], *tr_c1[3], *tr_acc[3];
     float kappa;
     bool tracer, graph_tracer;       // a tracer is set; the captured step holds the tracer's stages
+    // the Lagrangian particles (fb_particles.h; host side in fb_record.h): six float64 arrays of pt_n (base, stage position, RK
+    // accumulator, x then y of each) and the stage velocity u, v as two real fields [2][nx][ny]; NULL and 0 without particles
+    double *pt; int pt_n;
+    float *pt_uv;
 };
 
 static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool phase_flow)
@@ -1074,6 +1079,8 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
 static void model_drop_graph(fb_model *m);
 static void tracer_free(fb_model *m);
 static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_record.h
+static void particles_free(fb_model *m);
+static int particle_stage(fb_model *m, int stage);                      // fb_record.h
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1096,6 +1103,7 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->pres_ref) hipFree(m->pres_ref);
     if (m->spec_red) hipFree(m->spec_red);
     tracer_free(m);
+    particles_free(m);
     delete m;
     return FB_OK;
 }
@@ -1108,6 +1116,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         size_t n = m->src ? (size_t)c->XL * c->ny * 4 : 0;
         for (int g = 0; g < c->ngroups; ++g) n += (c->world > 1 ? (g < c->nact ? 13 : 11) : 8) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
+        if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
         *hbm = n;
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;
@@ -1265,6 +1274,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
     for (int s = 0; s < nsteps; ++s) {
         for (int k = 0; k < 4; ++k) {
             if (m->tracer && (rc = tracer_stage(m, nullptr, k))) return rc;       // the tracer's stage k, from the state this stage starts from
+            if (m->pt_n && (rc = particle_stage(m, k))) return rc;                // the particles' stage k, likewise
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
             PROF_BEGIN(1);
             if ((rc = launch_fused_row(m, 0, c->XL))) return rc;

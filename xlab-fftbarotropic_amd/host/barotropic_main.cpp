@@ -45,6 +45,10 @@
 // the four doubles xc, yc, flat index, value of the centre, so that the sequence over the records is the vortex track.  The last two
 // files of a record in ./log; on one GPU and with --world P, where rank 0 alone writes them.  Arguments that the C ABI would refuse
 // are refused here (exit status 2).
+// --particles FILE (no reference counterpart) reads FILE from the input directory, raw little-endian float64 [n][2] positions (x, y) [m]
+// with n from the file's size, and sets them as the model's Lagrangian particles (fb_model_set_particles); every record gains
+// particles_step_N.bin in the same format, the unwrapped positions, the last file of a record in ./log.  One GPU only: --world P > 1,
+// a file whose size is no positive multiple of 16 bytes and n above 2^24 are refused (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -89,6 +93,7 @@ struct Config {
     std::string tracer_file; float tracer_kappa = 0.0f;                            // the passive tracer's initial field and diffusivity (no reference counterpart)
     bool dump_azim = false; int azim_mode = FB_CENTER_PSI_MIN; double azim_xc = 0.0, azim_yc = 0.0;   // azimuthal means about a vortex centre (no reference counterpart)
     int azim_bins = 0, azim_modes = 4; double azim_dr = 0.0;                       // 0: the default number of bins / bin width
+    std::string particles_file; int n_particles = 0;                               // the Lagrangian particles' initial positions and their number (no reference counterpart)
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -237,7 +242,8 @@ struct RecordWriter {
     double *hk[2] = {nullptr, nullptr};                                                // the tracer's eddy diffusivity table (item buffer TRACER_KEFF_TABLE, table_bytes), rank 0 only
     double *ha[2] = {nullptr, nullptr}; size_t azim_bytes = 0;                         // the azimuthal-mean table (item buffer AZIM_TABLE), rank 0 only
     double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6 };
+    double *hp[2] = {nullptr, nullptr}; size_t part_bytes = 0;                         // the particles' positions (item buffer PARTICLES), one GPU only
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -269,6 +275,7 @@ struct RecordWriter {
                     case TRACER_KEFF_TABLE: tab = hk[job.set]; tb = table_bytes; break;
                     case SPECTRA_TABLE: tab = hs[job.set]; tb = spectra_bytes; break;
                     case AZIM_TABLE: tab = ha[job.set]; tb = azim_bytes; break;
+                    case PARTICLES: tab = hp[job.set]; tb = part_bytes; break;
                     default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
                     }
                     FILE *f = fopen(fn, "wb");
@@ -337,6 +344,8 @@ struct Engine {
     virtual void get_tracer(float *d) = 0;
     virtual void get_tracer_eddy_diffusivity(int nbins, double *d_table) = 0;         // --tracer with --dump-eddy-diffusivity (collective)
     virtual void get_azimuthal(const Config &cfg, double *d_table, double *d_center) = 0;     // --dump-azimuthal, on the compute stream (collective)
+    virtual void set_particles(const double *d_xy, int n) = 0;                        // --particles (one GPU)
+    virtual void get_particles(double *d_xy) = 0;
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -397,6 +406,8 @@ struct SingleEngine : Engine {
     {
         must(fb_model_get_azimuthal(model, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_model_get_azimuthal");
     }
+    void set_particles(const double *d_xy, int n) override { must(fb_model_set_particles(model, d_xy, n), "fb_model_set_particles"); }
+    void get_particles(double *d_xy) override { must(fb_model_get_particles(model, d_xy), "fb_model_get_particles"); }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -452,6 +463,8 @@ struct SlabEngine : Engine {
     {
         must(fb_slab_get_azimuthal(sl, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_slab_get_azimuthal");
     }
+    void set_particles(const double *d_xy, int n) override { must(fb_slab_set_particles(sl, d_xy, n), "fb_slab_set_particles"); }     // (refused in main() already)
+    void get_particles(double *d_xy) override { must(fb_slab_get_particles(sl, d_xy), "fb_slab_get_particles"); }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -488,6 +501,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t azim_bytes = cfg.dump_azim ? (size_t)cfg.azim_bins * (12 + 2 * cfg.azim_modes) * sizeof(double) : 0;
     double *d_azim = nullptr, *d_azim_center = nullptr;
     if (cfg.dump_azim) { must(fb_malloc((void **)&d_azim, azim_bytes), "fb_malloc"); must(fb_malloc((void **)&d_azim_center, 4 * sizeof(double)), "fb_malloc"); }
+    // the particles' positions (--particles): in once, out at every record
+    const size_t part_bytes = (size_t)cfg.n_particles * 2 * sizeof(double);
+    double *d_part = nullptr;
+    if (part_bytes) must(fb_malloc((void **)&d_part, part_bytes), "fb_malloc");
 
     RecordWriter writer;
     size_t set_bytes = 0;
@@ -500,6 +517,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (cfg.dump_keff && tracer && lead) must(fb_malloc_host((void **)&writer.hk[b], table_bytes), "fb_malloc_host");
         if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
         if (cfg.dump_azim && lead) { must(fb_malloc_host((void **)&writer.ha[b], azim_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hc[b], 4 * sizeof(double)), "fb_malloc_host"); }
+        if (part_bytes && lead) must(fb_malloc_host((void **)&writer.hp[b], part_bytes), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
@@ -512,7 +530,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (tracer) writer.items.push_back({"tracer", 10});
     if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
     if (cfg.dump_azim) { writer.items.push_back({"azimuthal", RecordWriter::AZIM_TABLE}); writer.items.push_back({"azimuthal_center", RecordWriter::AZIM_CENTER}); }
-    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes;
+    if (part_bytes) writer.items.push_back({"particles", RecordWriter::PARTICLES});
+    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -552,6 +571,17 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         read_rows(writer.h[0][10]);
         eng->set_tracer(d_in, cfg.tracer_kappa);
         eng->record(e_src);
+        must(fb_event_synchronize(e_h2d), "sync");
+    }
+    if (part_bytes) {                                                                  // the particles' positions, through a pinned record buffer
+        snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.particles_file.c_str());
+        FILE *f = fopen(filename, "rb");
+        if (!f || fread(writer.hp[0], 1, part_bytes, f) != part_bytes) { perror("Read particles."); std::exit(1); }
+        fclose(f);
+        must(fb_memcpy_h2d_async(copy, d_part, writer.hp[0], part_bytes), "h2d");
+        must(fb_event_record(e_h2d, copy), "record");
+        eng->wait(e_h2d);
+        eng->set_particles(d_part, cfg.n_particles);
         must(fb_event_synchronize(e_h2d), "sync");
     }
 
@@ -598,6 +628,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (tracer) eng->get_tracer(d_out[10]);
             if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
             if (cfg.dump_azim) eng->get_azimuthal(cfg, d_azim, d_azim_center);
+            if (d_part) eng->get_particles(d_part);
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
@@ -607,6 +638,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (writer.hk[set]) must(fb_memcpy_d2h_async(copy, writer.hk[set], d_ttable, table_bytes), "d2h");
             if (writer.ha[set]) must(fb_memcpy_d2h_async(copy, writer.ha[set], d_azim, azim_bytes), "d2h");
             if (writer.hc[set]) must(fb_memcpy_d2h_async(copy, writer.hc[set], d_azim_center, 4 * sizeof(double)), "d2h");
+            if (writer.hp[set]) must(fb_memcpy_d2h_async(copy, writer.hp[set], d_part, part_bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -672,6 +704,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (d_spectra) fb_free(d_spectra);
     if (d_azim) fb_free(d_azim);
     if (d_azim_center) fb_free(d_azim_center);
+    if (d_part) fb_free(d_part);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
@@ -679,6 +712,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (writer.hk[b]) fb_free_host(writer.hk[b]);
         if (writer.ha[b]) fb_free_host(writer.ha[b]);
         if (writer.hc[b]) fb_free_host(writer.hc[b]);
+        if (writer.hp[b]) fb_free_host(writer.hp[b]);
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -699,6 +733,7 @@ int main(int argc, char *args[])
                                     {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
                                     {"dump-spectra", 0, 0, 29}, {"tracer", 1, 0, 30}, {"tracer-kappa", 1, 0, 31},
                                     {"dump-azimuthal", 0, 0, 32}, {"azim-center", 1, 0, 33}, {"azim-bins", 1, 0, 34}, {"azim-dr", 1, 0, 35}, {"azim-modes", 1, 0, 36},
+                                    {"particles", 1, 0, 37},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -775,6 +810,7 @@ int main(int argc, char *args[])
             if (!*optarg || *end || !(cfg.azim_dr > 0.0) || cfg.azim_dr > 1.0e300) { fprintf(stderr, "--azim-dr: a finite number > 0\n"); return 2; }
             break;
         }
+        case 37: cfg.particles_file = optarg; break;    // particles_step_N.bin (one GPU only)
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
@@ -808,6 +844,16 @@ int main(int argc, char *args[])
         if (cfg.azim_mode == FB_CENTER_FIXED && !(cfg.azim_xc >= 0.0 && cfg.azim_xc < lx && cfg.azim_yc >= 0.0 && cfg.azim_yc < ly)) {
             fprintf(stderr, "--azim-center: X,Y must lie inside the domain, 0 <= X < Lx and 0 <= Y < Ly\n"); return 2;
         }
+    }
+    if (!cfg.particles_file.empty()) {                                                 // what fb_model_set_particles would refuse
+        if (cfg.world > 1) { fprintf(stderr, "--particles: one GPU only (particles are not supported with --world P > 1)\n"); return 2; }
+        struct stat st;
+        const std::string fn = cfg.input + "/" + cfg.particles_file;
+        if (stat(fn.c_str(), &st) != 0 || st.st_size <= 0 || st.st_size % 16 != 0) {
+            fprintf(stderr, "--particles: %s must hold float64 [n][2], a positive multiple of 16 bytes\n", fn.c_str()); return 2;
+        }
+        if (st.st_size / 16 > (off_t)(1 << 24)) { fprintf(stderr, "--particles: more than 2^24 particles\n"); return 2; }
+        cfg.n_particles = (int)(st.st_size / 16);
     }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
     if (cfg.total_steps < 0) cfg.total_steps = (int)(60 * 60 / cfg.dt);              // configuration.hpp:36

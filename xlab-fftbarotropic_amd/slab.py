@@ -330,6 +330,43 @@ class EngineSlab:
         self.synchronize()
         return (table, c, g) if fields else table
 
+    def set_particles(self, xy):
+        """The Lagrangian particles of binding.Model.set_particles (fb_slab_set_particles); xy=None removes them.  One rank only: on
+        world > 1 this and the three methods below raise FftBaroError with the engine's message."""
+        if xy is None:
+            self.B.check(self.L.fb_slab_set_particles(self._h, None, 0))
+        else:
+            a = self.B.particles_dev(self.torch, xy)
+            self.B.check(self.L.fb_slab_set_particles(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0])))
+        self.synchronize()
+
+    def particle_count(self):
+        n = C.c_int()
+        self.B.check(self.L.fb_slab_particle_count(self._h, C.byref(n)))
+        return n.value
+
+    def particles(self, wrap=False):
+        """The particles' positions, float64 [n, 2], unwrapped or (wrap=True) folded into the domain (fb_slab_get_particles)."""
+        t = self.torch
+        out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
+        self.B.check(self.L.fb_slab_get_particles(self._h, C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return self.B.wrap_positions(t, out, self.Lx, self.Ly) if wrap else out
+
+    def sample(self, field, xy=None):
+        """An [nx, ny] float32 field interpolated to the positions xy, float64 [n, 2], or to the particles (fb_slab_sample)."""
+        t = self.torch
+        if self.world > 1:                                      # (before any buffer is shaped for one rank)
+            self.B.check(self.L.fb_slab_sample(self._h, None, None, 0, None))      # raises with the engine's message
+        f = self._rows(field)
+        a = self.particles() if xy is None else self.B.particles_dev(t, xy)
+        out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()
+        self.B.check(self.L.fb_slab_sample(self._h, C.c_void_p(f.data_ptr()), C.c_void_p(a.data_ptr()), int(a.shape[0]), C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
