@@ -221,6 +221,28 @@ int fb_model_set_particles(fb_model *m, const double *d_xy, int n);        /* NU
 int fb_model_get_particles(fb_model *m, double *d_xy);
 int fb_model_particle_count(fb_model *m, int *n);
 int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out);
+/* Tangent-linear model (no reference counterpart): a perturbation dz of the vorticity, a real [nx][ny] field, carried along the
+ * evolving state by the linearisation of the DISCRETE step (not of the PDE), so that M(zeta + eps dz) - M(zeta) = eps T(dz) + O(eps^2)
+ * for the step M itself.  fb_model_set_tangent takes the device field d_dz_real in as fb_model_set_vort takes the vorticity and keeps
+ * it as a half spectrum dz_c; from then on every step advances dz_c by the RK4 step of main.cpp:288-317 beside vort_c, stage by
+ * stage: stage k uses the vorticity's state zeta of stage k (the state the tracer's stage k uses), psi_c = invertLaplacian(vort_c),
+ * dpsi_c = invertLaplacian(dz_c), u = -psi_y, v = psi_x, du = -dpsi_y, dv = dpsi_x, and
+ *   tend_dz = dealiase( r2c(-u dz_x - v dz_y) + r2c(-du zeta_x - dv zeta_y) + nu laplacian(dz_c) )
+ * in float32, each r2c(...) formed as the vorticity's own stage forms its advective tendency (no source: a vorticity source does not
+ * depend on the state), nu the model's own, the stage forms of main.cpp:246-251, :309-312.  Modes outside the dealiasing circle never
+ * change after fb_model_set_tangent.  One perturbation per model; d_dz_real == NULL removes it and frees its state.  The vorticity,
+ * its step, a tracer, particles and every record are bit for bit what they are without it; tangent, tracer and particles are
+ * independent, any subset may be set.  Setting or removing it drops a captured step (fb_model_use_graph); it is captured again with
+ * the tangent's stages.  fb_model_get_tangent: dz as fb_model_get_vort returns the vorticity.  fb_model_tangent_norm: into the device
+ * float64 *d_out, kind 0 the enstrophy norm <dz^2> / 2, kind 1 the energy norm <|grad dpsi|^2> / 2 (<.>: the mean over the grid), summed
+ * in float64 over the resident half spectrum (Hermitian weights 1 in the columns ky = 0 and ky = ny/2 and 2 elsewhere; the energy norm
+ * leaves the (0, 0) mode out) in a fixed order: two calls on one state give the same bits.  fb_model_tangent_scale: dz *= a (the
+ * renormalisation of a Lyapunov or bred-vector cycle).  FB_EINVAL before any HIP call: a NULL model, output or field, kind outside
+ * {0, 1}, a not finite or zero, get / norm / scale without a tangent set.  Enqueued on the context stream, no synchronisation. */
+int fb_model_set_tangent(fb_model *m, const float *d_dz_real);             /* NULL: remove the tangent */
+int fb_model_get_tangent(fb_model *m, float *d_dz_real);
+int fb_model_tangent_norm(fb_model *m, int kind, double *d_out);           /* 0 enstrophy, 1 energy */
+int fb_model_tangent_scale(fb_model *m, float a);                          /* finite, != 0 */
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -357,6 +379,12 @@ int fb_slab_get_azimuthal(fb_slab *s, int center_mode, double xc, double yc, int
 int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa);  /* NULL: remove the tracer */
 int fb_slab_get_tracer_local(fb_slab *s, float *d_rows);
 int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows);
+/* the tangent-linear model (fb_model_set_tangent) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
+ * world > 1 they return FB_EINVAL with a message. */
+int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real);               /* NULL: remove the tangent */
+int fb_slab_get_tangent(fb_slab *s, float *d_dz_real);
+int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out);
+int fb_slab_tangent_scale(fb_slab *s, float a);
 /* the Lagrangian particles (fb_model_set_particles) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EUNSUPPORTED: particles distributed over row slabs need neighbour halo rows that the all-to-all transport
  * does not provide. */

@@ -142,6 +142,16 @@ def lib():
     for n in ("fb_model_sample", "fb_slab_sample"):
         if hasattr(L, n):
             getattr(L, n).argtypes = [vp, fp, vp, ip, vp]
+    # (likewise the tangent-linear model)
+    for n in ("fb_model_set_tangent", "fb_model_get_tangent", "fb_slab_set_tangent", "fb_slab_get_tangent"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, fp]
+    for n in ("fb_model_tangent_norm", "fb_slab_tangent_norm"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, ip, vp]
+    for n in ("fb_model_tangent_scale", "fb_slab_tangent_scale"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, C.c_float]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -172,6 +182,8 @@ EXPORTS = [
     "fb_azimuthal_cols", "fb_model_get_azimuthal", "fb_slab_get_azimuthal",
     "fb_model_set_particles", "fb_model_get_particles", "fb_model_particle_count", "fb_model_sample",
     "fb_slab_set_particles", "fb_slab_get_particles", "fb_slab_particle_count", "fb_slab_sample",
+    "fb_model_set_tangent", "fb_model_get_tangent", "fb_model_tangent_norm", "fb_model_tangent_scale",
+    "fb_slab_set_tangent", "fb_slab_get_tangent", "fb_slab_tangent_norm", "fb_slab_tangent_scale",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
 
@@ -240,6 +252,39 @@ def _ptr(t):
 
 
 PARTICLES_MAX = 1 << 24
+TANGENT_NORMS = {"enstrophy": 0, "energy": 1}
+
+
+def tangent_kind(kind):
+    """the C ABI's number of a tangent norm: "enstrophy" | "energy" (an int is passed on for the engine to judge)"""
+    if isinstance(kind, str):
+        if kind not in TANGENT_NORMS:
+            raise ValueError("kind: 'enstrophy' or 'energy'")
+        return TANGENT_NORMS[kind]
+    return int(kind)
+
+
+def lyapunov(model, steps, renorm_every, kind="enstrophy"):
+    """Steps `model` (anything with step, tangent_norm, rescale_tangent and dt) by `steps` steps; after every renorm_every steps the
+    perturbation is rescaled to the norm it had at the call.  Returns (the sum of ln(growth factors) / (steps dt) [s^-1], the list of
+    the growth factors sqrt(norm after / norm before) per interval)."""
+    if steps < 1 or renorm_every < 1:
+        raise ValueError("lyapunov: steps and renorm_every must be >= 1")
+    n0 = model.tangent_norm(kind)
+    if not (n0 > 0.0 and np.isfinite(n0)):
+        raise FftBaroError("lyapunov: the tangent's norm is %r" % n0)
+    before, total, factors, done = n0, 0.0, [], 0
+    while done < steps:
+        k = min(renorm_every, steps - done)
+        model.step(k)
+        done += k
+        after = model.tangent_norm(kind)
+        g = float(np.sqrt(after / before))
+        factors.append(g)
+        total += 0.5 * float(np.log(after / before))
+        model.rescale_tangent(float(np.sqrt(n0 / after)))
+        before = model.tangent_norm(kind)
+    return total / (steps * model.dt), factors
 
 
 def particles_dev(torch, xy):
@@ -379,6 +424,7 @@ class Model:
         self.torch = self.fop.torch
         self.nx, self.ny, self.hy = nx, ny, ny // 2 + 1
         self.Lx, self.Ly = Lx, Ly
+        self.nu, self.dt = float(np.float32(nu)), float(np.float32(dt))
         h = C.c_void_p()
         check(lib().fb_model_create(C.byref(h), self.fop._h, nu, dt))
         self._h = h
@@ -537,6 +583,34 @@ class Model:
         check(lib().fb_model_sample(self._h, _ptr(f), _ptr(a), int(a.shape[0]), _ptr(out)))
         self.fop.synchronize()
         return out
+
+    def set_tangent(self, dz):
+        """Sets the perturbation of the tangent-linear model, an [nx, ny] field carried along the evolving vorticity by the
+        linearisation of the step itself (it is stepped beside the vorticity from now on); dz=None removes it."""
+        if dz is None:
+            check(lib().fb_model_set_tangent(self._h, None))
+        else:
+            a = self._dev(dz); check(lib().fb_model_set_tangent(self._h, _ptr(a))); self.fop.synchronize()
+
+    def tangent(self):
+        out = self.fop.empty_real(); check(lib().fb_model_get_tangent(self._h, _ptr(out))); return out
+
+    def tangent_norm(self, kind="enstrophy"):
+        """The perturbation's norm, a float: "enstrophy" <dz^2> / 2 or "energy" <|grad dpsi|^2> / 2, summed in float64 on the GPU."""
+        t = self.torch
+        out = t.empty(1, dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes it on ITS stream
+        check(lib().fb_model_tangent_norm(self._h, tangent_kind(kind), _ptr(out)))
+        self.fop.synchronize()
+        return float(out.item())
+
+    def rescale_tangent(self, a):
+        """dz *= a (a finite and not zero)"""
+        check(lib().fb_model_tangent_scale(self._h, float(a)))
+
+    def lyapunov(self, steps, renorm_every, kind="enstrophy"):
+        """(exponent [s^-1], growth factors): steps the model, renormalising the perturbation every renorm_every steps (lyapunov())."""
+        return lyapunov(self, steps, renorm_every, kind)
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

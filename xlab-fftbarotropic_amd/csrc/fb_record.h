@@ -83,8 +83,9 @@ static int record_to_rows(fb_model *m, fb_slab *s, int nf, RowView *M)
 
 // The record fields of `kind` (one, or three for REC_OW / REC_KEFF / REC_PRES) of every column group through the backward x pass in
 // rec_work[g] ([3][nx][ncols_g], field 0 for one field), and on a slab of several ranks their exchange; *M: the row pass's view.
-// tr: the record is taken of the tracer (its base array, in the 3-pass layout already) in the place of the vorticity.
-static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, bool tr = false)
+// of: the record is taken of a field stepped beside the vorticity (the base arrays of the tracer or of the tangent-linear model, in the
+// 3-pass layout already) in the place of the vorticity.
+static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, cf *const *of = nullptr)
 {
     fb_ctx *c = m->c;
     const int nf = kind >= REC_OW ? 3 : 1;
@@ -97,7 +98,7 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, bool
         if ((rc = rec_alloc(&m->rec_work[g], 3 * n)) || (xchg && (rc = rec_alloc(&m->rec_send[g], 3 * n)))) return rc;
         cf *z = m->rec_work[g];
         // copy of vort_c in the 3-pass layout into field 0 (main.cpp:273), then the kind's fields from it in place
-        if (tr) HIPCHK(hipMemcpyAsync(z, m->tr_c0[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        if (of) HIPCHK(hipMemcpyAsync(z, of[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
         else if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
         const SpecCoef k = make_coef(c);
         const dim3 grid(grid_for(c, n)), blk(256);
@@ -118,12 +119,12 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, bool
 
 // One record into the rows of this rank (one GPU: every row), normalised by 1/GRIDS: REC_VORT, REC_PSI, REC_U, REC_V into out0;
 // REC_OW: W into out0 and tau_fil into out1 (either may be NULL); REC_KEFF: zeta into out0 and |grad zeta|^2 into out1.
-static int record(fb_model *m, fb_slab *s, RecKind kind, float *out0, float *out1 = nullptr, bool tr = false)
+static int record(fb_model *m, fb_slab *s, RecKind kind, float *out0, float *out1 = nullptr, cf *const *of = nullptr)
 {
     fb_ctx *c = m->c;
     RowArgs a = row_args_base(c);
     int rc;
-    if ((rc = record_fields(m, s, kind, &a.M, tr))) return rc;
+    if ((rc = record_fields(m, s, kind, &a.M, of))) return rc;
     const float g = 1.0f / (float)((size_t)c->nx * c->ny);
     a.scale = kind == REC_U ? -g : g;                   // u = -dpsi/dy: normalise, then negate (SURVEY note N3): (x * g) * -1 == x * (-g) exactly
     a.rout = out0; a.rin = out1;                        // (ROW_OW, ROW_KEFF: rin carries the second output, fb_kernels.h row_rout2)
@@ -222,7 +223,7 @@ static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, floa
     if (!zeta) zeta = m->keff_fields;
     if (!grad2) grad2 = m->keff_fields + n;
     int rc;
-    if ((rc = record(m, s, REC_KEFF, zeta, grad2, tr))) return rc;
+    if ((rc = record(m, s, REC_KEFF, zeta, grad2, tr ? m->tr_c0 : nullptr))) return rc;
     return keff_finish(m, s, nbins, zeta, grad2, d_table, tr ? (double)m->kappa : (double)m->nu);
 }
 
@@ -731,6 +732,25 @@ static void tracer_free(fb_model *m)
     m->tracer = false;
 }
 
+// The vorticity's state of an RK stage of column group g in the 3-pass layout: *v0 the base, *v1 the stage state (staged: ZB, else
+// the base itself), a masked mode to be read from *v0.  Where the step keeps its state arrays in a layout of its own,
+// k_tracer_vstate_* merges the two into `vx` (a field of the record workspace) and both point there.
+static int stage_vstate(fb_model *m, int g, bool staged, cf *vx, const cf **v0, const cf **v1)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[g];
+    const SpecCoef coef = make_coef(c);
+    *v0 = m->gb[g].ZA; *v1 = staged ? m->gb[g].ZB : m->gb[g].ZA;
+    if (m->xpass != XP_COLS)
+        hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, *v0, *v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
+    else if (state_tm(c))
+        hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, grp_elems(c, G))), dim3(256), 0, c->stream, coef, *v0, *v1, vx, G.ncols, c->N1, c->N2, G.ky0);
+    else return FB_OK;
+    HIPCHK(hipGetLastError());
+    *v0 = *v1 = vx;
+    return FB_OK;
+}
+
 // One RK stage of the tracer, at the top of the step's stage `stage`: the vorticity's state of this stage is vort_c0 (ZA) at stage 0
 // and the stage state ZB afterwards (k_col_mid and k_col_full store it at every stage below 3), the tracer's likewise.  Launches per
 // column group: k_tracer_vstate (where the state arrays are not in the 3-pass layout), k_tracer_deriv; record_advect; per group of
@@ -742,16 +762,9 @@ static int tracer_stage(fb_model *m, fb_slab *s, int stage)
     int rc;
     auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
         const bool staged = stage > 0 && g < c->nact;       // the frozen columns' state is the base at every stage
-        const cf *v0 = m->gb[g].ZA, *v1 = staged ? m->gb[g].ZB : m->gb[g].ZA;
-        cf *vx = z + 2 * n;                                  // field 2: read by k_tracer_deriv before it writes grady psi there
-        if (m->xpass != XP_COLS) {
-            hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, v0, v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
-            v0 = v1 = vx;
-        } else if (state_tm(c)) {
-            hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, vx, G.ncols, c->N1, c->N2, G.ky0);
-            v0 = v1 = vx;
-        }
-        HIPCHK(hipGetLastError());
+        const cf *v0, *v1;
+        int r;
+        if ((r = stage_vstate(m, g, staged, z + 2 * n, &v0, &v1))) return r;      // field 2: read by k_tracer_deriv before it writes grady psi there
         hipLaunchKernelGGL(k_tracer_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, v0, v1, (const cf *)m->tr_c0[g],
                            (const cf *)(staged ? m->tr_c1[g] : m->tr_c0[g]), z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
         HIPCHK(hipGetLastError());
@@ -776,33 +789,22 @@ static int tracer_stage(fb_model *m, fb_slab *s, int stage)
     return FB_OK;
 }
 
-// readField + r2c of the tracer as state_in takes the vorticity (ROW_FWD, the transpose on a slab, the forward x pass), through the
-// record workspace into the tracer's base arrays; d_rows == NULL removes the tracer.  The vorticity, its derivative fields and
-// `primed` stay as they are.  The captured step is dropped and the next fb_model_step starts with an eager step, which launches every
-// kernel of the longer step once before it is captured (launch_lds).
-static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
+// readField + r2c of a second real field as state_in takes the vorticity (ROW_FWD, the transpose on a slab, the forward x pass),
+// through the record workspace into the field's own arrays in the 3-pass layout: the base c0 of every column group, and for the
+// groups of active columns the stage state c1 and the accumulator acc, zeroed (the tracer's, or the tangent-linear model's).
+static int beside_in(fb_model *m, fb_slab *s, const float *d_rows, cf **c0, cf **c1, cf **acc)
 {
     fb_ctx *c = m->c;
     const bool xchg = s && c->world > 1;
     int rc;
-    model_drop_graph(m);
-    m->warmed = false;
-    if (!d_rows) {
-        if (m->tracer) HIPCHK(hipStreamSynchronize(c->stream));
-        tracer_free(m);
-        return FB_OK;
-    }
     if ((rc = advect_workspace(m, s))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t n = grp_elems(c, c->grp[g]);
         if (n == 0) continue;
-        if ((rc = rec_alloc(&m->tr_c0[g], n)) || (g < c->nact && ((rc = rec_alloc(&m->tr_c1[g], n)) || (rc = rec_alloc(&m->tr_acc[g], n))))) {
-            tracer_free(m);
-            return rc;
-        }
+        if ((rc = rec_alloc(&c0[g], n)) || (g < c->nact && ((rc = rec_alloc(&c1[g], n)) || (rc = rec_alloc(&acc[g], n))))) return rc;
         if (g < c->nact) {                                  // pad columns and the columns beyond the last active tile stay zero
-            HIPCHK(hipMemsetAsync(m->tr_c1[g], 0, n * sizeof(cf), c->stream));
-            HIPCHK(hipMemsetAsync(m->tr_acc[g], 0, n * sizeof(cf), c->stream));
+            HIPCHK(hipMemsetAsync(c1[g], 0, n * sizeof(cf), c->stream));
+            HIPCHK(hipMemsetAsync(acc[g], 0, n * sizeof(cf), c->stream));
         }
     }
     RowArgs a = row_args_base(c);
@@ -829,8 +831,26 @@ static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
         if (n == 0) continue;
         cf *t = m->rec_work[g];
         if ((rc = launch_col_strided<-1>(c, G, t, 1, 0)) || (rc = launch_col_block<-1>(c, G, t, 1, 0))) return rc;
-        HIPCHK(hipMemcpyAsync(m->tr_c0[g], t, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c0[g], t, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
     }
+    return FB_OK;
+}
+
+// The tracer in (beside_in); d_rows == NULL removes the tracer.  The vorticity, its derivative fields and `primed` stay as they are.
+// The captured step is dropped and the next fb_model_step starts with an eager step, which launches every kernel of the longer step
+// once before it is captured (launch_lds).
+static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    model_drop_graph(m);
+    m->warmed = false;
+    if (!d_rows) {
+        if (m->tracer) HIPCHK(hipStreamSynchronize(c->stream));
+        tracer_free(m);
+        return FB_OK;
+    }
+    if ((rc = beside_in(m, s, d_rows, m->tr_c0, m->tr_c1, m->tr_acc))) { tracer_free(m); return rc; }
     m->kappa = kappa;
     m->tracer = true;
     return FB_OK;
@@ -856,7 +876,7 @@ extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real)
     if (!m || !d_c_real) return fail(FB_EINVAL, "fb_model_get_tracer: NULL");
     if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer: no tracer is set");
     NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_c_real, nullptr, true);
+    return record(m, nullptr, REC_VORT, d_c_real, nullptr, m->tr_c0);
 }
 
 extern "C" int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2)
@@ -884,7 +904,7 @@ extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows)
     if (!s || !d_rows) return fail(FB_EINVAL, "fb_slab_get_tracer_local: NULL");
     if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_local: no tracer is set");
     SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_rows, nullptr, true);
+    return record(s->m, s, REC_VORT, d_rows, nullptr, s->m->tr_c0);
 }
 
 // collective, as fb_slab_get_eddy_diffusivity
@@ -896,6 +916,211 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
     if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: no tracer is set");
     SLAB_READY(s);
     return record_keff(s->m, s, nbins, d_table, d_c_rows, d_grad2_rows, true);
+}
+
+// ---- the tangent-linear model (kernels: fb_tangent.h) ----
+static void tangent_free(fb_model *m)
+{
+    for (int g = 0; g < 3; ++g) {
+        cf **arr[] = {&m->tg_c0[g], &m->tg_c1[g], &m->tg_acc[g], &m->tg_j[g]};
+        for (cf **p : arr) if (*p) { hipFree(*p); *p = nullptr; }
+    }
+    if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
+    m->tangent = false;
+}
+
+// One RK stage of the perturbation, at the top of the step's stage `stage`, where tracer_stage runs and from the same states: the
+// vorticity's is ZA at stage 0 and ZB afterwards, the perturbation's its base and its stage state.  Two advect passes,
+//   pass 0: J(dz; psi)    k_tangent_deriv fills gradx dz, grady dz, grady psi, gradx psi
+//   pass 1: J(zeta; dpsi) k_tangent_deriv fills gradx zeta, grady zeta, grady dpsi, gradx dpsi
+// each per column group stage_vstate (k_tracer_vstate_* where the state arrays are not in the 3-pass layout), k_tangent_deriv, then
+// record_advect's backward x pass, row pass and forward x pass; the first pass's result is copied to tg_j before the second
+// overwrites the record workspace; then per group of active columns k_tangent_update with both.
+static int tangent_stage(fb_model *m, fb_slab *s, int stage)
+{
+    fb_ctx *c = m->c;
+    const SpecCoef coef = make_coef(c);
+    int rc;
+    for (int pass = 0; pass < 2; ++pass) {
+        auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
+            const bool staged = stage > 0 && g < c->nact;   // the frozen columns' state is the base at every stage
+            const cf *v0, *v1, *d0 = m->tg_c0[g], *d1 = staged ? m->tg_c1[g] : m->tg_c0[g];
+            int r;
+            if ((r = stage_vstate(m, g, staged, z + 2 * n, &v0, &v1))) return r;      // field 2: read by k_tangent_deriv before it writes there
+            hipLaunchKernelGGL(k_tangent_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, pass ? v0 : d0, pass ? v1 : d1, pass ? d0 : v0,
+                               pass ? d1 : v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+            HIPCHK(hipGetLastError());
+            return FB_OK;
+        };
+        if ((rc = record_advect(m, s, fill))) return rc;
+        for (int g = 0; g < c->nact && pass == 0; ++g) {
+            const size_t n = grp_elems(c, c->grp[g]);
+            if (n) HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        }
+    }
+    for (int g = 0; g < c->nact; ++g) {
+        const ColGroup &G = c->grp[g];
+        const int ncr = 16 * G.nct_active;
+        if (grp_elems(c, G) == 0 || ncr == 0) continue;
+        const dim3 grid(grid_for(c, (size_t)c->nx * ncr / 2)), blk(256);
+        const cf *j1 = m->tg_j[g], *j2 = advect_out(m, s, g);
+        cf *c0 = m->tg_c0[g], *c1 = m->tg_c1[g], *ac = m->tg_acc[g];
+        switch (stage) {
+        case 0: hipLaunchKernelGGL((k_tangent_update<0>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        case 1: hipLaunchKernelGGL((k_tangent_update<1>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        case 2: hipLaunchKernelGGL((k_tangent_update<2>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        default: hipLaunchKernelGGL((k_tangent_update<3>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
+        }
+        HIPCHK(hipGetLastError());
+    }
+    return FB_OK;
+}
+
+// The perturbation in (beside_in, as the tracer) with the scratch of the first advect pass and the partial sums of the norm
+// ([ngroups][max_wg] float64); d_rows == NULL removes it.  The vorticity, a tracer, particles and `primed` stay as they are.  As
+// tracer_in: the captured step is dropped and the next fb_model_step starts with an eager step before the longer step is captured.
+static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows)
+{
+    fb_ctx *c = m->c;
+    int rc = FB_OK;
+    model_drop_graph(m);
+    m->warmed = false;
+    if (!d_rows) {
+        if (m->tangent) HIPCHK(hipStreamSynchronize(c->stream));
+        tangent_free(m);
+        return FB_OK;
+    }
+    for (int g = 0; g < c->nact && !rc; ++g)
+        if (grp_elems(c, c->grp[g])) rc = rec_alloc(&m->tg_j[g], grp_elems(c, c->grp[g]));
+    if (!rc && !m->tg_red && hipMalloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double)) != hipSuccess) {
+        m->tg_red = nullptr;
+        rc = fail(FB_ENOMEM, "record-path allocation failed");
+    }
+    if (rc || (rc = beside_in(m, s, d_rows, m->tg_c0, m->tg_c1, m->tg_acc))) { tangent_free(m); return rc; }
+    m->tangent = true;
+    return FB_OK;
+}
+
+// kind 0: the enstrophy norm <dz^2> / 2, kind 1: the energy norm <|grad dpsi|^2> / 2 (means over the grid), of the resident spectrum
+// (k_tangent_norm per column group, then k_tangent_norm_final over every partial sum) into *d_out on the device
+static int tangent_norm(fb_model *m, int kind, double *d_out)
+{
+    fb_ctx *c = m->c;
+    const SpecCoef coef = make_coef(c);
+    int np = 0;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        const int nwg = grid_for(c, n / 2);
+        hipLaunchKernelGGL(k_tangent_norm, dim3(nwg), dim3(256), 0, c->stream, coef, (const cf *)m->tg_c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np);
+        HIPCHK(hipGetLastError());
+        np += nwg;
+    }
+    const double grids = (double)c->nx * c->ny;
+    hipLaunchKernelGGL(k_tangent_norm_final, dim3(1), dim3(256), 0, c->stream, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+static int tangent_scale(fb_model *m, float a)
+{
+    fb_ctx *c = m->c;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const size_t n = grp_elems(c, c->grp[g]);
+        if (n == 0) continue;
+        hipLaunchKernelGGL(k_tangent_scale, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, m->tg_c0[g], n, a);
+        HIPCHK(hipGetLastError());
+    }
+    return FB_OK;
+}
+
+// what the entry points refuse before any HIP call
+static int tangent_check(const char *fn, const fb_model *m, bool need_set)
+{
+    if (!m) return fail(FB_EINVAL, std::string(fn) + ": NULL model");
+    if (need_set && !m->tangent) return fail(FB_EINVAL, std::string(fn) + ": no tangent is set");
+    return FB_OK;
+}
+static int tangent_norm_check(const char *fn, int kind, const double *d_out)
+{
+    if (kind != 0 && kind != 1) return fail(FB_EINVAL, std::string(fn) + ": kind must be 0 (enstrophy) or 1 (energy)");
+    if (!d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL output");
+    return FB_OK;
+}
+static int tangent_scale_check(const char *fn, float a)
+{
+    if (!std::isfinite(a) || a == 0.0f) return fail(FB_EINVAL, std::string(fn) + ": the factor must be finite and not zero");
+    return FB_OK;
+}
+
+extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real)
+{
+    int rc;
+    if ((rc = tangent_check("fb_model_set_tangent", m, false))) return rc;
+    NEED_SINGLE(m->c);
+    return tangent_in(m, nullptr, d_dz_real);
+}
+
+extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real)
+{
+    int rc;
+    if (!d_dz_real) return fail(FB_EINVAL, "fb_model_get_tangent: NULL");
+    if ((rc = tangent_check("fb_model_get_tangent", m, true))) return rc;
+    NEED_SINGLE(m->c);
+    return record(m, nullptr, REC_VORT, d_dz_real, nullptr, m->tg_c0);
+}
+
+extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out)
+{
+    int rc;
+    if ((rc = tangent_norm_check("fb_model_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_model_tangent_norm", m, true))) return rc;
+    NEED_SINGLE(m->c);
+    return tangent_norm(m, kind, d_out);
+}
+
+extern "C" int fb_model_tangent_scale(fb_model *m, float a)
+{
+    int rc;
+    if ((rc = tangent_scale_check("fb_model_tangent_scale", a)) || (rc = tangent_check("fb_model_tangent_scale", m, true))) return rc;
+    NEED_SINGLE(m->c);
+    return tangent_scale(m, a);
+}
+
+// a slab of one rank goes through the same code; on several ranks the tangent-linear model is refused
+#define SLAB_TANGENT_ONE_RANK(s, fn) do { if (!(s)) return fail(FB_EINVAL, std::string(fn) + ": NULL slab"); if ((s)->c->world > 1) return fail(FB_EINVAL, std::string(fn) + ": the tangent-linear model is not supported on a slab of several ranks (world > 1)"); } while (0)
+
+extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real)
+{
+    SLAB_TANGENT_ONE_RANK(s, "fb_slab_set_tangent");
+    SLAB_READY(s);
+    return tangent_in(s->m, s, d_dz_real);
+}
+
+extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real)
+{
+    SLAB_TANGENT_ONE_RANK(s, "fb_slab_get_tangent");
+    int rc;
+    if (!d_dz_real) return fail(FB_EINVAL, "fb_slab_get_tangent: NULL");
+    if ((rc = tangent_check("fb_slab_get_tangent", s->m, true))) return rc;
+    SLAB_READY(s);
+    return record(s->m, s, REC_VORT, d_dz_real, nullptr, s->m->tg_c0);
+}
+
+extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out)
+{
+    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_norm");
+    int rc;
+    if ((rc = tangent_norm_check("fb_slab_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_slab_tangent_norm", s->m, true))) return rc;
+    return tangent_norm(s->m, kind, d_out);
+}
+
+extern "C" int fb_slab_tangent_scale(fb_slab *s, float a)
+{
+    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_scale");
+    int rc;
+    if ((rc = tangent_scale_check("fb_slab_tangent_scale", a)) || (rc = tangent_check("fb_slab_tangent_scale", s->m, true))) return rc;
+    return tangent_scale(s->m, a);
 }
 
 // ---- the Lagrangian particles (kernels: fb_particles.h) ----
@@ -928,16 +1153,9 @@ static int particle_stage(fb_model *m, int stage)
     const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
     const SpecCoef coef = make_coef(c);
     cf *z = m->rec_work[0];
-    const cf *v0 = m->gb[0].ZA, *v1 = stage > 0 ? m->gb[0].ZB : m->gb[0].ZA;
+    const cf *v0, *v1;
     int rc;
-    if (m->xpass != XP_COLS) {
-        hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, v0, v1, z + n, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
-        v0 = v1 = z + n;
-    } else if (state_tm(c)) {
-        hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z + n, G.ncols, c->N1, c->N2, G.ky0);
-        v0 = v1 = z + n;
-    }
-    HIPCHK(hipGetLastError());
+    if ((rc = stage_vstate(m, 0, stage > 0, z + n, &v0, &v1))) return rc;
     hipLaunchKernelGGL(k_particle_uv_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
     HIPCHK(hipGetLastError());
     if ((rc = launch_col_block<+1>(c, G, z, 2, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 2, (long)n))) return rc;

@@ -385,6 +385,7 @@ extern "C" int fb_slab_step(fb_slab *s, int nsteps)
         for (int k = 0; k < 4; ++k) {                       // main.cpp:288-317
             if (s->m->tracer && (rc = tracer_stage(s->m, s, k))) return rc;
             if (s->m->pt_n && (rc = particle_stage(s->m, k))) return rc;     // (one rank only: fb_slab_set_particles)
+            if (s->m->tangent && (rc = tangent_stage(s->m, s, k))) return rc; // (one rank only: fb_slab_set_tangent)
             if ((rc = slab_stage(s, k))) return rc;
         }
     return FB_OK;

@@ -19,6 +19,7 @@
 #include "fb_spectra.h"
 #include "fb_tracer.h"
 #include "fb_particles.h"
+#include "fb_tangent.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1039,6 +1040,11 @@ struct fb_model {
     // accumulator, x then y of each) and the stage velocity u, v as two real fields [2][nx][ny]; NULL and 0 without particles
     double *pt; int pt_n;
     float *pt_uv;
+    // the tangent-linear model (fb_tangent.h; host side in fb_record.h): the perturbation's base, stage state and RK accumulator as
+    // the tracer's, the first advect pass's tendency of a stage (groups of active columns) and the norm's partial sums; NULL without
+    cf *tg_c0[3], *tg_c1[3], *tg_acc[3], *tg_j[3];
+    double *tg_red;
+    bool tangent;
 };
 
 static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool phase_flow)
@@ -1081,6 +1087,8 @@ static void tracer_free(fb_model *m);
 static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_record.h
 static void particles_free(fb_model *m);
 static int particle_stage(fb_model *m, int stage);                      // fb_record.h
+static void tangent_free(fb_model *m);
+static int tangent_stage(fb_model *m, struct fb_slab *s, int stage);    // fb_record.h
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1104,6 +1112,7 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->spec_red) hipFree(m->spec_red);
     tracer_free(m);
     particles_free(m);
+    tangent_free(m);
     delete m;
     return FB_OK;
 }
@@ -1117,6 +1126,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups; ++g) n += (c->world > 1 ? (g < c->nact ? 13 : 11) : 8) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
         if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
+        for (int g = 0; g < c->ngroups && m->tangent; ++g) n += (g < c->nact ? 4 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);     // the tangent-linear model's
         *hbm = n;
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;
@@ -1275,6 +1285,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
         for (int k = 0; k < 4; ++k) {
             if (m->tracer && (rc = tracer_stage(m, nullptr, k))) return rc;       // the tracer's stage k, from the state this stage starts from
             if (m->pt_n && (rc = particle_stage(m, k))) return rc;                // the particles' stage k, likewise
+            if (m->tangent && (rc = tangent_stage(m, nullptr, k))) return rc;     // the tangent-linear model's stage k, likewise
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
             PROF_BEGIN(1);
             if ((rc = launch_fused_row(m, 0, c->XL))) return rc;

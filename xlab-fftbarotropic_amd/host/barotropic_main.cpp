@@ -49,12 +49,19 @@
 // with n from the file's size, and sets them as the model's Lagrangian particles (fb_model_set_particles); every record gains
 // particles_step_N.bin in the same format, the unwrapped positions, the last file of a record in ./log.  One GPU only: --world P > 1,
 // a file whose size is no positive multiple of 16 bytes and n above 2^24 are refused (exit status 2).
+// --tangent FILE [--tangent-renorm K] (no reference counterpart, K >= 0, default 0) reads FILE from the input directory as the initial
+// field is read and sets it as the perturbation of the model's tangent-linear model (fb_model_set_tangent); every record gains
+// tangent_step_N.bin and tangent_growth_step_N.bin, three float64: the time, the perturbation's enstrophy norm <dz^2> / 2 and the sum
+// of ln(growth) since the start (half the log of the norm's ratios, over every renormalisation), the last two files of a record in
+// ./log.  With K > 0 the perturbation is rescaled to its initial norm after every K steps.  One GPU only: --world P > 1 is refused
+// (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -93,6 +100,7 @@ struct Config {
     std::string tracer_file; float tracer_kappa = 0.0f;                            // the passive tracer's initial field and diffusivity (no reference counterpart)
     bool dump_azim = false; int azim_mode = FB_CENTER_PSI_MIN; double azim_xc = 0.0, azim_yc = 0.0;   // azimuthal means about a vortex centre (no reference counterpart)
     int azim_bins = 0, azim_modes = 4; double azim_dr = 0.0;                       // 0: the default number of bins / bin width
+    std::string tangent_file; int tangent_renorm = 0;                              // the tangent-linear model's initial perturbation; renormalise every K steps (no reference counterpart)
     std::string particles_file; int n_particles = 0;                               // the Lagrangian particles' initial positions and their number (no reference counterpart)
 };
 
@@ -236,14 +244,15 @@ struct RecordWriter {
     std::thread th; std::mutex mu; std::condition_variable cv;
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
-    void *e_copy[2] = {nullptr, nullptr}; float *h[2][11] = {};
+    void *e_copy[2] = {nullptr, nullptr}; float *h[2][12] = {};
     double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
     double *hs[2] = {nullptr, nullptr}; size_t spectra_bytes = 0;                      // the spectra table (item buffer SPECTRA_TABLE), rank 0 only
     double *hk[2] = {nullptr, nullptr};                                                // the tracer's eddy diffusivity table (item buffer TRACER_KEFF_TABLE, table_bytes), rank 0 only
     double *ha[2] = {nullptr, nullptr}; size_t azim_bytes = 0;                         // the azimuthal-mean table (item buffer AZIM_TABLE), rank 0 only
     double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
     double *hp[2] = {nullptr, nullptr}; size_t part_bytes = 0;                         // the particles' positions (item buffer PARTICLES), one GPU only
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7 };
+    double hg[2][3] = {};                                                              // the tangent's time, norm and sum of ln(growth) (item buffer TANGENT_GROWTH), filled by the step loop
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -276,6 +285,7 @@ struct RecordWriter {
                     case SPECTRA_TABLE: tab = hs[job.set]; tb = spectra_bytes; break;
                     case AZIM_TABLE: tab = ha[job.set]; tb = azim_bytes; break;
                     case PARTICLES: tab = hp[job.set]; tb = part_bytes; break;
+                    case TANGENT_GROWTH: tab = hg[job.set]; tb = 3 * sizeof(double); break;
                     default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
                     }
                     FILE *f = fopen(fn, "wb");
@@ -346,6 +356,10 @@ struct Engine {
     virtual void get_azimuthal(const Config &cfg, double *d_table, double *d_center) = 0;     // --dump-azimuthal, on the compute stream (collective)
     virtual void set_particles(const double *d_xy, int n) = 0;                        // --particles (one GPU)
     virtual void get_particles(double *d_xy) = 0;
+    virtual void set_tangent(const float *d) = 0;                                     // --tangent (one GPU)
+    virtual void get_tangent(float *d) = 0;
+    virtual double tangent_norm(double *d_scratch) = 0;                               // the enstrophy norm, on the host: waits for the compute stream
+    virtual void tangent_scale(float a) = 0;
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -408,6 +422,16 @@ struct SingleEngine : Engine {
     }
     void set_particles(const double *d_xy, int n) override { must(fb_model_set_particles(model, d_xy, n), "fb_model_set_particles"); }
     void get_particles(double *d_xy) override { must(fb_model_get_particles(model, d_xy), "fb_model_get_particles"); }
+    void set_tangent(const float *d) override { must(fb_model_set_tangent(model, d), "fb_model_set_tangent"); }
+    void get_tangent(float *d) override { must(fb_model_get_tangent(model, d), "fb_model_get_tangent"); }
+    double tangent_norm(double *d_scratch) override
+    {
+        double v = 0.0;
+        must(fb_model_tangent_norm(model, 0, d_scratch), "fb_model_tangent_norm");
+        must(fb_memcpy_d2h(fop, &v, d_scratch, sizeof v), "d2h");
+        return v;
+    }
+    void tangent_scale(float a) override { must(fb_model_tangent_scale(model, a), "fb_model_tangent_scale"); }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -465,6 +489,10 @@ struct SlabEngine : Engine {
     }
     void set_particles(const double *d_xy, int n) override { must(fb_slab_set_particles(sl, d_xy, n), "fb_slab_set_particles"); }     // (refused in main() already)
     void get_particles(double *d_xy) override { must(fb_slab_get_particles(sl, d_xy), "fb_slab_get_particles"); }
+    void set_tangent(const float *d) override { must(fb_slab_set_tangent(sl, d), "fb_slab_set_tangent"); }                             // (refused in main() already)
+    void get_tangent(float *d) override { must(fb_slab_get_tangent(sl, d), "fb_slab_get_tangent"); }
+    double tangent_norm(double *) override { std::fprintf(stderr, "--tangent: one GPU only\n"); std::exit(2); }
+    void tangent_scale(float a) override { must(fb_slab_tangent_scale(sl, a), "fb_slab_tangent_scale"); }
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -478,10 +506,11 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     must(fb_stream_create(&copy), "stream");
     for (void **e : {&e_rec, &e_h2d, &e_src}) must(fb_event_create(e), "event");
     // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt);
-    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure); 10 = tracer (--tracer)
-    constexpr int NB = 11;
-    const bool tracer = !cfg.tracer_file.empty();
-    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres, tracer};
+    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure); 10 = tracer (--tracer);
+    // 11 = the tangent-linear model's perturbation (--tangent)
+    constexpr int NB = 12;
+    const bool tracer = !cfg.tracer_file.empty(), tangent = !cfg.tangent_file.empty();
+    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres, tracer, tangent};
     float *d_in = nullptr, *d_out[NB] = {};
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
     for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
@@ -505,6 +534,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t part_bytes = (size_t)cfg.n_particles * 2 * sizeof(double);
     double *d_part = nullptr;
     if (part_bytes) must(fb_malloc((void **)&d_part, part_bytes), "fb_malloc");
+    // the tangent's norm (--tangent): one float64 on the device; its norm at the start, at the last renormalisation, and the sum of
+    // ln(growth) over the renormalisations so far
+    double *d_norm = nullptr, tg_norm0 = 0.0, tg_norm_ref = 0.0, tg_sum = 0.0;
+    if (tangent) must(fb_malloc((void **)&d_norm, sizeof(double)), "fb_malloc");
 
     RecordWriter writer;
     size_t set_bytes = 0;
@@ -531,6 +564,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
     if (cfg.dump_azim) { writer.items.push_back({"azimuthal", RecordWriter::AZIM_TABLE}); writer.items.push_back({"azimuthal_center", RecordWriter::AZIM_CENTER}); }
     if (part_bytes) writer.items.push_back({"particles", RecordWriter::PARTICLES});
+    if (tangent) { writer.items.push_back({"tangent", 11}); writer.items.push_back({"tangent_growth", RecordWriter::TANGENT_GROWTH}); }
     writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
@@ -584,6 +618,16 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         eng->set_particles(d_part, cfg.n_particles);
         must(fb_event_synchronize(e_h2d), "sync");
     }
+    if (tangent) {                                                                     // the perturbation's field, as the initial field was read
+        snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.tangent_file.c_str());
+        must(fb_stream_wait_event(copy, e_src), "wait");                               // set_vort / set_tracer has read d_in
+        read_rows(writer.h[0][11]);
+        eng->set_tangent(d_in);
+        eng->record(e_src);
+        must(fb_event_synchronize(e_h2d), "sync");
+        tg_norm0 = tg_norm_ref = eng->tangent_norm(d_norm);
+        if (!(tg_norm0 > 0.0) || !std::isfinite(tg_norm0)) { std::fprintf(stderr, "--tangent: the perturbation's norm is %g\n", tg_norm0); std::exit(1); }
+    }
 
     // [timing] ("add steps/s + GB/s summary"; the reference prints no timing, main.cpp:262-264).  The step loop is
     // never synchronised for it: time-stamped events on the compute stream bracket the stretches BETWEEN record steps -- a stretch ends
@@ -629,6 +673,11 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
             if (cfg.dump_azim) eng->get_azimuthal(cfg, d_azim, d_azim_center);
             if (d_part) eng->get_particles(d_part);
+            if (tangent) {
+                eng->get_tangent(d_out[11]);
+                const double now = eng->tangent_norm(d_norm);                          // (waits for the compute stream: one host round trip per record)
+                writer.hg[set][0] = (double)step * cfg.dt; writer.hg[set][1] = now; writer.hg[set][2] = tg_sum + 0.5 * std::log(now / tg_norm_ref);
+            }
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
@@ -659,6 +708,12 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             }
         }
         eng->step();                                                                   // main.cpp:286-317
+        if (tangent && cfg.tangent_renorm > 0 && (step + 1 - cfg.start_step) % cfg.tangent_renorm == 0) {       // back to the initial norm
+            const double now = eng->tangent_norm(d_norm);
+            tg_sum += 0.5 * std::log(now / tg_norm_ref);
+            eng->tangent_scale((float)std::sqrt(tg_norm0 / now));
+            tg_norm_ref = eng->tangent_norm(d_norm);
+        }
     }
     stamp(t_end);
     eng->sync();                                                                       // the last step has run ...
@@ -705,6 +760,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (d_azim) fb_free(d_azim);
     if (d_azim_center) fb_free(d_azim_center);
     if (d_part) fb_free(d_part);
+    if (d_norm) fb_free(d_norm);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
@@ -733,7 +789,7 @@ int main(int argc, char *args[])
                                     {"dump-pressure", 0, 0, 24}, {"pres-rho", 1, 0, 25}, {"pres-f", 1, 0, 26}, {"pres-ref-x", 1, 0, 27}, {"pres-ref-y", 1, 0, 28},
                                     {"dump-spectra", 0, 0, 29}, {"tracer", 1, 0, 30}, {"tracer-kappa", 1, 0, 31},
                                     {"dump-azimuthal", 0, 0, 32}, {"azim-center", 1, 0, 33}, {"azim-bins", 1, 0, 34}, {"azim-dr", 1, 0, 35}, {"azim-modes", 1, 0, 36},
-                                    {"particles", 1, 0, 37},
+                                    {"particles", 1, 0, 37}, {"tangent", 1, 0, 38}, {"tangent-renorm", 1, 0, 39},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -811,6 +867,14 @@ int main(int argc, char *args[])
             break;
         }
         case 37: cfg.particles_file = optarg; break;    // particles_step_N.bin (one GPU only)
+        case 38: cfg.tangent_file = optarg; break;      // tangent_step_N.bin, tangent_growth_step_N.bin (one GPU only)
+        case 39: {
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (!*optarg || *end || v < 0 || v > 0x7fffffffL) { fprintf(stderr, "--tangent-renorm: an integer >= 0\n"); return 2; }
+            cfg.tangent_renorm = (int)v;
+            break;
+        }
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
@@ -855,6 +919,7 @@ int main(int argc, char *args[])
         if (st.st_size / 16 > (off_t)(1 << 24)) { fprintf(stderr, "--particles: more than 2^24 particles\n"); return 2; }
         cfg.n_particles = (int)(st.st_size / 16);
     }
+    if (!cfg.tangent_file.empty() && cfg.world > 1) { fprintf(stderr, "--tangent: one GPU only (the tangent-linear model is not supported with --world P > 1)\n"); return 2; }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
     if (cfg.total_steps < 0) cfg.total_steps = (int)(60 * 60 / cfg.dt);              // configuration.hpp:36
     float dx = 0, dy = 0;                                                            // printed before being set, main.cpp:89-90

@@ -117,6 +117,7 @@ class EngineSlab:
         self.torch, self.B, self.L = torch, B, B.lib()
         self.nx, self.ny, self.rank, self.world, self.dist = nx, ny, rank, world, dist
         self.Lx, self.Ly = Lx, Ly
+        self.dt = float(np.float32(dt))
         h = C.c_void_p()
         B.check(self.L.fb_slab_create(C.byref(h), nx, ny, Lx, Ly, nu, dt, rank, world))
         self._h = h
@@ -366,6 +367,36 @@ class EngineSlab:
         self.B.check(self.L.fb_slab_sample(self._h, C.c_void_p(f.data_ptr()), C.c_void_p(a.data_ptr()), int(a.shape[0]), C.c_void_p(out.data_ptr())))
         self.synchronize()
         return out
+
+    def set_tangent(self, dz):
+        """The perturbation of the tangent-linear model of binding.Model.set_tangent (fb_slab_set_tangent); dz=None removes it.  One
+        rank only: on world > 1 this and the four methods below raise FftBaroError with the engine's message."""
+        if dz is None or self.world > 1:                        # (before any buffer is shaped for one rank)
+            self.B.check(self.L.fb_slab_set_tangent(self._h, None))
+        else:
+            a = self._rows(dz)
+            self.B.check(self.L.fb_slab_set_tangent(self._h, C.c_void_p(a.data_ptr())))
+        self.synchronize()
+
+    def tangent(self):
+        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
+        self.B.check(self.L.fb_slab_get_tangent(self._h, C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
+    def tangent_norm(self, kind="enstrophy"):
+        t = self.torch
+        out = t.empty(1, dtype=t.float64, device="cuda")
+        t.cuda.current_stream().synchronize()                   # the engine writes it on ITS stream
+        self.B.check(self.L.fb_slab_tangent_norm(self._h, self.B.tangent_kind(kind), C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return float(out.item())
+
+    def rescale_tangent(self, a):
+        self.B.check(self.L.fb_slab_tangent_scale(self._h, float(a)))
+
+    def lyapunov(self, steps, renorm_every, kind="enstrophy"):
+        return self.B.lyapunov(self, steps, renorm_every, kind)
 
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
