@@ -1,9 +1,9 @@
-"""The tangent-linear model on the GPU (fb_model_set_tangent; kernels csrc/fb_tangent.h) against the float64 reference of the coupled
+"""The tangent-linear model on the GPU (fb_model_set_tangent; kernels csrc/fb_tracer.h, csrc/fb_tangent.h) against the float64 reference of the coupled
 system (tests/tangent_numpy.py), on every kernel path of the engine.
 
 The inputs of the path matrix are tangent_numpy.tangent_inputs: the elliptic vortex and a perturbation, each with white noise that was
 never dealiased, and a vorticity source.  So both fields carry state in every mode outside the dealiasing circle, where the kernels
-have logic of their own (k_tracer_vstate_* and k_tangent_deriv pick the base or the stage array per mode, k_tangent_update leaves a
+have logic of their own (k_tracer_vstate_* and k_advect_deriv pick the base or the stage array per mode, k_beside_update leaves a
 masked mode alone and runs on the active column tiles only), and the source must reach the velocity and not the perturbation.
 tangent_numpy.PATH_CASES holds one row per grid class, with the probe shifts and the float32 figure that make the parity bar of 1e-5
 decisive (asserted on the CPU in tests/test_tangent_cpu.py, stored in the fixture for the slow cases).  One line of figures per case

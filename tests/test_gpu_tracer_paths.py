@@ -2,7 +2,7 @@
 
 The inputs are tracer_numpy.noisy_inputs: the elliptic vortex and an offset gaussian tracer, each with white noise that was never
 dealiased, and a vorticity source.  So both fields carry state in every mode outside the dealiasing circle, where the tracer kernels
-have logic of their own (k_tracer_vstate_* and k_tracer_deriv pick the base or the stage array per mode, k_tracer_update leaves a
+have logic of their own (k_tracer_vstate_* and k_advect_deriv pick the base or the stage array per mode, k_beside_update leaves a
 masked mode alone and runs on the active column tiles only, ZB is never written at a frozen mode), and the source must reach the
 velocity and not the tracer.  tracer_numpy.PATH_CASES holds one row per grid class, with the noise amplitude and step count at which
 a reference that is blind to the masked modes of either stage state differs from the true one by >= 1e-4, ten times the parity bar

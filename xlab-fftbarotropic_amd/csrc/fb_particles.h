@@ -60,7 +60,7 @@ FB_DEV double pt_gather(const float *__restrict__ f, int ny, const int ix[4], co
 
 // ---- the spectral fields of u and v ----
 // za: vort_c0, zb: the stage state, both in the 3-pass layout (a mode outside the dealiasing circle is read from the base, as
-// k_tracer_deriv reads it; stage 0 and exported states: zb == za).  Field 0 of z: grady(psi_c), field 1 (fstride further):
+// k_advect_deriv reads it; stage 0 and exported states: zb == za).  Field 0 of z: grady(psi_c), field 1 (fstride further):
 // gradx(psi_c), psi_c = invertLaplacian(state), in the float32 forms of k_psi_private<1> and <2> (no contraction); pad columns zero.
 // za, zb may be field 1 of z: each element is read before it is written, by the same thread.
 __global__ void __launch_bounds__(256) k_particle_uv_spec(SpecCoef c, const cf *za, const cf *zb, cf *z, long fstride, int P, int N1, int N2, int ky0)

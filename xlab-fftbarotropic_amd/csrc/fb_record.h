@@ -20,8 +20,9 @@ static int state_in(fb_model *m, fb_slab *s, const float *d_rows)
     RowArgs a = row_args_base(c);
     a.rin = d_rows;
     const cf *ts[3] = {m->gb[0].t_send, m->gb[1].t_send, m->gb[2].t_send};
+    cf *const tr[3] = {m->gb[0].t_recv, m->gb[1].t_recv, m->gb[2].t_recv};
     a.T = c->world == 1 ? view_single(c, m->gb[0].t_send, 0) : view_slab(c, ts, 1);
-    if ((rc = launch_row<ROW_FWD>(c, a)) || (s && (rc = slab_transpose_all(s)))) return rc;
+    if ((rc = launch_row<ROW_FWD>(c, a)) || (s && (rc = slab_rows_to_cols(s, ts, tr, c->ngroups)))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
         const ColGroup &G = c->grp[g];
         cf *t = m->gb[g].t_recv;
@@ -48,10 +49,20 @@ extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
 // ---- the record layer ----
 enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF, REC_PRES };
 
-static int rec_alloc(cf **p, size_t elems)
+// a buffer of the record path: allocated on first use, then kept
+static int rec_alloc(void **p, size_t bytes)
 {
-    if (!*p && hipMalloc((void **)p, elems * sizeof(cf)) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+    if (!*p && hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
     return FB_OK;
+}
+// a scratch buffer of the record path, grown to the largest request (hipFree waits for the device)
+static int rec_reserve(void **p, size_t *cap, size_t bytes)
+{
+    if (*p && *cap >= bytes) return FB_OK;
+    if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; *cap = 0; }
+    const int rc = rec_alloc(p, bytes);
+    if (!rc) *cap = bytes;
+    return rc;
 }
 
 // nf fields (one, three, or four for the spectra) of every column group, through the backward x pass in rec_work[g], to the row pass: *M is its view.  One
@@ -95,11 +106,11 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, cf *
         const ColGroup &G = c->grp[g];
         const size_t n = grp_elems(c, G);
         if (n == 0) continue;
-        if ((rc = rec_alloc(&m->rec_work[g], 3 * n)) || (xchg && (rc = rec_alloc(&m->rec_send[g], 3 * n)))) return rc;
+        if ((rc = rec_alloc((void **)&m->rec_work[g], 3 * n * sizeof(cf))) || (xchg && (rc = rec_alloc((void **)&m->rec_send[g], 3 * n * sizeof(cf))))) return rc;
         cf *z = m->rec_work[g];
         // copy of vort_c in the 3-pass layout into field 0 (main.cpp:273), then the kind's fields from it in place
         if (of) HIPCHK(hipMemcpyAsync(z, of[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-        else if ((rc = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return rc;
+        else if ((rc = export_state(m, g, z))) return rc;
         const SpecCoef k = make_coef(c);
         const dim3 grid(grid_for(c, n)), blk(256);
         switch (kind) {
@@ -155,7 +166,7 @@ static int keff_check(const char *fn, const double *d_table, int nbins)
 //   sum_part [nwg][nbins], hist_send [world][nbins][2], hist_recv [world][nbins][2] (f64); cnt_part [nwg][nbins] (u32);
 //   mm_part [nmm][2], mm_send [world][2], mm_recv [world][2] (f32).
 // One GPU (s == NULL or world 1): the rank's results are written straight to the receive buffers.  A slab: two small all-gathers
-// through the transport's all-to-all (each rank sends the same block to every peer), behind the compute stream's work.
+// (slab_gather), behind the compute stream's work.
 static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, const float *grad2, double *d_table, double kappa)
 {
     fb_ctx *c = m->c;
@@ -171,29 +182,19 @@ static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, co
     const size_t o_cnt = o_hrecv + world * nh * sizeof(double), o_mm = o_cnt + (size_t)nwg * nbins * sizeof(unsigned);
     const size_t o_mmsend = o_mm + 2 * (size_t)nmm * sizeof(float), o_mmrecv = o_mmsend + 2 * (size_t)world * sizeof(float);
     const size_t bytes = o_mmrecv + 2 * (size_t)world * sizeof(float);
-    if (!m->keff_red || m->keff_red_cap < bytes) {
-        if (m->keff_red) { HIPCHK(hipFree(m->keff_red)); m->keff_red = nullptr; m->keff_red_cap = 0; }      // (hipFree waits for the device)
-        if (hipMalloc(&m->keff_red, bytes) != hipSuccess) { m->keff_red = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
-        m->keff_red_cap = bytes;
-    }
+    int rc;
+    if ((rc = rec_reserve(&m->keff_red, &m->keff_red_cap, bytes))) return rc;
     char *base = (char *)m->keff_red;
     double *sum_part = (double *)base, *hsend = (double *)(base + o_hsend), *hrecv = (double *)(base + o_hrecv);
     unsigned *cnt_part = (unsigned *)(base + o_cnt);
     float *mm_part = (float *)(base + o_mm), *mmsend = (float *)(base + o_mmsend), *mmrecv = (float *)(base + o_mmrecv);
     const bool xchg = s && world > 1;
-    int rc;
-    auto gather = [&](const float *send, float *recv, size_t count) -> int {
-        int r;
-        if ((r = slab_after(s->comm, s->comp, s->ev_misc[0]))) return r;
-        if ((r = s->tp.alltoall(s->tp.self, send, recv, count, 0, count, s->comm))) return r;
-        return slab_after(s->comp, s->comm, s->ev_misc[1]);
-    };
     if (v4) hipLaunchKernelGGL((k_keff_minmax<true>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
     else hipLaunchKernelGGL((k_keff_minmax<false>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_keff_minmax_final, dim3(1), dim3(256), 0, c->stream, (const float *)mm_part, nmm, xchg ? mmsend : mmrecv, xchg ? world : 1);
     HIPCHK(hipGetLastError());
-    if (xchg && (rc = gather(mmsend, mmrecv, 2))) return rc;
+    if (xchg && (rc = slab_gather(s, mmsend, mmrecv, 2))) return rc;
     // dynamic LDS: 12 B per bin (histogram), 16 B per bin (table); the attribute once per kernel and device, for 4096 bins
     if ((rc = set_max_lds(c, (const void *)k_keff_hist<true>, 4096 * 12)) || (rc = set_max_lds(c, (const void *)k_keff_hist<false>, 4096 * 12)) ||
         (rc = set_max_lds(c, (const void *)k_keff_table, 4096 * 16)))
@@ -204,7 +205,7 @@ static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, co
     hipLaunchKernelGGL(k_keff_reduce, dim3((nbins + KEFF_RB - 1) / KEFF_RB), dim3(256), 0, c->stream, (const unsigned *)cnt_part, (const double *)sum_part, nwg, nbins,
                        xchg ? hsend : hrecv, xchg ? world : 1, nh);
     HIPCHK(hipGetLastError());
-    if (xchg && (rc = gather((const float *)hsend, (float *)hrecv, 2 * nh))) return rc;
+    if (xchg && (rc = slab_gather(s, hsend, hrecv, 2 * nh))) return rc;
     hipLaunchKernelGGL(k_keff_table, dim3(1), dim3(256), (size_t)nbins * 16, c->stream, (const double *)hrecv, world, (const float *)mmrecv, nbins,
                        (double)c->lx / c->nx, (double)c->ly / c->ny, kappa, d_table);
     HIPCHK(hipGetLastError());
@@ -212,19 +213,16 @@ static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, co
 }
 
 // the row pass's outputs: the caller's, or the model's own buffers (keff_fields [2][XL][ny]) for those the caller does not want
-// (tr: of the tracer, with its kappa where the table of the vorticity uses nu)
-static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, float *zeta, float *grad2, bool tr = false)
+// (of, kappa: the table of a field stepped beside the vorticity as record_fields takes it, with its diffusivity; NULL and nu for the vorticity's)
+static int record_keff(fb_model *m, fb_slab *s, int nbins, double *d_table, float *zeta, float *grad2, cf *const *of, double kappa)
 {
     const size_t n = (size_t)m->c->XL * m->c->ny;
-    if ((!zeta || !grad2) && !m->keff_fields && hipMalloc((void **)&m->keff_fields, 2 * n * sizeof(float)) != hipSuccess) {
-        m->keff_fields = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
-    }
+    int rc;
+    if ((!zeta || !grad2) && (rc = rec_alloc((void **)&m->keff_fields, 2 * n * sizeof(float)))) return rc;
     if (!zeta) zeta = m->keff_fields;
     if (!grad2) grad2 = m->keff_fields + n;
-    int rc;
-    if ((rc = record(m, s, REC_KEFF, zeta, grad2, tr ? m->tr_c0 : nullptr))) return rc;
-    return keff_finish(m, s, nbins, zeta, grad2, d_table, tr ? (double)m->kappa : (double)m->nu);
+    if ((rc = record(m, s, REC_KEFF, zeta, grad2, of))) return rc;
+    return keff_finish(m, s, nbins, zeta, grad2, d_table, kappa);
 }
 
 // ---- azimuthal means about a vortex centre (fb_azim.h): psi or zeta for the centre, then zeta, u, v and the table ----
@@ -285,8 +283,8 @@ template <int NM> static int azim_launch_bin(const fb_ctx *c, const AzimGeo &g, 
 // The fields: psi (FB_CENTER_PSI_MIN only) into field 1 and its argmin, or zeta into field 0 and its argmax; then zeta into field 0,
 // u into field 1, and v, the last record taken, into the record workspace where that record's row pass no longer reads or never
 // read: field 1 of rec_work on one GPU, the largest group's rec_work on a slab of several ranks (its one field has left for
-// rec_send by then).  On a slab two small all-gathers through the transport's all-to-all, as keff_finish: the ranks' candidates,
-// then their sums; a rank's global row is rank * XL + local row.
+// rec_send by then).  On a slab two small all-gathers (slab_gather), as keff_finish: the ranks' candidates, then their sums; a
+// rank's global row is rank * XL + local row.
 static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
 {
     fb_ctx *c = m->c;
@@ -295,29 +293,16 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
     const size_t n = (size_t)c->XL * c->ny, np = (size_t)nbins * ns;
     const int nparts = grid_for(c, n);
     int rc;
-    if (!m->azim_fields && hipMalloc((void **)&m->azim_fields, 2 * n * sizeof(float)) != hipSuccess) {
-        m->azim_fields = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
-    }
+    if ((rc = rec_alloc((void **)&m->azim_fields, 2 * n * sizeof(float)))) return rc;
     const size_t o_precv = (xchg ? world * np : 0) * sizeof(double), o_csend = o_precv + (xchg ? world : 1) * np * sizeof(double);
     const size_t o_crecv = o_csend + (xchg ? world : 0) * AZIM_ARG_W * sizeof(double), o_pi = o_crecv + (size_t)world * AZIM_ARG_W * sizeof(double);
     const size_t o_pk = o_pi + (size_t)nparts * sizeof(long long), bytes = o_pk + (size_t)nparts * sizeof(float);
-    if (!m->azim_red || m->azim_red_cap < bytes) {
-        if (m->azim_red) { HIPCHK(hipFree(m->azim_red)); m->azim_red = nullptr; m->azim_red_cap = 0; }      // (hipFree waits for the device)
-        if (hipMalloc(&m->azim_red, bytes) != hipSuccess) { m->azim_red = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
-        m->azim_red_cap = bytes;
-    }
+    if ((rc = rec_reserve(&m->azim_red, &m->azim_red_cap, bytes))) return rc;
     char *base = (char *)m->azim_red;
     double *psend = (double *)base, *precv = (double *)(base + o_precv), *csend = (double *)(base + o_csend), *crecv = (double *)(base + o_crecv);
     long long *pi = (long long *)(base + o_pi);
     float *pk = (float *)(base + o_pk);
     float *f0 = m->azim_fields, *f1 = m->azim_fields + n;
-    auto gather = [&](const double *send, double *recv, size_t count) -> int {
-        int r;
-        if ((r = slab_after(s->comm, s->comp, s->ev_misc[0]))) return r;
-        if ((r = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * count, 0, 2 * count, s->comm))) return r;
-        return slab_after(s->comp, s->comm, s->ev_misc[1]);
-    };
     AzimGeo g;
     g.lx = (double)c->lx; g.ly = (double)c->ly; g.dx = g.lx / c->nx; g.dy = g.ly / c->ny; g.dr = dr;
     g.nbins = nbins; g.XL = c->XL; g.ny = c->ny; g.row0 = c->rank * c->XL;
@@ -338,7 +323,7 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
         hipLaunchKernelGGL(k_azim_arg_final, dim3(1), dim3(256), 0, c->stream, (const float *)pk, (const long long *)pi, nparts, (const float *)q,
                            (long long)c->rank * (long long)n, xchg ? csend : crecv, xchg ? world : 1);
         HIPCHK(hipGetLastError());
-        if (xchg && (rc = gather(csend, crecv, AZIM_ARG_W))) return rc;
+        if (xchg && (rc = slab_gather(s, csend, crecv, 2 * AZIM_ARG_W))) return rc;
         hipLaunchKernelGGL(k_azim_center, dim3(1), dim3(64), 0, c->stream, (const double *)crecv, world, 0.0, 0.0, c->ny, g.dx, g.dy, d_center);
         HIPCHK(hipGetLastError());
     }
@@ -372,7 +357,7 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
     if (rc) return rc;
     if (xchg) {                                             // one copy of this rank's sums per peer
         for (int r = 1; r < world; ++r) HIPCHK(hipMemcpyAsync(psend + r * np, psend, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        if ((rc = gather(psend, precv, np))) return rc;
+        if ((rc = slab_gather(s, psend, precv, 2 * np))) return rc;
     }
     hipLaunchKernelGGL(k_azim_table, dim3(1), dim3(256), (size_t)nbins * sizeof(double), c->stream, (const double *)precv, xchg ? world : 1, nbins, nmodes, dr,
                        g.dx, g.dy, d_table);
@@ -403,24 +388,14 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
     const bool xchg = s && world > 1;
     const float g = 1.0f / (float)((size_t)c->nx * c->ny);
     int rc;
-    if (!m->pres_ref && hipMalloc((void **)&m->pres_ref, 2 * (size_t)world * sizeof(float)) != hipSuccess) {
-        m->pres_ref = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
-    }
+    if ((rc = rec_alloc((void **)&m->pres_ref, 2 * (size_t)world * sizeof(float)))) return rc;
     RowArgs a = row_args_base(c);
     if ((rc = record_fields(m, s, REC_PRES, &a.M))) return rc;
     const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
     a.T = xchg ? view_slab(c, ts, 1) : view_single(c, m->rec_work[0], 0);
     a.scale = g;
     if ((rc = launch_row<ROW_PRES>(c, a))) return rc;
-    if (xchg) {                                             // rows -> columns, the tendency's direction
-        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-        for (int k = 0; k < c->ngroups; ++k) {
-            const size_t blk = (size_t)c->XL * c->grp[k].ncols;
-            if ((rc = slab_xchg(s, m->rec_send[k], m->rec_work[k], blk, 0, blk))) return rc;
-        }
-        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    }
+    if (xchg && (rc = slab_rows_to_cols(s, m->rec_send, m->rec_work, c->ngroups))) return rc;
     const SpecCoef coef = make_coef(c);
     for (int k = 0; k < c->ngroups; ++k) {
         const ColGroup &G = c->grp[k];
@@ -428,7 +403,7 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
         if (n == 0) continue;
         cf *z = m->rec_work[k];
         if ((rc = launch_col_strided<-1>(c, G, z, 1, 0)) || (rc = launch_col_block<-1>(c, G, z, 1, 0))) return rc;
-        if ((rc = m->xpass != XP_COLS ? full_export_state(m, z + n) : state_convert(c, G, m->gb[k].ZA, z + n, false))) return rc;
+        if ((rc = export_state(m, k, z + n))) return rc;
         hipLaunchKernelGGL(k_pres_solve, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)(z + n), z, rho, f, G.ncols, c->N1, c->N2, G.ky0);
         HIPCHK(hipGetLastError());
         if ((rc = launch_col_block<+1>(c, G, z, 1, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 1, (long)n))) return rc;
@@ -437,19 +412,14 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
     if ((rc = record_to_rows(m, s, 1, &b.M))) return rc;
     b.scale = g; b.rout = out;
     if ((rc = launch_row<ROW_INV>(c, b))) return rc;
-    // the reference point: its owner's value to every rank (one float per peer through the transport's all-to-all, as keff_finish
-    // gathers), then p -= p_ref over this rank's rows
+    // the reference point: its owner's value to every rank (slab_gather of one float), then p -= p_ref over this rank's rows
     const size_t nloc = (size_t)c->XL * c->ny;
     const int owner = (int)((size_t)flat / nloc);
     float *ref_send = m->pres_ref, *ref_recv = m->pres_ref + world;
     const long at = (!xchg || owner == c->rank) ? (long)((size_t)flat - (size_t)owner * nloc) : -1;
     hipLaunchKernelGGL(k_pres_ref, dim3((world + 63) / 64), dim3(64), 0, c->stream, (const float *)out, at, xchg ? ref_send : ref_recv, xchg ? world : 1);
     HIPCHK(hipGetLastError());
-    if (xchg) {
-        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-        if ((rc = s->tp.alltoall(s->tp.self, ref_send, ref_recv, 1, 0, 1, s->comm))) return rc;
-        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    }
+    if (xchg && (rc = slab_gather(s, ref_send, ref_recv, 1))) return rc;
     const float *ref = ref_recv + (xchg ? owner : 0);
     const bool v4 = ((size_t)out & 15) == 0;                // nloc is a multiple of 4 (ny >= 64)
     const dim3 grid(grid_for(c, v4 ? nloc / 4 : nloc)), blk(256);
@@ -468,7 +438,7 @@ static int rec_grow(cf **p, unsigned char *have, size_t n, int nf)
 {
     if (*p && (*have ? *have : 3) >= nf) return FB_OK;
     if (*p) { HIPCHK(hipFree(*p)); *p = nullptr; *have = 0; }
-    if (hipMalloc((void **)p, nf * n * sizeof(cf)) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
+    if (int rc = rec_alloc((void **)p, nf * n * sizeof(cf))) return rc;
     *have = (unsigned char)nf;
     return FB_OK;
 }
@@ -535,14 +505,7 @@ template <class Fill> static int record_advect(fb_model *m, fb_slab *s, Fill fil
     }
     a.scale = 1.0f / (float)((size_t)c->nx * c->ny);
     if ((rc = launch_row<ROW_FUSED>(c, a, c->row))) return rc;             // main.cpp:151-227,237 without vort_src
-    if (xchg) {                                             // rows -> columns, the tendency's direction
-        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-        for (int k = 0; k < c->nact; ++k) {
-            const size_t blk = (size_t)c->XL * c->grp[k].ncols;
-            if ((rc = slab_xchg(s, m->rec_send[k], m->rec_work[k], blk, 0, blk))) return rc;
-        }
-        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    }
+    if (xchg && (rc = slab_rows_to_cols(s, m->rec_send, m->rec_work, c->nact))) return rc;
     for (int k = 0; k < c->nact; ++k) {
         const ColGroup &G = c->grp[k];
         if (grp_elems(c, G) == 0) continue;
@@ -565,14 +528,11 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
     const int nshells = spec_nshells(sg);
     const size_t np = (size_t)nshells * SPEC_SUMS;
     int rc;
-    if (!m->spec_red && hipMalloc((void **)&m->spec_red, (xchg ? 2 : 1) * (size_t)world * np * sizeof(double)) != hipSuccess) {
-        m->spec_red = nullptr;
-        return fail(FB_ENOMEM, "record-path allocation failed");
-    }
+    if ((rc = rec_alloc(&m->spec_red, (xchg ? 2 : 1) * (size_t)world * np * sizeof(double)))) return rc;
     const SpecCoef coef = make_coef(c);
     auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
         int r;
-        if ((r = m->xpass != XP_COLS ? full_export_state(m, z) : state_convert(c, G, m->gb[g].ZA, z, false))) return r;
+        if ((r = export_state(m, g, z))) return r;
         hipLaunchKernelGGL(k_spectra_deriv, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
         HIPCHK(hipGetLastError());
         return FB_OK;
@@ -586,7 +546,7 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
         if (n == 0) continue;
         const bool active = k < c->nact;
         cf *nh = advect_out(m, s, k), *st = xchg ? m->rec_work[k] + n : m->rec_work[k];
-        if ((rc = m->xpass != XP_COLS ? full_export_state(m, st) : state_convert(c, G, m->gb[k].ZA, st, false))) return rc;
+        if ((rc = export_state(m, k, st))) return rc;
         const int q = sgr.ng++;
         sgr.a[q] = st; sgr.nh[q] = active ? nh : nullptr; sgr.ncols[q] = G.ncols; sgr.ky0[q] = G.ky0;
     }
@@ -594,11 +554,7 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
     hipLaunchKernelGGL(k_spectra_gather, dim3(nshells), dim3(256), 0, c->stream, sg, sgr, c->N1, c->N2, coef.gws_i, (double)m->nu, xchg ? send : recv,
                        xchg ? world : 1, np);
     HIPCHK(hipGetLastError());
-    if (xchg) {
-        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-        if ((rc = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * np, 0, 2 * np, s->comm))) return rc;
-        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    }
+    if (xchg && (rc = slab_gather(s, send, recv, 2 * np))) return rc;
     hipLaunchKernelGGL(k_spectra_table, dim3(1), dim3(256), 0, c->stream, (const double *)recv, xchg ? world : 1, nshells, sg.dk, d_table);
     HIPCHK(hipGetLastError());
     return FB_OK;
@@ -632,7 +588,7 @@ extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_t
     int rc;
     if ((rc = keff_check("fb_model_get_eddy_diffusivity", d_table, nbins))) return rc;
     NEED_SINGLE(m->c);
-    return record_keff(m, nullptr, nbins, d_table, d_zeta, d_grad2);
+    return record_keff(m, nullptr, nbins, d_table, d_zeta, d_grad2, nullptr, m->nu);
 }
 
 extern "C" int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres)
@@ -682,7 +638,7 @@ extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_tab
     SLAB_READY(s);
     int rc;
     if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
-    return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows);
+    return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows, nullptr, s->m->nu);
 }
 
 extern "C" int fb_model_get_azimuthal(fb_model *m, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
@@ -720,588 +676,4 @@ extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table)
     if (!d_table) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL table");
     SLAB_READY(s);
     return record_spectra(s->m, s, d_table);
-}
-
-// ---- the passive tracer (kernels: fb_tracer.h) ----
-static void tracer_free(fb_model *m)
-{
-    for (int g = 0; g < 3; ++g) {
-        cf **arr[] = {&m->tr_c0[g], &m->tr_c1[g], &m->tr_acc[g]};
-        for (cf **p : arr) if (*p) { hipFree(*p); *p = nullptr; }
-    }
-    m->tracer = false;
-}
-
-// The vorticity's state of an RK stage of column group g in the 3-pass layout: *v0 the base, *v1 the stage state (staged: ZB, else
-// the base itself), a masked mode to be read from *v0.  Where the step keeps its state arrays in a layout of its own,
-// k_tracer_vstate_* merges the two into `vx` (a field of the record workspace) and both point there.
-static int stage_vstate(fb_model *m, int g, bool staged, cf *vx, const cf **v0, const cf **v1)
-{
-    fb_ctx *c = m->c;
-    const ColGroup &G = c->grp[g];
-    const SpecCoef coef = make_coef(c);
-    *v0 = m->gb[g].ZA; *v1 = staged ? m->gb[g].ZB : m->gb[g].ZA;
-    if (m->xpass != XP_COLS)
-        hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, *v0, *v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
-    else if (state_tm(c))
-        hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, grp_elems(c, G))), dim3(256), 0, c->stream, coef, *v0, *v1, vx, G.ncols, c->N1, c->N2, G.ky0);
-    else return FB_OK;
-    HIPCHK(hipGetLastError());
-    *v0 = *v1 = vx;
-    return FB_OK;
-}
-
-// One RK stage of the tracer, at the top of the step's stage `stage`: the vorticity's state of this stage is vort_c0 (ZA) at stage 0
-// and the stage state ZB afterwards (k_col_mid and k_col_full store it at every stage below 3), the tracer's likewise.  Launches per
-// column group: k_tracer_vstate (where the state arrays are not in the 3-pass layout), k_tracer_deriv; record_advect; per group of
-// active columns k_tracer_update.  On a slab the exchanges are record_advect's, on the streams and events the records use.
-static int tracer_stage(fb_model *m, fb_slab *s, int stage)
-{
-    fb_ctx *c = m->c;
-    const SpecCoef coef = make_coef(c);
-    int rc;
-    auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
-        const bool staged = stage > 0 && g < c->nact;       // the frozen columns' state is the base at every stage
-        const cf *v0, *v1;
-        int r;
-        if ((r = stage_vstate(m, g, staged, z + 2 * n, &v0, &v1))) return r;      // field 2: read by k_tracer_deriv before it writes grady psi there
-        hipLaunchKernelGGL(k_tracer_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, v0, v1, (const cf *)m->tr_c0[g],
-                           (const cf *)(staged ? m->tr_c1[g] : m->tr_c0[g]), z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
-    };
-    if ((rc = record_advect(m, s, fill))) return rc;
-    for (int g = 0; g < c->nact; ++g) {
-        const ColGroup &G = c->grp[g];
-        const int ncr = 16 * G.nct_active;
-        if (grp_elems(c, G) == 0 || ncr == 0) continue;
-        const dim3 grid(grid_for(c, (size_t)c->nx * ncr / 2)), blk(256);
-        const cf *jh = advect_out(m, s, g);
-        cf *c0 = m->tr_c0[g], *c1 = m->tr_c1[g], *ac = m->tr_acc[g];
-        switch (stage) {
-        case 0: hipLaunchKernelGGL((k_tracer_update<0>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 1: hipLaunchKernelGGL((k_tracer_update<1>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 2: hipLaunchKernelGGL((k_tracer_update<2>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        default: hipLaunchKernelGGL((k_tracer_update<3>), grid, blk, 0, c->stream, coef, jh, c0, c1, ac, m->kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        }
-        HIPCHK(hipGetLastError());
-    }
-    return FB_OK;
-}
-
-// readField + r2c of a second real field as state_in takes the vorticity (ROW_FWD, the transpose on a slab, the forward x pass),
-// through the record workspace into the field's own arrays in the 3-pass layout: the base c0 of every column group, and for the
-// groups of active columns the stage state c1 and the accumulator acc, zeroed (the tracer's, or the tangent-linear model's).
-static int beside_in(fb_model *m, fb_slab *s, const float *d_rows, cf **c0, cf **c1, cf **acc)
-{
-    fb_ctx *c = m->c;
-    const bool xchg = s && c->world > 1;
-    int rc;
-    if ((rc = advect_workspace(m, s))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t n = grp_elems(c, c->grp[g]);
-        if (n == 0) continue;
-        if ((rc = rec_alloc(&c0[g], n)) || (g < c->nact && ((rc = rec_alloc(&c1[g], n)) || (rc = rec_alloc(&acc[g], n))))) return rc;
-        if (g < c->nact) {                                  // pad columns and the columns beyond the last active tile stay zero
-            HIPCHK(hipMemsetAsync(c1[g], 0, n * sizeof(cf), c->stream));
-            HIPCHK(hipMemsetAsync(acc[g], 0, n * sizeof(cf), c->stream));
-        }
-    }
-    RowArgs a = row_args_base(c);
-    a.rin = d_rows;
-    if (xchg) {
-        const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
-        a.T = view_slab(c, ts, 1);
-    } else {
-        HIPCHK(hipMemsetAsync(m->rec_work[0], 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
-        a.T = view_single(c, m->rec_work[0], 0);
-    }
-    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
-    if (xchg) {
-        if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-        for (int g = 0; g < c->ngroups; ++g) {
-            const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-            if ((rc = slab_xchg(s, m->rec_send[g], m->rec_work[g], blk, 0, blk))) return rc;
-        }
-        if ((rc = slab_after(s->comp, s->comm, s->ev_misc[1]))) return rc;
-    }
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        const size_t n = grp_elems(c, G);
-        if (n == 0) continue;
-        cf *t = m->rec_work[g];
-        if ((rc = launch_col_strided<-1>(c, G, t, 1, 0)) || (rc = launch_col_block<-1>(c, G, t, 1, 0))) return rc;
-        HIPCHK(hipMemcpyAsync(c0[g], t, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-    }
-    return FB_OK;
-}
-
-// The tracer in (beside_in); d_rows == NULL removes the tracer.  The vorticity, its derivative fields and `primed` stay as they are.
-// The captured step is dropped and the next fb_model_step starts with an eager step, which launches every kernel of the longer step
-// once before it is captured (launch_lds).
-static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
-{
-    fb_ctx *c = m->c;
-    int rc;
-    model_drop_graph(m);
-    m->warmed = false;
-    if (!d_rows) {
-        if (m->tracer) HIPCHK(hipStreamSynchronize(c->stream));
-        tracer_free(m);
-        return FB_OK;
-    }
-    if ((rc = beside_in(m, s, d_rows, m->tr_c0, m->tr_c1, m->tr_acc))) { tracer_free(m); return rc; }
-    m->kappa = kappa;
-    m->tracer = true;
-    return FB_OK;
-}
-
-static int kappa_check(const char *fn, float kappa)
-{
-    if (!(kappa >= 0.0f) || !std::isfinite(kappa)) return fail(FB_EINVAL, std::string(fn) + ": kappa must be finite and >= 0");
-    return FB_OK;
-}
-
-extern "C" int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_set_tracer: NULL model");
-    int rc;
-    if ((rc = kappa_check("fb_model_set_tracer", kappa))) return rc;
-    NEED_SINGLE(m->c);
-    return tracer_in(m, nullptr, d_c_real, kappa);
-}
-
-extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real)
-{
-    if (!m || !d_c_real) return fail(FB_EINVAL, "fb_model_get_tracer: NULL");
-    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer: no tracer is set");
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_c_real, nullptr, m->tr_c0);
-}
-
-extern "C" int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: NULL model");
-    int rc;
-    if ((rc = keff_check("fb_model_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
-    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: no tracer is set");
-    NEED_SINGLE(m->c);
-    return record_keff(m, nullptr, nbins, d_table, d_c, d_grad2, true);
-}
-
-// collective on a slab of several ranks, as fb_slab_set_vort_local
-extern "C" int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_set_tracer_local: NULL slab");
-    int rc;
-    if ((rc = kappa_check("fb_slab_set_tracer_local", kappa))) return rc;
-    SLAB_READY(s);
-    return tracer_in(s->m, s, d_rows, kappa);
-}
-
-extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows)
-{
-    if (!s || !d_rows) return fail(FB_EINVAL, "fb_slab_get_tracer_local: NULL");
-    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_local: no tracer is set");
-    SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_rows, nullptr, s->m->tr_c0);
-}
-
-// collective, as fb_slab_get_eddy_diffusivity
-extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: NULL slab");
-    int rc;
-    if ((rc = keff_check("fb_slab_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
-    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: no tracer is set");
-    SLAB_READY(s);
-    return record_keff(s->m, s, nbins, d_table, d_c_rows, d_grad2_rows, true);
-}
-
-// ---- the tangent-linear model (kernels: fb_tangent.h) ----
-static void tangent_free(fb_model *m)
-{
-    for (int g = 0; g < 3; ++g) {
-        cf **arr[] = {&m->tg_c0[g], &m->tg_c1[g], &m->tg_acc[g], &m->tg_j[g]};
-        for (cf **p : arr) if (*p) { hipFree(*p); *p = nullptr; }
-    }
-    if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
-    m->tangent = false;
-}
-
-// One RK stage of the perturbation, at the top of the step's stage `stage`, where tracer_stage runs and from the same states: the
-// vorticity's is ZA at stage 0 and ZB afterwards, the perturbation's its base and its stage state.  Two advect passes,
-//   pass 0: J(dz; psi)    k_tangent_deriv fills gradx dz, grady dz, grady psi, gradx psi
-//   pass 1: J(zeta; dpsi) k_tangent_deriv fills gradx zeta, grady zeta, grady dpsi, gradx dpsi
-// each per column group stage_vstate (k_tracer_vstate_* where the state arrays are not in the 3-pass layout), k_tangent_deriv, then
-// record_advect's backward x pass, row pass and forward x pass; the first pass's result is copied to tg_j before the second
-// overwrites the record workspace; then per group of active columns k_tangent_update with both.
-static int tangent_stage(fb_model *m, fb_slab *s, int stage)
-{
-    fb_ctx *c = m->c;
-    const SpecCoef coef = make_coef(c);
-    int rc;
-    for (int pass = 0; pass < 2; ++pass) {
-        auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
-            const bool staged = stage > 0 && g < c->nact;   // the frozen columns' state is the base at every stage
-            const cf *v0, *v1, *d0 = m->tg_c0[g], *d1 = staged ? m->tg_c1[g] : m->tg_c0[g];
-            int r;
-            if ((r = stage_vstate(m, g, staged, z + 2 * n, &v0, &v1))) return r;      // field 2: read by k_tangent_deriv before it writes there
-            hipLaunchKernelGGL(k_tangent_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, pass ? v0 : d0, pass ? v1 : d1, pass ? d0 : v0,
-                               pass ? d1 : v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-            HIPCHK(hipGetLastError());
-            return FB_OK;
-        };
-        if ((rc = record_advect(m, s, fill))) return rc;
-        for (int g = 0; g < c->nact && pass == 0; ++g) {
-            const size_t n = grp_elems(c, c->grp[g]);
-            if (n) HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-        }
-    }
-    for (int g = 0; g < c->nact; ++g) {
-        const ColGroup &G = c->grp[g];
-        const int ncr = 16 * G.nct_active;
-        if (grp_elems(c, G) == 0 || ncr == 0) continue;
-        const dim3 grid(grid_for(c, (size_t)c->nx * ncr / 2)), blk(256);
-        const cf *j1 = m->tg_j[g], *j2 = advect_out(m, s, g);
-        cf *c0 = m->tg_c0[g], *c1 = m->tg_c1[g], *ac = m->tg_acc[g];
-        switch (stage) {
-        case 0: hipLaunchKernelGGL((k_tangent_update<0>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 1: hipLaunchKernelGGL((k_tangent_update<1>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 2: hipLaunchKernelGGL((k_tangent_update<2>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        default: hipLaunchKernelGGL((k_tangent_update<3>), grid, blk, 0, c->stream, coef, j1, j2, c0, c1, ac, m->nu, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        }
-        HIPCHK(hipGetLastError());
-    }
-    return FB_OK;
-}
-
-// The perturbation in (beside_in, as the tracer) with the scratch of the first advect pass and the partial sums of the norm
-// ([ngroups][max_wg] float64); d_rows == NULL removes it.  The vorticity, a tracer, particles and `primed` stay as they are.  As
-// tracer_in: the captured step is dropped and the next fb_model_step starts with an eager step before the longer step is captured.
-static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows)
-{
-    fb_ctx *c = m->c;
-    int rc = FB_OK;
-    model_drop_graph(m);
-    m->warmed = false;
-    if (!d_rows) {
-        if (m->tangent) HIPCHK(hipStreamSynchronize(c->stream));
-        tangent_free(m);
-        return FB_OK;
-    }
-    for (int g = 0; g < c->nact && !rc; ++g)
-        if (grp_elems(c, c->grp[g])) rc = rec_alloc(&m->tg_j[g], grp_elems(c, c->grp[g]));
-    if (!rc && !m->tg_red && hipMalloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double)) != hipSuccess) {
-        m->tg_red = nullptr;
-        rc = fail(FB_ENOMEM, "record-path allocation failed");
-    }
-    if (rc || (rc = beside_in(m, s, d_rows, m->tg_c0, m->tg_c1, m->tg_acc))) { tangent_free(m); return rc; }
-    m->tangent = true;
-    return FB_OK;
-}
-
-// kind 0: the enstrophy norm <dz^2> / 2, kind 1: the energy norm <|grad dpsi|^2> / 2 (means over the grid), of the resident spectrum
-// (k_tangent_norm per column group, then k_tangent_norm_final over every partial sum) into *d_out on the device
-static int tangent_norm(fb_model *m, int kind, double *d_out)
-{
-    fb_ctx *c = m->c;
-    const SpecCoef coef = make_coef(c);
-    int np = 0;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        const size_t n = grp_elems(c, G);
-        if (n == 0) continue;
-        const int nwg = grid_for(c, n / 2);
-        hipLaunchKernelGGL(k_tangent_norm, dim3(nwg), dim3(256), 0, c->stream, coef, (const cf *)m->tg_c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np);
-        HIPCHK(hipGetLastError());
-        np += nwg;
-    }
-    const double grids = (double)c->nx * c->ny;
-    hipLaunchKernelGGL(k_tangent_norm_final, dim3(1), dim3(256), 0, c->stream, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int tangent_scale(fb_model *m, float a)
-{
-    fb_ctx *c = m->c;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t n = grp_elems(c, c->grp[g]);
-        if (n == 0) continue;
-        hipLaunchKernelGGL(k_tangent_scale, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, m->tg_c0[g], n, a);
-        HIPCHK(hipGetLastError());
-    }
-    return FB_OK;
-}
-
-// what the entry points refuse before any HIP call
-static int tangent_check(const char *fn, const fb_model *m, bool need_set)
-{
-    if (!m) return fail(FB_EINVAL, std::string(fn) + ": NULL model");
-    if (need_set && !m->tangent) return fail(FB_EINVAL, std::string(fn) + ": no tangent is set");
-    return FB_OK;
-}
-static int tangent_norm_check(const char *fn, int kind, const double *d_out)
-{
-    if (kind != 0 && kind != 1) return fail(FB_EINVAL, std::string(fn) + ": kind must be 0 (enstrophy) or 1 (energy)");
-    if (!d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL output");
-    return FB_OK;
-}
-static int tangent_scale_check(const char *fn, float a)
-{
-    if (!std::isfinite(a) || a == 0.0f) return fail(FB_EINVAL, std::string(fn) + ": the factor must be finite and not zero");
-    return FB_OK;
-}
-
-extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real)
-{
-    int rc;
-    if ((rc = tangent_check("fb_model_set_tangent", m, false))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_in(m, nullptr, d_dz_real);
-}
-
-extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real)
-{
-    int rc;
-    if (!d_dz_real) return fail(FB_EINVAL, "fb_model_get_tangent: NULL");
-    if ((rc = tangent_check("fb_model_get_tangent", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_dz_real, nullptr, m->tg_c0);
-}
-
-extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out)
-{
-    int rc;
-    if ((rc = tangent_norm_check("fb_model_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_model_tangent_norm", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_norm(m, kind, d_out);
-}
-
-extern "C" int fb_model_tangent_scale(fb_model *m, float a)
-{
-    int rc;
-    if ((rc = tangent_scale_check("fb_model_tangent_scale", a)) || (rc = tangent_check("fb_model_tangent_scale", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_scale(m, a);
-}
-
-// a slab of one rank goes through the same code; on several ranks the tangent-linear model is refused
-#define SLAB_TANGENT_ONE_RANK(s, fn) do { if (!(s)) return fail(FB_EINVAL, std::string(fn) + ": NULL slab"); if ((s)->c->world > 1) return fail(FB_EINVAL, std::string(fn) + ": the tangent-linear model is not supported on a slab of several ranks (world > 1)"); } while (0)
-
-extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real)
-{
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_set_tangent");
-    SLAB_READY(s);
-    return tangent_in(s->m, s, d_dz_real);
-}
-
-extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real)
-{
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_get_tangent");
-    int rc;
-    if (!d_dz_real) return fail(FB_EINVAL, "fb_slab_get_tangent: NULL");
-    if ((rc = tangent_check("fb_slab_get_tangent", s->m, true))) return rc;
-    SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_dz_real, nullptr, s->m->tg_c0);
-}
-
-extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out)
-{
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_norm");
-    int rc;
-    if ((rc = tangent_norm_check("fb_slab_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_slab_tangent_norm", s->m, true))) return rc;
-    return tangent_norm(s->m, kind, d_out);
-}
-
-extern "C" int fb_slab_tangent_scale(fb_slab *s, float a)
-{
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_scale");
-    int rc;
-    if ((rc = tangent_scale_check("fb_slab_tangent_scale", a)) || (rc = tangent_check("fb_slab_tangent_scale", s->m, true))) return rc;
-    return tangent_scale(s->m, a);
-}
-
-// ---- the Lagrangian particles (kernels: fb_particles.h) ----
-#define FB_PARTICLES_MAX (1 << 24)
-
-static void particles_free(fb_model *m)
-{
-    if (m->pt) { hipFree(m->pt); m->pt = nullptr; }
-    if (m->pt_uv) { hipFree(m->pt_uv); m->pt_uv = nullptr; }
-    m->pt_n = 0;
-}
-
-static PartGeo part_geo(const fb_ctx *c)
-{
-    PartGeo g;
-    g.dx = (double)c->lx / c->nx; g.dy = (double)c->ly / c->ny; g.nx = c->nx; g.ny = c->ny;
-    return g;
-}
-
-// One RK stage of the particles, at the top of the step's stage `stage`, where tracer_stage runs: before the step's own stage
-// overwrites ZB.  The vorticity's state of the stage (tracer_stage: ZA at stage 0, ZB afterwards, a masked mode from ZA) goes into
-// the 3-pass layout (k_tracer_vstate_* into field 1 of the record workspace where the state arrays are laid out otherwise; read in
-// place where they are not); k_particle_uv_spec leaves the spectra of u and v in the fields 0 and 1; the backward x pass of both and
-// one ROW_INV row pass each, with the scales of record(), into the particles' own real fields; k_particle_stage.  One GPU or a slab
-// of one rank: one column group, no exchange.
-static int particle_stage(fb_model *m, int stage)
-{
-    fb_ctx *c = m->c;
-    const ColGroup &G = c->grp[0];
-    const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
-    const SpecCoef coef = make_coef(c);
-    cf *z = m->rec_work[0];
-    const cf *v0, *v1;
-    int rc;
-    if ((rc = stage_vstate(m, 0, stage > 0, z + n, &v0, &v1))) return rc;
-    hipLaunchKernelGGL(k_particle_uv_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-    HIPCHK(hipGetLastError());
-    if ((rc = launch_col_block<+1>(c, G, z, 2, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 2, (long)n))) return rc;
-    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
-    RowArgs a = row_args_base(c);
-    a.M = view_single(c, z, (long)n); a.scale = -g; a.rout = m->pt_uv;                // u = -dpsi/dy (record(), REC_U)
-    if ((rc = launch_row<ROW_INV>(c, a))) return rc;
-    a.M = view_single(c, z + n, (long)n); a.scale = g; a.rout = m->pt_uv + nr;        // v = dpsi/dx
-    if ((rc = launch_row<ROW_INV>(c, a))) return rc;
-    const dim3 grid(grid_for(c, (size_t)m->pt_n)), blk(256);
-    const PartGeo pg = part_geo(c);
-    const float *u = m->pt_uv, *v = m->pt_uv + nr;
-    const double dt = (double)m->dt;
-    switch (stage) {
-    case 0: hipLaunchKernelGGL((k_particle_stage<0>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    case 1: hipLaunchKernelGGL((k_particle_stage<1>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    case 2: hipLaunchKernelGGL((k_particle_stage<2>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    default: hipLaunchKernelGGL((k_particle_stage<3>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    }
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int particles_check(const char *fn, const double *d_xy, int n)
-{
-    if (!d_xy) return n == 0 ? FB_OK : fail(FB_EINVAL, std::string(fn) + ": NULL positions with n > 0");
-    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
-    return FB_OK;
-}
-
-// The particles in (d_xy == NULL removes them).  The vorticity, a tracer and `primed` stay as they are.  As tracer_in: the captured
-// step is dropped and the next fb_model_step starts with an eager step before the longer step is captured.  The record workspace is
-// grown to its largest size first (advect_workspace), so that no later record replaces the buffer a captured step reads.
-static int particles_in(fb_model *m, fb_slab *s, const double *d_xy, int n)
-{
-    fb_ctx *c = m->c;
-    int rc;
-    model_drop_graph(m);
-    m->warmed = false;
-    if (m->pt_n) HIPCHK(hipStreamSynchronize(c->stream));
-    particles_free(m);
-    if (!d_xy) return FB_OK;
-    if ((rc = advect_workspace(m, s))) return rc;
-    if (hipMalloc((void **)&m->pt, 6 * (size_t)n * sizeof(double)) != hipSuccess) { m->pt = nullptr; return fail(FB_ENOMEM, "particle allocation failed"); }
-    if (hipMalloc((void **)&m->pt_uv, 2 * (size_t)c->nx * c->ny * sizeof(float)) != hipSuccess) {
-        m->pt_uv = nullptr;
-        particles_free(m);
-        return fail(FB_ENOMEM, "particle allocation failed");
-    }
-    HIPCHK(hipMemsetAsync(m->pt, 0, 6 * (size_t)n * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_particle_unpack, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, d_xy, m->pt, m->pt + n, n);
-    HIPCHK(hipGetLastError());
-    m->pt_n = n;
-    return FB_OK;
-}
-
-static int particles_out(fb_model *m, double *d_xy)
-{
-    fb_ctx *c = m->c;
-    hipLaunchKernelGGL(k_particle_pack, dim3(grid_for(c, (size_t)m->pt_n)), dim3(256), 0, c->stream, (const double *)m->pt, (const double *)(m->pt + m->pt_n), d_xy, m->pt_n);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int sample_check(const char *fn, const float *d_field, const double *d_xy, int n, const double *d_out)
-{
-    if (!d_field || !d_xy || !d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL");
-    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
-    return FB_OK;
-}
-
-static int sample(fb_ctx *c, const float *d_field, const double *d_xy, int n, double *d_out)
-{
-    hipLaunchKernelGGL(k_sample, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, part_geo(c), d_field, d_xy, n, d_out);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-extern "C" int fb_model_set_particles(fb_model *m, const double *d_xy, int n)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_set_particles: NULL model");
-    int rc;
-    if ((rc = particles_check("fb_model_set_particles", d_xy, n))) return rc;
-    NEED_SINGLE(m->c);
-    if (m->phase_flow) return fail(FB_EINVAL, "fb_model_set_particles on a slab model: use fb_slab_set_particles");
-    return particles_in(m, nullptr, d_xy, n);
-}
-
-extern "C" int fb_model_get_particles(fb_model *m, double *d_xy)
-{
-    if (!m || !d_xy) return fail(FB_EINVAL, "fb_model_get_particles: NULL");
-    if (!m->pt_n) return fail(FB_EINVAL, "fb_model_get_particles: no particles are set");
-    return particles_out(m, d_xy);
-}
-
-extern "C" int fb_model_particle_count(fb_model *m, int *n)
-{
-    if (!m || !n) return fail(FB_EINVAL, "fb_model_particle_count: NULL");
-    *n = m->pt_n;
-    return FB_OK;
-}
-
-extern "C" int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_sample: NULL model");
-    int rc;
-    if ((rc = sample_check("fb_model_sample", d_field, d_xy, n, d_out))) return rc;
-    NEED_SINGLE(m->c);
-    return sample(m->c, d_field, d_xy, n, d_out);
-}
-
-// a slab of one rank goes through the same code; particles distributed over row slabs would need neighbour halo rows that the
-// all-to-all transport does not provide
-#define SLAB_PARTICLES_ONE_RANK(s, fn) do { if ((s)->c->world > 1) return fail(FB_EUNSUPPORTED, std::string(fn) + ": particles are not supported on a slab of several ranks (world > 1)"); } while (0)
-
-extern "C" int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_set_particles: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_set_particles");
-    int rc;
-    if ((rc = particles_check("fb_slab_set_particles", d_xy, n))) return rc;
-    SLAB_READY(s);
-    return particles_in(s->m, s, d_xy, n);
-}
-
-extern "C" int fb_slab_get_particles(fb_slab *s, double *d_xy)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_particles: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_get_particles");
-    if (!d_xy) return fail(FB_EINVAL, "fb_slab_get_particles: NULL");
-    if (!s->m->pt_n) return fail(FB_EINVAL, "fb_slab_get_particles: no particles are set");
-    return particles_out(s->m, d_xy);
-}
-
-extern "C" int fb_slab_particle_count(fb_slab *s, int *n)
-{
-    if (!s || !n) return fail(FB_EINVAL, "fb_slab_particle_count: NULL");
-    *n = s->m->pt_n;
-    return FB_OK;
-}
-
-extern "C" int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_sample: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_sample");
-    int rc;
-    if ((rc = sample_check("fb_slab_sample", d_field, d_xy, n, d_out))) return rc;
-    return sample(s->c, d_field, d_xy, n, d_out);
 }

@@ -246,17 +246,26 @@ static int slab_xchg(fb_slab *s, const cf *send, cf *recv, size_t stride, size_t
     ++s->step_ops;
     return s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, 2 * stride, 2 * offset, 2 * count, s->comm);
 }
-// every group's whole t_send through the transport into t_recv (rows -> columns), behind the compute stream's work so far and
-// ahead of what it does next
-static int slab_transpose_all(fb_slab *s)
+// rows -> columns, the tendency's direction: the whole send[g] ([dst][XL][ncols_g]) of the first `ngroups` column groups through the
+// transport into recv[g] ([nx][ncols_g]), behind the compute stream's work so far and ahead of what it does next
+static int slab_rows_to_cols(fb_slab *s, const cf *const *send, cf *const *recv, int ngroups)
 {
-    fb_ctx *c = s->c; fb_model *m = s->m;
+    fb_ctx *c = s->c;
     int rc;
     if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
+    for (int g = 0; g < ngroups; ++g) {
         const size_t blk = (size_t)c->XL * c->grp[g].ncols;
-        if ((rc = slab_xchg(s, m->gb[g].t_send, m->gb[g].t_recv, blk, 0, blk))) return rc;
+        if ((rc = slab_xchg(s, send[g], recv[g], blk, 0, blk))) return rc;
     }
+    return slab_after(s->comp, s->comm, s->ev_misc[1]);
+}
+// all-gather of one small block (nfloats 32-bit words) through the transport's all-to-all: each rank sends the same block to every
+// peer, between the same two waits.  A record's reduction, no exchange of the step: step_ops does not count it.
+static int slab_gather(fb_slab *s, const void *send, void *recv, size_t nfloats)
+{
+    int rc;
+    if ((rc = slab_after(s->comm, s->comp, s->ev_misc[0]))) return rc;
+    if ((rc = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, nfloats, 0, nfloats, s->comm))) return rc;
     return slab_after(s->comp, s->comm, s->ev_misc[1]);
 }
 #define SLAB_READY(s) do { if (!(s)) return fail(FB_EINVAL, "slab NULL"); if (!(s)->connected) return fail(FB_EINVAL, "slab model is not connected to a transport (fb_slab_connect_*)"); } while (0)

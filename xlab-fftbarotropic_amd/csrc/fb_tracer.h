@@ -1,4 +1,5 @@
-// fb_tracer.h -- kernels of the passive tracer (fb_model_set_tracer, fb_slab_set_tracer_local; host side: fb_record.h, tracer_stage).
+// fb_tracer.h -- kernels of the passive tracer (fb_model_set_tracer, fb_slab_set_tracer_local; host side: fb_beside.h, tracer_stage), shared
+// by every field stepped beside the vorticity (the tangent-linear model, fb_tangent.h, launches the same ones).
 //
 // A tracer c is a second real field advected by the model's velocity, with a diffusivity kappa of its own:
 //   tend_c = dealiase( r2c(-u c_x - v c_y) + kappa laplacian(c_c) ),   u = -psi_y, v = psi_x of the vorticity's state of the same RK stage,
@@ -6,17 +7,17 @@
 // kept per column group in the record layer's 3-pass layout [nx][ncols] (row N2*c + d holds kx = c + N1*d, local column j holds
 // ky = ky0 + j), pad columns zero.  Per stage:
 //   k_tracer_vstate    the vorticity's state of the stage out of the step's own layout into a field of the record workspace
-//   k_tracer_deriv     gradx c, grady c, grady psi, gradx psi: what k_col_mid hands to the row pass, with c in the place of zeta
+//   k_advect_deriv     gradx c, grady c, grady psi, gradx psi: what k_col_mid hands to the row pass, with c in the place of zeta
 //   (the backward x pass, the ROW_FUSED row pass without a source and the forward x pass: fb_record.h, record_advect)
-//   k_tracer_update    viscous term, mask, RK stage update of the tracer
+//   k_beside_update    viscous term, mask, RK stage update of the tracer
 // The step stores its stage state and accumulator only where a mode can change (SURVEY note N1): for a mode outside the dealiasing
-// circle the stage state IS the base, and both k_tracer_vstate and k_tracer_deriv read it from there.
+// circle the stage state IS the base, and both k_tracer_vstate and k_advect_deriv read it from there.
 // No reference counterpart: the reference advects no tracer.
 #pragma once
 
 // ---- the vorticity's stage state -> 3-pass layout ----
 // za: vort_c0, zb: the stage state (stage 0 and groups of frozen columns: zb == za).  The pad columns next to ny/2 are written as
-// zeros (k_tracer_deriv loads column pairs); it uses nothing at or beyond ny/2 + 1.
+// zeros (k_advect_deriv loads column pairs); it uses nothing at or beyond ny/2 + 1.
 // tile-major state arrays (k_state_relayout; three-kernel path with N2 >= 32)
 __global__ void __launch_bounds__(256) k_tracer_vstate_tm(SpecCoef c, const cf *__restrict__ za, const cf *__restrict__ zb, cf *__restrict__ out, int P,
                                                           int N1, int N2, int ky0)
@@ -59,13 +60,15 @@ FB_DEV cf tr_grad(cf a, float k)
     return cf_make(-a.y * k, a.x * k);                                              // fftwfop.cpp:87-103
 }
 
-// The four fields a stage hands to its row pass, with the tracer in the place of the vorticity, into the fields 0..3 of `z`, fstride
-// apart: gradx(c_c), grady(c_c), grady(psi_c), gradx(psi_c) with psi_c = invertLaplacian(vort_c); two modes (16 bytes) per lane and
-// access; pad columns zero.  v0 / v1: the vorticity's base / stage state, c0 / c1: the tracer's, all in the 3-pass layout; a mode
-// outside the dealiasing circle is read from the base.  v0, v1 may be field 2 of z: each element is read before it is written, by
-// the same thread.  Same float32 forms as k_spec_op (no contraction).
-__global__ void __launch_bounds__(256) k_tracer_deriv(SpecCoef c, const cf *v0, const cf *v1, const cf *__restrict__ c0, const cf *__restrict__ c1, cf *z,
-                                                      long fstride, int P, int N1, int N2, int ky0)
+// The four fields a stage hands to its row pass for the advective tendency J(a; phi) = -u a_x - v a_y, u = -phi_y, v = phi_x, into the
+// fields 0..3 of `z`, fstride apart: gradx(a_c), grady(a_c), grady(phi_c), gradx(phi_c) with phi_c = invertLaplacian(b_c) (the (0, 0)
+// mode divided by 1): what k_col_mid hands to the row pass, with a in the place of zeta.  a0 / a1: the base / stage state of the
+// advected field, b0 / b1: of the field whose streamfunction advects; all in the 3-pass layout, a mode outside the dealiasing circle
+// is read from the base.  Either pair may be field 2 of z (the vorticity's stage state out of k_tracer_vstate_*): each element is read
+// before it is written, by the same thread, so no pointer here is __restrict__.  Two modes (16 bytes) per lane and access; pad columns
+// zero.  Same float32 forms as k_spec_op (no contraction).
+__global__ void __launch_bounds__(256) k_advect_deriv(SpecCoef c, const cf *a0, const cf *a1, const cf *b0, const cf *b1, cf *z, long fstride, int P, int N1,
+                                                      int N2, int ky0)
 {
 #pragma clang fp contract(off)
     const size_t total = (size_t)c.nx * P / 2;
@@ -75,16 +78,16 @@ __global__ void __launch_bounds__(256) k_tracer_deriv(SpecCoef c, const cf *v0, 
         const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d;
         const size_t idx = 2 * p;
         cf o[4][2];
-        float4 cv = make_float4(0.f, 0.f, 0.f, 0.f), vv = cv;
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
         if (ky0 + col < c.hy) {
             // (uniform but at the circle's edge) both modes of the pair from one array where both are live or both are masked
             const bool l0 = coef_mask(c, i, ky0 + col) != 0.0f, l1 = coef_mask(c, i, ky0 + col + 1) != 0.0f;
             if (l0 == l1) {
-                cv = *reinterpret_cast<const float4 *>((l0 ? c1 : c0) + idx);
-                vv = *reinterpret_cast<const float4 *>((l0 ? v1 : v0) + idx);
+                av = *reinterpret_cast<const float4 *>((l0 ? a1 : a0) + idx);
+                bv = *reinterpret_cast<const float4 *>((l0 ? b1 : b0) + idx);
             } else {
-                const cf ca = (l0 ? c1 : c0)[idx], cb = (l1 ? c1 : c0)[idx + 1], va = (l0 ? v1 : v0)[idx], vb = (l1 ? v1 : v0)[idx + 1];
-                cv = make_float4(ca.x, ca.y, cb.x, cb.y); vv = make_float4(va.x, va.y, vb.x, vb.y);
+                const cf ax = (l0 ? a1 : a0)[idx], ay = (l1 ? a1 : a0)[idx + 1], bx = (l0 ? b1 : b0)[idx], by = (l1 ? b1 : b0)[idx + 1];
+                av = make_float4(ax.x, ax.y, ay.x, ay.y); bv = make_float4(bx.x, bx.y, by.x, by.y);
             }
         }
 #pragma unroll
@@ -92,14 +95,14 @@ __global__ void __launch_bounds__(256) k_tracer_deriv(SpecCoef c, const cf *v0, 
             const int j = ky0 + col + e;
             o[0][e] = o[1][e] = o[2][e] = o[3][e] = cf_make(0.f, 0.f);
             if (j < c.hy) {
-                const cf a = e ? cf_make(cv.z, cv.w) : cf_make(cv.x, cv.y), v = e ? cf_make(vv.z, vv.w) : cf_make(vv.x, vv.y);
+                const cf a = e ? cf_make(av.z, av.w) : cf_make(av.x, av.y), b = e ? cf_make(bv.z, bv.w) : cf_make(bv.x, bv.y);
                 const float kx = c.gx[i], ky = c.gy[j];
-                o[0][e] = tr_grad(a, kx);                                           // main.cpp:151 with c_c
-                o[1][e] = tr_grad(a, ky);                                           // main.cpp:165 with c_c
+                o[0][e] = tr_grad(a, kx);                                           // main.cpp:151 with a_c
+                o[1][e] = tr_grad(a, ky);                                           // main.cpp:165 with a_c
                 const float li = (i == 0 && j == 0) ? 1.0f : coef_lap(c, i, j);     // fftwfop.cpp:42-43,112-117 (main.cpp:179)
-                const cf ps = cf_make(v.x / li, v.y / li);
-                o[2][e] = tr_grad(ps, ky);                                          // main.cpp:198
-                o[3][e] = tr_grad(ps, kx);                                          // main.cpp:212
+                const cf ph = cf_make(b.x / li, b.y / li);
+                o[2][e] = tr_grad(ph, ky);                                          // main.cpp:198
+                o[3][e] = tr_grad(ph, kx);                                          // main.cpp:212
             }
         }
 #pragma unroll
@@ -108,16 +111,18 @@ __global__ void __launch_bounds__(256) k_tracer_deriv(SpecCoef c, const cf *v0, 
     }
 }
 
-// RK stage update of the tracer on the first `ncr` columns of a column group (the tiles that hold a mode inside the dealiasing
-// circle; the columns beyond never change): jh = r2c(-u c_x - v c_y) as the forward x pass left it, c0 the base, c1 the stage state,
-// acc the running rk1 + 2 rk2 + 2 rk3, all in the 3-pass layout with pitch P.
+// RK stage update of a field stepped beside the vorticity on the first `ncr` columns of a column group (the tiles that hold a mode
+// inside the dealiasing circle; the columns beyond never change), from NJ tendencies as the forward x pass left them: j1 alone (the
+// tracer: r2c(-u c_x - v c_y)) or j1 + j2 (the tangent-linear model: r2c(J(dz; psi)) and r2c(J(zeta; dpsi)), summed before the viscous
+// term and the mask; NJ == 1 never reads j2).  c0 the base, c1 the stage state, acc the running rk1 + 2 rk2 + 2 rk3, all in the 3-pass
+// layout with pitch P; kappa the field's diffusivity (the tangent's is the model's nu).
 //   k = (jh + (c_stage * laplacian_coe) * kappa) * mask     main.cpp:240-243 with kappa, main.cpp:148
 // and the stage forms of k_col_mid, in its rounding: the explicit fma at stage 0, the accumulator as ac + 2 k, the final combination
 // as z0 + (ac + k) * dt / 6 (main.cpp:246-251,296-312).  A masked mode keeps its bits: its stage state is the base, its accumulator
 // zero.  Stages 0..2 write acc and c1, stage 3 the new base into c0.  Two modes per lane and access (16 bytes), no LDS.
-template <int STAGE>
-__global__ void __launch_bounds__(256) k_tracer_update(SpecCoef c, const cf *__restrict__ jh, cf *c0, cf *c1, cf *acc, float kappa, float dt, int P, int ncr,
-                                                       int N1, int N2, int ky0)
+template <int STAGE, int NJ>
+__global__ void __launch_bounds__(256) k_beside_update(SpecCoef c, const cf *__restrict__ j1, const cf *__restrict__ j2, cf *c0, cf *c1, cf *acc, float kappa,
+                                                       float dt, int P, int ncr, int N1, int N2, int ky0)
 {
     const int hp = ncr >> 1;
     const size_t total = (size_t)c.nx * hp;
@@ -126,7 +131,9 @@ __global__ void __launch_bounds__(256) k_tracer_update(SpecCoef c, const cf *__r
         const int row = (int)(p / hp), col = 2 * (int)(p - (size_t)row * hp);
         const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d;
         const size_t q = ((size_t)row * P + col) >> 1;                                  // float4 index
-        const float4 t = reinterpret_cast<const float4 *>(jh)[q], z0 = reinterpret_cast<const float4 *>(c0)[q];
+        float4 t = reinterpret_cast<const float4 *>(j1)[q];
+        if (NJ == 2) { const float4 t2 = reinterpret_cast<const float4 *>(j2)[q]; t = make_float4(t.x + t2.x, t.y + t2.y, t.z + t2.z, t.w + t2.w); }
+        const float4 z0 = reinterpret_cast<const float4 *>(c0)[q];
         float4 zc = z0, ac = make_float4(0.f, 0.f, 0.f, 0.f);
         if (STAGE != 0) { zc = reinterpret_cast<const float4 *>(c1)[q]; ac = reinterpret_cast<const float4 *>(acc)[q]; }
         const float th[4] = {t.x, t.y, t.z, t.w}, b[4] = {z0.x, z0.y, z0.z, z0.w}, s[4] = {zc.x, zc.y, zc.z, zc.w}, a[4] = {ac.x, ac.y, ac.z, ac.w};

@@ -995,6 +995,11 @@ extern "C" int fb_c2r(fb_ctx *c, const float *d_in, float *d_out, int normalize)
 //   t_recv  [nx][ncols]          block s = rows of rank s, read by the column kernels
 struct GroupBufs { cf *ZA, *ZB, *ACC, *w4_send, *w4_recv, *t_send, *t_recv; };
 
+// a spectral field stepped beside the vorticity (fb_beside.h: the tracer, the tangent-linear model's perturbation): per column group in
+// the 3-pass layout [nx][ncols] the base, and for the groups of active columns the stage state and the RK accumulator; NULL while the
+// field is not set.  Never in the record workspace: a record taken between two steps overwrites that.
+struct Beside { cf *c0[3], *c1[3], *acc[3]; };
+
 struct fb_model {
     fb_ctx *c;
     float nu, dt;
@@ -1003,7 +1008,8 @@ struct fb_model {
     XPass xpass;                     // XP_FULL1/2 (fb_col_full.h): ZA/ZB/ACC then use k_col_full's private layout
     bool prescale;                   // k_col_full writes the derivative fields times 1/GRIDS and k_rowq<false, true> does not normalise (4096^2 on one GPU)
     // hipGraph replay of one RK4 step (launch-bound small grids): captured lazily on a non-null stream,
-    // dropped whenever something baked into the kernel arguments changes (source pointer, stream)
+    // dropped whenever something baked into the kernel arguments changes (source pointer, stream) and by whatever changes the
+    // step's launches: a tracer, particles or a tangent that comes or goes (beside_begin, fb_beside.h)
     bool use_graph, warmed;
     hipGraphExec_t graph_exec;
     const float *graph_src; hipStream_t graph_stream;
@@ -1030,19 +1036,18 @@ struct fb_model {
     // 0: derivative fields stale; 1: w4_send holds the derivatives with the backward x pass finished on the frozen
     // tiles only (the backward strided pass on the active tiles comes next); 2: finished on every tile (ready for the row pass)
     int primed;
-    // the passive tracer (fb_tracer.h; host side in fb_record.h): per column group in the 3-pass layout [nx][ncols] the base c_c, and
-    // for the groups of active columns the stage state and the RK accumulator; NULL without a tracer.  Never in the record workspace:
-    // a record taken between two steps overwrites that.
-    cf *tr_c0[3], *tr_c1[3], *tr_acc[3];
+    // the passive tracer (fb_tracer.h; host side in fb_beside.h) and its diffusivity
+    Beside tr;
     float kappa;
-    bool tracer, graph_tracer;       // a tracer is set; the captured step holds the tracer's stages
-    // the Lagrangian particles (fb_particles.h; host side in fb_record.h): six float64 arrays of pt_n (base, stage position, RK
+    bool tracer;                     // a tracer is set
+    // the Lagrangian particles (fb_particles.h; host side in fb_beside.h): six float64 arrays of pt_n (base, stage position, RK
     // accumulator, x then y of each) and the stage velocity u, v as two real fields [2][nx][ny]; NULL and 0 without particles
     double *pt; int pt_n;
     float *pt_uv;
-    // the tangent-linear model (fb_tangent.h; host side in fb_record.h): the perturbation's base, stage state and RK accumulator as
-    // the tracer's, the first advect pass's tendency of a stage (groups of active columns) and the norm's partial sums; NULL without
-    cf *tg_c0[3], *tg_c1[3], *tg_acc[3], *tg_j[3];
+    // the tangent-linear model (fb_tangent.h; host side in fb_beside.h): the perturbation, the first advect pass's tendency of a stage
+    // (groups of active columns) and the norm's partial sums; NULL without
+    Beside tg;
+    cf *tg_j[3];
     double *tg_red;
     bool tangent;
 };
@@ -1084,11 +1089,11 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
 
 static void model_drop_graph(fb_model *m);
 static void tracer_free(fb_model *m);
-static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_record.h
+static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_beside.h
 static void particles_free(fb_model *m);
-static int particle_stage(fb_model *m, int stage);                      // fb_record.h
+static int particle_stage(fb_model *m, int stage);                      // fb_beside.h
 static void tangent_free(fb_model *m);
-static int tangent_stage(fb_model *m, struct fb_slab *s, int stage);    // fb_record.h
+static int tangent_stage(fb_model *m, struct fb_slab *s, int stage);    // fb_beside.h
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1212,6 +1217,12 @@ static int full_export_state(fb_model *m, cf *dst)
     return FB_OK;
 }
 
+// vort_c of column group g -> 3-pass layout in `dst`, whichever layout the state arrays have
+static int export_state(fb_model *m, int g, cf *dst)
+{
+    return m->xpass != XP_COLS ? full_export_state(m, dst) : state_convert(m->c, m->c->grp[g], m->gb[g].ZA, dst, false);
+}
+
 // ---- the local passes of one RK stage, shared by the fused single-GPU flow and the multi-GPU driver ----------------
 // priming: derivatives of vort_c for every column of every group; the frozen tiles get their backward strided
 // sub-pass here, once -- the per-stage passes only touch the active tiles of group 0
@@ -1333,7 +1344,7 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
     if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
     int rc;
     if (!m->warmed) { if ((rc = model_step_impl(m, 1, nullptr))) return rc; m->warmed = true; --nsteps; }
-    if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream || m->graph_tracer != m->tracer)) model_drop_graph(m);
+    if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream)) model_drop_graph(m);
     if (!m->graph_exec) {
         hipGraph_t g = nullptr;
         HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
@@ -1344,7 +1355,7 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
         e = hipGraphInstantiate(&m->graph_exec, g, nullptr, nullptr, 0);
         hipGraphDestroy(g);
         HIPCHK(e);
-        m->graph_src = m->src; m->graph_stream = c->stream; m->graph_tracer = m->tracer;
+        m->graph_src = m->src; m->graph_stream = c->stream;
         // the captured step has NOT executed: replay it below like the others
     }
     for (int s = 0; s < nsteps; ++s) HIPCHK(hipGraphLaunch(m->graph_exec, c->stream));
@@ -1390,8 +1401,7 @@ extern "C" int fb_model_get_spectrum(fb_model *m, float *d_spec)
     NEED_SINGLE(m->c);
     int rc;
     if ((rc = ensure_scratch(m->c))) return rc;
-    if (m->xpass != XP_COLS) { if ((rc = full_export_state(m, m->c->d_scratch))) return rc; }
-    else if ((rc = state_convert(m->c, m->c->grp[0], m->gb[0].ZA, m->c->d_scratch, false))) return rc;
+    if ((rc = export_state(m, 0, m->c->d_scratch))) return rc;
     return relayout(m->c, m->c->d_scratch, (cf *)d_spec, false);
 }
 
@@ -1409,5 +1419,6 @@ extern "C" int fb_model_set_spectrum(fb_model *m, const float *d_spec)
 
 #include "fb_slab_driver.h"
 #include "fb_record.h"
+#include "fb_beside.h"
 
 // field I/O (fb_write_field / fb_read_field, writeField / readField): fb_fieldio.cpp
