@@ -243,6 +243,30 @@ int fb_model_set_tangent(fb_model *m, const float *d_dz_real);             /* NU
 int fb_model_get_tangent(fb_model *m, float *d_dz_real);
 int fb_model_tangent_norm(fb_model *m, int kind, double *d_out);           /* 0 enstrophy, 1 energy */
 int fb_model_tangent_scale(fb_model *m, float a);                          /* finite, != 0 */
+/* Adjoint model (no reference counterpart): the transpose T^T of the tangent-linear step above under the inner product
+ * <a, b> = sum over the grid of a b, so that <T dz, lam> = <dz, T^T lam> for the DISCRETE step: sensitivities of a scalar of the
+ * final state to the initial vorticity, singular vectors of T, gradients for fitting an initial state to later data.  It runs
+ * backward over steps taken earlier, so the forward steps record a tape.  fb_model_adjoint_record(m, depth): depth >= 1 allocates
+ * room for depth steps x 4 stage states of the vorticity (4 half spectra per step: 271 MB per step at 4096^2) and from then on every
+ * stage of fb_model_step stores the state it starts from; depth == 0 frees the tape; either way the tape starts empty.  While it is
+ * on, fb_model_step steps eagerly (a captured step would bake in a slot; the captured step is dropped and captured again after
+ * depth == 0), and a call that would overrun the tape is refused with FB_EINVAL before anything is launched.  fb_model_set_vort and
+ * fb_model_set_spectrum empty the tape.  fb_model_adjoint_recorded: the number of steps on the tape.  fb_model_set_adjoint takes the
+ * device field d_lambda_real in as fb_model_set_vort takes the vorticity and keeps it as a half spectrum; NULL removes it and frees its
+ * state.  fb_model_adjoint_back(m, nsteps) pops the last nsteps recorded steps, newest first, and applies each step's transpose to
+ * lam: per stage, about the recorded stage state zeta with u, v its velocity and mu~ = dealiase(mu),
+ *   L^T mu = gradx(u mu~) + grady(v mu~) + invertLaplacian( gradx(zeta_y mu~) - grady(zeta_x mu~) ) + nu laplacian(mu~)
+ * (products in physical space, the result not dealiased again), combined by the transposed RK4 recurrences (csrc/fb_adjoint.h).  A
+ * cost term at an intermediate time is get, add, set between two sweeps.  fb_model_get_adjoint: lam as fb_model_get_vort returns the
+ * vorticity.  The vorticity, its step, a tracer, particles and a tangent are bit for bit what they are without the tape; two equal
+ * runs give the same bits of lam.  FB_EINVAL before any HIP call: a NULL model, output or count, depth < 0, nsteps < 0 or beyond
+ * what is recorded, get / back without an adjoint set.  FB_ENOMEM: the tape does not fit; nothing stays allocated.  Enqueued on the
+ * context stream, no synchronisation. */
+int fb_model_adjoint_record(fb_model *m, int depth);                       /* 0: stop recording, free the tape */
+int fb_model_adjoint_recorded(fb_model *m, int *n);
+int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real);         /* NULL: remove the adjoint variable */
+int fb_model_get_adjoint(fb_model *m, float *d_real);
+int fb_model_adjoint_back(fb_model *m, int nsteps);
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -385,6 +409,13 @@ int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real);               /* NU
 int fb_slab_get_tangent(fb_slab *s, float *d_dz_real);
 int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out);
 int fb_slab_tangent_scale(fb_slab *s, float a);
+/* the adjoint model (fb_model_adjoint_record) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
+ * world > 1 they return FB_EINVAL with a message. */
+int fb_slab_adjoint_record(fb_slab *s, int depth);
+int fb_slab_adjoint_recorded(fb_slab *s, int *n);
+int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real);           /* NULL: remove the adjoint variable */
+int fb_slab_get_adjoint(fb_slab *s, float *d_real);
+int fb_slab_adjoint_back(fb_slab *s, int nsteps);
 /* the Lagrangian particles (fb_model_set_particles) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EUNSUPPORTED: particles distributed over row slabs need neighbour halo rows that the all-to-all transport
  * does not provide. */

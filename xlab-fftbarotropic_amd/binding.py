@@ -152,6 +152,16 @@ def lib():
     for n in ("fb_model_tangent_scale", "fb_slab_tangent_scale"):
         if hasattr(L, n):
             getattr(L, n).argtypes = [vp, C.c_float]
+    # (likewise the adjoint model)
+    for n in ("fb_model_adjoint_record", "fb_model_adjoint_back", "fb_slab_adjoint_record", "fb_slab_adjoint_back"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, ip]
+    for n in ("fb_model_adjoint_recorded", "fb_slab_adjoint_recorded"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, C.POINTER(ip)]
+    for n in ("fb_model_set_adjoint", "fb_model_get_adjoint", "fb_slab_set_adjoint", "fb_slab_get_adjoint"):
+        if hasattr(L, n):
+            getattr(L, n).argtypes = [vp, fp]
     L.fb_slab_step.argtypes = [vp, ip]
     L.fb_slab_synchronize.argtypes = [vp]
     L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
@@ -184,6 +194,8 @@ EXPORTS = [
     "fb_slab_set_particles", "fb_slab_get_particles", "fb_slab_particle_count", "fb_slab_sample",
     "fb_model_set_tangent", "fb_model_get_tangent", "fb_model_tangent_norm", "fb_model_tangent_scale",
     "fb_slab_set_tangent", "fb_slab_get_tangent", "fb_slab_tangent_norm", "fb_slab_tangent_scale",
+    "fb_model_adjoint_record", "fb_model_adjoint_recorded", "fb_model_set_adjoint", "fb_model_get_adjoint", "fb_model_adjoint_back",
+    "fb_slab_adjoint_record", "fb_slab_adjoint_recorded", "fb_slab_set_adjoint", "fb_slab_get_adjoint", "fb_slab_adjoint_back",
     "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
 ]
 
@@ -285,6 +297,42 @@ def lyapunov(model, steps, renorm_every, kind="enstrophy"):
         model.rescale_tangent(float(np.sqrt(n0 / after)))
         before = model.tangent_norm(kind)
     return total / (steps * model.dt), factors
+
+
+def singular_values(model, steps, iters, start, save=None, restore=None):
+    """Power iteration on T^T T in the L2 (enstrophy) norm on `model` (anything with set_tangent, tangent, record_adjoint, step,
+    set_adjoint, adjoint_back, adjoint; save / restore: how its state is kept and put back, by default spectrum / set_spectrum,
+    which restores every bit), T the tangent of `steps` steps from the model's current state.  Each
+    iteration restores that state, sets the tangent to the unit vector v (from `start`, an [nx, ny] field), steps with recording on,
+    sets lam = T v, sweeps back and normalises v = T^T T v.  Returns (sigma = |T v| per iteration, the final v as a tensor); the model
+    is left at its starting state with the tape freed, the tangent set to the last v and lam to T^T T of it."""
+    if steps < 1 or iters < 1:
+        raise ValueError("singular_values: steps and iters must be >= 1")
+    t = model.torch
+    save, restore = save or model.spectrum, restore or model.set_spectrum
+    z0 = save()
+    if isinstance(start, np.ndarray):
+        start = t.from_numpy(np.ascontiguousarray(start, dtype=np.float64))
+    v = start.cuda().double()
+    v = v / v.norm()
+    sig = []
+    model.record_adjoint(steps)
+    try:
+        for _ in range(iters):
+            restore(z0)
+            model.set_tangent(v.float().contiguous())
+            model.step(steps)
+            w = model.tangent()
+            t.cuda.current_stream().synchronize()
+            sig.append(float(w.double().norm()))
+            model.set_adjoint(w)
+            model.adjoint_back(steps)
+            v = model.adjoint().double()
+            v = v / v.norm()
+        restore(z0)
+    finally:
+        model.record_adjoint(0)
+    return sig, v.float()
 
 
 def particles_dev(torch, xy):
@@ -611,6 +659,35 @@ class Model:
     def lyapunov(self, steps, renorm_every, kind="enstrophy"):
         """(exponent [s^-1], growth factors): steps the model, renormalising the perturbation every renorm_every steps (lyapunov())."""
         return lyapunov(self, steps, renorm_every, kind)
+
+    def record_adjoint(self, depth):
+        """Turns the adjoint's tape on (depth >= 1: room for depth steps; every step from now on records its four stage states, and a
+        step call beyond depth is refused) or off (depth = 0, the tape freed).  Either way the tape starts empty."""
+        check(lib().fb_model_adjoint_record(self._h, int(depth)))
+
+    def adjoint_recorded(self):
+        n = C.c_int()
+        check(lib().fb_model_adjoint_recorded(self._h, C.byref(n)))
+        return n.value
+
+    def set_adjoint(self, lam):
+        """Sets the adjoint variable, an [nx, ny] field (the gradient of a scalar of the state with respect to the vorticity, at the
+        time of the newest recorded step); lam=None removes it."""
+        if lam is None:
+            check(lib().fb_model_set_adjoint(self._h, None))
+        else:
+            a = self._dev(lam); check(lib().fb_model_set_adjoint(self._h, _ptr(a))); self.fop.synchronize()
+
+    def adjoint(self):
+        out = self.fop.empty_real(); check(lib().fb_model_get_adjoint(self._h, _ptr(out))); return out
+
+    def adjoint_back(self, n=1):
+        """lam <- T^T lam over the last n recorded steps, newest first (the transpose of the tangent-linear step); they leave the tape."""
+        check(lib().fb_model_adjoint_back(self._h, int(n)))
+
+    def singular_values(self, steps, iters, start):
+        """(sigmas, v): power iteration on T^T T over `steps` steps from the current state in the L2 norm (singular_values())."""
+        return singular_values(self, steps, iters, start)
 
     def spectrum(self):
         out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out

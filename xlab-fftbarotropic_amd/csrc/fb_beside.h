@@ -572,3 +572,245 @@ extern "C" int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_
     if ((rc = sample_check("fb_slab_sample", d_field, d_xy, n, d_out))) return rc;
     return sample(s->c, d_field, d_xy, n, d_out);
 }
+
+// ---- the adjoint model (kernels: fb_adjoint.h) ----
+// One GPU or a slab of one rank: one column group, no exchange (as the particles).
+static void adjoint_tape_free(fb_model *m)
+{
+    if (m->ad_tape) { hipFree(m->ad_tape); m->ad_tape = nullptr; }
+    m->ad_depth = m->ad_fill = 0;
+}
+
+static void adjoint_free(fb_model *m)
+{
+    beside_free(m->ad);
+    if (m->ad_real) { hipFree(m->ad_real); m->ad_real = nullptr; }
+    m->adjoint = false;
+}
+
+// a step call that would overrun the tape is refused before anything is launched
+static int adjoint_room(const fb_model *m, int nsteps, const char *fn)
+{
+    if (m->ad_depth && nsteps > m->ad_depth - m->ad_fill)
+        return fail(FB_EINVAL, std::string(fn) + ": the adjoint's tape has room for " + std::to_string(m->ad_depth - m->ad_fill) + " more steps (fb_model_adjoint_record)");
+    return FB_OK;
+}
+
+// The tape on (depth >= 1: room for depth steps x 4 stage states) or off (depth == 0); either way it starts empty.  While it is on
+// fb_model_step steps eagerly, so the captured step is dropped here (beside_begin) and never holds a slot of the tape.
+static int adjoint_record(fb_model *m, int depth)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if ((rc = beside_begin(m, m->ad_tape != nullptr))) return rc;
+    adjoint_tape_free(m);
+    if (depth == 0) return FB_OK;
+    const size_t n = grp_elems(c, c->grp[0]);
+    if (hipMalloc((void **)&m->ad_tape, (size_t)depth * 4 * n * sizeof(cf)) != hipSuccess) {
+        m->ad_tape = nullptr;
+        (void)hipGetLastError();
+        return fail(FB_ENOMEM, "the adjoint's tape: allocation failed");
+    }
+    m->ad_depth = depth;
+    return FB_OK;
+}
+
+// The state the step's stage `stage` starts from into the tape's next slot, where tangent_stage runs: stage_vstate merges base and
+// stage state into the slot itself where the step keeps its state in a layout of its own; where it hands ZA / ZB back in place,
+// k_adjoint_merge does.
+static int adjoint_stash(fb_model *m, int stage)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    const size_t n = grp_elems(c, G);
+    cf *slot = m->ad_tape + ((size_t)m->ad_fill * 4 + stage) * n;
+    const cf *v0, *v1;
+    int rc;
+    if ((rc = stage_vstate(m, 0, stage > 0 && c->nact > 0, slot, &v0, &v1))) return rc;
+    if (v0 == slot) return FB_OK;
+    hipLaunchKernelGGL(k_adjoint_merge, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, make_coef(c), v0, v1, slot, G.ncols, c->N1, c->N2, G.ky0);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+// The adjoint variable in (beside_in: lam, with the k-bar and the accumulator of a backward step) and the real fields of the product
+// pass; d_rows == NULL removes it.  The step's launches do not depend on it: the captured step stays.
+static int adjoint_in(fb_model *m, fb_slab *s, const float *d_rows)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if (!d_rows) {
+        if (m->adjoint) HIPCHK(hipStreamSynchronize(c->stream));
+        adjoint_free(m);
+        return FB_OK;
+    }
+    rc = rec_alloc((void **)&m->ad_real, 5 * (size_t)c->nx * c->ny * sizeof(float));
+    if (rc || (rc = beside_in(m, s, d_rows, m->ad))) { adjoint_free(m); return rc; }
+    m->adjoint = true;
+    return FB_OK;
+}
+
+// One RK stage of a backward step: L_stage^T of the k-bar about the recorded stage state zs, then the recurrences (fb_adjoint.h).
+// Five fields back to physical space as particle_stage takes u and v, with its scales; four products forward as beside_in takes a
+// field; through the record workspace, which the step never reads.
+static int adjoint_stage(fb_model *m, int stage, const cf *zs)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
+    const SpecCoef coef = make_coef(c);
+    cf *z = m->rec_work[0];
+    cf *lam = m->ad.c0[0], *kb = m->ad.c1[0], *acc = m->ad.acc[0];
+    const dim3 grid(grid_for(c, n / 2)), blk(256);
+    int rc;
+    hipLaunchKernelGGL(k_adjoint_deriv, grid, blk, 0, c->stream, coef, zs, (const cf *)(stage == 3 ? lam : kb), stage == 3 ? m->dt / 6.0f : 1.0f, z, (long)n, G.ncols,
+                       c->N1, c->N2, G.ky0);
+    HIPCHK(hipGetLastError());
+    if ((rc = launch_col_block<+1>(c, G, z, 5, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 5, (long)n))) return rc;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    for (int f = 0; f < 5; ++f) {
+        RowArgs a = row_args_base(c);
+        a.M = view_single(c, z + f * n, (long)n); a.scale = f == 1 ? -g : g; a.rout = m->ad_real + f * nr;      // u = -dpsi/dy (record(), REC_U)
+        if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+    }
+    hipLaunchKernelGGL(k_adjoint_prod, dim3(grid_for(c, nr / 4)), blk, 0, c->stream, m->ad_real, nr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(z, 0, 4 * n * sizeof(cf), c->stream));                                                 // pad columns zero
+    for (int f = 0; f < 4; ++f) {
+        RowArgs a = row_args_base(c);
+        a.rin = m->ad_real + (f + 1) * nr; a.T = view_single(c, z + f * n, 0);
+        if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+    }
+    if ((rc = launch_col_strided<-1>(c, G, z, 4, (long)n)) || (rc = launch_col_block<-1>(c, G, z, 4, (long)n))) return rc;
+    switch (stage) {
+    case 3: hipLaunchKernelGGL((k_adjoint_update<3>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
+    case 2: hipLaunchKernelGGL((k_adjoint_update<2>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
+    case 1: hipLaunchKernelGGL((k_adjoint_update<1>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
+    default: hipLaunchKernelGGL((k_adjoint_update<0>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
+    }
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+
+// The last nsteps recorded steps popped, newest first, each step's transpose applied to lam (its stages in the order 3, 2, 1, 0).
+static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
+{
+    fb_ctx *c = m->c;
+    const size_t n = grp_elems(c, c->grp[0]);
+    int rc;
+    if ((rc = advect_workspace(m, s))) return rc;
+    for (int k = 0; k < nsteps; ++k) {
+        const cf *step = m->ad_tape + (size_t)(m->ad_fill - 1) * 4 * n;
+        for (int stage = 3; stage >= 0; --stage)
+            if ((rc = adjoint_stage(m, stage, step + (size_t)stage * n))) return rc;
+        --m->ad_fill;
+    }
+    return FB_OK;
+}
+
+// what the entry points refuse before any HIP call
+static int adjoint_check(const char *fn, const fb_model *m, bool need_set)
+{
+    if (!m) return fail(FB_EINVAL, std::string(fn) + ": NULL model");
+    if (need_set && !m->adjoint) return fail(FB_EINVAL, std::string(fn) + ": no adjoint is set");
+    return FB_OK;
+}
+static int adjoint_record_check(const char *fn, int depth)
+{
+    if (depth < 0 || depth > (1 << 20)) return fail(FB_EINVAL, std::string(fn) + ": depth outside [0, 2^20]");
+    return FB_OK;
+}
+static int adjoint_back_check(const char *fn, const fb_model *m, int nsteps)
+{
+    if (nsteps < 0) return fail(FB_EINVAL, std::string(fn) + ": nsteps < 0");
+    if (int rc = adjoint_check(fn, m, true)) return rc;
+    if (nsteps > m->ad_fill) return fail(FB_EINVAL, std::string(fn) + ": " + std::to_string(nsteps) + " steps asked for, " + std::to_string(m->ad_fill) + " recorded");
+    return FB_OK;
+}
+
+extern "C" int fb_model_adjoint_record(fb_model *m, int depth)
+{
+    int rc;
+    if ((rc = adjoint_record_check("fb_model_adjoint_record", depth)) || (rc = adjoint_check("fb_model_adjoint_record", m, false))) return rc;
+    NEED_SINGLE(m->c);
+    if (m->phase_flow) return fail(FB_EINVAL, "fb_model_adjoint_record on a slab model: use fb_slab_adjoint_record");
+    return adjoint_record(m, depth);
+}
+
+extern "C" int fb_model_adjoint_recorded(fb_model *m, int *n)
+{
+    if (!m || !n) return fail(FB_EINVAL, "fb_model_adjoint_recorded: NULL");
+    *n = m->ad_fill;
+    return FB_OK;
+}
+
+extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real)
+{
+    int rc;
+    if ((rc = adjoint_check("fb_model_set_adjoint", m, false))) return rc;
+    NEED_SINGLE(m->c);
+    return adjoint_in(m, nullptr, d_lambda_real);
+}
+
+extern "C" int fb_model_get_adjoint(fb_model *m, float *d_real)
+{
+    int rc;
+    if (!d_real) return fail(FB_EINVAL, "fb_model_get_adjoint: NULL");
+    if ((rc = adjoint_check("fb_model_get_adjoint", m, true))) return rc;
+    NEED_SINGLE(m->c);
+    return record(m, nullptr, REC_VORT, d_real, nullptr, m->ad.c0);
+}
+
+extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps)
+{
+    int rc;
+    if ((rc = adjoint_back_check("fb_model_adjoint_back", m, nsteps))) return rc;
+    NEED_SINGLE(m->c);
+    return adjoint_back(m, nullptr, nsteps);
+}
+
+// a slab of one rank goes through the same code; on several ranks the adjoint model is refused
+#define SLAB_ADJOINT_ONE_RANK(s, fn) do { if (!(s)) return fail(FB_EINVAL, std::string(fn) + ": NULL slab"); if ((s)->c->world > 1) return fail(FB_EINVAL, std::string(fn) + ": the adjoint model is not supported on a slab of several ranks (world > 1)"); } while (0)
+
+extern "C" int fb_slab_adjoint_record(fb_slab *s, int depth)
+{
+    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_record");
+    int rc;
+    if ((rc = adjoint_record_check("fb_slab_adjoint_record", depth))) return rc;
+    SLAB_READY(s);
+    return adjoint_record(s->m, depth);
+}
+
+extern "C" int fb_slab_adjoint_recorded(fb_slab *s, int *n)
+{
+    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_recorded");
+    if (!n) return fail(FB_EINVAL, "fb_slab_adjoint_recorded: NULL");
+    *n = s->m->ad_fill;
+    return FB_OK;
+}
+
+extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real)
+{
+    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_set_adjoint");
+    SLAB_READY(s);
+    return adjoint_in(s->m, s, d_lambda_real);
+}
+
+extern "C" int fb_slab_get_adjoint(fb_slab *s, float *d_real)
+{
+    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_get_adjoint");
+    int rc;
+    if (!d_real) return fail(FB_EINVAL, "fb_slab_get_adjoint: NULL");
+    if ((rc = adjoint_check("fb_slab_get_adjoint", s->m, true))) return rc;
+    SLAB_READY(s);
+    return record(s->m, s, REC_VORT, d_real, nullptr, s->m->ad.c0);
+}
+
+extern "C" int fb_slab_adjoint_back(fb_slab *s, int nsteps)
+{
+    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_back");
+    int rc;
+    if ((rc = adjoint_back_check("fb_slab_adjoint_back", s->m, nsteps))) return rc;
+    SLAB_READY(s);
+    return adjoint_back(s->m, s, nsteps);
+}

@@ -16,6 +16,7 @@ static int state_in(fb_model *m, fb_slab *s, const float *d_rows)
     int rc;
     m->warmed = false;                                      // the next fb_model_step starts with an eager (priming) step
     m->primed = 0;
+    m->ad_fill = 0;                                         // the adjoint's tape belongs to the state that is replaced
     if (!s) HIPCHK(hipMemsetAsync(m->gb[0].t_send, 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
     RowArgs a = row_args_base(c);
     a.rin = d_rows;

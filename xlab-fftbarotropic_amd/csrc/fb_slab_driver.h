@@ -384,6 +384,7 @@ extern "C" int fb_slab_step(fb_slab *s, int nsteps)
     if (nsteps < 0) return fail(FB_EINVAL, "fb_slab_step: nsteps < 0");
     if (nsteps == 0) return FB_OK;
     int rc;
+    if ((rc = adjoint_room(s->m, nsteps, "fb_slab_step"))) return rc;
     if (!s->m->primed) {
         if ((rc = slab_prime(s))) return rc;
         HIPCHK(hipEventRecord(s->ev_rows_done, s->comp));
@@ -395,7 +396,9 @@ extern "C" int fb_slab_step(fb_slab *s, int nsteps)
             if (s->m->tracer && (rc = tracer_stage(s->m, s, k))) return rc;
             if (s->m->pt_n && (rc = particle_stage(s->m, k))) return rc;     // (one rank only: fb_slab_set_particles)
             if (s->m->tangent && (rc = tangent_stage(s->m, s, k))) return rc; // (one rank only: fb_slab_set_tangent)
+            if (s->m->ad_depth && (rc = adjoint_stash(s->m, k))) return rc;   // (one rank only: fb_slab_adjoint_record)
             if ((rc = slab_stage(s, k))) return rc;
+            if (k == 3 && s->m->ad_depth) ++s->m->ad_fill;
         }
     return FB_OK;
 }

@@ -20,6 +20,7 @@
 #include "fb_tracer.h"
 #include "fb_particles.h"
 #include "fb_tangent.h"
+#include "fb_adjoint.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1050,6 +1051,14 @@ struct fb_model {
     cf *tg_j[3];
     double *tg_red;
     bool tangent;
+    // the adjoint model (fb_adjoint.h; host side in fb_beside.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
+    // 3-pass layout, masked modes merged in from the base, ad_fill steps of it recorded; NULL and 0 while nothing is recorded.  The
+    // adjoint variable lam (ad.c0) with the k-bar (ad.c1) and the accumulator (ad.acc) of a backward step, and the five real fields
+    // [5][nx][ny] of its product pass; NULL without
+    cf *ad_tape; int ad_depth, ad_fill;
+    Beside ad;
+    float *ad_real;
+    bool adjoint;
 };
 
 static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool phase_flow)
@@ -1094,6 +1103,10 @@ static void particles_free(fb_model *m);
 static int particle_stage(fb_model *m, int stage);                      // fb_beside.h
 static void tangent_free(fb_model *m);
 static int tangent_stage(fb_model *m, struct fb_slab *s, int stage);    // fb_beside.h
+static void adjoint_free(fb_model *m);
+static void adjoint_tape_free(fb_model *m);
+static int adjoint_room(const fb_model *m, int nsteps, const char *fn); // fb_beside.h: a step call that would overrun the tape is refused
+static int adjoint_stash(fb_model *m, int stage);                       // fb_beside.h
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1118,6 +1131,8 @@ extern "C" int fb_model_destroy(fb_model *m)
     tracer_free(m);
     particles_free(m);
     tangent_free(m);
+    adjoint_free(m);
+    adjoint_tape_free(m);
     delete m;
     return FB_OK;
 }
@@ -1287,6 +1302,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
     if (c->world != 1 || m->phase_flow) return fail(FB_EINVAL, "fb_model_step on a slab model: drive it with fb_slab_step");
     int rc;
     if (nsteps == 0) return FB_OK;
+    if ((rc = adjoint_room(m, nsteps, "fb_model_step"))) return rc;
     if (m->xpass != XP_COLS && !m->primed) return fail(FB_EINVAL, "fb_model_step: set the state first");
     if (!m->primed && (rc = model_prime(m))) return rc;
     if (m->primed == 1 && m->xpass == XP_COLS) { if ((rc = model_col_bwd_active(m))) return rc; m->primed = 2; }
@@ -1297,6 +1313,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
             if (m->tracer && (rc = tracer_stage(m, nullptr, k))) return rc;       // the tracer's stage k, from the state this stage starts from
             if (m->pt_n && (rc = particle_stage(m, k))) return rc;                // the particles' stage k, likewise
             if (m->tangent && (rc = tangent_stage(m, nullptr, k))) return rc;     // the tangent-linear model's stage k, likewise
+            if (m->ad_depth && (rc = adjoint_stash(m, k))) return rc;             // the adjoint's tape: the state stage k starts from
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
             PROF_BEGIN(1);
             if ((rc = launch_fused_row(m, 0, c->XL))) return rc;
@@ -1318,6 +1335,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
             if ((rc = launch_col_strided<+1>(c, G, B.w4_send, 4, (long)priv_elems(c), rowmap_natural(), 0, G.nct_active))) return rc;
             PROF_END(0);
         }
+        if (m->ad_depth) ++m->ad_fill;
     }
     return FB_OK;
 }
@@ -1340,8 +1358,9 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
     if (!m || nsteps < 0) return fail(FB_EINVAL, "fb_model_step: bad argument");
     fb_ctx *c = m->c;
     // graph replay needs a capturable (non-null) stream, a primed pipeline and at least one eager step behind
-    // us (kernel attributes are set on first launch); anything else runs eagerly
-    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
+    // us (kernel attributes are set on first launch); anything else runs eagerly.  So does a model that records the adjoint's tape:
+    // every step writes another slot, which a captured step would bake in
+    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2 || m->ad_depth) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
     int rc;
     if (!m->warmed) { if ((rc = model_step_impl(m, 1, nullptr))) return rc; m->warmed = true; --nsteps; }
     if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream)) model_drop_graph(m);
@@ -1411,6 +1430,7 @@ extern "C" int fb_model_set_spectrum(fb_model *m, const float *d_spec)
     NEED_SINGLE(m->c);
     m->primed = 0;
     m->warmed = false;
+    m->ad_fill = 0;                                         // the adjoint's tape belongs to the state that is replaced
     int rc = relayout(m->c, (const cf *)d_spec, m->gb[0].ZB, true);
     if (rc) return rc;
     if (m->xpass != XP_COLS) return full_import_state(m, m->gb[0].ZB);

@@ -398,6 +398,39 @@ class EngineSlab:
     def lyapunov(self, steps, renorm_every, kind="enstrophy"):
         return self.B.lyapunov(self, steps, renorm_every, kind)
 
+    def record_adjoint(self, depth):
+        """The adjoint's tape of binding.Model.record_adjoint (fb_slab_adjoint_record).  One rank only: on world > 1 this and the five
+        methods below raise FftBaroError with the engine's message."""
+        self.B.check(self.L.fb_slab_adjoint_record(self._h, int(depth)))
+
+    def adjoint_recorded(self):
+        n = C.c_int()
+        self.B.check(self.L.fb_slab_adjoint_recorded(self._h, C.byref(n)))
+        return n.value
+
+    def set_adjoint(self, lam):
+        if lam is None or self.world > 1:                       # (before any buffer is shaped for one rank)
+            self.B.check(self.L.fb_slab_set_adjoint(self._h, None))
+        else:
+            a = self._rows(lam)
+            self.B.check(self.L.fb_slab_set_adjoint(self._h, C.c_void_p(a.data_ptr())))
+        self.synchronize()
+
+    def adjoint(self):
+        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
+        self.B.check(self.L.fb_slab_get_adjoint(self._h, C.c_void_p(out.data_ptr())))
+        self.synchronize()
+        return out
+
+    def adjoint_back(self, n=1):
+        self.B.check(self.L.fb_slab_adjoint_back(self._h, int(n)))
+
+    def singular_values(self, steps, iters, start):
+        """binding.singular_values on one rank; the state is kept and put back as a field of rows (vort_local / set_vort_local)"""
+        if self.world > 1:
+            self.record_adjoint(steps)                          # raises with the engine's message
+        return self.B.singular_values(self, steps, iters, start, save=self.vort_local, restore=self.set_vort_local)
+
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
         Collective: every rank calls it."""
