@@ -277,6 +277,33 @@ def test_slab_of_one_rank_matches_the_model():
     s.close()
 
 
+def test_slab_of_one_rank_singular_values_match_the_model():
+    """EngineSlab.singular_values on one rank at 64^2 against Model.singular_values.  The slab keeps and puts back its state as a field
+    of rows (one c2r and one r2c, each rounding to float32) where the model keeps the spectrum bit for bit, so the two iterations are
+    not the same bits; the bars are the ones this file holds singular values and the final vector to, SV_BAR and 1e-4."""
+    import xlab_fftbarotropic_amd as X
+    S = _slab()
+    n = 64
+    v, d, src, _ = A.adjoint_inputs(n, n, A.PATH_CASES[0].vort_noise)
+    m = _gpu_model(n, n, v, None, src, dt=3.0)
+    sm, vm = m.singular_values(A.SV_STEPS, A.SV_ITERS, d)
+    m.close()
+    s = S.EngineSlab(n, n, nu=A.G.NU, dt=3.0)
+    s.set_vort_local(v)
+    s.set_source_local(src)
+    before = _np(s.vort_local())
+    ss, vs = s.singular_values(A.SV_STEPS, A.SV_ITERS, d)
+    assert s.adjoint_recorded() == 0
+    assert rel_l2(_np(s.vort_local()), before) <= 1e-5          # (the parity bar: the state went through the field round trip)
+    s.close()
+    vs, vm = _np(vs), _np(vm)
+    print("singular_values 64^2 on one rank: slab %s, model %s; the vector off by %.3g" % (ss, sm, rel_l2(vs, vm)))
+    assert len(ss) == A.SV_ITERS and all(isinstance(x, float) and np.isfinite(x) for x in ss)
+    assert vs.shape == (n, n) and vs.dtype == np.float32 and np.isfinite(vs).all()
+    assert max(abs(a / b - 1) for a, b in zip(ss, sm)) <= A.SV_BAR
+    assert rel_l2(vs, vm) <= 1e-4
+
+
 def test_slab_of_two_ranks_is_refused():
     """world = 2, ranks as threads of this process: every adjoint entry point raises with the engine's message"""
     import threading

@@ -105,6 +105,32 @@ def test_engine_slab_matches_fused_path(world, n, steps, env):
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
 
 
+def test_time_steps_on_both_classes():
+    """Model.time_steps and EngineSlab.time_steps (one rank) at 64^2: the device time of the batch, a float, and the state stepped on as
+    step() steps it.  Both classes run the three-kernel column path here, where the test above finds equal bits; between the two
+    classes the bar is the float32 format's: 4 stages of 3 steps, each rounding the state once, 12 eps32 in relative L2."""
+    import xlab_fftbarotropic_amd as X
+    n, steps = 64, 3
+    v0 = X.make_field("elliptic", n)
+    out = []
+    for m in (X.Model(n, n), _slab().EngineSlab(n, n)):
+        one = isinstance(m, X.Model)
+        (m.set_vort if one else m.set_vort_local)(v0)
+        ms = m.time_steps(steps)
+        got = (m.vort() if one else m.vort_local()).cpu().numpy()
+        (m.set_vort if one else m.set_vort_local)(v0)
+        m.step(steps)
+        want = (m.vort() if one else m.vort_local()).cpu().numpy()
+        m.close()
+        assert isinstance(ms, float) and np.isfinite(ms) and ms > 0.0
+        assert got.shape == (n, n) and got.dtype == np.float32 and np.isfinite(got).all()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))           # the same steps on the same path of ONE class
+        out.append(got)
+    err = float(np.linalg.norm((out[0] - out[1]).astype(np.float64)) / np.linalg.norm(out[0].astype(np.float64)))
+    print("time_steps 64^2: model against one-rank slab rel L2 = %.3g" % err)
+    assert err <= 12 * float(np.finfo(np.float32).eps)
+
+
 @pytest.mark.parametrize("nx,world", [(512, 2), (128, 8)])
 def test_engine_slab_4096_uses_the_headline_row_kernel(nx, world):
     """ny = 4096 on 2 and 8 ranks (different slab widths, both column groups present): the slab row pass is k_rowq too (slab-blocked addressing); the column

@@ -308,6 +308,31 @@ def test_slab_of_one_rank_matches_the_model():
     s.close()
 
 
+def test_slab_of_one_rank_lyapunov_matches_the_model():
+    """EngineSlab.lyapunov on one rank at 64^2 against Model.lyapunov.  The bar is the one the test above holds the slab's norm to
+    against the model's, 4 eps32 relative: a growth factor is the root of a ratio of two norms, and the exponent the sum over the
+    intervals of half the log of such ratios."""
+    import xlab_fftbarotropic_amd as X
+    S = _slab()
+    n, steps, every = 64, 6, 2
+    v0, d0, _ = _inputs(n, n, G.PATH_CASES[0].vort_noise)
+    out = []
+    for m in (X.Model(n, n, nu=G.NU, dt=3.0), S.EngineSlab(n, n, nu=G.NU, dt=3.0)):
+        (m.set_vort if isinstance(m, X.Model) else m.set_vort_local)(v0)
+        m.set_tangent(d0)
+        lam, factors = m.lyapunov(steps, every)
+        out.append((lam, factors, _np(m.tangent())))
+        m.close()
+    (lm, fm, tm), (ls, fs, ts) = out
+    assert isinstance(ls, float) and np.isfinite(ls) and len(fs) == steps // every and all(isinstance(g, float) and np.isfinite(g) for g in fs)
+    assert ts.shape == (n, n) and ts.dtype == np.float32 and np.isfinite(ts).all()
+    print("lyapunov 64^2 on one rank: slab %.9g s^-1, model %.9g s^-1, factors %s against %s" % (ls, lm, fs, fm))
+    for a, b in zip(fs, fm):
+        assert abs(a / b - 1) <= 4 * EPS32
+    assert abs(ls - lm) * steps * 3.0 <= len(fm) * 4 * EPS32
+    assert rel_l2(ts, tm) <= 4 * EPS32
+
+
 def test_slab_of_two_ranks_is_refused():
     """world = 2, ranks as threads of this process: every tangent entry point raises with the engine's message"""
     import threading

@@ -7,6 +7,7 @@ the compute is entirely in libfftbaro.so.  There is no CPU fallback: a missing l
 missing GPU raises.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -20,6 +21,60 @@ ALLTOALL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_
 
 class FftBaroError(RuntimeError):
     pass
+
+
+# The C ABI of include/fftbaro.h: name -> (argtypes, restype; None: the int status).  A data pointer is a c_void_p (it takes byref(...),
+# ctypes arrays and buffers, bytes, None, ints and c_void_p alike), or a POINTER(...) where the callers pass byref.
+_vp, _ip, _fl, _db, _sz, _cp = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t, C.c_char_p
+_pvp, _pip, _pfl, _psz = C.POINTER(_vp), C.POINTER(_ip), C.POINTER(_fl), C.POINTER(_sz)
+SIGNATURES = {
+    "fb_strerror": ([_ip], _cp), "fb_last_error": ([], _cp), "fb_version": ([], None),
+    "fb_device_count": ([_pip], None), "fb_set_device": ([_ip], None), "fb_size_supported": ([_ip, _ip], None),
+    "fb_create": ([_pvp, _ip, _ip, _fl, _fl], None), "fb_destroy": ([_vp], None),
+    "fb_set_stream": ([_vp, _vp], None), "fb_synchronize": ([_vp], None), "fb_get_tables": ([_vp] * 6, None),
+    "fb_malloc": ([_pvp, _sz], None), "fb_free": ([_vp], None),
+    "fb_memcpy_h2d": ([_vp, _vp, _vp, _sz], None), "fb_memcpy_d2h": ([_vp, _vp, _vp, _sz], None), "fb_memset0": ([_vp, _vp, _sz], None),
+    "fb_malloc_host": ([_vp, _sz], None), "fb_free_host": ([_vp], None),
+    "fb_stream_create": ([_vp], None), "fb_stream_destroy": ([_vp], None), "fb_stream_synchronize": ([_vp], None),
+    "fb_event_create": ([_vp], None), "fb_event_create_timing": ([_vp], None), "fb_event_destroy": ([_vp], None),
+    "fb_event_record": ([_vp, _vp], None), "fb_stream_wait_event": ([_vp, _vp], None), "fb_event_synchronize": ([_vp], None),
+    "fb_event_elapsed_ms": ([_vp, _vp, _vp], None),
+    "fb_memcpy_d2h_async": ([_vp, _vp, _vp, _sz], None), "fb_memcpy_h2d_async": ([_vp, _vp, _vp, _sz], None),
+    "fb_gradx": ([_vp] * 3, None), "fb_grady": ([_vp] * 3, None), "fb_laplacian": ([_vp] * 3, None),
+    "fb_invert_laplacian": ([_vp] * 3, None), "fb_dealiase": ([_vp] * 3, None),
+    "fb_r2c": ([_vp] * 3, None), "fb_c2r": ([_vp, _vp, _vp, _ip], None),
+    "fb_backward_normalize": ([_vp, _vp], None), "fb_negate": ([_vp, _vp], None), "fb_jacobian": ([_vp] * 7, None),
+    "fb_spec_axpy": ([_vp, _vp, _vp, _fl], None), "fb_spec_evolve": ([_vp, _vp, _vp, _fl, _vp], None),
+    "fb_spec_rk4_combine": ([_vp] * 6 + [_fl, _vp], None),
+    "fb_model_create": ([_pvp, _vp, _fl, _fl], None), "fb_model_use_graph": ([_vp, _ip], None),
+    "fb_model_get_spectrum": ([_vp, _vp], None), "fb_model_set_spectrum": ([_vp, _vp], None),
+    "fb_model_info": ([_vp, _psz, _psz], None), "fb_model_profile_steps": ([_vp, _ip, _pfl, _pip], None),
+    "fb_spectra_shells": ([_ip, _ip, _fl, _fl, _pip], None), "fb_azimuthal_cols": ([_ip, _pip], None),
+    "fb_slab_unique_id": ([_cp], None), "fb_slab_create": ([_pvp, _ip, _ip, _fl, _fl, _fl, _fl, _ip, _ip], None),
+    "fb_slab_connect_rccl": ([_vp, _cp], None), "fb_local_hub_create": ([_pvp, _ip], None), "fb_local_hub_destroy": ([_vp], None),
+    "fb_slab_connect_local": ([_vp, _vp], None), "fb_slab_connect_callback": ([_vp, ALLTOALL_FN, _vp], None),
+    "fb_slab_synchronize": ([_vp], None), "fb_slab_record_event": ([_vp, _vp], None), "fb_slab_wait_event": ([_vp, _vp], None),
+    "fb_slab_transport_selftest": ([_vp, _sz, _psz], None), "fb_slab_transport_info": ([_vp, _cp, _sz] + [_pip] * 4, None),
+    "fb_slab_info": ([_vp] + [_pip] * 7, None), "fb_slab_geometry": ([_ip, _ip, _ip] + [_pip] * 3, None),
+    "fb_slab_col_groups": ([_ip, _ip, _ip, _pip, _pip], None), "fb_slab_plan": ([_ip, _ip, _ip, _pip, _pip, _pip, _ip], None),
+    "fb_create_slab": ([_pvp, _ip, _ip, _fl, _fl, _ip, _ip], None),
+    "fb_write_field": ([_cp, _vp, _sz], None), "fb_read_field": ([_cp, _vp, _sz], None),
+    "fb_make_field": ([_cp, _ip, _ip, _fl, _fl, _vp], None), "fb_make_source_kuo2004": ([_ip, _ip, _fl, _fl, _fl, _vp], None),
+}
+# fb_model_X and fb_slab_X (fb_slab_X_local where the slab's call works on this rank's rows) take the same parameters after the handle
+_PAIRS = {
+    "destroy": [], "step": [_ip], "time_steps": [_ip, _pfl],
+    "set_vort_local": [_vp], "set_source_local": [_vp], "get_vort_local": [_vp], "get_diag_local": [_vp] * 3,
+    "get_okubo_weiss_local": [_vp, _vp], "get_eddy_diffusivity": [_ip, _vp, _vp, _vp], "get_pressure_local": [_fl, _fl, _ip, _ip, _vp],
+    "get_spectra": [_vp], "get_azimuthal": [_ip, _db, _db, _ip, _db, _ip, _vp, _vp],
+    "set_tracer_local": [_vp, _fl], "get_tracer_local": [_vp], "get_tracer_eddy_diffusivity": [_ip, _vp, _vp, _vp],
+    "set_particles": [_vp, _ip], "get_particles": [_vp], "particle_count": [_pip], "sample": [_vp, _vp, _ip, _vp],
+    "set_tangent": [_vp], "get_tangent": [_vp], "tangent_norm": [_ip, _vp], "tangent_scale": [_fl],
+    "adjoint_record": [_ip], "adjoint_recorded": [_pip], "set_adjoint": [_vp], "get_adjoint": [_vp], "adjoint_back": [_ip],
+}
+for _name, _args in _PAIRS.items():
+    SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
+EXPORTS = list(SIGNATURES)
 
 
 def lib():
@@ -43,161 +98,15 @@ def lib():
             if not (os.environ.get("FFTBARO_ALLOW_STALE") and os.path.exists(path)):
                 raise FftBaroError("libfftbaro.so is missing or stale and could not be rebuilt: %s" % e)
     L = C.CDLL(path)
-    vp, fp, ip = C.c_void_p, C.c_void_p, C.c_int
-    L.fb_strerror.restype = C.c_char_p
-    L.fb_strerror.argtypes = [ip]
-    L.fb_last_error.restype = C.c_char_p
-    L.fb_version.restype = ip
-    L.fb_size_supported.argtypes = [ip, ip]
-    L.fb_device_count.argtypes = [C.POINTER(ip)]
-    L.fb_set_device.argtypes = [ip]
-    L.fb_create.argtypes = [C.POINTER(vp), ip, ip, C.c_float, C.c_float]
-    L.fb_destroy.argtypes = [vp]
-    L.fb_set_stream.argtypes = [vp, vp]
-    L.fb_synchronize.argtypes = [vp]
-    L.fb_get_tables.argtypes = [vp] + [C.c_void_p] * 5
-    L.fb_malloc.argtypes = [C.POINTER(vp), C.c_size_t]
-    L.fb_free.argtypes = [vp]
-    L.fb_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-    L.fb_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-    L.fb_memset0.argtypes = [vp, vp, C.c_size_t]
-    for n in ("fb_gradx", "fb_grady", "fb_laplacian", "fb_invert_laplacian", "fb_dealiase"):
-        getattr(L, n).argtypes = [vp, fp, fp]
-    L.fb_r2c.argtypes = [vp, fp, fp]
-    L.fb_c2r.argtypes = [vp, fp, fp, ip]
-    L.fb_backward_normalize.argtypes = [vp, fp]
-    L.fb_negate.argtypes = [vp, fp]
-    L.fb_jacobian.argtypes = [vp, fp, fp, fp, fp, fp, fp]
-    L.fb_spec_axpy.argtypes = [vp, fp, fp, C.c_float]
-    L.fb_spec_evolve.argtypes = [vp, fp, fp, C.c_float, fp]
-    L.fb_spec_rk4_combine.argtypes = [vp, fp, fp, fp, fp, fp, C.c_float, fp]
-    L.fb_model_create.argtypes = [C.POINTER(vp), vp, C.c_float, C.c_float]
-    L.fb_model_destroy.argtypes = [vp]
-    L.fb_model_set_vort.argtypes = [vp, fp]
-    L.fb_model_set_source.argtypes = [vp, fp]
-    L.fb_model_step.argtypes = [vp, ip]
-    L.fb_model_use_graph.argtypes = [vp, ip]
-    L.fb_model_get_vort.argtypes = [vp, fp]
-    L.fb_model_get_diag.argtypes = [vp, fp, fp, fp]
-    L.fb_model_get_okubo_weiss.argtypes = [vp, fp, fp]
-    L.fb_model_get_eddy_diffusivity.argtypes = [vp, ip, vp, fp, fp]
-    L.fb_model_get_spectrum.argtypes = [vp, fp]
-    L.fb_model_set_spectrum.argtypes = [vp, fp]
-    L.fb_model_info.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
-    L.fb_model_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
-    L.fb_model_profile_steps.argtypes = [vp, ip, C.POINTER(C.c_float), C.POINTER(C.c_int)]
-    L.fb_make_field.argtypes = [C.c_char_p, ip, ip, C.c_float, C.c_float, C.c_void_p]
-    L.fb_make_source_kuo2004.argtypes = [ip, ip, C.c_float, C.c_float, C.c_float, C.c_void_p]
-    L.fb_create_slab.argtypes = [C.POINTER(vp), ip, ip, C.c_float, C.c_float, ip, ip]
-    L.fb_slab_unique_id.argtypes = [C.c_char_p]
-    L.fb_slab_create.argtypes = [C.POINTER(vp), ip, ip, C.c_float, C.c_float, C.c_float, C.c_float, ip, ip]
-    L.fb_slab_destroy.argtypes = [vp]
-    L.fb_slab_connect_rccl.argtypes = [vp, C.c_char_p]
-    L.fb_local_hub_create.argtypes = [C.POINTER(vp), ip]
-    L.fb_local_hub_destroy.argtypes = [vp]
-    L.fb_slab_connect_local.argtypes = [vp, vp]
-    L.fb_slab_connect_callback.argtypes = [vp, ALLTOALL_FN, vp]
-    L.fb_slab_set_vort_local.argtypes = [vp, fp]
-    L.fb_slab_set_source_local.argtypes = [vp, fp]
-    L.fb_slab_get_vort_local.argtypes = [vp, fp]
-    L.fb_slab_get_diag_local.argtypes = [vp, fp, fp, fp]
-    L.fb_slab_get_okubo_weiss_local.argtypes = [vp, fp, fp]
-    L.fb_slab_get_eddy_diffusivity.argtypes = [vp, ip, vp, fp, fp]
-    # (an older build chosen through FFTBARO_LIB for an A/B run lacks the pressure record: calling it there is an AttributeError)
-    for n in ("fb_model_get_pressure", "fb_slab_get_pressure_local"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, C.c_float, C.c_float, ip, ip, fp]
-    # (likewise the spectra record)
-    for n in ("fb_model_get_spectra", "fb_slab_get_spectra"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, vp]
-    if hasattr(L, "fb_spectra_shells"):
-        L.fb_spectra_shells.argtypes = [ip, ip, C.c_float, C.c_float, C.POINTER(ip)]
-    # (likewise the passive tracer)
-    for n in ("fb_model_set_tracer", "fb_slab_set_tracer_local"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, fp, C.c_float]
-    for n in ("fb_model_get_tracer", "fb_slab_get_tracer_local"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, fp]
-    for n in ("fb_model_get_tracer_eddy_diffusivity", "fb_slab_get_tracer_eddy_diffusivity"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, ip, vp, fp, fp]
-    # (likewise the azimuthal-mean record)
-    for n in ("fb_model_get_azimuthal", "fb_slab_get_azimuthal"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, ip, C.c_double, C.c_double, ip, C.c_double, ip, vp, vp]
-    if hasattr(L, "fb_azimuthal_cols"):
-        L.fb_azimuthal_cols.argtypes = [ip, C.POINTER(ip)]
-    # (likewise the Lagrangian particles)
-    for n in ("fb_model_set_particles", "fb_slab_set_particles"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, vp, ip]
-    for n in ("fb_model_get_particles", "fb_slab_get_particles"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, vp]
-    for n in ("fb_model_particle_count", "fb_slab_particle_count"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, C.POINTER(ip)]
-    for n in ("fb_model_sample", "fb_slab_sample"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, fp, vp, ip, vp]
-    # (likewise the tangent-linear model)
-    for n in ("fb_model_set_tangent", "fb_model_get_tangent", "fb_slab_set_tangent", "fb_slab_get_tangent"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, fp]
-    for n in ("fb_model_tangent_norm", "fb_slab_tangent_norm"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, ip, vp]
-    for n in ("fb_model_tangent_scale", "fb_slab_tangent_scale"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, C.c_float]
-    # (likewise the adjoint model)
-    for n in ("fb_model_adjoint_record", "fb_model_adjoint_back", "fb_slab_adjoint_record", "fb_slab_adjoint_back"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, ip]
-    for n in ("fb_model_adjoint_recorded", "fb_slab_adjoint_recorded"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, C.POINTER(ip)]
-    for n in ("fb_model_set_adjoint", "fb_model_get_adjoint", "fb_slab_set_adjoint", "fb_slab_get_adjoint"):
-        if hasattr(L, n):
-            getattr(L, n).argtypes = [vp, fp]
-    L.fb_slab_step.argtypes = [vp, ip]
-    L.fb_slab_synchronize.argtypes = [vp]
-    L.fb_slab_time_steps.argtypes = [vp, ip, C.POINTER(C.c_float)]
-    L.fb_slab_transport_selftest.argtypes = [vp, C.c_size_t, C.POINTER(C.c_size_t)]
-    L.fb_slab_info.argtypes = [vp] + [C.POINTER(ip)] * 7
-    L.fb_slab_transport_info.argtypes = [vp, C.c_char_p, C.c_size_t] + [C.POINTER(ip)] * 4
-    L.fb_slab_geometry.argtypes = [ip, ip, ip] + [C.POINTER(ip)] * 3
-    L.fb_slab_plan.argtypes = [ip, ip, ip, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), ip]
-    L.fb_write_field.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
-    L.fb_read_field.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+    # (an older build chosen through FFTBARO_LIB for an A/B run lacks the newer entry points: calling one there is an AttributeError)
+    for name, (argtypes, restype) in SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is not None:
+            fn.argtypes = argtypes
+            if restype is not None:
+                fn.restype = restype
     _lib = L
     return L
-
-
-EXPORTS = [
-    "fb_strerror", "fb_last_error", "fb_version", "fb_size_supported", "fb_device_count", "fb_set_device", "fb_create", "fb_destroy", "fb_set_stream",
-    "fb_synchronize", "fb_get_tables", "fb_malloc", "fb_free", "fb_memcpy_h2d", "fb_memcpy_d2h", "fb_memset0",
-    "fb_gradx", "fb_grady", "fb_laplacian", "fb_invert_laplacian", "fb_dealiase", "fb_r2c", "fb_c2r",
-    "fb_backward_normalize", "fb_negate", "fb_jacobian", "fb_spec_axpy", "fb_spec_evolve", "fb_spec_rk4_combine",
-    "fb_model_create", "fb_model_destroy", "fb_model_set_vort", "fb_model_set_source", "fb_model_step",
-    "fb_model_use_graph", "fb_model_get_vort", "fb_model_get_diag", "fb_model_get_okubo_weiss", "fb_model_get_eddy_diffusivity", "fb_model_get_pressure", "fb_model_get_spectra", "fb_spectra_shells", "fb_model_get_spectrum", "fb_model_set_spectrum", "fb_model_info",
-    "fb_model_time_steps", "fb_model_profile_steps", "fb_write_field", "fb_read_field", "fb_make_field", "fb_make_source_kuo2004",
-    "fb_create_slab", "fb_slab_unique_id", "fb_slab_create", "fb_slab_destroy", "fb_slab_connect_rccl", "fb_local_hub_create",
-    "fb_local_hub_destroy", "fb_slab_connect_local", "fb_slab_connect_callback", "fb_slab_set_vort_local", "fb_slab_set_source_local",
-    "fb_slab_get_vort_local", "fb_slab_get_diag_local", "fb_slab_get_okubo_weiss_local", "fb_slab_get_eddy_diffusivity", "fb_slab_get_pressure_local", "fb_slab_get_spectra", "fb_slab_step", "fb_slab_synchronize", "fb_slab_time_steps", "fb_slab_transport_selftest", "fb_slab_transport_info", "fb_slab_info", "fb_slab_geometry", "fb_slab_plan", "fb_slab_col_groups",
-    "fb_malloc_host", "fb_free_host", "fb_stream_create", "fb_stream_destroy", "fb_stream_synchronize", "fb_event_create", "fb_event_create_timing", "fb_event_elapsed_ms",
-    "fb_model_set_tracer", "fb_model_get_tracer", "fb_model_get_tracer_eddy_diffusivity", "fb_slab_set_tracer_local", "fb_slab_get_tracer_local", "fb_slab_get_tracer_eddy_diffusivity",
-    "fb_azimuthal_cols", "fb_model_get_azimuthal", "fb_slab_get_azimuthal",
-    "fb_model_set_particles", "fb_model_get_particles", "fb_model_particle_count", "fb_model_sample",
-    "fb_slab_set_particles", "fb_slab_get_particles", "fb_slab_particle_count", "fb_slab_sample",
-    "fb_model_set_tangent", "fb_model_get_tangent", "fb_model_tangent_norm", "fb_model_tangent_scale",
-    "fb_slab_set_tangent", "fb_slab_get_tangent", "fb_slab_tangent_norm", "fb_slab_tangent_scale",
-    "fb_model_adjoint_record", "fb_model_adjoint_recorded", "fb_model_set_adjoint", "fb_model_get_adjoint", "fb_model_adjoint_back",
-    "fb_slab_adjoint_record", "fb_slab_adjoint_recorded", "fb_slab_set_adjoint", "fb_slab_get_adjoint", "fb_slab_adjoint_back",
-    "fb_event_destroy", "fb_event_record", "fb_stream_wait_event", "fb_event_synchronize", "fb_memcpy_d2h_async", "fb_memcpy_h2d_async", "fb_slab_record_event", "fb_slab_wait_event",
-]
 
 
 def check(status):
@@ -260,7 +169,14 @@ def _torch():
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+@functools.lru_cache(maxsize=None)
+def _entry(prefix, name):
+    """the C function prefix + name + "_local" where the library has it (a slab's calls on this rank's rows), else prefix + name"""
+    fn = getattr(lib(), prefix + name + "_local", None)
+    return fn if fn is not None else getattr(lib(), prefix + name)
 
 
 PARTICLES_MAX = 1 << 24
@@ -463,25 +379,52 @@ class FftwfOperation:
     def synchronize(self): check(lib().fb_synchronize(self._h))
 
 
-class Model:
-    """The main.cpp RK4 driver state (main.cpp:103-317) resident in HBM, fused stepping."""
+class ModelSurface:
+    """What Model (fb_model_*, the whole [nx, ny] grid) and slab.EngineSlab (fb_slab_*, this rank's [XL, ny] rows; its calls are
+    collective) share: every call of the C ABI that both have, written once.  A subclass supplies _PREFIX, the handle _h, _shape
+    (of a real field), _wait() (until the engine has finished what it was handed) and, where it can have several ranks, _one_rank().
+    The engine works on ITS streams: torch's current stream is waited for before any call that is handed a tensor."""
 
-    def __init__(self, nx, ny=None, Lx=600000.0, Ly=600000.0, nu=6.5, dt=3.0):
-        ny = ny or nx
-        self.fop = FftwfOperation(nx, ny, Lx, Ly)
-        self.torch = self.fop.torch
-        self.nx, self.ny, self.hy = nx, ny, ny // 2 + 1
-        self.Lx, self.Ly = Lx, Ly
-        self.nu, self.dt = float(np.float32(nu)), float(np.float32(dt))
-        h = C.c_void_p()
-        check(lib().fb_model_create(C.byref(h), self.fop._h, nu, dt))
-        self._h = h
+    _PREFIX = None
+    _STATE = None           # (getter, setter) of the state that singular_values keeps and puts back
+
+    def _call(self, name, *args):
+        """check(fb_<PREFIX>_<name>_local(handle, *args)), or fb_<PREFIX>_<name> where the library has no _local form"""
+        check(_entry(self._PREFIX, name)(self._h, *args))
+
+    def _hand(self, name, *args):
+        """_call with tensors among the arguments, handed over as they are so that they live until the engine is done with them: what
+        torch has queued for them lands first, and the engine is waited for after"""
+        self.torch.cuda.current_stream().synchronize()
+        self._call(name, *[_ptr(a) if isinstance(a, self.torch.Tensor) else a for a in args])
+        self._wait()
+
+    def _one_rank(self, name, *nulls):
+        """for a call that only one rank supports, before any buffer is shaped: nothing to refuse here"""
+
+    def _dev(self, a):
+        """a real field (numpy or torch; None passes through) as a contiguous float32 tensor of _shape on the GPU"""
+        t = self.torch
+        if isinstance(a, np.ndarray):
+            a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+        assert a is None or (a.is_cuda and a.dtype == t.float32 and a.is_contiguous() and tuple(a.shape) == self._shape)
+        return a
+
+    def _get(self, name, k, *args):
+        """k fresh real fields filled by fb_*_get_<name>(handle, *args, fields ...)"""
+        out = tuple(self.torch.empty(self._shape, dtype=self.torch.float32, device="cuda") for _ in range(k))
+        self._hand("get_" + name, *args, *out)
+        return out
+
+    def _count(self, name):
+        n = C.c_int()
+        self._call(name, C.byref(n))
+        return n.value
 
     def close(self):
         if getattr(self, "_h", None):
-            lib().fb_model_destroy(self._h)
+            getattr(lib(), self._PREFIX + "destroy")(self._h)
             self._h = None
-        self.fop.close()
 
     def __del__(self):
         try:
@@ -489,78 +432,54 @@ class Model:
         except Exception:
             pass
 
-    def _dev(self, a):
-        t = self.torch
-        if isinstance(a, np.ndarray):
-            a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-        assert a.is_cuda and a.dtype == t.float32 and a.is_contiguous() and tuple(a.shape) == (self.nx, self.ny)
-        # the engine reads the buffer on ITS stream: whatever torch still has queued for it (a fill, a copy) must have landed
-        t.cuda.current_stream().synchronize()
-        return a
-
-    def set_vort(self, vort): a = self._dev(vort); check(lib().fb_model_set_vort(self._h, _ptr(a))); self.fop.synchronize()
+    def set_vort(self, vort): self._hand("set_vort", self._dev(vort))
 
     def set_source(self, src):
         if src is None:
-            check(lib().fb_model_set_source(self._h, None))
+            self._call("set_source", None)
         else:
-            a = self._dev(src); check(lib().fb_model_set_source(self._h, _ptr(a))); self.fop.synchronize()
+            self._hand("set_source", self._dev(src))
 
-    def step(self, n=1): check(lib().fb_model_step(self._h, n))
-
-    def use_graph(self, enable=True):
-        """hipGraph replay of the step; call under a non-default torch stream (after fop.use_current_stream())."""
-        check(lib().fb_model_use_graph(self._h, 1 if enable else 0))
+    def step(self, n=1): self._call("step", n)
 
     def time_steps(self, n):
         ms = C.c_float()
-        check(lib().fb_model_time_steps(self._h, n, C.byref(ms)))
+        self._call("time_steps", n, C.byref(ms))
         return ms.value
 
-    KERNEL_CLASSES = ("k_col_strided_bwd4", "k_row_fused", "k_col_strided_fwd1", "k_col_mid")
-
-    def profile_steps(self, n):
-        """HIP-event time per kernel class over n steps: {class: (total_ms, launches)}."""
-        ms = (C.c_float * 4)(); cnt = (C.c_int * 4)()
-        check(lib().fb_model_profile_steps(self._h, n, ms, cnt))
-        return {k: (ms[i], cnt[i]) for i, k in enumerate(self.KERNEL_CLASSES)}
-
-    def vort(self):
-        out = self.fop.empty_real(); check(lib().fb_model_get_vort(self._h, _ptr(out))); return out
+    def vort(self): return self._get("vort", 1)[0]
 
     def diag(self):
-        psi, u, v = self.fop.empty_real(), self.fop.empty_real(), self.fop.empty_real()
-        check(lib().fb_model_get_diag(self._h, _ptr(psi), _ptr(u), _ptr(v)))
-        return psi, u, v
+        """psi, u, v (the stage-0 record dumps, main.cpp:181-222)"""
+        return self._get("diag", 3)
 
     def okubo_weiss(self):
-        """(W, tau_fil): the Okubo-Weiss parameter [s^-2] and the filamentation time [s] (+inf where W <= 0), [nx, ny] tensors."""
-        w, tau = self.fop.empty_real(), self.fop.empty_real()
-        check(lib().fb_model_get_okubo_weiss(self._h, _ptr(w), _ptr(tau)))
-        return w, tau
+        """(W, tau_fil): the Okubo-Weiss parameter [s^-2] and the filamentation time [s] (+inf where W <= 0)."""
+        return self._get("okubo_weiss", 2)
 
-    def eddy_diffusivity(self, nbins=256, fields=False):
-        """The effective eddy diffusivity table, float64 [nbins, 9] (columns EDDY_DIFFUSIVITY_COLUMNS), of the vorticity binned in
-        nbins contour intervals; with fields=True also (zeta, grad2): the vorticity and |grad zeta|^2, [nx, ny] tensors."""
+    def _eddy(self, name, nbins, fields):
         t = self.torch
         table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
-        zeta, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
-        check(lib().fb_model_get_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(zeta) if fields else None, _ptr(g) if fields else None))
-        return (table, zeta, g) if fields else table
+        a, g = (t.empty(self._shape, dtype=t.float32, device="cuda") for _ in range(2)) if fields else (None, None)
+        self._hand(name, nbins, table, a, g)
+        return (table, a, g) if fields else table
+
+    def eddy_diffusivity(self, nbins=256, fields=False):
+        """The effective eddy diffusivity table of the whole domain, float64 [nbins, 9] (columns EDDY_DIFFUSIVITY_COLUMNS), of the
+        vorticity binned in nbins contour intervals; with fields=True also (zeta, grad2): the vorticity and |grad zeta|^2."""
+        return self._eddy("get_eddy_diffusivity", nbins, fields)
 
     def pressure(self, rho=1.0, f=1e-5, ref=(0, 0)):
-        """The nonlinear-balance pressure of the current state (invert_pres.cpp:135-185), an [nx, ny] tensor, minus its value at the
-        reference point ref = (ref_x, ref_y): the element ref_x + nx * ref_y of the flattened field, as the reference indexes it."""
-        out = self.fop.empty_real()
-        check(lib().fb_model_get_pressure(self._h, rho, f, int(ref[0]), int(ref[1]), _ptr(out)))
-        return out
+        """The nonlinear-balance pressure of the current state (invert_pres.cpp:135-185) minus its value at the reference point
+        ref = (ref_x, ref_y): the element ref_x + nx * ref_y of the flattened [nx, ny] field, as the reference indexes it."""
+        return self._get("pressure", 1, rho, f, int(ref[0]), int(ref[1]))[0]
 
     def spectra(self):
         """The shell spectra and cascade fluxes of the current state, float64 [nshells, 10] (columns SPECTRA_COLUMNS): energy and
-        enstrophy spectra, advective transfers and fluxes, enstrophy dissipation per wavenumber shell."""
+        enstrophy spectra, advective transfers and fluxes, enstrophy dissipation per wavenumber shell of the whole domain."""
         t = self.torch
         table = t.empty((spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
-        check(lib().fb_model_get_spectra(self._h, _ptr(table)))
+        self._hand("get_spectra", table)
         return table
 
     def azimuthal(self, center="psi-min", nbins=None, dr=None, nmodes=4):
@@ -568,93 +487,71 @@ class Model:
         smallest psi), "vort-max" (of the largest zeta) or a fixed (xc, yc) [m]; nbins radial bins of the width dr [m] (defaults:
         dr = max(dx, dy), nbins = floor(min(Lx, Ly) / 2 / dr), at most 4096); table float64 [nbins, 12 + 2 nmodes] (columns
         AZIMUTHAL_COLUMNS, then Re, Im of the azimuthal wavenumbers 1 .. nmodes of zeta), center float64 [4] = xc, yc, flat index,
-        value; both on the GPU."""
+        value; both on the GPU, of the whole domain."""
         t = self.torch
         mode, xc, yc, nbins, dr = azimuthal_args(self.nx, self.ny, self.Lx, self.Ly, center, nbins, dr)
         table = t.empty((max(nbins, 0), 12 + 2 * max(int(nmodes), 0)), dtype=t.float64, device="cuda")
         cen = t.empty(4, dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
-        check(lib().fb_model_get_azimuthal(self._h, mode, xc, yc, nbins, dr, int(nmodes), _ptr(table), _ptr(cen)))
+        self._hand("get_azimuthal", mode, xc, yc, nbins, dr, int(nmodes), table, cen)
         return table, cen
 
     def set_tracer(self, c, kappa=0.0):
-        """Sets the passive tracer, an [nx, ny] field advected by the model's flow with the diffusivity kappa [m^2 s^-1] (it is stepped
-        beside the vorticity from now on); c=None removes it."""
-        if c is None:
-            check(lib().fb_model_set_tracer(self._h, None, 0.0))
-        else:
-            a = self._dev(c); check(lib().fb_model_set_tracer(self._h, _ptr(a), float(kappa))); self.fop.synchronize()
+        """Sets the passive tracer, a field advected by the model's flow with the diffusivity kappa [m^2 s^-1] (it is stepped beside
+        the vorticity from now on); c=None removes it."""
+        self._hand("set_tracer", self._dev(c), 0.0 if c is None else float(kappa))
 
-    def tracer(self):
-        out = self.fop.empty_real(); check(lib().fb_model_get_tracer(self._h, _ptr(out))); return out
+    def tracer(self): return self._get("tracer", 1)[0]
 
     def tracer_eddy_diffusivity(self, nbins=256, fields=False):
         """eddy_diffusivity() of the passive tracer, with its kappa in the place of nu; with fields=True also (c, |grad c|^2)."""
-        t = self.torch
-        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
-        c, g = (self.fop.empty_real(), self.fop.empty_real()) if fields else (None, None)
-        check(lib().fb_model_get_tracer_eddy_diffusivity(self._h, nbins, _ptr(table), _ptr(c) if fields else None, _ptr(g) if fields else None))
-        return (table, c, g) if fields else table
+        return self._eddy("get_tracer_eddy_diffusivity", nbins, fields)
 
     def set_particles(self, xy):
         """Sets the Lagrangian particles, float64 [n, 2] positions (x, y) [m] (numpy or torch), advected by the model's flow from now
-        on with the RK4 scheme of the step itself; xy=None removes them."""
-        if xy is None:
-            check(lib().fb_model_set_particles(self._h, None, 0))
-        else:
-            a = particles_dev(self.torch, xy)
-            check(lib().fb_model_set_particles(self._h, _ptr(a), int(a.shape[0]))); self.fop.synchronize()
+        on with the RK4 scheme of the step itself; xy=None removes them.  One rank only: on several ranks this and the three methods
+        below raise FftBaroError with the engine's message."""
+        a = None if xy is None else particles_dev(self.torch, xy)
+        self._hand("set_particles", a, 0 if a is None else int(a.shape[0]))
 
-    def particle_count(self):
-        n = C.c_int()
-        check(lib().fb_model_particle_count(self._h, C.byref(n)))
-        return n.value
+    def particle_count(self): return self._count("particle_count")
 
     def particles(self, wrap=False):
         """The particles' positions, a float64 [n, 2] tensor: unwrapped (a particle that left through one side keeps counting), or with
         wrap=True folded into [0, Lx) x [0, Ly)."""
         t = self.torch
         out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
-        check(lib().fb_model_get_particles(self._h, _ptr(out)))
-        self.fop.synchronize()
+        self._hand("get_particles", out)
         return wrap_positions(t, out, self.Lx, self.Ly) if wrap else out
 
     def sample(self, field, xy=None):
         """An [nx, ny] float32 field (numpy or torch: the vorticity, the tracer, W, the pressure ...) interpolated to the positions
         xy, float64 [n, 2], or to the particles (xy=None), by the particles' cubic Lagrange scheme: a float64 [n] tensor."""
         t = self.torch
+        self._one_rank("sample", None, None, 0, None)
         f = self._dev(field)
         a = self.particles() if xy is None else particles_dev(t, xy)
         out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()
-        check(lib().fb_model_sample(self._h, _ptr(f), _ptr(a), int(a.shape[0]), _ptr(out)))
-        self.fop.synchronize()
+        self._hand("sample", f, a, int(a.shape[0]), out)
         return out
 
     def set_tangent(self, dz):
-        """Sets the perturbation of the tangent-linear model, an [nx, ny] field carried along the evolving vorticity by the
-        linearisation of the step itself (it is stepped beside the vorticity from now on); dz=None removes it."""
-        if dz is None:
-            check(lib().fb_model_set_tangent(self._h, None))
-        else:
-            a = self._dev(dz); check(lib().fb_model_set_tangent(self._h, _ptr(a))); self.fop.synchronize()
+        """Sets the perturbation of the tangent-linear model, a field carried along the evolving vorticity by the linearisation of the
+        step itself (it is stepped beside the vorticity from now on); dz=None removes it.  One rank only: on several ranks this and the
+        four methods below raise FftBaroError with the engine's message."""
+        self._one_rank("set_tangent", None)
+        self._hand("set_tangent", self._dev(dz))
 
-    def tangent(self):
-        out = self.fop.empty_real(); check(lib().fb_model_get_tangent(self._h, _ptr(out))); return out
+    def tangent(self): return self._get("tangent", 1)[0]
 
     def tangent_norm(self, kind="enstrophy"):
         """The perturbation's norm, a float: "enstrophy" <dz^2> / 2 or "energy" <|grad dpsi|^2> / 2, summed in float64 on the GPU."""
-        t = self.torch
-        out = t.empty(1, dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes it on ITS stream
-        check(lib().fb_model_tangent_norm(self._h, tangent_kind(kind), _ptr(out)))
-        self.fop.synchronize()
+        out = self.torch.empty(1, dtype=self.torch.float64, device="cuda")
+        self._hand("tangent_norm", tangent_kind(kind), out)
         return float(out.item())
 
     def rescale_tangent(self, a):
         """dz *= a (a finite and not zero)"""
-        check(lib().fb_model_tangent_scale(self._h, float(a)))
+        self._call("tangent_scale", float(a))
 
     def lyapunov(self, steps, renorm_every, kind="enstrophy"):
         """(exponent [s^-1], growth factors): steps the model, renormalising the perturbation every renorm_every steps (lyapunov())."""
@@ -662,41 +559,74 @@ class Model:
 
     def record_adjoint(self, depth):
         """Turns the adjoint's tape on (depth >= 1: room for depth steps; every step from now on records its four stage states, and a
-        step call beyond depth is refused) or off (depth = 0, the tape freed).  Either way the tape starts empty."""
-        check(lib().fb_model_adjoint_record(self._h, int(depth)))
+        step call beyond depth is refused) or off (depth = 0, the tape freed).  Either way the tape starts empty.  One rank only: on
+        several ranks this and the five methods below raise FftBaroError with the engine's message."""
+        self._call("adjoint_record", int(depth))
 
-    def adjoint_recorded(self):
-        n = C.c_int()
-        check(lib().fb_model_adjoint_recorded(self._h, C.byref(n)))
-        return n.value
+    def adjoint_recorded(self): return self._count("adjoint_recorded")
 
     def set_adjoint(self, lam):
-        """Sets the adjoint variable, an [nx, ny] field (the gradient of a scalar of the state with respect to the vorticity, at the
-        time of the newest recorded step); lam=None removes it."""
-        if lam is None:
-            check(lib().fb_model_set_adjoint(self._h, None))
-        else:
-            a = self._dev(lam); check(lib().fb_model_set_adjoint(self._h, _ptr(a))); self.fop.synchronize()
+        """Sets the adjoint variable, a field (the gradient of a scalar of the state with respect to the vorticity, at the time of the
+        newest recorded step); lam=None removes it."""
+        self._one_rank("set_adjoint", None)
+        self._hand("set_adjoint", self._dev(lam))
 
-    def adjoint(self):
-        out = self.fop.empty_real(); check(lib().fb_model_get_adjoint(self._h, _ptr(out))); return out
+    def adjoint(self): return self._get("adjoint", 1)[0]
 
     def adjoint_back(self, n=1):
         """lam <- T^T lam over the last n recorded steps, newest first (the transpose of the tangent-linear step); they leave the tape."""
-        check(lib().fb_model_adjoint_back(self._h, int(n)))
+        self._call("adjoint_back", int(n))
 
     def singular_values(self, steps, iters, start):
-        """(sigmas, v): power iteration on T^T T over `steps` steps from the current state in the L2 norm (singular_values())."""
-        return singular_values(self, steps, iters, start)
+        """(sigmas, v): power iteration on T^T T over `steps` steps from the current state in the L2 norm (singular_values()); the
+        state is kept and put back through _STATE."""
+        self._one_rank("adjoint_record", int(steps))
+        return singular_values(self, steps, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]))
+
+
+class Model(ModelSurface):
+    """The main.cpp RK4 driver state (main.cpp:103-317) resident in HBM, fused stepping."""
+
+    _PREFIX, _STATE = "fb_model_", ("spectrum", "set_spectrum")      # (the spectrum restores every bit)
+
+    def __init__(self, nx, ny=None, Lx=600000.0, Ly=600000.0, nu=6.5, dt=3.0):
+        ny = ny or nx
+        self.fop = FftwfOperation(nx, ny, Lx, Ly)
+        self.torch = self.fop.torch
+        self.nx, self.ny, self.hy = nx, ny, ny // 2 + 1
+        self._shape = (nx, ny)
+        self.Lx, self.Ly = Lx, Ly
+        self.nu, self.dt = float(np.float32(nu)), float(np.float32(dt))
+        h = C.c_void_p()
+        check(lib().fb_model_create(C.byref(h), self.fop._h, nu, dt))
+        self._h = h
+
+    def close(self):
+        ModelSurface.close(self)
+        self.fop.close()
+
+    def _wait(self): self.fop.synchronize()
+
+    def use_graph(self, enable=True):
+        """hipGraph replay of the step; call under a non-default torch stream (after fop.use_current_stream())."""
+        self._call("use_graph", 1 if enable else 0)
+
+    KERNEL_CLASSES = ("k_col_strided_bwd4", "k_row_fused", "k_col_strided_fwd1", "k_col_mid")
+
+    def profile_steps(self, n):
+        """HIP-event time per kernel class over n steps: {class: (total_ms, launches)}."""
+        ms = (C.c_float * 4)(); cnt = (C.c_int * 4)()
+        self._call("profile_steps", n, ms, cnt)
+        return {k: (ms[i], cnt[i]) for i, k in enumerate(self.KERNEL_CLASSES)}
 
     def spectrum(self):
-        out = self.fop.empty_spec(); check(lib().fb_model_get_spectrum(self._h, _ptr(out))); return out
+        out = self.fop.empty_spec(); self._call("get_spectrum", _ptr(out)); return out
 
-    def set_spectrum(self, spec): check(lib().fb_model_set_spectrum(self._h, self.fop._spec(spec)))
+    def set_spectrum(self, spec): self._call("set_spectrum", self.fop._spec(spec))
 
     def info(self):
         a, b = C.c_size_t(), C.c_size_t()
-        check(lib().fb_model_info(self._h, C.byref(a), C.byref(b)))
+        self._call("info", C.byref(a), C.byref(b))
         return {"hbm_bytes": a.value, "alg_bytes_per_step": b.value}
 
 

@@ -22,6 +22,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import binding as B
+
 OP_COL_BWD, OP_XCHG_W4, OP_ROW, OP_XCHG_T, OP_COL_FWD, OP_COL_ALL_BWD = 1, 2, 3, 4, 5, 6
 
 
@@ -34,7 +36,6 @@ def plan(nx, ny, world):
     per rank; col_groups: the columns of each active column group (two where a stage is pipelined by column groups; a rank's active
     slab [rank*KA, (rank+1)*KA) is cut locally, group 0 its first columns); ops: one RK stage in issue order, as (kind, argument)
     with the meanings of FB_OP_* in csrc/fb_slab_driver.h.  Raises FftBaroError on a geometry the engine refuses."""
-    from . import binding as B
     L = B.lib()
     xl, ka, kf = C.c_int(), C.c_int(), C.c_int()
     B.check(L.fb_slab_geometry(nx, ny, world, C.byref(xl), C.byref(ka), C.byref(kf)))
@@ -102,17 +103,19 @@ class _DevMem:
         self.__cuda_array_interface__ = {"shape": (int(nfloats),), "typestr": "<f4", "data": (int(ptr), False), "version": 2}
 
 
-class EngineSlab:
+class EngineSlab(B.ModelSurface):
     """One rank of the engine-driven multi-GPU model (fb_slab_*).  transport:
        "rccl"  -- ncclCommInitRank with an id that rank 0 creates and torch.distributed broadcasts (the product path)
        "gloo"  -- torch.distributed point-to-point behind the callback transport (ranks may share one GPU: rehearsal)
        hub     -- an integer handle from `local_hub(world)`: all ranks are threads of this process (rehearsal)
        "null"  -- exchanges move nothing (wrong fields, right timing of the local passes)
-       None    -- world == 1"""
+       None    -- world == 1
+    The model surface is binding.ModelSurface's on this rank's rows [XL, ny]; its calls are collective: every rank makes them."""
+
+    _PREFIX, _STATE = "fb_slab_", ("vort_local", "set_vort_local")
 
     def __init__(self, nx, ny=None, Lx=600000.0, Ly=600000.0, nu=6.5, dt=3.0, rank=0, world=1, transport=None, dist=None):
         import torch
-        from . import binding as B
         ny = ny or nx
         self.torch, self.B, self.L = torch, B, B.lib()
         self.nx, self.ny, self.rank, self.world, self.dist = nx, ny, rank, world, dist
@@ -124,6 +127,7 @@ class EngineSlab:
         v = [C.c_int() for _ in range(7)]
         B.check(self.L.fb_slab_info(self._h, *[C.byref(x) for x in v]))
         self.XL, self.KA, self.KF, self.kyA0, self.kyF0, self.field_groups, self.row_chunks = [x.value for x in v]
+        self._shape = (self.XL, ny)
         self.col_groups = slab_col_groups(nx, ny, world)                                      # 2 entries: the stage is pipelined by column groups
         self._cb = None
         self.transport = "none"
@@ -213,223 +217,16 @@ class EngineSlab:
         self._cb = self.B.ALLTOALL_FN(alltoall)                               # keep the trampoline alive
         self.B.check(self.L.fb_slab_connect_callback(self._h, self._cb, None))
 
-    # -- model surface (this rank's rows)
-    def _rows(self, a):
-        t = self.torch
-        if isinstance(a, np.ndarray):
-            a = t.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
-        assert a.is_cuda and a.dtype == t.float32 and a.is_contiguous() and tuple(a.shape) == (self.XL, self.ny)
-        # the engine reads the buffer on ITS streams: whatever torch still has queued for it (a fill, a copy) must have landed
-        t.cuda.current_stream().synchronize()
-        return a
+    # -- model surface: the names this rank's rows have always gone by
+    set_vort_local, set_source_local, vort_local = B.ModelSurface.set_vort, B.ModelSurface.set_source, B.ModelSurface.vort
+    diag_local, okubo_weiss_local, pressure_local = B.ModelSurface.diag, B.ModelSurface.okubo_weiss, B.ModelSurface.pressure
+    set_tracer_local, tracer_local = B.ModelSurface.set_tracer, B.ModelSurface.tracer
 
-    def set_vort_local(self, rows):
-        a = self._rows(rows)
-        self.B.check(self.L.fb_slab_set_vort_local(self._h, C.c_void_p(a.data_ptr())))
-        self.synchronize()
-
-    def set_source_local(self, rows):
-        if rows is None:
-            self.B.check(self.L.fb_slab_set_source_local(self._h, None))
-        else:
-            a = self._rows(rows)
-            self.B.check(self.L.fb_slab_set_source_local(self._h, C.c_void_p(a.data_ptr())))
-            self.synchronize()
-
-    def step(self, n=1):
-        self.B.check(self.L.fb_slab_step(self._h, n))
-
-    def vort_local(self):
-        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
-        self.B.check(self.L.fb_slab_get_vort_local(self._h, C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def diag_local(self):
-        """This rank's rows of psi, u, v (the stage-0 record dumps, main.cpp:181-222)."""
-        t = self.torch
-        psi, u, v = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(3))
-        self.B.check(self.L.fb_slab_get_diag_local(self._h, C.c_void_p(psi.data_ptr()), C.c_void_p(u.data_ptr()), C.c_void_p(v.data_ptr())))
-        self.synchronize()
-        return psi, u, v
-
-    def okubo_weiss_local(self):
-        """This rank's rows of the Okubo-Weiss parameter and the filamentation time (fb_slab_get_okubo_weiss_local).  Collective."""
-        t = self.torch
-        w, tau = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2))
-        self.B.check(self.L.fb_slab_get_okubo_weiss_local(self._h, C.c_void_p(w.data_ptr()), C.c_void_p(tau.data_ptr())))
-        self.synchronize()
-        return w, tau
-
-    def eddy_diffusivity(self, nbins=256, fields=False):
-        """The effective eddy diffusivity table of the whole domain, float64 [nbins, 9] (fb_slab_get_eddy_diffusivity), the same on
-        every rank; with fields=True also this rank's rows (zeta, grad2), [XL, ny].  Collective."""
-        t = self.torch
-        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
-        zeta, g = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2)) if fields else (None, None)
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        self.B.check(self.L.fb_slab_get_eddy_diffusivity(self._h, nbins, ptr(table), ptr(zeta), ptr(g)))
-        self.synchronize()
-        return (table, zeta, g) if fields else table
-
-    def pressure_local(self, rho=1.0, f=1e-5, ref=(0, 0)):
-        """This rank's rows of the nonlinear-balance pressure (fb_slab_get_pressure_local), minus its value at the reference point
-        ref = (ref_x, ref_y) of the whole domain (flat element ref_x + nx * ref_y).  Collective."""
-        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
-        self.B.check(self.L.fb_slab_get_pressure_local(self._h, rho, f, int(ref[0]), int(ref[1]), C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def spectra(self):
-        """The shell spectra and cascade fluxes of the whole domain, float64 [nshells, 10] (fb_slab_get_spectra; columns
-        binding.SPECTRA_COLUMNS), the same on every rank.  Collective."""
-        t = self.torch
-        table = t.empty((self.B.spectra_shells(self.nx, self.ny, self.Lx, self.Ly), 10), dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes the table on ITS stream
-        self.B.check(self.L.fb_slab_get_spectra(self._h, C.c_void_p(table.data_ptr())))
-        self.synchronize()
-        return table
-
-    def azimuthal(self, center="psi-min", nbins=None, dr=None, nmodes=4):
-        """(table, center): the azimuthal means of the whole domain about a vortex centre (fb_slab_get_azimuthal; arguments and
-        columns as binding.Model.azimuthal), the same on every rank.  Collective."""
-        t = self.torch
-        mode, xc, yc, nbins, dr = self.B.azimuthal_args(self.nx, self.ny, self.Lx, self.Ly, center, nbins, dr)
-        table = t.empty((max(nbins, 0), 12 + 2 * max(int(nmodes), 0)), dtype=t.float64, device="cuda")
-        cen = t.empty(4, dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
-        self.B.check(self.L.fb_slab_get_azimuthal(self._h, mode, xc, yc, nbins, dr, int(nmodes), C.c_void_p(table.data_ptr()), C.c_void_p(cen.data_ptr())))
-        self.synchronize()
-        return table, cen
-
-    def set_tracer_local(self, rows, kappa=0.0):
-        """This rank's rows of the passive tracer and its diffusivity (fb_slab_set_tracer_local); rows=None removes the tracer.
-        Collective."""
-        if rows is None:
-            self.B.check(self.L.fb_slab_set_tracer_local(self._h, None, 0.0))
-        else:
-            a = self._rows(rows)
-            self.B.check(self.L.fb_slab_set_tracer_local(self._h, C.c_void_p(a.data_ptr()), float(kappa)))
-        self.synchronize()
-
-    def tracer_local(self):
-        """This rank's rows of the passive tracer (fb_slab_get_tracer_local).  Collective."""
-        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
-        self.B.check(self.L.fb_slab_get_tracer_local(self._h, C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def tracer_eddy_diffusivity(self, nbins=256, fields=False):
-        """eddy_diffusivity() of the passive tracer, with its kappa in the place of nu (fb_slab_get_tracer_eddy_diffusivity); with
-        fields=True also this rank's rows (c, |grad c|^2).  Collective."""
-        t = self.torch
-        table = t.empty((nbins, 9), dtype=t.float64, device="cuda")
-        c, g = (t.empty((self.XL, self.ny), dtype=t.float32, device="cuda") for _ in range(2)) if fields else (None, None)
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None
-        t.cuda.current_stream().synchronize()                   # the engine writes the table on ITS stream
-        self.B.check(self.L.fb_slab_get_tracer_eddy_diffusivity(self._h, nbins, ptr(table), ptr(c), ptr(g)))
-        self.synchronize()
-        return (table, c, g) if fields else table
-
-    def set_particles(self, xy):
-        """The Lagrangian particles of binding.Model.set_particles (fb_slab_set_particles); xy=None removes them.  One rank only: on
-        world > 1 this and the three methods below raise FftBaroError with the engine's message."""
-        if xy is None:
-            self.B.check(self.L.fb_slab_set_particles(self._h, None, 0))
-        else:
-            a = self.B.particles_dev(self.torch, xy)
-            self.B.check(self.L.fb_slab_set_particles(self._h, C.c_void_p(a.data_ptr()), int(a.shape[0])))
-        self.synchronize()
-
-    def particle_count(self):
-        n = C.c_int()
-        self.B.check(self.L.fb_slab_particle_count(self._h, C.byref(n)))
-        return n.value
-
-    def particles(self, wrap=False):
-        """The particles' positions, float64 [n, 2], unwrapped or (wrap=True) folded into the domain (fb_slab_get_particles)."""
-        t = self.torch
-        out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes them on ITS stream
-        self.B.check(self.L.fb_slab_get_particles(self._h, C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return self.B.wrap_positions(t, out, self.Lx, self.Ly) if wrap else out
-
-    def sample(self, field, xy=None):
-        """An [nx, ny] float32 field interpolated to the positions xy, float64 [n, 2], or to the particles (fb_slab_sample)."""
-        t = self.torch
-        if self.world > 1:                                      # (before any buffer is shaped for one rank)
-            self.B.check(self.L.fb_slab_sample(self._h, None, None, 0, None))      # raises with the engine's message
-        f = self._rows(field)
-        a = self.particles() if xy is None else self.B.particles_dev(t, xy)
-        out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()
-        self.B.check(self.L.fb_slab_sample(self._h, C.c_void_p(f.data_ptr()), C.c_void_p(a.data_ptr()), int(a.shape[0]), C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def set_tangent(self, dz):
-        """The perturbation of the tangent-linear model of binding.Model.set_tangent (fb_slab_set_tangent); dz=None removes it.  One
-        rank only: on world > 1 this and the four methods below raise FftBaroError with the engine's message."""
-        if dz is None or self.world > 1:                        # (before any buffer is shaped for one rank)
-            self.B.check(self.L.fb_slab_set_tangent(self._h, None))
-        else:
-            a = self._rows(dz)
-            self.B.check(self.L.fb_slab_set_tangent(self._h, C.c_void_p(a.data_ptr())))
-        self.synchronize()
-
-    def tangent(self):
-        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
-        self.B.check(self.L.fb_slab_get_tangent(self._h, C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def tangent_norm(self, kind="enstrophy"):
-        t = self.torch
-        out = t.empty(1, dtype=t.float64, device="cuda")
-        t.cuda.current_stream().synchronize()                   # the engine writes it on ITS stream
-        self.B.check(self.L.fb_slab_tangent_norm(self._h, self.B.tangent_kind(kind), C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return float(out.item())
-
-    def rescale_tangent(self, a):
-        self.B.check(self.L.fb_slab_tangent_scale(self._h, float(a)))
-
-    def lyapunov(self, steps, renorm_every, kind="enstrophy"):
-        return self.B.lyapunov(self, steps, renorm_every, kind)
-
-    def record_adjoint(self, depth):
-        """The adjoint's tape of binding.Model.record_adjoint (fb_slab_adjoint_record).  One rank only: on world > 1 this and the five
-        methods below raise FftBaroError with the engine's message."""
-        self.B.check(self.L.fb_slab_adjoint_record(self._h, int(depth)))
-
-    def adjoint_recorded(self):
-        n = C.c_int()
-        self.B.check(self.L.fb_slab_adjoint_recorded(self._h, C.byref(n)))
-        return n.value
-
-    def set_adjoint(self, lam):
-        if lam is None or self.world > 1:                       # (before any buffer is shaped for one rank)
-            self.B.check(self.L.fb_slab_set_adjoint(self._h, None))
-        else:
-            a = self._rows(lam)
-            self.B.check(self.L.fb_slab_set_adjoint(self._h, C.c_void_p(a.data_ptr())))
-        self.synchronize()
-
-    def adjoint(self):
-        out = self.torch.empty((self.XL, self.ny), dtype=self.torch.float32, device="cuda")
-        self.B.check(self.L.fb_slab_get_adjoint(self._h, C.c_void_p(out.data_ptr())))
-        self.synchronize()
-        return out
-
-    def adjoint_back(self, n=1):
-        self.B.check(self.L.fb_slab_adjoint_back(self._h, int(n)))
-
-    def singular_values(self, steps, iters, start):
-        """binding.singular_values on one rank; the state is kept and put back as a field of rows (vort_local / set_vort_local)"""
+    def _one_rank(self, name, *nulls):
         if self.world > 1:
-            self.record_adjoint(steps)                          # raises with the engine's message
-        return self.B.singular_values(self, steps, iters, start, save=self.vort_local, restore=self.set_vort_local)
+            self._call(name, *nulls)                            # raises with the engine's message
+
+    def _wait(self): self.synchronize()
 
     def transport_selftest(self, count=1 << 18):
         """A known pattern of world*count floats through the connected transport; returns the number of wrong words (0 = links fine).
@@ -448,36 +245,18 @@ class EngineSlab:
         return {"name": name.value.decode(), "comm_ranks": v[0].value, "comm_rank": v[1].value, "comm_device": v[2].value,
                 "hip_device": v[3].value}
 
-    def time_steps(self, n):
-        ms = C.c_float()
-        self.B.check(self.L.fb_slab_time_steps(self._h, n, C.byref(ms)))
-        return ms.value
-
     def synchronize(self):
         self.B.check(self.L.fb_slab_synchronize(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.L.fb_slab_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def local_hub(world):
     """Handle of an in-process rendezvous for `world` EngineSlab ranks driven by `world` threads (one GPU)."""
-    from . import binding as B
     h = C.c_void_p()
     B.check(B.lib().fb_local_hub_create(C.byref(h), world))
     return h.value
 
 
 def local_hub_destroy(hub):
-    from . import binding as B
     B.lib().fb_local_hub_destroy(C.c_void_p(hub))
 
 
