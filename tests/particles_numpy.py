@@ -1,6 +1,8 @@
 """float64 numpy reference of the Lagrangian particles: the 4-point cubic Lagrange interpolation of include/fftbaro.h
 (fb_model_sample), the RK4 of particles in given stage velocities, and ref_numpy.Model64 extended by particles that are advanced
 with the velocity of its own stage states, coupled stage by stage.  Used ONLY by tests."""
+from collections import namedtuple
+
 import numpy as np
 
 from ref_numpy import Model64
@@ -143,3 +145,164 @@ def grid_points(nx, ny, lx, ly, n, seed=7):
     xy = ij * np.array([dx, dy])
     keep = (xy[:, 0] / dx == ij[:, 0]) & (xy[:, 1] / dy == ij[:, 1])
     return xy[keep][:n]
+
+
+# ---- the particles' path matrix: inputs, sensitivity probes, float32 restatement (tests/test_gpu_particle_paths.py) ----
+PARTICLE_SEED = 7
+NPART = 1000
+PROBES = ("masked", "base")
+
+
+def particle_inputs(nx, ny, vort_noise, seed=PARTICLE_SEED, make_field=None):
+    """(vort, source, xy): the vorticity and the source of tracer_numpy.noisy_inputs (the elliptic vortex plus never-dealiased white noise
+    of the amplitude vort_noise, a white-noise source of 1e-9 s^-2) and seed_positions(nx, ny, 600000, 600000, 1000, seed).  To be run
+    with nu = tracer_numpy.RECIPE_NU and dt = tracer_numpy.recipe_dt(nx, ny); the source stays on."""
+    from tracer_numpy import noisy_inputs
+    vort, _, source = noisy_inputs(nx, ny, vort_noise, make_field=make_field)
+    return vort, source, seed_positions(nx, ny, 600000.0, 600000.0, NPART, seed)
+
+
+class ProbedParticleModel64(ParticleModel64):
+    """ParticleModel64 that carries, beside the true particles, two sets whose stage velocities at the stages 1 to 3 are formed wrongly:
+      "masked"  from the stage state times the dealiasing mask: the stage array read at a masked mode (the engine never writes it there);
+      "base"    from the base state v0: the base read everywhere, the stage array never picked.
+    All three ride on ONE vorticity trajectory, whose step is Model64's formula for formula (the stage velocity of the true particles is
+    the u, v that the tendency forms anyway), so a large grid costs one float64 run.  xy is the true set, probe[name] a wrong one."""
+
+    def set_particles(self, xy):
+        super().set_particles(xy)
+        self.probe = {k: self.xy.copy() for k in PROBES}
+
+    def _tendency_uv(self, vc):
+        lv = vc * self.lap
+        dzdx = self._c2r(self.ikx * vc)
+        dzdy = self._c2r(self.iky * vc)
+        psi = vc / self.lapi
+        u = -self._c2r(self.iky * psi)
+        v = self._c2r(self.ikx * psi)
+        t = -u * dzdx - v * dzdy + self.src
+        return (np.fft.rfft2(t) + lv * self.nu) * self.mask, u, v
+
+    def step(self, n=1):
+        dt = self.dt
+        h = (None, dt / 2, dt / 2, dt)
+        for _ in range(n):
+            v0 = self.vc
+            sets = {"true": self.xy, **self.probe}
+            x = dict(sets)
+            acc = {k: 0.0 for k in sets}
+            ks, vs = [], v0
+            for s in range(4):
+                k, u, v = self._tendency_uv(vs)
+                ks.append(k)
+                if s == 0:
+                    uv = {name: (u, v) for name in sets}
+                    base = (u, v)
+                else:
+                    uv = {"true": (u, v), "masked": self.velocity(vs * self.mask), "base": base}
+                for name in sets:
+                    p = sample_uv(uv[name][0], uv[name][1], x[name], self.lx, self.ly)
+                    acc[name] = p if s == 0 else (acc[name] + (2 * p if s < 3 else p))
+                    if s < 3:
+                        x[name] = sets[name] + h[s + 1] * p
+                del uv, u, v
+                if s < 3:
+                    vs = v0 + k * h[s + 1]
+            self.vc = v0 + (ks[0] + 2 * ks[1] + 2 * ks[2] + ks[3]) * dt / 6
+            self.xy = sets["true"] + (dt / 6) * acc["true"]
+            self.probe = {k: sets[k] + (dt / 6) * acc[k] for k in PROBES}
+
+
+def particle_model(nx, ny, vort, source, xy, cls=ParticleModel64):
+    """the float64 reference (cls=ProbedParticleModel64: with the two probes) loaded with the path matrix's inputs"""
+    from tracer_numpy import RECIPE_NU, recipe_dt
+    m = cls(nx, ny, nu=RECIPE_NU, dt=recipe_dt(nx, ny))
+    m.set_vort(vort)
+    m.src = np.asarray(source).astype(np.float64)
+    m.set_particles(xy)
+    return m
+
+
+def float32_positions(nx, ny, vort, source, xy, steps, ref):
+    """The positions of the ordinary float32 evaluation of the coupled run: the model stepped with torch's float32 / complex64 FFTs on
+    the CPU in the formula order of Model64 (ref supplies the tables, nu and dt), u and v float32 fields, the interpolation and the
+    positions in float64, as the engine does.  What a correct float32 engine can be expected to reach."""
+    import torch
+    f, c64 = torch.float32, torch.complex64
+    ikx, iky = torch.from_numpy(ref.ikx).to(c64), torch.from_numpy(ref.iky).to(c64)
+    lap, lapi, mask = (torch.from_numpy(a).to(f) for a in (ref.lap, ref.lapi, ref.mask))
+    src = torch.from_numpy(np.asarray(source, dtype=np.float32))
+    nu, dt = float(np.float32(ref.nu)), float(np.float32(ref.dt))
+    lx, ly = ref.lx, ref.ly
+
+    def c2r(a):
+        return torch.fft.irfft2(a, s=(nx, ny))
+
+    def tend(vc, x):
+        psi = vc / lapi
+        u, v = -c2r(iky * psi), c2r(ikx * psi)
+        tv = -u * c2r(ikx * vc) - v * c2r(iky * vc) + src
+        return (torch.fft.rfft2(tv) + vc * lap * nu) * mask, sample_uv(u.numpy(), v.numpy(), x, lx, ly)
+    vc = torch.fft.rfft2(torch.from_numpy(np.asarray(vort, dtype=np.float32)))
+    x0 = np.array(xy, dtype=np.float64).reshape(-1, 2)
+    for _ in range(steps):
+        k1, p1 = tend(vc, x0)
+        k2, p2 = tend(vc + k1 * (dt / 2), x0 + (dt / 2) * p1)
+        k3, p3 = tend(vc + k2 * (dt / 2), x0 + (dt / 2) * p2)
+        k4, p4 = tend(vc + k3 * dt, x0 + dt * p3)
+        vc = vc + (k1 + 2 * k2 + 2 * k3 + k4) * dt / 6
+        x0 = x0 + (dt / 6) * (((p1 + 2 * p2) + 2 * p3) + p4)
+    return x0
+
+
+def max_shift(a, b):
+    """max |a - b| over particles and both coordinates, in metres"""
+    return float(np.max(np.abs(np.asarray(a, dtype=np.float64) - np.asarray(b, dtype=np.float64))))
+
+
+def path_figures(nx, ny, vort_noise, steps, progress=None):
+    """One float64 run of a case with both probes, and its float32 restatement: a dict of the final float64 positions `xy`, the final
+    float64 vorticity `vort`, `f32` (the float32 figure), `masked` and `base` (the probes' shifts), `moved` (all max |.| in metres) and
+    `finite`."""
+    vort, source, xy = particle_inputs(nx, ny, vort_noise)
+    m = particle_model(nx, ny, vort, source, xy, cls=ProbedParticleModel64)
+    for k in range(steps):
+        m.step(1)
+        if progress:
+            progress(k + 1)
+    x32 = float32_positions(nx, ny, vort, source, xy, steps, m)
+    return {"xy": m.xy, "vort": m.vort(), "f32": max_shift(x32, m.xy), "masked": max_shift(m.probe["masked"], m.xy),
+            "base": max_shift(m.probe["base"], m.xy), "moved": max_shift(m.xy, xy), "finite": bool(np.isfinite(m.xy).all())}
+
+
+# The path matrix: one row per grid class of the engine, the grids, noise and step counts of tracer_numpy.PATH_CASES.
+# f32: max |X_f32 - X_64| of float32_positions against the float64 run; the bar of the GPU test is BAR_FACTOR * f32 (the factor is the
+# margin for the engine's FFT factorisations and operation order, which differ from torch's; the tracer's suite allows 40 on the same
+# grounds, 1e-5 against 2.5e-7).  masked / base: the shifts of the two probes of ProbedParticleModel64; moved: the largest displacement.
+# All in metres, measured on the CPU, never taken from the engine.  Conditions (tests/test_particles_cpu.py): each probe >= PROBE_FACTOR
+# bars, moved >= MOVED_FACTOR bars, every position finite.  fixture: the float64 run takes over 20 s, so the positions and the figures are
+# read from tests/golden (tests/golden/make_particle_fixtures.py); the others run live.
+ParticleCase = namedtuple("ParticleCase", "nx ny vort_noise steps fixture f32 masked base moved what")
+BAR_FACTOR, PROBE_FACTOR, MOVED_FACTOR = 10.0, 10.0, 100.0
+PATH_CASES = (
+    ParticleCase(256, 256, 3e-2, 5, False, 0.000391, 257, 60, 2.66e+03, "ZA/ZB read in place (N2 = 16 < 32), plain row kernels"),
+    ParticleCase(192, 192, 3e-2, 5, False, 0.000545, 304, 91.5, 2.97e+03, "ZA/ZB read in place; k_row3; N1 = 24, N2 = 8"),
+    ParticleCase(3072, 64, 3e-2, 5, False, 7.27e-05, 15.5, 6.44, 489, "k_tracer_vstate_tm at N1 = 24, N2 = 128"),
+    ParticleCase(1024, 64, 3e-2, 5, False, 0.000429, 98.2, 115, 2.59e+03, "k_tracer_vstate_tm at N2 = 32; the slab's entry points"),
+    ParticleCase(4096, 64, 3e-2, 5, False, 5.09e-05, 7.51, 3.04, 304, "k_tracer_vstate_tm, N1 = N2 = 64; the three-kernel x pass (live Nyquist column)"),
+    ParticleCase(8192, 64, 3e-2, 12, False, 5.32e-05, 3.5, 3.61, 421, "k_tracer_vstate_tm, N1 = 128, N2 = 64"),
+    ParticleCase(16384, 64, 3e-2, 56, True, 0.000159, 3.73, 2.32, 852, "k_tracer_vstate_tm, N1 = N2 = 128"),
+    ParticleCase(64, 4096, 3e-2, 5, False, 5.35e-05, 7.73, 5.19, 335, "ZA/ZB read in place; ROW_INV through k_rowq (FB_ROWQ=0: k_row8)"),
+    ParticleCase(64, 8192, 3e-2, 12, False, 4.81e-05, 5.29, 2.41, 425, "ZA/ZB read in place; ROW_INV through k_rowh<1>"),
+    ParticleCase(128, 16384, 3e-2, 56, True, 0.000309, 5.31, 3.11, 851, "ZA/ZB read in place; ROW_INV through k_rowh<2>"),
+    ParticleCase(4096, 4096, 3e-2, 3, True, 2.22e-05, 2.98, 2.03, 185, "XP_FULL1: k_tracer_vstate_full at nsub = 1; ROW_INV through k_rowq"),
+    ParticleCase(8192, 8192, 3e-2, 2, True, 6.47e-06, 0.369, 0.196, 58.6, "XP_FULL2: k_tracer_vstate_full at nsub = 2; ROW_INV through k_rowh<1>"),
+)
+
+
+def path_case(nx, ny):
+    return [k for k in PATH_CASES if (k.nx, k.ny) == (nx, ny)][0]
+
+
+def fixture_name(case):
+    return "particles_%dx%d_step%d.npz" % (case.nx, case.ny, case.steps)

@@ -1,13 +1,16 @@
 """CPU tests of the float64 reference of the Lagrangian particles (tests/particles_numpy.py): the interpolation that
-fb_model_sample is tested against, and the coupled RK4 of ParticleModel64.  No GPU."""
+fb_model_sample is tested against, the coupled RK4 of ParticleModel64, and the conditions on the particles' path matrix
+(particles_numpy.PATH_CASES, tests/test_gpu_particle_paths.py).  No GPU."""
 import os
 import sys
 
 import numpy as np
+import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-if HERE not in sys.path:
-    sys.path.insert(0, HERE)
+for p in (HERE, os.path.join(os.path.dirname(HERE), "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
 
 import particles_numpy as P  # noqa: E402
 from tracer_numpy import cellular_flow  # noqa: E402
@@ -116,3 +119,85 @@ def test_cellular_flow_keeps_psi_at_the_particle():
     assert moved > 1000.0
     assert drift <= bound
     assert bound < 1e-3 * amp                                   # the bound itself is tight: a thousandth of psi's range
+
+
+# ---- the path matrix ----
+def test_path_matrix_has_the_tracers_grids():
+    import tracer_numpy as T
+    assert [(k.nx, k.ny) for k in P.PATH_CASES] == [(k.nx, k.ny) for k in T.PATH_CASES]
+    assert len(P.PATH_CASES) == 12
+    for k in P.PATH_CASES:
+        assert 2 <= k.steps <= 56 and k.what
+
+
+def test_probes_ride_on_the_unmodified_run():
+    """ProbedParticleModel64 at 96 x 64, 3 steps of the path matrix's inputs: its vorticity is Model64's and its true particles are
+    ParticleModel64's, bit for bit (the probes change no state of the run), both probes move the particles, and they differ from each
+    other; the positions hold grid points, first and last cells and points 3 domain lengths away"""
+    from ref_numpy import Model64
+    import tracer_numpy as T
+    nx, ny, steps = 96, 64, 3
+    vort, source, xy = P.particle_inputs(nx, ny, 3e-2)
+    assert xy.shape == (P.NPART, 2) and xy.dtype == np.float64
+    cell = np.floor(xy / (P.widen(600000.0) / np.array([nx, ny]))).astype(np.int64)
+    for ax, n in ((0, nx), (1, ny)):
+        assert (cell[:, ax] == 0).any() and (cell[:, ax] == n - 1).any() and (np.abs(xy[:, ax]) > 2.5 * 600000.0).any()
+    assert np.array_equal(xy[:6], P.grid_points(nx, ny, 600000.0, 600000.0, 8, P.PARTICLE_SEED)[:6])
+    m = P.particle_model(nx, ny, vort, source, xy, cls=P.ProbedParticleModel64)
+    r = P.particle_model(nx, ny, vort, source, xy)
+    b = Model64(nx, ny, nu=T.RECIPE_NU, dt=T.recipe_dt(nx, ny))
+    b.set_vort(vort)
+    b.src = source.astype(np.float64)
+    for q in (m, r, b):
+        q.step(steps)
+    assert np.array_equal(m.vc, b.vc) and np.array_equal(r.vc, b.vc)
+    assert np.array_equal(m.xy, r.xy)
+    shifts = {k: P.max_shift(m.probe[k], m.xy) for k in P.PROBES}
+    print("probes at %dx%d, %d steps: %s; apart by %.3g m" % (nx, ny, steps, shifts, P.max_shift(m.probe["masked"], m.probe["base"])))
+    assert all(v > 1.0 for v in shifts.values())
+    assert P.max_shift(m.probe["masked"], m.probe["base"]) > 1.0
+
+
+def _check_conditions(case, f32, masked, base, moved, finite):
+    bar = P.BAR_FACTOR * f32
+    print("%dx%d, noise %g, %d steps: float32 %.3g m, bar %.3g m, probes %.3g (masked) / %.3g (base) m, moved %.3g m"
+          % (case.nx, case.ny, case.vort_noise, case.steps, f32, bar, masked, base, moved))
+    assert finite
+    assert f32 > 0
+    assert masked >= P.PROBE_FACTOR * bar and base >= P.PROBE_FACTOR * bar
+    assert moved >= P.MOVED_FACTOR * bar
+    for got, row in ((f32, case.f32), (masked, case.masked), (base, case.base), (moved, case.moved)):
+        assert 0.5 <= got / row <= 2.0, (got, row)                  # a stale row of the table fails
+    # and the row's own figures, which the GPU test of a live case takes its bar from, meet the conditions as well
+    assert min(case.masked, case.base) >= P.PROBE_FACTOR * P.BAR_FACTOR * case.f32 and case.moved >= P.MOVED_FACTOR * P.BAR_FACTOR * case.f32
+
+
+LIVE_CASES = [k for k in P.PATH_CASES if not k.fixture]
+FIXTURE_CASES = [k for k in P.PATH_CASES if k.fixture]
+
+
+@pytest.mark.parametrize("case", LIVE_CASES, ids=["%dx%d" % (k.nx, k.ny) for k in LIVE_CASES])
+def test_path_case_conditions_live(case):
+    """The conditions on the inputs of the GPU path matrix, for every case whose float64 run takes under about 20 s: one float64 run
+    with both probes and the float32 restatement.  The bar is 10 x the float32 figure; each probe (stage velocities at the stages 1 to
+    3 from the stage state times the mask; from the base) shifts the float64 positions by >= 10 bars; the particles moved by >= 100
+    bars; every position is finite; the figures are those of the case's row within a factor 2."""
+    r = P.path_figures(case.nx, case.ny, case.vort_noise, case.steps)
+    _check_conditions(case, r["f32"], r["masked"], r["base"], r["moved"], r["finite"])
+
+
+@pytest.mark.parametrize("case", FIXTURE_CASES, ids=["%dx%d" % (k.nx, k.ny) for k in FIXTURE_CASES])
+def test_path_case_conditions_stored(case):
+    """the same conditions for the slow cases, from the figures that tests/golden/make_particle_fixtures.py stored with the float64
+    positions; the stored parameters are the case's and the fixture is small"""
+    import tracer_numpy as T
+    path = os.path.join(HERE, "golden", P.fixture_name(case))
+    assert os.path.getsize(path) <= 64 * 1024
+    G = np.load(path)
+    assert (int(G["seed"]), float(G["vort_noise"]), int(G["steps"])) == (P.PARTICLE_SEED, case.vort_noise, case.steps)
+    assert (float(G["dt"]), float(G["nu"])) == (T.recipe_dt(case.nx, case.ny), T.RECIPE_NU)
+    xy = G["xy"]
+    assert xy.shape == (P.NPART, 2) and xy.dtype == np.float64
+    x0 = P.seed_positions(case.nx, case.ny, 600000.0, 600000.0, P.NPART, int(G["seed"]))
+    assert abs(P.max_shift(xy, x0) / float(G["moved"]) - 1) <= 1e-12
+    _check_conditions(case, float(G["f32"]), float(G["shift_masked"]), float(G["shift_base"]), float(G["moved"]), bool(np.isfinite(xy).all()))
