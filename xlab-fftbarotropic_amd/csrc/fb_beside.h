@@ -35,14 +35,12 @@ static int stage_vstate(fb_model *m, int g, bool staged, cf *vx, const cf **v0, 
     const ColGroup &G = c->grp[g];
     const SpecCoef coef = make_coef(c);
     *v0 = m->gb[g].ZA; *v1 = staged ? m->gb[g].ZB : m->gb[g].ZA;
-    if (m->xpass != XP_COLS)
-        hipLaunchKernelGGL(k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, c->stream, coef, *v0, *v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
-    else if (state_tm(c))
-        hipLaunchKernelGGL(k_tracer_vstate_tm, dim3(grid_for(c, grp_elems(c, G))), dim3(256), 0, c->stream, coef, *v0, *v1, vx, G.ncols, c->N1, c->N2, G.ky0);
+    int rc;
+    if (m->xpass != XP_COLS) rc = launch(c, k_tracer_vstate_full, dim3(c->max_wg), dim3(256), 0, coef, *v0, *v1, vx, c->P, c->N1, c->N2, (c->ny / 2) / 8, (int)m->xpass);
+    else if (state_tm(c)) rc = launch_n(c, k_tracer_vstate_tm, grp_elems(c, G), coef, *v0, *v1, vx, G.ncols, c->N1, c->N2, G.ky0);
     else return FB_OK;
-    HIPCHK(hipGetLastError());
     *v0 = *v1 = vx;
-    return FB_OK;
+    return rc;
 }
 
 // The advective tendency r2c(J(a; psi of b)) of an RK stage through record_advect, at the top of the step's stage `stage`; a, b: a
@@ -63,10 +61,7 @@ static int beside_advect(fb_model *m, fb_slab *s, int stage, const Beside *a, co
             if (f[k]) { p[k][0] = f[k]->c0[g]; p[k][1] = staged ? f[k]->c1[g] : f[k]->c0[g]; }
             else if (int r = stage_vstate(m, g, staged, z + 2 * n, &p[k][0], &p[k][1])) return r;
         }
-        hipLaunchKernelGGL(k_advect_deriv, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, coef, p[0][0], p[0][1], p[1][0], p[1][1], z, (long)n, G.ncols, c->N1,
-                           c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
+        return launch_n(c, k_advect_deriv, n / 2, coef, p[0][0], p[0][1], p[1][0], p[1][1], z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
     };
     return record_advect(m, s, fill);
 }
@@ -81,16 +76,12 @@ template <int NJ> static int beside_update_nj(fb_model *m, fb_slab *s, int stage
         const ColGroup &G = c->grp[g];
         const int ncr = 16 * G.nct_active;
         if (grp_elems(c, G) == 0 || ncr == 0) continue;
-        const dim3 grid(grid_for(c, (size_t)c->nx * ncr / 2)), blk(256);
         const cf *jh = advect_out(m, s, g), *ja = NJ == 2 ? j1[g] : jh, *jb = NJ == 2 ? jh : nullptr;     // NJ == 1: the second is never read
         cf *c0 = f.c0[g], *c1 = f.c1[g], *ac = f.acc[g];
-        switch (stage) {
-        case 0: hipLaunchKernelGGL((k_beside_update<0, NJ>), grid, blk, 0, c->stream, coef, ja, jb, c0, c1, ac, kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 1: hipLaunchKernelGGL((k_beside_update<1, NJ>), grid, blk, 0, c->stream, coef, ja, jb, c0, c1, ac, kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        case 2: hipLaunchKernelGGL((k_beside_update<2, NJ>), grid, blk, 0, c->stream, coef, ja, jb, c0, c1, ac, kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        default: hipLaunchKernelGGL((k_beside_update<3, NJ>), grid, blk, 0, c->stream, coef, ja, jb, c0, c1, ac, kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0); break;
-        }
-        HIPCHK(hipGetLastError());
+        const int rc = dispatch<4>(stage, [&](auto S) {
+            return launch_n(c, k_beside_update<S(), NJ>, (size_t)c->nx * ncr / 2, coef, ja, jb, c0, c1, ac, kappa, m->dt, G.ncols, ncr, c->N1, c->N2, G.ky0);
+        });
+        if (rc) return rc;
     }
     return FB_OK;
 }
@@ -167,66 +158,36 @@ static int tracer_in(fb_model *m, fb_slab *s, const float *d_rows, float kappa)
     return FB_OK;
 }
 
-static int kappa_check(const char *fn, float kappa)
+// collective on a slab of several ranks, as fb_slab_set_vort_local
+static int set_tracer(const Call &k, const float *d_rows, float kappa)
 {
-    if (!(kappa >= 0.0f) || !std::isfinite(kappa)) return fail(FB_EINVAL, std::string(fn) + ": kappa must be finite and >= 0");
-    return FB_OK;
+    if (!(kappa >= 0.0f) || !std::isfinite(kappa)) return refuse(k, "kappa must be finite and >= 0");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return tracer_in(k.m, k.s, d_rows, kappa);
 }
+extern "C" int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa) { return set_tracer(on_model("fb_model_set_tracer", m), d_c_real, kappa); }
+extern "C" int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa) { return set_tracer(on_slab("fb_slab_set_tracer_local", s), d_rows, kappa); }
 
-extern "C" int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa)
+// the real field of a field stepped beside the vorticity (the model's member `f`: its base arrays, in the 3-pass layout), as the
+// vorticity's own record
+static int get_beside(const Call &k, unsigned needs, Beside fb_model::*f, float *d_rows)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_set_tracer: NULL model");
-    int rc;
-    if ((rc = kappa_check("fb_model_set_tracer", kappa))) return rc;
-    NEED_SINGLE(m->c);
-    return tracer_in(m, nullptr, d_c_real, kappa);
+    if (!d_rows) return refuse(k, "NULL output");
+    if (int rc = enter(k, needs)) return rc;
+    return record(k.m, k.s, REC_VORT, d_rows, nullptr, (k.m->*f).c0);
 }
+static int get_tracer(const Call &k, float *d_rows) { return get_beside(k, NEED_TRANSPORT | NEED_TRACER, &fb_model::tr, d_rows); }
+extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real) { return get_tracer(on_model("fb_model_get_tracer", m), d_c_real); }
+extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows) { return get_tracer(on_slab("fb_slab_get_tracer_local", s), d_rows); }
 
-extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real)
-{
-    if (!m || !d_c_real) return fail(FB_EINVAL, "fb_model_get_tracer: NULL");
-    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer: no tracer is set");
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_c_real, nullptr, m->tr.c0);
-}
-
+// the pair's body is the vorticity's (get_eddy_diffusivity, fb_record.h) with the tracer in its place
 extern "C" int fb_model_get_tracer_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_c, float *d_grad2)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: NULL model");
-    int rc;
-    if ((rc = keff_check("fb_model_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
-    if (!m->tracer) return fail(FB_EINVAL, "fb_model_get_tracer_eddy_diffusivity: no tracer is set");
-    NEED_SINGLE(m->c);
-    return record_keff(m, nullptr, nbins, d_table, d_c, d_grad2, m->tr.c0, m->kappa);
+    return get_eddy_diffusivity(on_model("fb_model_get_tracer_eddy_diffusivity", m), NEED_TRACER, nbins, d_table, d_c, d_grad2);
 }
-
-// collective on a slab of several ranks, as fb_slab_set_vort_local
-extern "C" int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_set_tracer_local: NULL slab");
-    int rc;
-    if ((rc = kappa_check("fb_slab_set_tracer_local", kappa))) return rc;
-    SLAB_READY(s);
-    return tracer_in(s->m, s, d_rows, kappa);
-}
-
-extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows)
-{
-    if (!s || !d_rows) return fail(FB_EINVAL, "fb_slab_get_tracer_local: NULL");
-    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_local: no tracer is set");
-    SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_rows, nullptr, s->m->tr.c0);
-}
-
-// collective, as fb_slab_get_eddy_diffusivity
 extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_c_rows, float *d_grad2_rows)
 {
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: NULL slab");
-    int rc;
-    if ((rc = keff_check("fb_slab_get_tracer_eddy_diffusivity", d_table, nbins))) return rc;
-    if (!s->m->tracer) return fail(FB_EINVAL, "fb_slab_get_tracer_eddy_diffusivity: no tracer is set");
-    SLAB_READY(s);
-    return record_keff(s->m, s, nbins, d_table, d_c_rows, d_grad2_rows, s->m->tr.c0, s->m->kappa);
+    return get_eddy_diffusivity(on_slab("fb_slab_get_tracer_eddy_diffusivity", s), NEED_TRACER, nbins, d_table, d_c_rows, d_grad2_rows);
 }
 
 // ---- the tangent-linear model (kernels: fb_tangent.h) ----
@@ -282,14 +243,11 @@ static int tangent_norm(fb_model *m, int kind, double *d_out)
         const size_t n = grp_elems(c, G);
         if (n == 0) continue;
         const int nwg = grid_for(c, n / 2);
-        hipLaunchKernelGGL(k_tangent_norm, dim3(nwg), dim3(256), 0, c->stream, coef, (const cf *)m->tg.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np);
-        HIPCHK(hipGetLastError());
+        if (int rc = launch(c, k_tangent_norm, dim3(nwg), dim3(256), 0, coef, (const cf *)m->tg.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
         np += nwg;
     }
     const double grids = (double)c->nx * c->ny;
-    hipLaunchKernelGGL(k_tangent_norm_final, dim3(1), dim3(256), 0, c->stream, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_tangent_norm_final, dim3(1), dim3(256), 0, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
 }
 
 static int tangent_scale(fb_model *m, float a)
@@ -298,99 +256,44 @@ static int tangent_scale(fb_model *m, float a)
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t n = grp_elems(c, c->grp[g]);
         if (n == 0) continue;
-        hipLaunchKernelGGL(k_tangent_scale, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, m->tg.c0[g], n, a);
-        HIPCHK(hipGetLastError());
+        if (int rc = launch_n(c, k_tangent_scale, n / 2, m->tg.c0[g], n, a)) return rc;
     }
     return FB_OK;
 }
 
-// what the entry points refuse before any HIP call
-static int tangent_check(const char *fn, const fb_model *m, bool need_set)
-{
-    if (!m) return fail(FB_EINVAL, std::string(fn) + ": NULL model");
-    if (need_set && !m->tangent) return fail(FB_EINVAL, std::string(fn) + ": no tangent is set");
-    return FB_OK;
-}
-static int tangent_norm_check(const char *fn, int kind, const double *d_out)
-{
-    if (kind != 0 && kind != 1) return fail(FB_EINVAL, std::string(fn) + ": kind must be 0 (enstrophy) or 1 (energy)");
-    if (!d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL output");
-    return FB_OK;
-}
-static int tangent_scale_check(const char *fn, float a)
-{
-    if (!std::isfinite(a) || a == 0.0f) return fail(FB_EINVAL, std::string(fn) + ": the factor must be finite and not zero");
-    return FB_OK;
-}
-
-extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real)
-{
-    int rc;
-    if ((rc = tangent_check("fb_model_set_tangent", m, false))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_in(m, nullptr, d_dz_real);
-}
-
-extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real)
-{
-    int rc;
-    if (!d_dz_real) return fail(FB_EINVAL, "fb_model_get_tangent: NULL");
-    if ((rc = tangent_check("fb_model_get_tangent", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_dz_real, nullptr, m->tg.c0);
-}
-
-extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out)
-{
-    int rc;
-    if ((rc = tangent_norm_check("fb_model_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_model_tangent_norm", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_norm(m, kind, d_out);
-}
-
-extern "C" int fb_model_tangent_scale(fb_model *m, float a)
-{
-    int rc;
-    if ((rc = tangent_scale_check("fb_model_tangent_scale", a)) || (rc = tangent_check("fb_model_tangent_scale", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return tangent_scale(m, a);
-}
-
 // a slab of one rank goes through the same code; on several ranks the tangent-linear model is refused
-#define SLAB_TANGENT_ONE_RANK(s, fn) do { if (!(s)) return fail(FB_EINVAL, std::string(fn) + ": NULL slab"); if ((s)->c->world > 1) return fail(FB_EINVAL, std::string(fn) + ": the tangent-linear model is not supported on a slab of several ranks (world > 1)"); } while (0)
+constexpr unsigned TANGENT = NEED_TRANSPORT | ONE_RANK_TANGENT, TANGENT_SET = TANGENT | NEED_TANGENT;
 
-extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real)
+static int set_tangent(const Call &k, const float *d_dz_real)
 {
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_set_tangent");
-    SLAB_READY(s);
-    return tangent_in(s->m, s, d_dz_real);
+    if (int rc = enter(k, TANGENT)) return rc;
+    return tangent_in(k.m, k.s, d_dz_real);
 }
+extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real) { return set_tangent(on_model("fb_model_set_tangent", m), d_dz_real); }
+extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real) { return set_tangent(on_slab("fb_slab_set_tangent", s), d_dz_real); }
 
-extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real)
-{
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_get_tangent");
-    int rc;
-    if (!d_dz_real) return fail(FB_EINVAL, "fb_slab_get_tangent: NULL");
-    if ((rc = tangent_check("fb_slab_get_tangent", s->m, true))) return rc;
-    SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_dz_real, nullptr, s->m->tg.c0);
-}
+static int get_tangent(const Call &k, float *d_dz_real) { return get_beside(k, TANGENT_SET, &fb_model::tg, d_dz_real); }
+extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real) { return get_tangent(on_model("fb_model_get_tangent", m), d_dz_real); }
+extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real) { return get_tangent(on_slab("fb_slab_get_tangent", s), d_dz_real); }
 
-extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out)
+static int tangent_norm(const Call &k, int kind, double *d_out)
 {
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_norm");
-    int rc;
-    if ((rc = tangent_norm_check("fb_slab_tangent_norm", kind, d_out)) || (rc = tangent_check("fb_slab_tangent_norm", s->m, true))) return rc;
-    return tangent_norm(s->m, kind, d_out);
+    if (kind != 0 && kind != 1) return refuse(k, "kind must be 0 (enstrophy) or 1 (energy)");
+    if (!d_out) return refuse(k, "NULL output");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    return tangent_norm(k.m, kind, d_out);
 }
+extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out) { return tangent_norm(on_model("fb_model_tangent_norm", m), kind, d_out); }
+extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out) { return tangent_norm(on_slab("fb_slab_tangent_norm", s), kind, d_out); }
 
-extern "C" int fb_slab_tangent_scale(fb_slab *s, float a)
+static int tangent_scale(const Call &k, float a)
 {
-    SLAB_TANGENT_ONE_RANK(s, "fb_slab_tangent_scale");
-    int rc;
-    if ((rc = tangent_scale_check("fb_slab_tangent_scale", a)) || (rc = tangent_check("fb_slab_tangent_scale", s->m, true))) return rc;
-    return tangent_scale(s->m, a);
+    if (!std::isfinite(a) || a == 0.0f) return refuse(k, "the factor must be finite and not zero");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    return tangent_scale(k.m, a);
 }
+extern "C" int fb_model_tangent_scale(fb_model *m, float a) { return tangent_scale(on_model("fb_model_tangent_scale", m), a); }
+extern "C" int fb_slab_tangent_scale(fb_slab *s, float a) { return tangent_scale(on_slab("fb_slab_tangent_scale", s), a); }
 
 // ---- the Lagrangian particles (kernels: fb_particles.h) ----
 #define FB_PARTICLES_MAX (1 << 24)
@@ -425,8 +328,7 @@ static int particle_stage(fb_model *m, int stage)
     const cf *v0, *v1;
     int rc;
     if ((rc = stage_vstate(m, 0, stage > 0, z + n, &v0, &v1))) return rc;
-    hipLaunchKernelGGL(k_particle_uv_spec, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, v0, v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_n(c, k_particle_uv_spec, n, coef, v0, v1, z, (long)n, G.ncols, c->N1, c->N2, G.ky0))) return rc;
     if ((rc = launch_col_block<+1>(c, G, z, 2, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 2, (long)n))) return rc;
     const float g = 1.0f / (float)((size_t)c->nx * c->ny);
     RowArgs a = row_args_base(c);
@@ -434,25 +336,10 @@ static int particle_stage(fb_model *m, int stage)
     if ((rc = launch_row<ROW_INV>(c, a))) return rc;
     a.M = view_single(c, z + n, (long)n); a.scale = g; a.rout = m->pt_uv + nr;        // v = dpsi/dx
     if ((rc = launch_row<ROW_INV>(c, a))) return rc;
-    const dim3 grid(grid_for(c, (size_t)m->pt_n)), blk(256);
     const PartGeo pg = part_geo(c);
     const float *u = m->pt_uv, *v = m->pt_uv + nr;
     const double dt = (double)m->dt;
-    switch (stage) {
-    case 0: hipLaunchKernelGGL((k_particle_stage<0>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    case 1: hipLaunchKernelGGL((k_particle_stage<1>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    case 2: hipLaunchKernelGGL((k_particle_stage<2>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    default: hipLaunchKernelGGL((k_particle_stage<3>), grid, blk, 0, c->stream, pg, u, v, m->pt, m->pt_n, dt); break;
-    }
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int particles_check(const char *fn, const double *d_xy, int n)
-{
-    if (!d_xy) return n == 0 ? FB_OK : fail(FB_EINVAL, std::string(fn) + ": NULL positions with n > 0");
-    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
-    return FB_OK;
+    return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_stage<S()>, (size_t)m->pt_n, pg, u, v, m->pt, m->pt_n, dt); });
 }
 
 // The particles in (d_xy == NULL removes them).  The vorticity, a tracer and `primed` stay as they are.  As tracer_in: the captured
@@ -473,8 +360,7 @@ static int particles_in(fb_model *m, fb_slab *s, const double *d_xy, int n)
         return fail(FB_ENOMEM, "particle allocation failed");
     }
     HIPCHK(hipMemsetAsync(m->pt, 0, 6 * (size_t)n * sizeof(double), c->stream));
-    hipLaunchKernelGGL(k_particle_unpack, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, d_xy, m->pt, m->pt + n, n);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_n(c, k_particle_unpack, (size_t)n, d_xy, m->pt, m->pt + n, n))) return rc;
     m->pt_n = n;
     return FB_OK;
 }
@@ -482,95 +368,63 @@ static int particles_in(fb_model *m, fb_slab *s, const double *d_xy, int n)
 static int particles_out(fb_model *m, double *d_xy)
 {
     fb_ctx *c = m->c;
-    hipLaunchKernelGGL(k_particle_pack, dim3(grid_for(c, (size_t)m->pt_n)), dim3(256), 0, c->stream, (const double *)m->pt, (const double *)(m->pt + m->pt_n), d_xy, m->pt_n);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
-}
-
-static int sample_check(const char *fn, const float *d_field, const double *d_xy, int n, const double *d_out)
-{
-    if (!d_field || !d_xy || !d_out) return fail(FB_EINVAL, std::string(fn) + ": NULL");
-    if (n < 1 || n > FB_PARTICLES_MAX) return fail(FB_EINVAL, std::string(fn) + ": n outside [1, 2^24]");
-    return FB_OK;
+    return launch_n(c, k_particle_pack, (size_t)m->pt_n, (const double *)m->pt, (const double *)(m->pt + m->pt_n), d_xy, m->pt_n);
 }
 
 static int sample(fb_ctx *c, const float *d_field, const double *d_xy, int n, double *d_out)
 {
-    hipLaunchKernelGGL(k_sample, dim3(grid_for(c, (size_t)n)), dim3(256), 0, c->stream, part_geo(c), d_field, d_xy, n, d_out);
-    HIPCHK(hipGetLastError());
+    return launch_n(c, k_sample, (size_t)n, part_geo(c), d_field, d_xy, n, d_out);
+}
+
+// a slab of one rank goes through the same code; on several ranks the particles are refused
+constexpr unsigned PARTICLES = NEED_TRANSPORT | ONE_RANK_PARTICLES;
+static bool particle_count_ok(int n) { return n >= 1 && n <= FB_PARTICLES_MAX; }
+
+static int set_particles(const Call &k, const double *d_xy, int n)
+{
+    if (!d_xy && n != 0) return refuse(k, "NULL positions with n > 0");
+    if (d_xy && !particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (int rc = enter(k, PARTICLES)) return rc;
+    return particles_in(k.m, k.s, d_xy, n);
+}
+extern "C" int fb_model_set_particles(fb_model *m, const double *d_xy, int n) { return set_particles(on_model("fb_model_set_particles", m), d_xy, n); }
+extern "C" int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n) { return set_particles(on_slab("fb_slab_set_particles", s), d_xy, n); }
+
+static int get_particles(const Call &k, double *d_xy)
+{
+    if (!d_xy) return refuse(k, "NULL output");
+    if (int rc = enter(k, PARTICLES | NEED_PARTICLES)) return rc;
+    return particles_out(k.m, d_xy);
+}
+extern "C" int fb_model_get_particles(fb_model *m, double *d_xy) { return get_particles(on_model("fb_model_get_particles", m), d_xy); }
+extern "C" int fb_slab_get_particles(fb_slab *s, double *d_xy) { return get_particles(on_slab("fb_slab_get_particles", s), d_xy); }
+
+// (0 on a slab of several ranks, which can have none, and before the slab is connected)
+static int particle_count(const Call &k, int *n)
+{
+    if (!n) return refuse(k, "NULL output");
+    if (int rc = enter(k)) return rc;
+    *n = k.m->pt_n;
     return FB_OK;
 }
+extern "C" int fb_model_particle_count(fb_model *m, int *n) { return particle_count(on_model("fb_model_particle_count", m), n); }
+extern "C" int fb_slab_particle_count(fb_slab *s, int *n) { return particle_count(on_slab("fb_slab_particle_count", s), n); }
 
-extern "C" int fb_model_set_particles(fb_model *m, const double *d_xy, int n)
+// (the handle's refusals first, for once: EngineSlab.sample asks a slab of several ranks for its refusal before it shapes any buffer)
+static int sample(const Call &k, const float *d_field, const double *d_xy, int n, double *d_out)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_set_particles: NULL model");
-    int rc;
-    if ((rc = particles_check("fb_model_set_particles", d_xy, n))) return rc;
-    NEED_SINGLE(m->c);
-    if (m->phase_flow) return fail(FB_EINVAL, "fb_model_set_particles on a slab model: use fb_slab_set_particles");
-    return particles_in(m, nullptr, d_xy, n);
+    if (int rc = enter(k, PARTICLES)) return rc;
+    if (!d_field || !d_xy || !d_out) return refuse(k, "NULL field, positions or output");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    return sample(k.m->c, d_field, d_xy, n, d_out);
 }
-
-extern "C" int fb_model_get_particles(fb_model *m, double *d_xy)
-{
-    if (!m || !d_xy) return fail(FB_EINVAL, "fb_model_get_particles: NULL");
-    if (!m->pt_n) return fail(FB_EINVAL, "fb_model_get_particles: no particles are set");
-    return particles_out(m, d_xy);
-}
-
-extern "C" int fb_model_particle_count(fb_model *m, int *n)
-{
-    if (!m || !n) return fail(FB_EINVAL, "fb_model_particle_count: NULL");
-    *n = m->pt_n;
-    return FB_OK;
-}
-
 extern "C" int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_sample: NULL model");
-    int rc;
-    if ((rc = sample_check("fb_model_sample", d_field, d_xy, n, d_out))) return rc;
-    NEED_SINGLE(m->c);
-    return sample(m->c, d_field, d_xy, n, d_out);
+    return sample(on_model("fb_model_sample", m), d_field, d_xy, n, d_out);
 }
-
-// a slab of one rank goes through the same code; particles distributed over row slabs would need neighbour halo rows that the
-// all-to-all transport does not provide
-#define SLAB_PARTICLES_ONE_RANK(s, fn) do { if ((s)->c->world > 1) return fail(FB_EUNSUPPORTED, std::string(fn) + ": particles are not supported on a slab of several ranks (world > 1)"); } while (0)
-
-extern "C" int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_set_particles: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_set_particles");
-    int rc;
-    if ((rc = particles_check("fb_slab_set_particles", d_xy, n))) return rc;
-    SLAB_READY(s);
-    return particles_in(s->m, s, d_xy, n);
-}
-
-extern "C" int fb_slab_get_particles(fb_slab *s, double *d_xy)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_particles: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_get_particles");
-    if (!d_xy) return fail(FB_EINVAL, "fb_slab_get_particles: NULL");
-    if (!s->m->pt_n) return fail(FB_EINVAL, "fb_slab_get_particles: no particles are set");
-    return particles_out(s->m, d_xy);
-}
-
-extern "C" int fb_slab_particle_count(fb_slab *s, int *n)
-{
-    if (!s || !n) return fail(FB_EINVAL, "fb_slab_particle_count: NULL");
-    *n = s->m->pt_n;
-    return FB_OK;
-}
-
 extern "C" int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out)
 {
-    if (!s) return fail(FB_EINVAL, "fb_slab_sample: NULL slab");
-    SLAB_PARTICLES_ONE_RANK(s, "fb_slab_sample");
-    int rc;
-    if ((rc = sample_check("fb_slab_sample", d_field, d_xy, n, d_out))) return rc;
-    return sample(s->c, d_field, d_xy, n, d_out);
+    return sample(on_slab("fb_slab_sample", s), d_field, d_xy, n, d_out);
 }
 
 // ---- the adjoint model (kernels: fb_adjoint.h) ----
@@ -586,14 +440,6 @@ static void adjoint_free(fb_model *m)
     beside_free(m->ad);
     if (m->ad_real) { hipFree(m->ad_real); m->ad_real = nullptr; }
     m->adjoint = false;
-}
-
-// a step call that would overrun the tape is refused before anything is launched
-static int adjoint_room(const fb_model *m, int nsteps, const char *fn)
-{
-    if (m->ad_depth && nsteps > m->ad_depth - m->ad_fill)
-        return fail(FB_EINVAL, std::string(fn) + ": the adjoint's tape has room for " + std::to_string(m->ad_depth - m->ad_fill) + " more steps (fb_model_adjoint_record)");
-    return FB_OK;
 }
 
 // The tape on (depth >= 1: room for depth steps x 4 stage states) or off (depth == 0); either way it starts empty.  While it is on
@@ -628,9 +474,7 @@ static int adjoint_stash(fb_model *m, int stage)
     int rc;
     if ((rc = stage_vstate(m, 0, stage > 0 && c->nact > 0, slot, &v0, &v1))) return rc;
     if (v0 == slot) return FB_OK;
-    hipLaunchKernelGGL(k_adjoint_merge, dim3(grid_for(c, n / 2)), dim3(256), 0, c->stream, make_coef(c), v0, v1, slot, G.ncols, c->N1, c->N2, G.ky0);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch_n(c, k_adjoint_merge, n / 2, make_coef(c), v0, v1, slot, G.ncols, c->N1, c->N2, G.ky0);
 }
 
 // The adjoint variable in (beside_in: lam, with the k-bar and the accumulator of a backward step) and the real fields of the product
@@ -661,11 +505,9 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
     const SpecCoef coef = make_coef(c);
     cf *z = m->rec_work[0];
     cf *lam = m->ad.c0[0], *kb = m->ad.c1[0], *acc = m->ad.acc[0];
-    const dim3 grid(grid_for(c, n / 2)), blk(256);
     int rc;
-    hipLaunchKernelGGL(k_adjoint_deriv, grid, blk, 0, c->stream, coef, zs, (const cf *)(stage == 3 ? lam : kb), stage == 3 ? m->dt / 6.0f : 1.0f, z, (long)n, G.ncols,
-                       c->N1, c->N2, G.ky0);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_n(c, k_adjoint_deriv, n / 2, coef, zs, (const cf *)(stage == 3 ? lam : kb), stage == 3 ? m->dt / 6.0f : 1.0f, z, (long)n, G.ncols, c->N1, c->N2, G.ky0)))
+        return rc;
     if ((rc = launch_col_block<+1>(c, G, z, 5, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 5, (long)n))) return rc;
     const float g = 1.0f / (float)((size_t)c->nx * c->ny);
     for (int f = 0; f < 5; ++f) {
@@ -673,8 +515,7 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
         a.M = view_single(c, z + f * n, (long)n); a.scale = f == 1 ? -g : g; a.rout = m->ad_real + f * nr;      // u = -dpsi/dy (record(), REC_U)
         if ((rc = launch_row<ROW_INV>(c, a))) return rc;
     }
-    hipLaunchKernelGGL(k_adjoint_prod, dim3(grid_for(c, nr / 4)), blk, 0, c->stream, m->ad_real, nr);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch_n(c, k_adjoint_prod, nr / 4, m->ad_real, nr))) return rc;
     HIPCHK(hipMemsetAsync(z, 0, 4 * n * sizeof(cf), c->stream));                                                 // pad columns zero
     for (int f = 0; f < 4; ++f) {
         RowArgs a = row_args_base(c);
@@ -682,14 +523,9 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
         if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
     }
     if ((rc = launch_col_strided<-1>(c, G, z, 4, (long)n)) || (rc = launch_col_block<-1>(c, G, z, 4, (long)n))) return rc;
-    switch (stage) {
-    case 3: hipLaunchKernelGGL((k_adjoint_update<3>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
-    case 2: hipLaunchKernelGGL((k_adjoint_update<2>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
-    case 1: hipLaunchKernelGGL((k_adjoint_update<1>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
-    default: hipLaunchKernelGGL((k_adjoint_update<0>), grid, blk, 0, c->stream, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0); break;
-    }
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return dispatch<4>(stage, [&](auto S) {
+        return launch_n(c, k_adjoint_update<S()>, n / 2, coef, (const cf *)z, (long)n, lam, kb, acc, m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0);
+    });
 }
 
 // The last nsteps recorded steps popped, newest first, each step's transpose applied to lam (its stages in the order 3, 2, 1, 0).
@@ -708,109 +544,73 @@ static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
     return FB_OK;
 }
 
-// what the entry points refuse before any HIP call
-static int adjoint_check(const char *fn, const fb_model *m, bool need_set)
-{
-    if (!m) return fail(FB_EINVAL, std::string(fn) + ": NULL model");
-    if (need_set && !m->adjoint) return fail(FB_EINVAL, std::string(fn) + ": no adjoint is set");
-    return FB_OK;
-}
-static int adjoint_record_check(const char *fn, int depth)
-{
-    if (depth < 0 || depth > (1 << 20)) return fail(FB_EINVAL, std::string(fn) + ": depth outside [0, 2^20]");
-    return FB_OK;
-}
-static int adjoint_back_check(const char *fn, const fb_model *m, int nsteps)
-{
-    if (nsteps < 0) return fail(FB_EINVAL, std::string(fn) + ": nsteps < 0");
-    if (int rc = adjoint_check(fn, m, true)) return rc;
-    if (nsteps > m->ad_fill) return fail(FB_EINVAL, std::string(fn) + ": " + std::to_string(nsteps) + " steps asked for, " + std::to_string(m->ad_fill) + " recorded");
-    return FB_OK;
-}
-
-extern "C" int fb_model_adjoint_record(fb_model *m, int depth)
-{
-    int rc;
-    if ((rc = adjoint_record_check("fb_model_adjoint_record", depth)) || (rc = adjoint_check("fb_model_adjoint_record", m, false))) return rc;
-    NEED_SINGLE(m->c);
-    if (m->phase_flow) return fail(FB_EINVAL, "fb_model_adjoint_record on a slab model: use fb_slab_adjoint_record");
-    return adjoint_record(m, depth);
-}
-
-extern "C" int fb_model_adjoint_recorded(fb_model *m, int *n)
-{
-    if (!m || !n) return fail(FB_EINVAL, "fb_model_adjoint_recorded: NULL");
-    *n = m->ad_fill;
-    return FB_OK;
-}
-
-extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real)
-{
-    int rc;
-    if ((rc = adjoint_check("fb_model_set_adjoint", m, false))) return rc;
-    NEED_SINGLE(m->c);
-    return adjoint_in(m, nullptr, d_lambda_real);
-}
-
-extern "C" int fb_model_get_adjoint(fb_model *m, float *d_real)
-{
-    int rc;
-    if (!d_real) return fail(FB_EINVAL, "fb_model_get_adjoint: NULL");
-    if ((rc = adjoint_check("fb_model_get_adjoint", m, true))) return rc;
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_real, nullptr, m->ad.c0);
-}
-
-extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps)
-{
-    int rc;
-    if ((rc = adjoint_back_check("fb_model_adjoint_back", m, nsteps))) return rc;
-    NEED_SINGLE(m->c);
-    return adjoint_back(m, nullptr, nsteps);
-}
-
 // a slab of one rank goes through the same code; on several ranks the adjoint model is refused
-#define SLAB_ADJOINT_ONE_RANK(s, fn) do { if (!(s)) return fail(FB_EINVAL, std::string(fn) + ": NULL slab"); if ((s)->c->world > 1) return fail(FB_EINVAL, std::string(fn) + ": the adjoint model is not supported on a slab of several ranks (world > 1)"); } while (0)
+constexpr unsigned ADJOINT = NEED_TRANSPORT | ONE_RANK_ADJOINT, ADJOINT_SET = ADJOINT | NEED_ADJOINT;
 
-extern "C" int fb_slab_adjoint_record(fb_slab *s, int depth)
+static int adjoint_record(const Call &k, int depth)
 {
-    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_record");
-    int rc;
-    if ((rc = adjoint_record_check("fb_slab_adjoint_record", depth))) return rc;
-    SLAB_READY(s);
-    return adjoint_record(s->m, depth);
+    if (depth < 0 || depth > (1 << 20)) return refuse(k, "depth outside [0, 2^20]");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return adjoint_record(k.m, depth);
 }
+extern "C" int fb_model_adjoint_record(fb_model *m, int depth) { return adjoint_record(on_model("fb_model_adjoint_record", m), depth); }
+extern "C" int fb_slab_adjoint_record(fb_slab *s, int depth) { return adjoint_record(on_slab("fb_slab_adjoint_record", s), depth); }
 
-extern "C" int fb_slab_adjoint_recorded(fb_slab *s, int *n)
+static int adjoint_recorded(const Call &k, int *n)
 {
-    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_recorded");
-    if (!n) return fail(FB_EINVAL, "fb_slab_adjoint_recorded: NULL");
-    *n = s->m->ad_fill;
+    if (!n) return refuse(k, "NULL output");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    *n = k.m->ad_fill;
+    return FB_OK;
+}
+extern "C" int fb_model_adjoint_recorded(fb_model *m, int *n) { return adjoint_recorded(on_model("fb_model_adjoint_recorded", m), n); }
+extern "C" int fb_slab_adjoint_recorded(fb_slab *s, int *n) { return adjoint_recorded(on_slab("fb_slab_adjoint_recorded", s), n); }
+
+static int set_adjoint(const Call &k, const float *d_lambda_real)
+{
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return adjoint_in(k.m, k.s, d_lambda_real);
+}
+extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real) { return set_adjoint(on_model("fb_model_set_adjoint", m), d_lambda_real); }
+extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real) { return set_adjoint(on_slab("fb_slab_set_adjoint", s), d_lambda_real); }
+
+static int get_adjoint(const Call &k, float *d_real) { return get_beside(k, ADJOINT_SET, &fb_model::ad, d_real); }
+extern "C" int fb_model_get_adjoint(fb_model *m, float *d_real) { return get_adjoint(on_model("fb_model_get_adjoint", m), d_real); }
+extern "C" int fb_slab_get_adjoint(fb_slab *s, float *d_real) { return get_adjoint(on_slab("fb_slab_get_adjoint", s), d_real); }
+
+static int adjoint_back(const Call &k, int nsteps)
+{
+    if (nsteps < 0) return refuse(k, "nsteps < 0");
+    if (int rc = enter(k, ADJOINT_SET)) return rc;
+    if (nsteps > k.m->ad_fill) return refuse(k, std::to_string(nsteps) + " steps asked for, " + std::to_string(k.m->ad_fill) + " recorded");
+    return adjoint_back(k.m, k.s, nsteps);
+}
+extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps) { return adjoint_back(on_model("fb_model_adjoint_back", m), nsteps); }
+extern "C" int fb_slab_adjoint_back(fb_slab *s, int nsteps) { return adjoint_back(on_slab("fb_slab_adjoint_back", s), nsteps); }
+
+// ---- what the step and the model's end know of all of them (declared in fftbaro.hip) ----
+// At the top of RK stage `stage`, from the state the vorticity's stage starts from: the tracer's stage, the particles', the
+// tangent-linear model's, and the state into the adjoint's tape (the last three on one rank only: their set calls refuse more).
+static int beside_stage(fb_model *m, fb_slab *s, int stage)
+{
+    int rc;
+    if (m->tracer && (rc = tracer_stage(m, s, stage))) return rc;
+    if (m->pt_n && (rc = particle_stage(m, stage))) return rc;
+    if (m->tangent && (rc = tangent_stage(m, s, stage))) return rc;
+    if (m->ad_depth && (rc = adjoint_stash(m, stage))) return rc;
     return FB_OK;
 }
 
-extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real)
+static void beside_step_done(fb_model *m)
 {
-    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_set_adjoint");
-    SLAB_READY(s);
-    return adjoint_in(s->m, s, d_lambda_real);
+    if (m->ad_depth) ++m->ad_fill;                          // the four stage states of this step are on the tape
 }
 
-extern "C" int fb_slab_get_adjoint(fb_slab *s, float *d_real)
+static void beside_free_all(fb_model *m)
 {
-    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_get_adjoint");
-    int rc;
-    if (!d_real) return fail(FB_EINVAL, "fb_slab_get_adjoint: NULL");
-    if ((rc = adjoint_check("fb_slab_get_adjoint", s->m, true))) return rc;
-    SLAB_READY(s);
-    return record(s->m, s, REC_VORT, d_real, nullptr, s->m->ad.c0);
-}
-
-extern "C" int fb_slab_adjoint_back(fb_slab *s, int nsteps)
-{
-    SLAB_ADJOINT_ONE_RANK(s, "fb_slab_adjoint_back");
-    int rc;
-    if ((rc = adjoint_back_check("fb_slab_adjoint_back", s->m, nsteps))) return rc;
-    SLAB_READY(s);
-    return adjoint_back(s->m, s, nsteps);
+    tracer_free(m);
+    particles_free(m);
+    tangent_free(m);
+    adjoint_free(m);
+    adjoint_tape_free(m);
 }

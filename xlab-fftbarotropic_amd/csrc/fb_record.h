@@ -14,9 +14,7 @@ static int state_in(fb_model *m, fb_slab *s, const float *d_rows)
 {
     fb_ctx *c = m->c;
     int rc;
-    m->warmed = false;                                      // the next fb_model_step starts with an eager (priming) step
-    m->primed = 0;
-    m->ad_fill = 0;                                         // the adjoint's tape belongs to the state that is replaced
+    state_replaced(m);
     if (!s) HIPCHK(hipMemsetAsync(m->gb[0].t_send, 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
     RowArgs a = row_args_base(c);
     a.rin = d_rows;
@@ -33,19 +31,14 @@ static int state_in(fb_model *m, fb_slab *s, const float *d_rows)
     return FB_OK;
 }
 
-extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort)
+static int set_vort(const Call &k, const float *d_rows)
 {
-    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_set_vort: NULL");
-    NEED_SINGLE(m->c);
-    return state_in(m, nullptr, d_vort);
+    if (!d_rows) return refuse(k, "NULL input");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return state_in(k.m, k.s, d_rows);
 }
-
-extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows)
-{
-    SLAB_READY(s);
-    if (!d_rows) return fail(FB_EINVAL, "fb_slab_set_vort_local: NULL");
-    return state_in(s->m, s, d_rows);
-}
+extern "C" int fb_model_set_vort(fb_model *m, const float *d_vort) { return set_vort(on_model("fb_model_set_vort", m), d_vort); }
+extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows) { return set_vort(on_slab("fb_slab_set_vort_local", s), d_rows); }
 
 // ---- the record layer ----
 enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF, REC_PRES };
@@ -113,17 +106,13 @@ static int record_fields(fb_model *m, fb_slab *s, RecKind kind, RowView *M, cf *
         if (of) HIPCHK(hipMemcpyAsync(z, of[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
         else if ((rc = export_state(m, g, z))) return rc;
         const SpecCoef k = make_coef(c);
-        const dim3 grid(grid_for(c, n)), blk(256);
-        switch (kind) {
-        case REC_VORT: break;
-        case REC_PSI: hipLaunchKernelGGL((k_psi_private<0>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
-        case REC_U: hipLaunchKernelGGL((k_psi_private<1>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
-        case REC_V: hipLaunchKernelGGL((k_psi_private<2>), grid, blk, 0, c->stream, k, z, G.ncols, c->N1, c->N2, G.ky0); break;
-        case REC_OW: hipLaunchKernelGGL(k_ow_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
-        case REC_KEFF: hipLaunchKernelGGL(k_keff_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
-        case REC_PRES: hipLaunchKernelGGL(k_pres_spec, grid, blk, 0, c->stream, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0); break;
-        }
-        HIPCHK(hipGetLastError());
+        rc = FB_OK;                                         // (REC_VORT: the state as it is)
+        if (kind >= REC_OW) {
+            const auto spec = kind == REC_OW ? k_ow_spec : kind == REC_KEFF ? k_keff_spec : k_pres_spec;
+            rc = launch_n(c, spec, n, k, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
+        } else if (kind != REC_VORT)
+            rc = dispatch<3>(kind - REC_PSI, [&](auto W) { return launch_n(c, k_psi_private<W()>, n, k, z, G.ncols, c->N1, c->N2, G.ky0); });
+        if (rc) return rc;
         if ((rc = launch_col_block<+1>(c, G, z, nf, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, nf, (long)n))) return rc;
     }
     return record_to_rows(m, s, nf, M);
@@ -156,10 +145,10 @@ static int record_diag(fb_model *m, fb_slab *s, float *d_psi, float *d_u, float 
 }
 
 // ---- effective eddy diffusivity: zeta and |grad zeta|^2 (REC_KEFF), then the table ----
-static int keff_check(const char *fn, const double *d_table, int nbins)
+static int keff_check(const Call &k, const double *d_table, int nbins)
 {
-    if (!d_table) return fail(FB_EINVAL, std::string(fn) + ": NULL table");
-    if (nbins < 2 || nbins > 4096) return fail(FB_EINVAL, std::string(fn) + ": nbins outside [2, 4096]");
+    if (!d_table) return refuse(k, "NULL table");
+    if (nbins < 2 || nbins > 4096) return refuse(k, "nbins outside [2, 4096]");
     return FB_OK;
 }
 
@@ -190,27 +179,23 @@ static int keff_finish(fb_model *m, fb_slab *s, int nbins, const float *zeta, co
     unsigned *cnt_part = (unsigned *)(base + o_cnt);
     float *mm_part = (float *)(base + o_mm), *mmsend = (float *)(base + o_mmsend), *mmrecv = (float *)(base + o_mmrecv);
     const bool xchg = s && world > 1;
-    if (v4) hipLaunchKernelGGL((k_keff_minmax<true>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
-    else hipLaunchKernelGGL((k_keff_minmax<false>), dim3(nmm), dim3(256), 0, c->stream, zeta, n, mm_part);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_keff_minmax_final, dim3(1), dim3(256), 0, c->stream, (const float *)mm_part, nmm, xchg ? mmsend : mmrecv, xchg ? world : 1);
-    HIPCHK(hipGetLastError());
+    const dim3 one(1), blk(256);
+    if ((rc = launch(c, v4 ? k_keff_minmax<true> : k_keff_minmax<false>, dim3(nmm), blk, 0, zeta, n, mm_part)) ||
+        (rc = launch(c, k_keff_minmax_final, one, blk, 0, (const float *)mm_part, nmm, xchg ? mmsend : mmrecv, xchg ? world : 1)))
+        return rc;
     if (xchg && (rc = slab_gather(s, mmsend, mmrecv, 2))) return rc;
     // dynamic LDS: 12 B per bin (histogram), 16 B per bin (table); the attribute once per kernel and device, for 4096 bins
     if ((rc = set_max_lds(c, (const void *)k_keff_hist<true>, 4096 * 12)) || (rc = set_max_lds(c, (const void *)k_keff_hist<false>, 4096 * 12)) ||
         (rc = set_max_lds(c, (const void *)k_keff_table, 4096 * 16)))
         return rc;
-    if (v4) hipLaunchKernelGGL((k_keff_hist<true>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
-    else hipLaunchKernelGGL((k_keff_hist<false>), dim3(nwg), dim3(256), (size_t)nbins * 12, c->stream, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part, sum_part);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_keff_reduce, dim3((nbins + KEFF_RB - 1) / KEFF_RB), dim3(256), 0, c->stream, (const unsigned *)cnt_part, (const double *)sum_part, nwg, nbins,
-                       xchg ? hsend : hrecv, xchg ? world : 1, nh);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(c, v4 ? k_keff_hist<true> : k_keff_hist<false>, dim3(nwg), blk, (size_t)nbins * 12, zeta, grad2, n, (const float *)mmrecv, world, nbins, cnt_part,
+                     sum_part)) ||
+        (rc = launch(c, k_keff_reduce, dim3((nbins + KEFF_RB - 1) / KEFF_RB), blk, 0, (const unsigned *)cnt_part, (const double *)sum_part, nwg, nbins,
+                     xchg ? hsend : hrecv, xchg ? world : 1, nh)))
+        return rc;
     if (xchg && (rc = slab_gather(s, hsend, hrecv, 2 * nh))) return rc;
-    hipLaunchKernelGGL(k_keff_table, dim3(1), dim3(256), (size_t)nbins * 16, c->stream, (const double *)hrecv, world, (const float *)mmrecv, nbins,
-                       (double)c->lx / c->nx, (double)c->ly / c->ny, kappa, d_table);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_keff_table, one, blk, (size_t)nbins * 16, (const double *)hrecv, world, (const float *)mmrecv, nbins, (double)c->lx / c->nx, (double)c->ly / c->ny,
+                  kappa, d_table);
 }
 
 // the row pass's outputs: the caller's, or the model's own buffers (keff_fields [2][XL][ny]) for those the caller does not want
@@ -236,20 +221,17 @@ extern "C" int fb_azimuthal_cols(int nmodes, int *ncols)
     return FB_OK;
 }
 
-static int azim_check(const char *fn, const fb_ctx *c, int mode, double xc, double yc, int nbins, double dr, int nmodes, const double *d_table,
-                      const double *d_center)
+static int azim_check(const Call &k, const fb_ctx *c, int mode, double xc, double yc, int nbins, double dr, int nmodes)
 {
-    const std::string f(fn);
-    if (!d_table || !d_center) return fail(FB_EINVAL, f + ": NULL table or centre");
-    if (mode != FB_CENTER_FIXED && mode != FB_CENTER_PSI_MIN && mode != FB_CENTER_VORT_MAX) return fail(FB_EINVAL, f + ": unknown centre mode");
+    if (mode != FB_CENTER_FIXED && mode != FB_CENTER_PSI_MIN && mode != FB_CENTER_VORT_MAX) return refuse(k, "unknown centre mode");
     const double lx = (double)c->lx, ly = (double)c->ly, dx = lx / c->nx, dy = ly / c->ny;
     if (mode == FB_CENTER_FIXED && !(std::isfinite(xc) && std::isfinite(yc) && xc >= 0.0 && xc < lx && yc >= 0.0 && yc < ly))
-        return fail(FB_EINVAL, f + ": the fixed centre must be finite with 0 <= xc < Lx, 0 <= yc < Ly");
-    if (nbins < 2 || nbins > 4096) return fail(FB_EINVAL, f + ": nbins outside [2, 4096]");
-    if (nmodes < 0 || nmodes > AZIM_MAX_MODES) return fail(FB_EINVAL, f + ": nmodes outside [0, 8]");
-    if (!std::isfinite(dr)) return fail(FB_EINVAL, f + ": dr is not finite");
-    if (dr < std::min(dx, dy)) return fail(FB_EINVAL, f + ": dr below min(dx, dy)");
-    if ((double)nbins * dr > std::min(lx, ly) / 2) return fail(FB_EINVAL, f + ": nbins * dr beyond min(Lx, Ly) / 2 (the minimum-image cell)");
+        return refuse(k, "the fixed centre must be finite with 0 <= xc < Lx, 0 <= yc < Ly");
+    if (nbins < 2 || nbins > 4096) return refuse(k, "nbins outside [2, 4096]");
+    if (nmodes < 0 || nmodes > AZIM_MAX_MODES) return refuse(k, "nmodes outside [0, 8]");
+    if (!std::isfinite(dr)) return refuse(k, "dr is not finite");
+    if (dr < std::min(dx, dy)) return refuse(k, "dr below min(dx, dy)");
+    if ((double)nbins * dr > std::min(lx, ly) / 2) return refuse(k, "nbins * dr beyond min(Lx, Ly) / 2 (the minimum-image cell)");
     return FB_OK;
 }
 
@@ -273,9 +255,7 @@ template <int NM> static int azim_launch_bin(const fb_ctx *c, const AzimGeo &g, 
     const int ns = AZIM_BASE_SUMS + 2 * NM, tiles = ((g.XL + g.TX - 1) / g.TX) * (g.ny / g.TY);
     int rc;
     if ((rc = set_max_lds(c, (const void *)k_azim_bin<NM>, 65536))) return rc;
-    hipLaunchKernelGGL((k_azim_bin<NM>), dim3(tiles), dim3(256), (size_t)g.W * ns * sizeof(double), c->stream, g, zeta, u, v, center, part);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_azim_bin<NM>, dim3(tiles), dim3(256), (size_t)g.W * ns * sizeof(double), g, zeta, u, v, center, part);
 }
 
 // The record's own buffers: azim_fields [2][XL][ny] (f32) and one reduction buffer, grown on demand:
@@ -311,22 +291,18 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
     // the centre
     bool have_zeta = false;
     if (mode == FB_CENTER_FIXED) {
-        hipLaunchKernelGGL(k_azim_center, dim3(1), dim3(64), 0, c->stream, (const double *)nullptr, world, xc, yc, c->ny, g.dx, g.dy, d_center);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch(c, k_azim_center, dim3(1), dim3(64), 0, (const double *)nullptr, world, xc, yc, c->ny, g.dx, g.dy, d_center))) return rc;
     } else {
         const bool vmax = mode == FB_CENTER_VORT_MAX;
         float *q = vmax ? f0 : f1;
         if ((rc = record(m, s, vmax ? REC_VORT : REC_PSI, q))) return rc;
         have_zeta = vmax;
-        if (vmax) hipLaunchKernelGGL((k_azim_arg<true>), dim3(nparts), dim3(256), 0, c->stream, (const float *)q, n, pk, pi);
-        else hipLaunchKernelGGL((k_azim_arg<false>), dim3(nparts), dim3(256), 0, c->stream, (const float *)q, n, pk, pi);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_azim_arg_final, dim3(1), dim3(256), 0, c->stream, (const float *)pk, (const long long *)pi, nparts, (const float *)q,
-                           (long long)c->rank * (long long)n, xchg ? csend : crecv, xchg ? world : 1);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch(c, vmax ? k_azim_arg<true> : k_azim_arg<false>, dim3(nparts), dim3(256), 0, (const float *)q, n, pk, pi)) ||
+            (rc = launch(c, k_azim_arg_final, dim3(1), dim3(256), 0, (const float *)pk, (const long long *)pi, nparts, (const float *)q, (long long)c->rank * (long long)n,
+                         xchg ? csend : crecv, xchg ? world : 1)))
+            return rc;
         if (xchg && (rc = slab_gather(s, csend, crecv, 2 * AZIM_ARG_W))) return rc;
-        hipLaunchKernelGGL(k_azim_center, dim3(1), dim3(64), 0, c->stream, (const double *)crecv, world, 0.0, 0.0, c->ny, g.dx, g.dy, d_center);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch(c, k_azim_center, dim3(1), dim3(64), 0, (const double *)crecv, world, 0.0, 0.0, c->ny, g.dx, g.dy, d_center))) return rc;
     }
     // the fields
     if (!have_zeta && (rc = record(m, s, REC_VORT, f0))) return rc;
@@ -344,26 +320,12 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
     if ((rc = record(m, s, REC_V, f2))) return rc;
     // the sums and the table
     HIPCHK(hipMemsetAsync(psend, 0, np * sizeof(double), c->stream));
-    switch (nmodes) {
-    case 0: rc = azim_launch_bin<0>(c, g, f0, f1, f2, d_center, psend); break;
-    case 1: rc = azim_launch_bin<1>(c, g, f0, f1, f2, d_center, psend); break;
-    case 2: rc = azim_launch_bin<2>(c, g, f0, f1, f2, d_center, psend); break;
-    case 3: rc = azim_launch_bin<3>(c, g, f0, f1, f2, d_center, psend); break;
-    case 4: rc = azim_launch_bin<4>(c, g, f0, f1, f2, d_center, psend); break;
-    case 5: rc = azim_launch_bin<5>(c, g, f0, f1, f2, d_center, psend); break;
-    case 6: rc = azim_launch_bin<6>(c, g, f0, f1, f2, d_center, psend); break;
-    case 7: rc = azim_launch_bin<7>(c, g, f0, f1, f2, d_center, psend); break;
-    default: rc = azim_launch_bin<8>(c, g, f0, f1, f2, d_center, psend); break;
-    }
-    if (rc) return rc;
+    if ((rc = dispatch<AZIM_MAX_MODES + 1>(nmodes, [&](auto NM) { return azim_launch_bin<NM()>(c, g, f0, f1, f2, d_center, psend); }))) return rc;
     if (xchg) {                                             // one copy of this rank's sums per peer
         for (int r = 1; r < world; ++r) HIPCHK(hipMemcpyAsync(psend + r * np, psend, np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         if ((rc = slab_gather(s, psend, precv, 2 * np))) return rc;
     }
-    hipLaunchKernelGGL(k_azim_table, dim3(1), dim3(256), (size_t)nbins * sizeof(double), c->stream, (const double *)precv, xchg ? world : 1, nbins, nmodes, dr,
-                       g.dx, g.dy, d_table);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_azim_table, dim3(1), dim3(256), (size_t)nbins * sizeof(double), (const double *)precv, xchg ? world : 1, nbins, nmodes, dr, g.dx, g.dy, d_table);
 }
 
 // ---- balanced pressure (REC_PRES): there and back ----
@@ -373,11 +335,10 @@ static int record_azimuthal(fb_model *m, fb_slab *s, int mode, double xc, double
 // before it stores; a slab: into rec_send as [dst][XL][ncols], one all-to-all back into field 0 of rec_work = [nx][ncols]); the
 // forward x pass as state_in runs it; the state once more into field 1 (free by now) and k_pres_solve; then one field back as
 // every one-field record goes, and the reference point.
-static int pres_check(const char *fn, const fb_ctx *c, const float *out, int ref_x, int ref_y, long *flat)
+static int pres_check(const Call &k, const fb_ctx *c, int ref_x, int ref_y, long *flat)
 {
-    if (!out) return fail(FB_EINVAL, std::string(fn) + ": NULL output");
     const long long at = (long long)ref_x + (long long)c->nx * ref_y;    // the reference's flat index (invert_pres.cpp:182), kept as it is
-    if (ref_x < 0 || ref_y < 0 || at >= (long long)c->nx * c->ny) return fail(FB_EINVAL, std::string(fn) + ": reference point outside the grid");
+    if (ref_x < 0 || ref_y < 0 || at >= (long long)c->nx * c->ny) return refuse(k, "reference point outside the grid");
     *flat = (long)at;
     return FB_OK;
 }
@@ -405,8 +366,7 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
         cf *z = m->rec_work[k];
         if ((rc = launch_col_strided<-1>(c, G, z, 1, 0)) || (rc = launch_col_block<-1>(c, G, z, 1, 0))) return rc;
         if ((rc = export_state(m, k, z + n))) return rc;
-        hipLaunchKernelGGL(k_pres_solve, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)(z + n), z, rho, f, G.ncols, c->N1, c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
+        if ((rc = launch_n(c, k_pres_solve, n, coef, (const cf *)(z + n), z, rho, f, G.ncols, c->N1, c->N2, G.ky0))) return rc;
         if ((rc = launch_col_block<+1>(c, G, z, 1, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 1, (long)n))) return rc;
     }
     RowArgs b = row_args_base(c);
@@ -418,16 +378,11 @@ static int record_pres(fb_model *m, fb_slab *s, float rho, float f, long flat, f
     const int owner = (int)((size_t)flat / nloc);
     float *ref_send = m->pres_ref, *ref_recv = m->pres_ref + world;
     const long at = (!xchg || owner == c->rank) ? (long)((size_t)flat - (size_t)owner * nloc) : -1;
-    hipLaunchKernelGGL(k_pres_ref, dim3((world + 63) / 64), dim3(64), 0, c->stream, (const float *)out, at, xchg ? ref_send : ref_recv, xchg ? world : 1);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(c, k_pres_ref, dim3((world + 63) / 64), dim3(64), 0, (const float *)out, at, xchg ? ref_send : ref_recv, xchg ? world : 1))) return rc;
     if (xchg && (rc = slab_gather(s, ref_send, ref_recv, 1))) return rc;
     const float *ref = ref_recv + (xchg ? owner : 0);
     const bool v4 = ((size_t)out & 15) == 0;                // nloc is a multiple of 4 (ny >= 64)
-    const dim3 grid(grid_for(c, v4 ? nloc / 4 : nloc)), blk(256);
-    if (v4) hipLaunchKernelGGL((k_pres_sub<true>), grid, blk, 0, c->stream, out, nloc, ref);
-    else hipLaunchKernelGGL((k_pres_sub<false>), grid, blk, 0, c->stream, out, nloc, ref);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch_n(c, v4 ? k_pres_sub<true> : k_pres_sub<false>, v4 ? nloc / 4 : nloc, out, nloc, ref);
 }
 
 // ---- shell spectra and cascade fluxes: there and back, then the gather (fb_spectra.h) ----
@@ -534,9 +489,7 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
     auto fill = [&](int g, const ColGroup &G, cf *z, size_t n) -> int {
         int r;
         if ((r = export_state(m, g, z))) return r;
-        hipLaunchKernelGGL(k_spectra_deriv, dim3(grid_for(c, n)), dim3(256), 0, c->stream, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
-        HIPCHK(hipGetLastError());
-        return FB_OK;
+        return launch_n(c, k_spectra_deriv, n, coef, (const cf *)z, z, (long)n, G.ncols, c->N1, c->N2, G.ky0);
     };
     if ((rc = record_advect(m, s, fill))) return rc;
     SpecGroups sgr;
@@ -552,129 +505,101 @@ static int record_spectra(fb_model *m, fb_slab *s, double *d_table)
         sgr.a[q] = st; sgr.nh[q] = active ? nh : nullptr; sgr.ncols[q] = G.ncols; sgr.ky0[q] = G.ky0;
     }
     double *send = (double *)m->spec_red, *recv = send + (xchg ? (size_t)world * np : 0);
-    hipLaunchKernelGGL(k_spectra_gather, dim3(nshells), dim3(256), 0, c->stream, sg, sgr, c->N1, c->N2, coef.gws_i, (double)m->nu, xchg ? send : recv,
-                       xchg ? world : 1, np);
-    HIPCHK(hipGetLastError());
+    if ((rc = launch(c, k_spectra_gather, dim3(nshells), dim3(256), 0, sg, sgr, c->N1, c->N2, coef.gws_i, (double)m->nu, xchg ? send : recv, xchg ? world : 1, np))) return rc;
     if (xchg && (rc = slab_gather(s, send, recv, 2 * np))) return rc;
-    hipLaunchKernelGGL(k_spectra_table, dim3(1), dim3(256), 0, c->stream, (const double *)recv, xchg ? world : 1, nshells, sg.dk, d_table);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_spectra_table, dim3(1), dim3(256), 0, (const double *)recv, xchg ? world : 1, nshells, sg.dk, d_table);
 }
 
-// ---- the entry points ----
-extern "C" int fb_model_get_vort(fb_model *m, float *d_vort)
+// ---- the entry points: one body per fb_model_X / fb_slab_X[_local] pair (fb_entry.h) ----
+static int get_vort(const Call &k, float *d_rows)
 {
-    if (!m || !d_vort) return fail(FB_EINVAL, "fb_model_get_vort: NULL");
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_VORT, d_vort);            // main.cpp:273-275
+    if (!d_rows) return refuse(k, "NULL output");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return record(k.m, k.s, REC_VORT, d_rows);              // main.cpp:273-275
 }
+extern "C" int fb_model_get_vort(fb_model *m, float *d_vort) { return get_vort(on_model("fb_model_get_vort", m), d_vort); }
+extern "C" int fb_slab_get_vort_local(fb_slab *s, float *d_rows) { return get_vort(on_slab("fb_slab_get_vort_local", s), d_rows); }
 
-extern "C" int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v)
+static int get_diag(const Call &k, float *d_psi, float *d_u, float *d_v)
 {
-    if (!m) return fail(FB_EINVAL, "model NULL");
-    NEED_SINGLE(m->c);
-    return record_diag(m, nullptr, d_psi, d_u, d_v);
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return record_diag(k.m, k.s, d_psi, d_u, d_v);
 }
+extern "C" int fb_model_get_diag(fb_model *m, float *d_psi, float *d_u, float *d_v) { return get_diag(on_model("fb_model_get_diag", m), d_psi, d_u, d_v); }
+extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v) { return get_diag(on_slab("fb_slab_get_diag_local", s), d_psi, d_u, d_v); }
 
-extern "C" int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau)
+static int get_okubo_weiss(const Call &k, float *d_w, float *d_tau)
 {
-    if (!m || (!d_w && !d_tau)) return fail(FB_EINVAL, "fb_model_get_okubo_weiss: NULL");
-    NEED_SINGLE(m->c);
-    return record(m, nullptr, REC_OW, d_w, d_tau);
+    if (!d_w && !d_tau) return refuse(k, "NULL outputs");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return record(k.m, k.s, REC_OW, d_w, d_tau);
 }
-
-extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_get_eddy_diffusivity: NULL model");
-    int rc;
-    if ((rc = keff_check("fb_model_get_eddy_diffusivity", d_table, nbins))) return rc;
-    NEED_SINGLE(m->c);
-    return record_keff(m, nullptr, nbins, d_table, d_zeta, d_grad2, nullptr, m->nu);
-}
-
-extern "C" int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres)
-{
-    if (!m) return fail(FB_EINVAL, "fb_model_get_pressure: NULL model");
-    long flat = 0;
-    int rc;
-    if ((rc = pres_check("fb_model_get_pressure", m->c, d_pres, ref_x, ref_y, &flat))) return rc;
-    NEED_SINGLE(m->c);
-    return record_pres(m, nullptr, rho, f, flat, d_pres);   // invert_pres.cpp:135-185
-}
-
-extern "C" int fb_slab_get_vort_local(fb_slab *s, float *d_rows)
-{
-    SLAB_READY(s);
-    if (!d_rows) return fail(FB_EINVAL, "fb_slab_get_vort_local: NULL");
-    return record(s->m, s, REC_VORT, d_rows);
-}
-
-extern "C" int fb_slab_get_diag_local(fb_slab *s, float *d_psi, float *d_u, float *d_v)
-{
-    SLAB_READY(s);
-    return record_diag(s->m, s, d_psi, d_u, d_v);
-}
-
+extern "C" int fb_model_get_okubo_weiss(fb_model *m, float *d_w, float *d_tau) { return get_okubo_weiss(on_model("fb_model_get_okubo_weiss", m), d_w, d_tau); }
 extern "C" int fb_slab_get_okubo_weiss_local(fb_slab *s, float *d_w_rows, float *d_tau_rows)
 {
-    SLAB_READY(s);
-    if (!d_w_rows && !d_tau_rows) return fail(FB_EINVAL, "fb_slab_get_okubo_weiss_local: NULL");
-    return record(s->m, s, REC_OW, d_w_rows, d_tau_rows);
+    return get_okubo_weiss(on_slab("fb_slab_get_okubo_weiss_local", s), d_w_rows, d_tau_rows);
 }
 
-// collective: the reference point's value reaches every rank through the transport (record_pres)
-extern "C" int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int ref_y, float *d_pres_rows)
+// the table of the vorticity, or with NEED_TRACER of the tracer with its own diffusivity.  Collective on a slab: the ranks' (min, max)
+// and histograms are all-gathered through the transport (keff_finish), every rank gets the whole table
+static int get_eddy_diffusivity(const Call &k, unsigned of, int nbins, double *d_table, float *d_field, float *d_grad2)
 {
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_pressure_local: NULL slab");
-    long flat = 0;
     int rc;
-    if ((rc = pres_check("fb_slab_get_pressure_local", s->c, d_pres_rows, ref_x, ref_y, &flat))) return rc;
-    SLAB_READY(s);
-    return record_pres(s->m, s, rho, f, flat, d_pres_rows);
+    if ((rc = keff_check(k, d_table, nbins)) || (rc = enter(k, NEED_TRANSPORT | of))) return rc;
+    fb_model *m = k.m;
+    return record_keff(m, k.s, nbins, d_table, d_field, d_grad2, of ? m->tr.c0 : nullptr, of ? m->kappa : m->nu);
 }
-
-// collective: the ranks' (min, max) and histograms are all-gathered through the transport (keff_finish), every rank gets the whole table
+extern "C" int fb_model_get_eddy_diffusivity(fb_model *m, int nbins, double *d_table, float *d_zeta, float *d_grad2)
+{
+    return get_eddy_diffusivity(on_model("fb_model_get_eddy_diffusivity", m), 0, nbins, d_table, d_zeta, d_grad2);
+}
 extern "C" int fb_slab_get_eddy_diffusivity(fb_slab *s, int nbins, double *d_table, float *d_zeta_rows, float *d_grad2_rows)
 {
-    SLAB_READY(s);
-    int rc;
-    if ((rc = keff_check("fb_slab_get_eddy_diffusivity", d_table, nbins))) return rc;
-    return record_keff(s->m, s, nbins, d_table, d_zeta_rows, d_grad2_rows, nullptr, s->m->nu);
+    return get_eddy_diffusivity(on_slab("fb_slab_get_eddy_diffusivity", s), 0, nbins, d_table, d_zeta_rows, d_grad2_rows);
 }
 
+// collective on a slab: the reference point's value reaches every rank through the transport (record_pres)
+static int get_pressure(const Call &k, float rho, float f, int ref_x, int ref_y, float *d_pres)
+{
+    if (!d_pres) return refuse(k, "NULL output");
+    long flat = 0;
+    int rc;
+    if ((rc = have_handle(k)) || (rc = pres_check(k, k.m->c, ref_x, ref_y, &flat)) || (rc = enter(k, NEED_TRANSPORT))) return rc;
+    return record_pres(k.m, k.s, rho, f, flat, d_pres);     // invert_pres.cpp:135-185
+}
+extern "C" int fb_model_get_pressure(fb_model *m, float rho, float f, int ref_x, int ref_y, float *d_pres)
+{
+    return get_pressure(on_model("fb_model_get_pressure", m), rho, f, ref_x, ref_y, d_pres);
+}
+extern "C" int fb_slab_get_pressure_local(fb_slab *s, float rho, float f, int ref_x, int ref_y, float *d_pres_rows)
+{
+    return get_pressure(on_slab("fb_slab_get_pressure_local", s), rho, f, ref_x, ref_y, d_pres_rows);
+}
+
+// collective on a slab: the ranks' centre candidates and sums are all-gathered through the transport (record_azimuthal), every rank
+// gets the whole table and the centre
+static int get_azimuthal(const Call &k, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
+{
+    if (!d_table || !d_center) return refuse(k, "NULL table or centre");
+    int rc;
+    if ((rc = have_handle(k)) || (rc = azim_check(k, k.m->c, center_mode, xc, yc, nbins, dr, nmodes)) || (rc = enter(k, NEED_TRANSPORT))) return rc;
+    return record_azimuthal(k.m, k.s, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
+}
 extern "C" int fb_model_get_azimuthal(fb_model *m, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_get_azimuthal: NULL model");
-    int rc;
-    if ((rc = azim_check("fb_model_get_azimuthal", m->c, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center))) return rc;
-    NEED_SINGLE(m->c);
-    return record_azimuthal(m, nullptr, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
+    return get_azimuthal(on_model("fb_model_get_azimuthal", m), center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
 }
-
-// collective: the ranks' centre candidates and sums are all-gathered through the transport (record_azimuthal), every rank gets the
-// whole table and the centre
 extern "C" int fb_slab_get_azimuthal(fb_slab *s, int center_mode, double xc, double yc, int nbins, double dr, int nmodes, double *d_table, double *d_center)
 {
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_azimuthal: NULL slab");
-    int rc;
-    if ((rc = azim_check("fb_slab_get_azimuthal", s->c, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center))) return rc;
-    SLAB_READY(s);
-    return record_azimuthal(s->m, s, center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
+    return get_azimuthal(on_slab("fb_slab_get_azimuthal", s), center_mode, xc, yc, nbins, dr, nmodes, d_table, d_center);
 }
 
-extern "C" int fb_model_get_spectra(fb_model *m, double *d_table)
+// collective on a slab: the ranks' partial sums are all-gathered through the transport (record_spectra), every rank gets the whole table
+static int get_spectra(const Call &k, double *d_table)
 {
-    if (!m) return fail(FB_EINVAL, "fb_model_get_spectra: NULL model");
-    if (!d_table) return fail(FB_EINVAL, "fb_model_get_spectra: NULL table");
-    NEED_SINGLE(m->c);
-    return record_spectra(m, nullptr, d_table);
+    if (!d_table) return refuse(k, "NULL table");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    return record_spectra(k.m, k.s, d_table);
 }
-
-// collective: the ranks' partial sums are all-gathered through the transport (record_spectra), every rank gets the whole table
-extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table)
-{
-    if (!s) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL slab");
-    if (!d_table) return fail(FB_EINVAL, "fb_slab_get_spectra: NULL table");
-    SLAB_READY(s);
-    return record_spectra(s->m, s, d_table);
-}
+extern "C" int fb_model_get_spectra(fb_model *m, double *d_table) { return get_spectra(on_model("fb_model_get_spectra", m), d_table); }
+extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table) { return get_spectra(on_slab("fb_slab_get_spectra", s), d_table); }

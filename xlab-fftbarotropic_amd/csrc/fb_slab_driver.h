@@ -21,19 +21,6 @@
 // first row chunk is exposed.  The granularity follows the local work a piece hides (slab_layout in fftbaro.hip): a
 // piece that hides less than a collective's latency is not cut off.
 #pragma once
-#include "fb_transport.h"
-
-struct fb_slab {
-    fb_ctx *c;
-    fb_model *m;
-    fb_transport tp;
-    bool connected, owns_streams;
-    hipStream_t comp, comm;
-    hipEvent_t ev_f[4], ev_r[8], ev_w4, ev_t, ev_tg[2], ev_rows_done, ev_fwd_done, ev_misc[2];
-    int nfg, nch;               // field groups of the derivative exchange (1, 2 or 4), row chunks of the tendency exchange (1..8)
-    int ncg;                    // active column groups (fb_ctx::nact): 2 = the stage is pipelined by column groups, and nfg == 1
-    int step_ops;               // exchange operations issued per RK stage (diagnostics)
-};
 
 // ---- schedule (host logic, no GPU needed): how finely one stage's two transposes are pipelined ----
 #define FB_OP_COL_BWD   1       /* arg = field group */
@@ -136,34 +123,35 @@ extern "C" int fb_slab_create(fb_slab **out, int nx, int ny, float lx, float ly,
     return FB_OK;
 }
 
-static int slab_connected(fb_slab *s, int rc)
+// the three ways to connect: `make` builds the transport of a slab that has none yet (a slab of one rank may connect one all the same)
+template <class Make> static int slab_connect(const Call &k, Make make)
 {
-    if (rc) return rc;
+    if (int rc = enter(k)) return rc;
+    fb_slab *s = k.s;
+    if (s->connected && s->c->world > 1) return refuse(k, "the slab is already connected");
+    if (int rc = make(&s->tp, s->c->rank, s->c->world)) return rc;
     s->connected = true;
     return FB_OK;
 }
-#define SLAB_CONNECT_GUARD(s) do { if (!(s)) return fail(FB_EINVAL, "slab NULL"); if ((s)->connected && (s)->c->world > 1) return fail(FB_EINVAL, "slab already connected"); } while (0)
 extern "C" int fb_slab_connect_rccl(fb_slab *s, const char *unique_id)
 {
-    SLAB_CONNECT_GUARD(s);
-    if (!unique_id) return fail(FB_EINVAL, "fb_slab_connect_rccl: NULL id");
-    return slab_connected(s, fb_transport_rccl(&s->tp, unique_id, s->c->rank, s->c->world));
+    const Call k = on_slab("fb_slab_connect_rccl", s);
+    if (!unique_id) return refuse(k, "NULL id");
+    return slab_connect(k, [&](fb_transport *tp, int rank, int world) { return fb_transport_rccl(tp, unique_id, rank, world); });
 }
 extern "C" int fb_slab_connect_local(fb_slab *s, void *hub)
 {
-    SLAB_CONNECT_GUARD(s);
-    return slab_connected(s, fb_transport_local(&s->tp, hub, s->c->rank, s->c->world));
+    return slab_connect(on_slab("fb_slab_connect_local", s), [&](fb_transport *tp, int rank, int world) { return fb_transport_local(tp, hub, rank, world); });
 }
 extern "C" int fb_slab_connect_callback(fb_slab *s, fb_alltoall_fn fn, void *user)
 {
-    SLAB_CONNECT_GUARD(s);
-    return slab_connected(s, fb_transport_callback(&s->tp, fn, user, s->c->rank, s->c->world));
+    return slab_connect(on_slab("fb_slab_connect_callback", s), [&](fb_transport *tp, int rank, int world) { return fb_transport_callback(tp, fn, user, rank, world); });
 }
 
 extern "C" int fb_slab_info(fb_slab *s, int *rows_local, int *cols_active, int *cols_frozen, int *ky0_active, int *ky0_frozen,
                             int *field_groups, int *row_chunks)
 {
-    if (!s) return fail(FB_EINVAL, "slab NULL");
+    if (int rc = enter(on_slab("fb_slab_info", s))) return rc;
     const fb_ctx *c = s->c;
     if (rows_local) *rows_local = c->XL;
     if (cols_active) *cols_active = c->world > 1 ? c->KA : c->grp[0].ncols;        // every active column group together
@@ -179,7 +167,7 @@ extern "C" int fb_slab_info(fb_slab *s, int *rows_local, int *cols_active, int *
 // -1 for transports without one) and the HIP device this rank computes on.
 extern "C" int fb_slab_transport_info(fb_slab *s, char *name, size_t cap, int *comm_ranks, int *comm_rank, int *comm_device, int *hip_device)
 {
-    if (!s) return fail(FB_EINVAL, "slab NULL");
+    if (int rc = enter(on_slab("fb_slab_transport_info", s))) return rc;
     // a transport that is connected is named, also on one rank (the one-GPU test of the RCCL call path connects one); "none" = one rank, nothing connected
     const char *nm = (s->tp.alltoall && s->tp.name) ? s->tp.name : (s->c->world == 1 ? "none" : "unconnected");
     if (name && cap) { strncpy(name, nm, cap - 1); name[cap - 1] = 0; }
@@ -206,8 +194,10 @@ __global__ void k_slab_pattern(float *buf, size_t count, int world, int rank, in
 }
 extern "C" int fb_slab_transport_selftest(fb_slab *s, size_t count, size_t *wrong_words)
 {
-    if (!s || !wrong_words || count == 0) return fail(FB_EINVAL, "fb_slab_transport_selftest: bad argument");
-    if (!s->tp.alltoall) return fail(FB_EINVAL, "fb_slab_transport_selftest: no transport connected");
+    const Call k = on_slab("fb_slab_transport_selftest", s);
+    if (!wrong_words || count == 0) return refuse(k, "bad argument");
+    if (int rc0 = enter(k)) return rc0;
+    if (!s->tp.alltoall) return refuse(k, "no transport connected");
     const int W = s->c->world;
     float *snd = nullptr, *rcv = nullptr; unsigned long long *bad = nullptr, hbad = 0;
     int rc = FB_OK;
@@ -268,16 +258,8 @@ static int slab_gather(fb_slab *s, const void *send, void *recv, size_t nfloats)
     if ((rc = s->tp.alltoall(s->tp.self, (const float *)send, (float *)recv, nfloats, 0, nfloats, s->comm))) return rc;
     return slab_after(s->comp, s->comm, s->ev_misc[1]);
 }
-#define SLAB_READY(s) do { if (!(s)) return fail(FB_EINVAL, "slab NULL"); if (!(s)->connected) return fail(FB_EINVAL, "slab model is not connected to a transport (fb_slab_connect_*)"); } while (0)
 
-// ---- the source (state in and the record outputs: fb_record.h) ----
-extern "C" int fb_slab_set_source_local(fb_slab *s, const float *d_rows)
-{
-    if (!s) return fail(FB_EINVAL, "slab NULL");
-    return fb_model_set_source(s->m, d_rows);               // this rank's [XL][ny] rows of vort_src (main-shallow-water.cpp:304), NULL = zeros
-}
-
-// ---- the step ----
+// ---- the step (the source: set_source, fftbaro.hip; state in and the record outputs: fb_record.h) ----
 static int slab_prime(fb_slab *s)
 {
     fb_ctx *c = s->c; fb_model *m = s->m;
@@ -378,13 +360,10 @@ static int slab_stage(fb_slab *s, int stage)
     return FB_OK;
 }
 
-extern "C" int fb_slab_step(fb_slab *s, int nsteps)
+// nsteps steps of this rank of the multi-GPU model
+static int slab_steps(fb_slab *s, int nsteps)
 {
-    SLAB_READY(s);
-    if (nsteps < 0) return fail(FB_EINVAL, "fb_slab_step: nsteps < 0");
-    if (nsteps == 0) return FB_OK;
     int rc;
-    if ((rc = adjoint_room(s->m, nsteps, "fb_slab_step"))) return rc;
     if (!s->m->primed) {
         if ((rc = slab_prime(s))) return rc;
         HIPCHK(hipEventRecord(s->ev_rows_done, s->comp));
@@ -393,19 +372,44 @@ extern "C" int fb_slab_step(fb_slab *s, int nsteps)
     if (s->ncg > 1 && s->m->primed == 1 && (rc = slab_groups_prologue(s))) return rc;
     for (int n = 0; n < nsteps; ++n)
         for (int k = 0; k < 4; ++k) {                       // main.cpp:288-317
-            if (s->m->tracer && (rc = tracer_stage(s->m, s, k))) return rc;
-            if (s->m->pt_n && (rc = particle_stage(s->m, k))) return rc;     // (one rank only: fb_slab_set_particles)
-            if (s->m->tangent && (rc = tangent_stage(s->m, s, k))) return rc; // (one rank only: fb_slab_set_tangent)
-            if (s->m->ad_depth && (rc = adjoint_stash(s->m, k))) return rc;   // (one rank only: fb_slab_adjoint_record)
-            if ((rc = slab_stage(s, k))) return rc;
-            if (k == 3 && s->m->ad_depth) ++s->m->ad_fill;
+            if ((rc = beside_stage(s->m, s, k)) || (rc = slab_stage(s, k))) return rc;
+            if (k == 3) beside_step_done(s->m);
         }
     return FB_OK;
 }
 
+// the step pair: fb_model_step (hipGraph replay where it applies, model_steps) and fb_slab_step
+static int run_steps(const Call &k, int nsteps) { return nsteps == 0 ? FB_OK : k.s ? slab_steps(k.s, nsteps) : model_steps(k.m, nsteps); }
+static int step(const Call &k, int nsteps)
+{
+    if (int rc = step_refusals(k, nsteps)) return rc;
+    return run_steps(k, nsteps);
+}
+extern "C" int fb_model_step(fb_model *m, int nsteps) { return step(on_model("fb_model_step", m), nsteps); }
+extern "C" int fb_slab_step(fb_slab *s, int nsteps) { return step(on_slab("fb_slab_step", s), nsteps); }
+
+// wall time of `nsteps` steps on the compute stream (HIP events); on a slab the caller takes the maximum over ranks
+static int time_steps(const Call &k, int nsteps, float *total_ms)
+{
+    if (!total_ms) return refuse(k, "NULL output");
+    if (int rc = step_refusals(k, nsteps)) return rc;
+    const hipStream_t st = k.m->c->stream;                  // (a slab's compute stream is its context's)
+    hipEvent_t e0, e1;
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    HIPCHK(hipEventRecord(e0, st));
+    const int rc = run_steps(k, nsteps);
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventElapsedTime(total_ms, e0, e1));
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    return rc;
+}
+extern "C" int fb_model_time_steps(fb_model *m, int nsteps, float *total_ms) { return time_steps(on_model("fb_model_time_steps", m), nsteps, total_ms); }
+extern "C" int fb_slab_time_steps(fb_slab *s, int nsteps, float *total_ms) { return time_steps(on_slab("fb_slab_time_steps", s), nsteps, total_ms); }
+
 extern "C" int fb_slab_synchronize(fb_slab *s)
 {
-    if (!s) return fail(FB_EINVAL, "slab NULL");
+    if (int rc = enter(on_slab("fb_slab_synchronize", s))) return rc;
     HIPCHK(hipStreamSynchronize(s->comp));
     HIPCHK(hipStreamSynchronize(s->comm));
     return FB_OK;
@@ -414,29 +418,17 @@ extern "C" int fb_slab_synchronize(fb_slab *s)
 // hand-overs between the rank's compute stream and a host-side copy stream (record path and source staging of the driver)
 extern "C" int fb_slab_record_event(fb_slab *s, void *event)
 {
-    if (!s || !event) return fail(FB_EINVAL, "fb_slab_record_event: NULL");
+    const Call k = on_slab("fb_slab_record_event", s);
+    if (!event) return refuse(k, "NULL event");
+    if (int rc = enter(k)) return rc;
     HIPCHK(hipEventRecord((hipEvent_t)event, s->comp));
     return FB_OK;
 }
 extern "C" int fb_slab_wait_event(fb_slab *s, void *event)
 {
-    if (!s || !event) return fail(FB_EINVAL, "fb_slab_wait_event: NULL");
+    const Call k = on_slab("fb_slab_wait_event", s);
+    if (!event) return refuse(k, "NULL event");
+    if (int rc = enter(k)) return rc;
     HIPCHK(hipStreamWaitEvent(s->comp, (hipEvent_t)event, 0));
     return FB_OK;
-}
-
-// wall time of `nsteps` steps on this rank's compute stream (HIP events); the caller takes the maximum over ranks
-extern "C" int fb_slab_time_steps(fb_slab *s, int nsteps, float *total_ms)
-{
-    SLAB_READY(s);
-    if (!total_ms) return fail(FB_EINVAL, "fb_slab_time_steps: NULL");
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, s->comp));
-    int rc = fb_slab_step(s, nsteps);
-    HIPCHK(hipEventRecord(e1, s->comp));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(total_ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return rc;
 }

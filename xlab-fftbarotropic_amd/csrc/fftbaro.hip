@@ -9,6 +9,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -534,14 +535,32 @@ static int grid_for(const fb_ctx *c, size_t n, int block = 256)
 
 #define NEED_SINGLE(c) do { if ((c)->world != 1) return fail(FB_EINVAL, "natural-layout entry point on a slab context (world > 1)"); } while (0)
 
+// one kernel launch on the context's stream, checked
+template <typename K, typename... A> static int launch(const fb_ctx *c, K kern, dim3 grid, dim3 block, size_t lds, const A &...args)
+{
+    hipLaunchKernelGGL(kern, grid, block, lds, c->stream, args...);
+    HIPCHK(hipGetLastError());
+    return FB_OK;
+}
+// pointwise: n elements over 256-thread workgroups, capped by the context's grid
+template <typename K, typename... A> static int launch_n(const fb_ctx *c, K kern, size_t n, const A &...args)
+{
+    return launch(c, kern, dim3(grid_for(c, n)), dim3(256), 0, args...);
+}
+
+// f(std::integral_constant<int, i>) for the run-time i in [0, N) (anything else: 0): a kernel's compile-time stage or mode count
+template <int N, class F> static int dispatch(int i, F &&f)
+{
+    if constexpr (N == 1) return f(std::integral_constant<int, 0>());
+    else return i == N - 1 ? f(std::integral_constant<int, N - 1>()) : dispatch<N - 1>(i, f);
+}
+
 template <int OP> static int launch_op(fb_ctx *c, const float *in, float *out)
 {
     if (!c || !in || !out) return fail(FB_EINVAL, "operator: NULL argument");
     NEED_SINGLE(c);
     const size_t total = (size_t)c->nx * c->hy;
-    hipLaunchKernelGGL((k_spec_op<OP>), dim3(grid_for(c, total)), dim3(256), 0, c->stream, make_coef(c), (const cf *)in, (cf *)out, c->hy, total);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch_n(c, k_spec_op<OP>, total, make_coef(c), (const cf *)in, (cf *)out, c->hy, total);
 }
 extern "C" int fb_gradx(fb_ctx *c, const float *i, float *o) { return launch_op<OP_GRADX>(c, i, o); }
 extern "C" int fb_grady(fb_ctx *c, const float *i, float *o) { return launch_op<OP_GRADY>(c, i, o); }
@@ -553,44 +572,38 @@ extern "C" int fb_backward_normalize(fb_ctx *c, float *d)
 {
     if (!c || !d) return fail(FB_EINVAL, "fb_backward_normalize: NULL");
     const size_t n = (size_t)c->nx * c->ny;
-    hipLaunchKernelGGL(k_scale_real, dim3(grid_for(c, n)), dim3(256), 0, c->stream, d, (float)(int)n, 1, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_scale_real, n, d, (float)(int)n, 1, n);
 }
 extern "C" int fb_negate(fb_ctx *c, float *d)
 {
     if (!c || !d) return fail(FB_EINVAL, "fb_negate: NULL");
     const size_t n = (size_t)c->nx * c->ny;
-    hipLaunchKernelGGL(k_scale_real, dim3(grid_for(c, n)), dim3(256), 0, c->stream, d, -1.0f, 0, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_scale_real, n, d, -1.0f, 0, n);
 }
 extern "C" int fb_jacobian(fb_ctx *c, const float *u, const float *v, const float *dx, const float *dy, const float *src, float *out)
 {
     if (!c || !u || !v || !dx || !dy || !out) return fail(FB_EINVAL, "fb_jacobian: NULL");
     const size_t n = (size_t)c->nx * c->ny;
-    hipLaunchKernelGGL(k_jacobian, dim3(grid_for(c, n)), dim3(256), 0, c->stream, u, v, dx, dy, src, out, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_jacobian, n, u, v, dx, dy, src, out, n);
 }
 extern "C" int fb_spec_axpy(fb_ctx *c, float *acc, const float *x, float a)
 {
     if (!c || !acc || !x) return fail(FB_EINVAL, "fb_spec_axpy: NULL");
     const size_t n = 2 * (size_t)c->nx * c->hy;
-    hipLaunchKernelGGL(k_spec_axpy, dim3(grid_for(c, n)), dim3(256), 0, c->stream, (const float *)acc, x, a, acc, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_spec_axpy, n, (const float *)acc, x, a, acc, n);
 }
 extern "C" int fb_spec_evolve(fb_ctx *c, const float *base, const float *rk, float a, float *out)
 {
     if (!c || !base || !rk || !out) return fail(FB_EINVAL, "fb_spec_evolve: NULL");
     const size_t n = 2 * (size_t)c->nx * c->hy;
-    hipLaunchKernelGGL(k_spec_axpy, dim3(grid_for(c, n)), dim3(256), 0, c->stream, base, rk, a, out, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_spec_axpy, n, base, rk, a, out, n);
 }
 extern "C" int fb_spec_rk4_combine(fb_ctx *c, const float *base, const float *k1, const float *k2, const float *k3,
                                    const float *k4, float dt, float *out)
 {
     if (!c || !base || !k1 || !k2 || !k3 || !k4 || !out) return fail(FB_EINVAL, "fb_spec_rk4_combine: NULL");
     const size_t n = 2 * (size_t)c->nx * c->hy;
-    hipLaunchKernelGGL(k_rk4_combine, dim3(grid_for(c, n)), dim3(256), 0, c->stream, base, k1, k2, k3, k4, dt, out, n);
-    HIPCHK(hipGetLastError()); return FB_OK;
+    return launch_n(c, k_rk4_combine, n, base, k1, k2, k3, k4, dt, out, n);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -612,11 +625,8 @@ static int set_max_lds(const fb_ctx *c, const void *fn, size_t bytes)
 // (its warm-up step) has launched every kernel of the step, and the pitch probe and the PRIME launch of k_col_full run eagerly too.
 template <typename K, typename... A> static int launch_lds(const fb_ctx *c, K kern, int grid, int block, size_t lds, const A &...args)
 {
-    int rc = set_max_lds(c, (const void *)kern, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(block), lds, c->stream, args...);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    if (int rc = set_max_lds(c, (const void *)kern, lds)) return rc;
+    return launch(c, kern, dim3(grid), dim3(block), lds, args...);
 }
 
 template <int N, int MODE> static int launch_row_t(fb_ctx *c, const RowArgs &a)
@@ -948,19 +958,13 @@ static int state_convert(fb_ctx *c, const ColGroup &G, const cf *in, cf *out, bo
     if (G.ncols == 0) return FB_OK;
     if (!state_tm(c)) { HIPCHK(hipMemcpyAsync(out, in, grp_elems(c, G) * sizeof(cf), hipMemcpyDeviceToDevice, c->stream)); return FB_OK; }
     const size_t total = grp_elems(c, G);
-    if (to_tm) hipLaunchKernelGGL((k_state_relayout<true>), dim3(grid_for(c, total)), dim3(256), 0, c->stream, in, out, c->nx, G.ncols, c->N2);
-    else hipLaunchKernelGGL((k_state_relayout<false>), dim3(grid_for(c, total)), dim3(256), 0, c->stream, in, out, c->nx, G.ncols, c->N2);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch_n(c, to_tm ? k_state_relayout<true> : k_state_relayout<false>, total, in, out, c->nx, G.ncols, c->N2);
 }
 
 static int relayout(fb_ctx *c, const cf *in, cf *out, bool to_private)
 {
     const size_t total = priv_elems(c);
-    if (to_private) hipLaunchKernelGGL((k_spec_relayout<true>), dim3(grid_for(c, total)), dim3(256), 0, c->stream, in, out, c->nx, c->hy, c->P, c->N1, c->N2);
-    else hipLaunchKernelGGL((k_spec_relayout<false>), dim3(grid_for(c, total)), dim3(256), 0, c->stream, in, out, c->nx, c->hy, c->P, c->N1, c->N2);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch_n(c, to_private ? k_spec_relayout<true> : k_spec_relayout<false>, total, in, out, c->nx, c->hy, c->P, c->N1, c->N2);
 }
 
 extern "C" int fb_r2c(fb_ctx *c, const float *d_in, float *d_out)
@@ -1061,6 +1065,21 @@ struct fb_model {
     bool adjoint;
 };
 
+// one rank of the multi-GPU model (fb_slab_driver.h)
+#include "fb_transport.h"
+struct fb_slab {
+    fb_ctx *c;
+    fb_model *m;
+    fb_transport tp;
+    bool connected, owns_streams;
+    hipStream_t comp, comm;
+    hipEvent_t ev_f[4], ev_r[8], ev_w4, ev_t, ev_tg[2], ev_rows_done, ev_fwd_done, ev_misc[2];
+    int nfg, nch;               // field groups of the derivative exchange (1, 2 or 4), row chunks of the tendency exchange (1..8)
+    int ncg;                    // active column groups (fb_ctx::nact): 2 = the stage is pipelined by column groups, and nfg == 1
+    int step_ops;               // exchange operations issued per RK stage (diagnostics)
+};
+#include "fb_entry.h"
+
 static int model_create_impl(fb_model **out, fb_ctx *c, float nu, float dt, bool phase_flow)
 {
     if (!out || !c) return fail(FB_EINVAL, "fb_model_create: NULL");
@@ -1096,17 +1115,24 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
     return model_create_impl(out, c, nu, dt, false);
 }
 
-static void model_drop_graph(fb_model *m);
-static void tracer_free(fb_model *m);
-static int tracer_stage(fb_model *m, struct fb_slab *s, int stage);     // fb_beside.h
-static void particles_free(fb_model *m);
-static int particle_stage(fb_model *m, int stage);                      // fb_beside.h
-static void tangent_free(fb_model *m);
-static int tangent_stage(fb_model *m, struct fb_slab *s, int stage);    // fb_beside.h
-static void adjoint_free(fb_model *m);
-static void adjoint_tape_free(fb_model *m);
-static int adjoint_room(const fb_model *m, int nsteps, const char *fn); // fb_beside.h: a step call that would overrun the tape is refused
-static int adjoint_stash(fb_model *m, int stage);                       // fb_beside.h
+// the fields stepped beside the vorticity (fb_beside.h): what the step and the model's end know of them
+static int beside_stage(fb_model *m, fb_slab *s, int stage);            // at the top of RK stage `stage` of fb_model_step and fb_slab_step
+static void beside_step_done(fb_model *m);                              // after the step's fourth stage
+static void beside_free_all(fb_model *m);
+
+static void model_drop_graph(fb_model *m)
+{
+    if (m->graph_exec) { hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
+}
+
+// the vorticity is replaced (state_in, fb_model_set_spectrum): the next fb_model_step starts with an eager (priming) step, and the
+// adjoint's tape belonged to the state that went
+static void state_replaced(fb_model *m)
+{
+    m->warmed = false;
+    m->primed = 0;
+    m->ad_fill = 0;
+}
 
 extern "C" int fb_model_destroy(fb_model *m)
 {
@@ -1128,18 +1154,14 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->azim_red) hipFree(m->azim_red);
     if (m->pres_ref) hipFree(m->pres_ref);
     if (m->spec_red) hipFree(m->spec_red);
-    tracer_free(m);
-    particles_free(m);
-    tangent_free(m);
-    adjoint_free(m);
-    adjoint_tape_free(m);
+    beside_free_all(m);
     delete m;
     return FB_OK;
 }
 
 extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
 {
-    if (!m) return fail(FB_EINVAL, "model NULL");
+    if (int rc = enter(on_model("fb_model_info", m))) return rc;
     const fb_ctx *c = m->c;
     if (hbm) {
         size_t n = m->src ? (size_t)c->XL * c->ny * 4 : 0;
@@ -1153,9 +1175,11 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
     return FB_OK;
 }
 
-extern "C" int fb_model_set_source(fb_model *m, const float *d_src)
+// this rank's [XL][ny] rows of vort_src (main-shallow-water.cpp:304; one GPU: every row), NULL = zeros
+static int set_source(const Call &k, const float *d_src)
 {
-    if (!m) return fail(FB_EINVAL, "model NULL");
+    if (int rc = enter(k)) return rc;
+    fb_model *m = k.m;
     fb_ctx *c = m->c;
     const size_t n = (size_t)c->XL * c->ny * sizeof(float);       // the caller's local rows
     // NULL: no source.  The row kernels test m->src alone, so the row flags (XL ints) are kept for the next source.
@@ -1163,19 +1187,18 @@ extern "C" int fb_model_set_source(fb_model *m, const float *d_src)
     if (!m->src_nz && hipMalloc((void **)&m->src_nz, (size_t)c->XL * sizeof(int)) != hipSuccess) { m->src_nz = nullptr; return fail(FB_ENOMEM, "source allocation failed"); }
     // the flags exist before the source is published: a model that goes on stepping after FB_ENOMEM never pairs a source with NULL flags
     if (!m->src && hipMalloc((void **)&m->src, n) != hipSuccess) { m->src = nullptr; return fail(FB_ENOMEM, "source allocation failed"); }
-    hipLaunchKernelGGL(k_src_row_flags, dim3(c->XL), dim3(256), 0, c->stream, d_src, m->src_nz, c->ny);
-    HIPCHK(hipGetLastError());
+    if (int rc = launch(c, k_src_row_flags, dim3(c->XL), dim3(256), 0, d_src, m->src_nz, c->ny)) return rc;
     // k_rowq and k_rowh read vort_src in their own physical-space order (so does k_rowh2, on an RK_ROWH_8192 context)
-    const dim3 grid(grid_for(c, (size_t)c->XL * c->ny / 2)), blk(256);
+    const size_t half = (size_t)c->XL * c->ny / 2;
     switch (c->row) {
-    case RK_ROWQ: hipLaunchKernelGGL(k_rowq_permute_src, grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
-    case RK_ROWH_8192: hipLaunchKernelGGL((k_rowh_permute_src<1>), grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
-    case RK_ROWH_16384: hipLaunchKernelGGL((k_rowh_permute_src<2>), grid, blk, 0, c->stream, d_src, m->src, c->XL); break;
+    case RK_ROWQ: return launch_n(c, k_rowq_permute_src, half, d_src, m->src, c->XL);
+    case RK_ROWH_8192: return launch_n(c, k_rowh_permute_src<1>, half, d_src, m->src, c->XL);
+    case RK_ROWH_16384: return launch_n(c, k_rowh_permute_src<2>, half, d_src, m->src, c->XL);
     default: HIPCHK(hipMemcpyAsync(m->src, d_src, n, hipMemcpyDeviceToDevice, c->stream)); return FB_OK;
     }
-    HIPCHK(hipGetLastError());
-    return FB_OK;
 }
+extern "C" int fb_model_set_source(fb_model *m, const float *d_src) { return set_source(on_model("fb_model_set_source", m), d_src); }
+extern "C" int fb_slab_set_source_local(fb_slab *s, const float *d_rows) { return set_source(on_slab("fb_slab_set_source_local", s), d_rows); }
 
 static MidArgs mid_args(fb_model *m, int g, int stage)
 {
@@ -1213,10 +1236,10 @@ static int full_import_state(fb_model *m, cf *spec3)
 {
     fb_ctx *c = m->c;
     const int ntiles = (c->ny / 2) / 8;
-    hipLaunchKernelGGL((k_full_relayout<true>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)spec3, m->gb[0].ZA, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy);
-    HIPCHK(hipGetLastError());
-    int rc = launch_col_full(m, 4);
-    if (rc) return rc;
+    int rc;
+    if ((rc = launch(c, k_full_relayout<true>, dim3(c->max_wg), dim3(256), 0, (const cf *)spec3, m->gb[0].ZA, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy)) ||
+        (rc = launch_col_full(m, 4)))
+        return rc;
     m->primed = 2;
     return FB_OK;
 }
@@ -1227,9 +1250,7 @@ static int full_export_state(fb_model *m, cf *dst)
     fb_ctx *c = m->c;
     HIPCHK(hipMemsetAsync(dst, 0, priv_elems(c) * sizeof(cf), c->stream));
     const int ntiles = (c->ny / 2) / 8;
-    hipLaunchKernelGGL((k_full_relayout<false>), dim3(c->max_wg), dim3(256), 0, c->stream, (const cf *)m->gb[0].ZA, dst, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy);
-    HIPCHK(hipGetLastError());
-    return FB_OK;
+    return launch(c, k_full_relayout<false>, dim3(c->max_wg), dim3(256), 0, (const cf *)m->gb[0].ZA, dst, c->P, c->N1, c->N2, ntiles, (int)m->xpass, c->hy);
 }
 
 // vort_c of column group g -> 3-pass layout in `dst`, whichever layout the state arrays have
@@ -1295,14 +1316,22 @@ struct StepProf {
 #define PROF_BEGIN(cls) do { if (prof && prof->begin(cls)) return fail(FB_EHIP, "event record failed"); } while (0)
 #define PROF_END(cls) do { if (prof && prof->end(cls)) return fail(FB_EHIP, "event record failed"); } while (0)
 
+// what a step call refuses before anything is launched: a bad count, the handle (enter), a call that would overrun the adjoint's tape
+static int step_refusals(const Call &k, int nsteps)
+{
+    if (nsteps < 0) return refuse(k, "bad argument: nsteps < 0");
+    if (int rc = enter(k, NEED_TRANSPORT)) return rc;
+    const fb_model *m = k.m;
+    if (m->ad_depth && nsteps > m->ad_depth - m->ad_fill)
+        return refuse(k, "the adjoint's tape has room for " + std::to_string(m->ad_depth - m->ad_fill) + " more steps (fb_model_adjoint_record)");
+    return FB_OK;
+}
+
 static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
 {
-    if (!m || nsteps < 0) return fail(FB_EINVAL, "fb_model_step: bad argument");
     fb_ctx *c = m->c;
-    if (c->world != 1 || m->phase_flow) return fail(FB_EINVAL, "fb_model_step on a slab model: drive it with fb_slab_step");
     int rc;
     if (nsteps == 0) return FB_OK;
-    if ((rc = adjoint_room(m, nsteps, "fb_model_step"))) return rc;
     if (m->xpass != XP_COLS && !m->primed) return fail(FB_EINVAL, "fb_model_step: set the state first");
     if (!m->primed && (rc = model_prime(m))) return rc;
     if (m->primed == 1 && m->xpass == XP_COLS) { if ((rc = model_col_bwd_active(m))) return rc; m->primed = 2; }
@@ -1310,10 +1339,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
     GroupBufs &B = m->gb[0];
     for (int s = 0; s < nsteps; ++s) {
         for (int k = 0; k < 4; ++k) {
-            if (m->tracer && (rc = tracer_stage(m, nullptr, k))) return rc;       // the tracer's stage k, from the state this stage starts from
-            if (m->pt_n && (rc = particle_stage(m, k))) return rc;                // the particles' stage k, likewise
-            if (m->tangent && (rc = tangent_stage(m, nullptr, k))) return rc;     // the tangent-linear model's stage k, likewise
-            if (m->ad_depth && (rc = adjoint_stash(m, k))) return rc;             // the adjoint's tape: the state stage k starts from
+            if ((rc = beside_stage(m, nullptr, k))) return rc;                    // their stage k, from the state this stage starts from
             // row pass on the derivative fields left by the previous stage (or the priming pass) ...
             PROF_BEGIN(1);
             if ((rc = launch_fused_row(m, 0, c->XL))) return rc;
@@ -1335,27 +1361,22 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
             if ((rc = launch_col_strided<+1>(c, G, B.w4_send, 4, (long)priv_elems(c), rowmap_natural(), 0, G.nct_active))) return rc;
             PROF_END(0);
         }
-        if (m->ad_depth) ++m->ad_fill;
+        beside_step_done(m);
     }
     return FB_OK;
 }
 
-static void model_drop_graph(fb_model *m)
-{
-    if (m->graph_exec) { hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
-}
-
 extern "C" int fb_model_use_graph(fb_model *m, int enable)
 {
-    if (!m) return fail(FB_EINVAL, "model NULL");
+    if (int rc = enter(on_model("fb_model_use_graph", m))) return rc;
     m->use_graph = enable != 0;
     if (!m->use_graph) model_drop_graph(m);
     return FB_OK;
 }
 
-extern "C" int fb_model_step(fb_model *m, int nsteps)
+// nsteps steps of the one-GPU model (the step pair's body: fb_slab_driver.h)
+static int model_steps(fb_model *m, int nsteps)
 {
-    if (!m || nsteps < 0) return fail(FB_EINVAL, "fb_model_step: bad argument");
     fb_ctx *c = m->c;
     // graph replay needs a capturable (non-null) stream, a primed pipeline and at least one eager step behind
     // us (kernel attributes are set on first launch); anything else runs eagerly.  So does a model that records the adjoint's tape:
@@ -1381,26 +1402,14 @@ extern "C" int fb_model_step(fb_model *m, int nsteps)
     return FB_OK;
 }
 
-extern "C" int fb_model_time_steps(fb_model *m, int nsteps, float *total_ms)
-{
-    if (!m || !total_ms) return fail(FB_EINVAL, "fb_model_time_steps: NULL");
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, m->c->stream));
-    int rc = fb_model_step(m, nsteps);
-    HIPCHK(hipEventRecord(e1, m->c->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    HIPCHK(hipEventElapsedTime(total_ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    return rc;
-}
-
 extern "C" int fb_model_profile_steps(fb_model *m, int nsteps, float *ms_sum, int *launches)
 {
-    if (!m || !ms_sum || !launches) return fail(FB_EINVAL, "fb_model_profile_steps: NULL");
+    const Call k = on_model("fb_model_profile_steps", m);
+    if (!ms_sum || !launches) return refuse(k, "NULL output");
+    int rc;
+    if ((rc = step_refusals(k, nsteps))) return rc;
     StepProf prof; prof.stream = m->c->stream;
-    if (!m->primed) { int rc0 = model_step_impl(m, 0, nullptr); (void)rc0; }
-    int rc = model_step_impl(m, nsteps, &prof);
+    rc = model_step_impl(m, nsteps, &prof);
     HIPCHK(hipStreamSynchronize(m->c->stream));
     for (int cls = 0; cls < 4; ++cls) {
         ms_sum[cls] = 0.f; launches[cls] = (int)prof.ev0[cls].size();
@@ -1416,9 +1425,10 @@ extern "C" int fb_model_profile_steps(fb_model *m, int nsteps, float *ms_sum, in
 
 extern "C" int fb_model_get_spectrum(fb_model *m, float *d_spec)
 {
-    if (!m || !d_spec) return fail(FB_EINVAL, "fb_model_get_spectrum: NULL");
-    NEED_SINGLE(m->c);
+    const Call k = on_model("fb_model_get_spectrum", m);
+    if (!d_spec) return refuse(k, "NULL output");
     int rc;
+    if ((rc = enter(k, NEED_TRANSPORT))) return rc;
     if ((rc = ensure_scratch(m->c))) return rc;
     if ((rc = export_state(m, 0, m->c->d_scratch))) return rc;
     return relayout(m->c, m->c->d_scratch, (cf *)d_spec, false);
@@ -1426,12 +1436,12 @@ extern "C" int fb_model_get_spectrum(fb_model *m, float *d_spec)
 
 extern "C" int fb_model_set_spectrum(fb_model *m, const float *d_spec)
 {
-    if (!m || !d_spec) return fail(FB_EINVAL, "fb_model_set_spectrum: NULL");
-    NEED_SINGLE(m->c);
-    m->primed = 0;
-    m->warmed = false;
-    m->ad_fill = 0;                                         // the adjoint's tape belongs to the state that is replaced
-    int rc = relayout(m->c, (const cf *)d_spec, m->gb[0].ZB, true);
+    const Call k = on_model("fb_model_set_spectrum", m);
+    if (!d_spec) return refuse(k, "NULL input");
+    int rc;
+    if ((rc = enter(k, NEED_TRANSPORT))) return rc;
+    state_replaced(m);
+    rc = relayout(m->c, (const cf *)d_spec, m->gb[0].ZB, true);
     if (rc) return rc;
     if (m->xpass != XP_COLS) return full_import_state(m, m->gb[0].ZB);
     return state_convert(m->c, m->c->grp[0], m->gb[0].ZB, m->gb[0].ZA, true);
