@@ -243,6 +243,37 @@ int fb_model_set_tangent(fb_model *m, const float *d_dz_real);             /* NU
 int fb_model_get_tangent(fb_model *m, float *d_dz_real);
 int fb_model_tangent_norm(fb_model *m, int kind, double *d_out);           /* 0 enstrophy, 1 energy */
 int fb_model_tangent_scale(fb_model *m, float a);                          /* finite, != 0 */
+/* Tangent subspace (no reference counterpart): up to FB_TANGENTS_MAX = 32 perturbations carried along the ONE trajectory, for several
+ * Lyapunov exponents, the Kaplan-Yorke dimension and the backward Lyapunov vectors.  fb_model_set_tangents takes `count` device fields
+ * [count][nx][ny] in, each as fb_model_set_tangent takes its one, and replaces whatever set was there; NULL removes all.  Every step
+ * advances them one after the other, each with exactly the launches of the single tangent: perturbation k is bit for bit what
+ * fb_model_set_tangent of the same field gives, and the vorticity, a tracer, particles, the adjoint and every record do not depend on
+ * the count.  fb_model_set_tangent(dz) is fb_model_set_tangents(dz, 1); fb_model_get_tangent, fb_model_tangent_norm and
+ * fb_model_tangent_scale act on perturbation 0.  fb_model_get_tangents: all of them, [count][nx][ny].  fb_model_tangent_count: 0 while
+ * none is set (not an error).  Memory per perturbation: 3 half spectra on the active columns, 1 on the frozen ones (at most 203 MB at 4096^2).
+ * The inner product of two perturbations is the bilinear form of fb_model_tangent_norm,
+ *   <a, b> = 1 / (2 GRIDS^2) sum over kx and ky <= ny/2 of w q Re(a_c conj(b_c)),   GRIDS = nx ny,
+ * summed in float64 over the resident half spectra, w = 1 in the columns ky = 0 and ky = ny/2 and 2 elsewhere; kind 0 (enstrophy):
+ * q = 1, <a, b> = <a b> / 2 (the mean over the grid); kind 1 (energy): q = |k|^2 / laplacian_coe^2 with the (0, 0) mode left out,
+ * <a, b> = <grad psi_a . grad psi_b> / 2.  <a, a> is what fb_model_tangent_norm returns.  The energy kind is a seminorm: a
+ * perturbation that is a constant has length 0.  Modes outside the dealiasing circle never evolve but do count in both kinds, so a
+ * set meant for exponents should be dealiased before it is set (or it keeps a component that neither grows nor decays).
+ * fb_model_tangent_gram: every <v_i, v_j> into the device array d_gram [count][count] float64, row-major, symmetric bit for bit (the
+ * upper triangle is computed, the lower copied).  fb_model_tangent_qr: modified Gram-Schmidt in place, in index order: for every j,
+ * r_ij = <q_i, v_j> of the current v_j and v_j -= r_ij q_i for i < j, then r_jj = sqrt(<v_j, v_j>) and v_j /= r_jj; every element
+ * formed in float64 and rounded once to float32 per update.  d_r [count][count] float64, row-major, is upper triangular with zeros
+ * below the diagonal and v_j(before) = sum over i <= j of r_ij q_i; ln r_jj summed over a run and divided by the time is the j-th
+ * Lyapunov exponent.  The coefficients stay on the device: nothing waits for the host.  A rank-deficient set shows as a diagonal
+ * element that is not finite and positive and as perturbations that are not finite; the engine does not test for it (the caller
+ * reads d_r anyway).  Every sum runs in a fixed order: two calls on one state give the same bits.  FB_EINVAL before any HIP call:
+ * count outside [1, 32] with a non-NULL field, kind outside {0, 1}, a NULL output, a NULL model, get / gram / qr without a tangent
+ * set.  Enqueued on the context stream, no synchronisation. */
+#define FB_TANGENTS_MAX 32
+int fb_model_set_tangents(fb_model *m, const float *d_dz_real, int count);  /* [count][nx][ny]; NULL: remove all */
+int fb_model_get_tangents(fb_model *m, float *d_dz_real);                   /* [count][nx][ny] */
+int fb_model_tangent_count(fb_model *m, int *count);                        /* 0 when none is set */
+int fb_model_tangent_gram(fb_model *m, int kind, double *d_gram);           /* [count][count] */
+int fb_model_tangent_qr(fb_model *m, int kind, double *d_r);                /* [count][count], upper triangular */
 /* Adjoint model (no reference counterpart): the transpose T^T of the tangent-linear step above under the inner product
  * <a, b> = sum over the grid of a b, so that <T dz, lam> = <dz, T^T lam> for the DISCRETE step: sensitivities of a scalar of the
  * final state to the initial vorticity, singular vectors of T, gradients for fitting an initial state to later data.  It runs
@@ -409,6 +440,12 @@ int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real);               /* NU
 int fb_slab_get_tangent(fb_slab *s, float *d_dz_real);
 int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out);
 int fb_slab_tangent_scale(fb_slab *s, float a);
+/* the tangent subspace (fb_model_set_tangents) of a slab of ONE rank, likewise */
+int fb_slab_set_tangents(fb_slab *s, const float *d_dz_real, int count);   /* NULL: remove all */
+int fb_slab_get_tangents(fb_slab *s, float *d_dz_real);
+int fb_slab_tangent_count(fb_slab *s, int *count);
+int fb_slab_tangent_gram(fb_slab *s, int kind, double *d_gram);
+int fb_slab_tangent_qr(fb_slab *s, int kind, double *d_r);
 /* the adjoint model (fb_model_adjoint_record) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EINVAL with a message. */
 int fb_slab_adjoint_record(fb_slab *s, int depth);

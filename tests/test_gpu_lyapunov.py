@@ -1,0 +1,371 @@
+"""The tangent subspace on the GPU (fb_model_set_tangents, fb_model_tangent_gram, fb_model_tangent_qr; kernels csrc/fb_tangent.h, host
+side csrc/fb_beside.h) against the single tangent it must reproduce bit for bit, the float64 subspace of tests/lyapunov_numpy.py and
+the analytic spectrum of a fluid at rest.  Every bar here is fixed by reasoning or by a CPU figure (tests/test_lyapunov_cpu.py), none
+by what the GPU gave; one line of figures per case (pytest -s); DESIGN.md, "Tangent subspace and Lyapunov spectrum", has the table."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (HERE, ROOT, os.path.join(ROOT, "oracle")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import entry_cases as E                                         # noqa: E402
+import lyapunov_numpy as Y                                      # noqa: E402
+import tangent_numpy as G                                       # noqa: E402
+import tracer_numpy as T                                        # noqa: E402
+from ref_numpy import rel_l2                                    # noqa: E402
+
+EPS32 = float(np.finfo(np.float32).eps)
+# the six grids of the adjoint's path matrix: every state-layout class of stage_vstate
+LAYOUT_GRIDS = ((256, 256), (192, 192), (1024, 64), (3072, 64), (4096, 64), (64, 4096))
+DEFECT_BAR = 4 * Y.MGS_F32_DEFECT       # the GPU's other summation order and its float32 r2c on top of the CPU's float32 storage
+
+
+def _ids(grids):
+    return ["%dx%d" % g for g in grids]
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _same(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    u = np.uint32 if a.dtype == np.float32 else np.uint64
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(u), b.view(u))
+
+
+def _slab():
+    from importlib import import_module
+    return import_module("xlab-fftbarotropic_amd.slab")
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(nx, ny):
+    out = Y.subspace_inputs(nx, ny)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def _gpu_model(nx, ny, vort, source=None, nu=G.NU, dt=None):
+    import xlab_fftbarotropic_amd as X
+    m = X.Model(nx, ny, nu=nu, dt=T.recipe_dt(nx, ny) if dt is None else dt)
+    m.set_vort(vort)
+    if source is not None:
+        m.set_source(source)
+    return m
+
+
+# ---- 1. each perturbation is the single tangent ----
+@pytest.mark.parametrize("nx,ny", LAYOUT_GRIDS, ids=_ids(LAYOUT_GRIDS))
+def test_each_perturbation_is_the_single_tangent_bit_for_bit(nx, ny):
+    """three perturbations, 5 steps with a source: tangents()[k] has the bits of tangent() of a run with set_tangent(w_k) alone, and
+    vort() those of a run without a tangent; at step 0 tangents() gives the input back to 1e-6.  At 256^2 also against the float64
+    subspace, with the single tangent's bars: 1e-5 and 4 times the vorticity's error."""
+    steps = 5
+    v0, W, src = _inputs(nx, ny)
+    m = _gpu_model(nx, ny, v0, src)
+    m.set_tangents(W)
+    assert m.tangent_count() == 3
+    e0 = max(rel_l2(a, b) for a, b in zip(_np(m.tangents()), W))
+    m.step(steps)
+    got, gv = _np(m.tangents()), _np(m.vort())
+    assert _same(got[0], _np(m.tangent()))                      # (the single-perturbation calls act on perturbation 0)
+    m.close()
+    assert e0 <= 1e-6
+    for k in range(3):
+        s = _gpu_model(nx, ny, v0, src)
+        s.set_tangent(W[k])
+        s.step(steps)
+        one = _np(s.tangent())
+        s.close()
+        assert _same(got[k], one), k
+        assert rel_l2(one, W[k]) > 1e-4
+    p = _gpu_model(nx, ny, v0, src)
+    p.step(steps)
+    assert _same(gv, _np(p.vort()))
+    p.close()
+    if (nx, ny) == (256, 256):
+        r = Y.SubspaceModel64(nx, ny, nu=G.NU, dt=T.recipe_dt(nx, ny))
+        r.set_vort(v0)
+        r.src = src.astype(np.float64)
+        r.set_tangents(W)
+        r.step(steps)
+        ev = rel_l2(gv, r.vort())
+        et = [rel_l2(a, b) for a, b in zip(got, r.tangents())]
+        print("subspace 256^2, %d steps, against float64: perturbations rel L2 = %s, vorticity %.3g" % (steps, ["%.3g" % e for e in et], ev))
+        assert ev <= 1e-5
+        for e in et:
+            assert e <= 1e-5 and e <= 4 * ev
+
+
+# ---- 2. the Gram matrix ----
+GRAM_GRIDS = ((64, 64), (192, 192), (1024, 64))
+
+
+@pytest.mark.parametrize("nx,ny", GRAM_GRIDS, ids=_ids(GRAM_GRIDS))
+def test_gram_matrix_against_float64(nx, ny):
+    """|G_ij - <w_i, w_j>| <= 1e-6 sqrt(<w_i, w_i> <w_j, w_j>), the bar tangent_norm is held to; G_00 is tangent_norm; two calls give
+    the same bits; G is symmetric bit for bit"""
+    v0, W, _ = _inputs(nx, ny)
+    ref = Y.SubspaceModel64(nx, ny)
+    V = Y.spectra(W)
+    m = _gpu_model(nx, ny, v0)
+    m.set_tangents(W)
+    for kind in Y.KINDS:
+        a, b, want = _np(m.tangent_gram(kind)), _np(m.tangent_gram(kind)), Y.gram(ref, V, kind)
+        d = np.sqrt(np.diagonal(want))
+        err = float((np.abs(a - want) / np.outer(d, d)).max())
+        n0 = m.tangent_norm(kind)
+        print("tangent_gram(%s) %dx%d: largest |G_ij - ref_ij| / sqrt(ref_ii ref_jj) = %.3g; G_00 / tangent_norm - 1 = %.3g" % (kind, nx, ny, err, a[0, 0] / n0 - 1))
+        assert a.shape == (3, 3) and a.dtype == np.float64
+        assert err <= 1e-6
+        assert abs(a[0, 0] / n0 - 1) <= 1e-12
+        assert _same(a, b)
+        assert _same(a, np.ascontiguousarray(a.T))
+        assert abs(want[0, 1]) > 0.1 * d[0] * d[1]               # (not a diagonal matrix)
+    m.close()
+
+
+# ---- 3. the orthonormalisation ----
+@pytest.mark.parametrize("kind", Y.KINDS)
+@pytest.mark.parametrize("nx,ny", Y.QR_GRIDS, ids=_ids(Y.QR_GRIDS))
+def test_orthonormalisation(nx, ny, kind):
+    """After orthonormalize_tangents: max |tangent_gram - I| <= 4 times the largest defect of the float32-storage restatement on the
+    CPU; R within 1e-6 max |R| of float64 modified Gram-Schmidt on the perturbations read back before it, upper triangular with a
+    positive diagonal; sum_i r_ij q_i gives those perturbations back to 1e-6; a second run gives the same bits; a second
+    orthonormalisation returns the identity to the defect bar."""
+    v0, W, _ = _inputs(nx, ny)
+    ref = Y.SubspaceModel64(nx, ny)
+    out = []
+    for run in range(2):
+        m = _gpu_model(nx, ny, v0)
+        m.set_tangents(W)
+        before = _np(m.tangents())
+        R = m.orthonormalize_tangents(kind)
+        out.append((R, _np(m.tangents())))
+        if run == 0:
+            gram = _np(m.tangent_gram(kind))
+            R2 = m.orthonormalize_tangents(kind)
+        m.close()
+    (R, Q), (Rb, Qb) = out
+    assert _same(R, Rb) and _same(Q, Qb)
+    _, want = Y.mgs(ref, Y.spectra(before), kind)
+    defect, dr = float(np.abs(gram - np.eye(3)).max()), float(np.abs(R - want).max() / np.abs(want).max())
+    back = max(rel_l2(sum(R[i, j] * Q[i].astype(np.float64) for i in range(j + 1)), before[j]) for j in range(3))
+    again = float(np.abs(R2 - np.eye(3)).max())
+    print("orthonormalize_tangents(%s) %dx%d: max |gram - I| = %.3g (bar %.3g, CPU float32 storage %.3g); max |R - R64| / max |R64| = %.3g; "
+          "Q R against the input, rel L2 = %.3g; second R: max |R - I| = %.3g" % (kind, nx, ny, defect, DEFECT_BAR, Y.MGS_F32_DEFECT, dr, back, again))
+    assert defect <= DEFECT_BAR
+    assert dr <= 1e-6
+    assert np.array_equal(R, np.triu(R)) and (np.diagonal(R) > 0).all()
+    assert abs(R[0, 1]) > 0.1 * R[1, 1]
+    assert back <= 1e-6
+    assert again <= DEFECT_BAR
+
+
+# ---- 4. fluid at rest ----
+def test_lyapunov_spectrum_of_three_modes_in_a_fluid_at_rest():
+    """zeta = 0, nu = 1e4: mode i decays by R(z_i) per step, z_i = -nu k_i^2 dt, and A, A + B, A + B + C are nested invariant
+    subspaces, so exponent i is ln R(z_i) / dt.  The bar is the single mode's (tests/test_gpu_tangent.py: about 4 n eps in the log
+    of the amplitude after n steps) plus two float32 roundings of every element per orthonormalisation.  The modes: every |z_i| >= 1e-3,
+    and steps |z_i - z_j| <= 1, so that what rounding leaves of a slower mode in a faster one's vector cannot outgrow it by more than e."""
+    n, nu, dt, steps, every = 256, 1.0e4, 3.0, 100, 25
+    modes = ((20, 30), (25, 35), (30, 40))
+    fields, z = [], []
+    for mx, my in modes:
+        psi, _, k2 = T.cellular_flow(n, n, amp=1.0e-6, mx=mx, my=my)
+        fields.append(psi)
+        z.append(-nu * k2 * dt)
+    z = np.array(z)
+    assert (np.abs(z) >= 1e-3).all() and steps * np.ptp(z) <= 1.0
+    A, B, Cm = fields
+    m = _gpu_model(n, n, np.zeros((n, n), np.float32), nu=nu, dt=dt)
+    m.set_tangents(np.array([A, A + B, A + B + Cm], dtype=np.float32))
+    lam, growth = m.lyapunov_spectrum(steps, every)
+    m.close()
+    want = np.log(T.rk4_factor(z)) / dt
+    bar = (4 * steps + 2 * (steps // every)) * EPS32 / (steps * np.abs(z)) + 1e-6
+    print("lyapunov_spectrum, 256^2, z = %s per step: %s s^-1, ln R / dt = %s; off by %s (bars %s)" % (z, lam, want, np.abs(lam / want - 1), bar))
+    assert growth.shape == (steps // every, 3) and lam.shape == (3,)
+    assert (np.abs(lam / want - 1) <= bar).all()
+
+
+# ---- 5. one perturbation ----
+def test_one_perturbation_agrees_with_lyapunov():
+    """set_tangents of one field and lyapunov_spectrum against set_tangent and lyapunov: the growth factors agree to the rounding of
+    `every` steps, every 4 eps32 + 1e-6 (the two renormalise to different lengths; the step is linear up to rounding)"""
+    n, steps, every = 64, 6, 2
+    v0, W, _ = _inputs(n, n)
+    a = _gpu_model(n, n, v0, dt=3.0)
+    a.set_tangent(W[0])
+    la, fa = a.lyapunov(steps, every)
+    a.close()
+    b = _gpu_model(n, n, v0, dt=3.0)
+    b.set_tangents(W[:1])
+    lb, gb = b.lyapunov_spectrum(steps, every)
+    b.close()
+    fb = np.exp(gb[:, 0])
+    print("one perturbation, 64^2: lyapunov %.9g s^-1, factors %s; lyapunov_spectrum %.9g s^-1, factors %s" % (la, fa, lb[0], fb))
+    assert gb.shape == (steps // every, 1)
+    for x, y in zip(fa, fb):
+        assert abs(x / y - 1) <= every * 4 * EPS32 + 1e-6
+    assert abs(la - lb[0]) * steps * 3.0 <= len(fa) * (every * 4 * EPS32 + 1e-6)
+
+
+# ---- 6. the captured step and combinations ----
+def test_graph_replay_gives_the_same_bits():
+    import torch
+    n = 256
+    v0, W, src = _inputs(n, n)
+    out = []
+    for graph in (False, True):
+        with torch.cuda.stream(torch.cuda.Stream()):
+            m = _gpu_model(n, n, v0, src)
+            m.fop.use_current_stream()
+            m.use_graph(graph)
+            m.set_tangents(W)
+            m.step(3)
+            m.step(3)                                           # captured and replayed
+            R = m.orthonormalize_tangents()                     # between replays, on the model's stream
+            m.step(3)
+            out.append((_np(m.tangents()), R, _np(m.vort())))
+            m.close()
+    for a, b in zip(*out):
+        assert _same(a, b)
+
+
+def test_tracer_particles_tape_and_tangents_together_match_each_alone():
+    import particles_numpy as P
+    n, steps = 256, 4
+    v0, W, src = _inputs(n, n)
+    c0 = T.noisy_inputs(n, n, Y.NOISE)[1]
+    x0 = P.seed_positions(n, n, 600000.0, 600000.0, 64, seed=5)
+
+    def run(tracer, particles, tape, tangents):
+        m = _gpu_model(n, n, v0, src, dt=3.0)
+        if tracer:
+            m.set_tracer(c0, kappa=T.RECIPE_KAPPA)
+        if particles:
+            m.set_particles(x0)
+        if tape:
+            m.record_adjoint(steps)
+        if tangents:
+            m.set_tangents(W)
+        m.step(steps)
+        lam = None
+        if tape:
+            m.set_adjoint(v0)
+            m.adjoint_back(steps)
+            lam = _np(m.adjoint())
+            m.record_adjoint(0)
+        out = (_np(m.vort()), _np(m.tracer()) if tracer else None, _np(m.particles()) if particles else None, lam, _np(m.tangents()) if tangents else None)
+        m.close()
+        return out
+    allv, allc, allp, alll, allt = run(True, True, True, True)
+    assert _same(allv, run(False, False, False, False)[0])
+    assert _same(allc, run(True, False, False, False)[1])
+    assert _same(allp, run(False, True, False, False)[2])
+    assert _same(alll, run(False, False, True, False)[3])
+    assert _same(allt, run(False, False, False, True)[4])
+    assert all(rel_l2(allt[k], W[k]) > 1e-4 for k in range(3))
+
+
+def test_slab_of_one_rank_matches_the_model():
+    import xlab_fftbarotropic_amd as X
+    S = _slab()
+    n, steps = 256, 3
+    v0, W, _ = _inputs(n, n)
+    out = []
+    for m in (X.Model(n, n, nu=G.NU, dt=3.0), S.EngineSlab(n, n, nu=G.NU, dt=3.0)):
+        (m.set_vort if isinstance(m, X.Model) else m.set_vort_local)(v0)
+        m.set_tangents(W)
+        m.step(steps)
+        t = _np(m.tangents())
+        out.append((t, m.orthonormalize_tangents("energy"), _np(m.tangents()), _np(m.tangent_gram("energy")), m.tangent_count()))
+        m.close()
+    for a, b in zip(*out):
+        assert _same(np.asarray(a), np.asarray(b))
+    assert out[0][4] == 3 and rel_l2(out[0][0][1], W[1]) > 1e-4
+
+
+# ---- 7. removal and refusals ----
+def test_removal_and_refusals():
+    import xlab_fftbarotropic_amd as X
+    n = 256
+    v0, W, _ = _inputs(n, n)
+    m = _gpu_model(n, n, v0)
+    for call in (m.tangents, m.tangent_gram, m.orthonormalize_tangents):
+        with pytest.raises(X.FftBaroError, match="no tangent is set"):
+            call()
+    assert m.tangent_count() == 0
+    m.set_tangents(W)
+    assert m.tangent_count() == 3
+    m.step(2)
+    m.set_tangent(W[1])
+    assert m.tangent_count() == 1 and tuple(m.tangents().shape) == (1, n, n)
+    assert rel_l2(_np(m.tangents())[0], W[1]) <= 1e-6
+    for kind in (2, -1):
+        for call in (m.tangent_gram, m.orthonormalize_tangents):
+            with pytest.raises(X.FftBaroError, match="kind"):
+                call(kind)
+    t = m.torch
+    for count in (0, 33):
+        with pytest.raises(X.FftBaroError, match="count outside"):
+            m._hand("set_tangents", t.zeros((1, n, n), dtype=t.float32, device="cuda"), count)
+    assert m.tangent_count() == 1
+    with_tangents = _np(m.vort())
+    m.set_tangents(None)
+    assert m.tangent_count() == 0
+    with pytest.raises(X.FftBaroError, match="no tangent is set"):
+        m.tangents()
+    m.step(2)                                                   # stepping goes on
+    after = _np(m.vort())
+    m.close()
+    ref = _gpu_model(n, n, v0)
+    ref.step(2)
+    assert _same(with_tangents, _np(ref.vort()))
+    ref.step(2)
+    assert _same(after, _np(ref.vort()))
+    ref.close()
+
+
+def test_identical_perturbations_are_refused_by_the_python_layer():
+    import xlab_fftbarotropic_amd as X
+    n = 64
+    v0, W, _ = _inputs(n, n)
+    m = _gpu_model(n, n, v0)
+    m.set_tangents(np.array([W[0], W[0], W[0]]))
+    with pytest.raises(X.FftBaroError, match="not linearly independent"):
+        m.orthonormalize_tangents()
+    m.set_tangents(None)
+    m.set_tangents(W)                                           # the model is usable again
+    R = m.orthonormalize_tangents()
+    m.step(2)
+    assert (np.diagonal(R) > 0).all() and np.isfinite(_np(m.tangents())).all() and np.isfinite(_np(m.vort())).all()
+    m.close()
+
+
+def test_slab_of_two_ranks_refuses_all_five():
+    """an unconnected slab, rank 0 of world 2 (tests/entry_cases.py): the tangent's refusal of several ranks, under each function's own name"""
+    h = E.Handles()
+    try:
+        calls = [("fb_slab_set_tangents", ["S", "field", 1]), ("fb_slab_get_tangents", ["S", "buf"]), ("fb_slab_tangent_count", ["S", "host"]),
+                 ("fb_slab_tangent_gram", ["S", 0, "buf"]), ("fb_slab_tangent_qr", ["S", 0, "buf"])]
+        for fn, args in calls:
+            rc, msg = h.call(fn, args)
+            assert rc == 1 and msg.startswith(fn + ": ") and "several ranks" in msg, (fn, rc, msg)
+        for fn, args in (("fb_model_get_tangents", ["M", "buf"]), ("fb_model_tangent_gram", ["M", 0, "buf"]), ("fb_model_tangent_qr", ["M", 0, "buf"])):
+            rc, msg = h.call(fn, args)
+            assert rc == 1 and msg.startswith(fn + ": ") and "no tangent is set" in msg, (fn, rc, msg)
+    finally:
+        h.close()

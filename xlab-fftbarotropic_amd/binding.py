@@ -72,7 +72,12 @@ _PAIRS = {
     "set_tangent": [_vp], "get_tangent": [_vp], "tangent_norm": [_ip, _vp], "tangent_scale": [_fl],
     "adjoint_record": [_ip], "adjoint_recorded": [_pip], "set_adjoint": [_vp], "get_adjoint": [_vp], "adjoint_back": [_ip],
 }
-for _name, _args in _PAIRS.items():
+# the tangent subspace's pairs, in a table of their own: _PAIRS is the set that the recorded refusal table (tests/golden/entry_refusals.json)
+# covers name by name, and that recording predates these
+_SUBSPACE_PAIRS = {
+    "set_tangents": [_vp, _ip], "get_tangents": [_vp], "tangent_count": [_pip], "tangent_gram": [_ip, _vp], "tangent_qr": [_ip, _vp],
+}
+for _name, _args in list(_PAIRS.items()) + list(_SUBSPACE_PAIRS.items()):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -180,6 +185,10 @@ def _entry(prefix, name):
 
 
 PARTICLES_MAX = 1 << 24
+TANGENTS_MAX = 32
+# orthonormalize_tangents: an update v -= r q rounds every element of v to float32, an error of up to eps32 / 2 of |v| + |r q|, about
+# eps32 |v|; what is left of a v that lay in the span of the q is that noise.  8 eps32 of its length: below this nothing but it is left.
+RANK_TOL = 8 * float(np.finfo(np.float32).eps)
 TANGENT_NORMS = {"enstrophy": 0, "energy": 1}
 
 
@@ -215,13 +224,47 @@ def lyapunov(model, steps, renorm_every, kind="enstrophy"):
     return total / (steps * model.dt), factors
 
 
+def lyapunov_spectrum(model, steps, renorm_every, kind="enstrophy"):
+    """The leading Lyapunov exponents from the tangent subspace of `model` (anything with step, orthonormalize_tangents and dt): one QR
+    first (its R discarded: the set as given need not be orthonormal), then per interval of renorm_every steps the model is stepped,
+    the perturbations are orthonormalised again and ln r_ii is accumulated.  Returns (exponents, float64 [M] in s^-1: the sums of
+    ln r_ii / (steps dt), in the order of the perturbations; log_growth, float64 [intervals, M]: ln r_ii per interval).  The
+    perturbations are left orthonormal: the backward Lyapunov vectors of the run so far."""
+    if steps < 1 or renorm_every < 1:
+        raise ValueError("lyapunov_spectrum: steps and renorm_every must be >= 1")
+    model.orthonormalize_tangents(kind)
+    rows, done = [], 0
+    while done < steps:
+        k = min(renorm_every, steps - done)
+        model.step(k)
+        done += k
+        rows.append(np.log(np.diagonal(model.orthonormalize_tangents(kind))))
+    log_growth = np.array(rows, dtype=np.float64)
+    return log_growth.sum(axis=0) / (steps * model.dt), log_growth
+
+
+def kaplan_yorke(exponents):
+    """The Kaplan-Yorke (Lyapunov) dimension of a set of exponents, in any order: with them sorted downward and j the largest count
+    whose partial sum is >= 0, j + (that sum) / |lambda_(j+1)|; 0.0 when the largest is negative, float(M) when the whole sum is >= 0
+    (the M exponents do not reach the attractor's dimension).  Host logic, no GPU."""
+    lam = np.sort(np.asarray(exponents, dtype=np.float64).ravel())[::-1]
+    if lam.size == 0 or lam[0] < 0.0:
+        return 0.0
+    sums = np.cumsum(lam)
+    j = int(np.nonzero(sums >= 0.0)[0].max()) + 1
+    if j == lam.size:
+        return float(j)
+    return j + float(sums[j - 1]) / abs(float(lam[j]))
+
+
 def singular_values(model, steps, iters, start, save=None, restore=None):
     """Power iteration on T^T T in the L2 (enstrophy) norm on `model` (anything with set_tangent, tangent, record_adjoint, step,
     set_adjoint, adjoint_back, adjoint; save / restore: how its state is kept and put back, by default spectrum / set_spectrum,
     which restores every bit), T the tangent of `steps` steps from the model's current state.  Each
     iteration restores that state, sets the tangent to the unit vector v (from `start`, an [nx, ny] field), steps with recording on,
     sets lam = T v, sweeps back and normalises v = T^T T v.  Returns (sigma = |T v| per iteration, the final v as a tensor); the model
-    is left at its starting state with the tape freed, the tangent set to the last v and lam to T^T T of it."""
+    is left at its starting state with the tape freed, the tangent set to the last v and lam to T^T T of it.  It works through
+    set_tangent, which replaces whatever set of perturbations was there (a tangent subspace too) by the one."""
     if steps < 1 or iters < 1:
         raise ValueError("singular_values: steps and iters must be >= 1")
     t = model.torch
@@ -556,6 +599,61 @@ class ModelSurface:
     def lyapunov(self, steps, renorm_every, kind="enstrophy"):
         """(exponent [s^-1], growth factors): steps the model, renormalising the perturbation every renorm_every steps (lyapunov())."""
         return lyapunov(self, steps, renorm_every, kind)
+
+    def set_tangents(self, dz):
+        """Sets a tangent subspace: M perturbations, [M, nx, ny] (numpy or torch, 1 <= M <= TANGENTS_MAX), carried along the ONE
+        trajectory, each as set_tangent carries its one (perturbation k is bit for bit what set_tangent of dz[k] gives); whatever set
+        was there is replaced; dz=None removes all.  tangent(), tangent_norm() and rescale_tangent() act on perturbation 0.  Modes
+        outside the dealiasing circle never evolve but count in every inner product: dealiase a set that is meant for exponents.  One
+        rank only, as set_tangent."""
+        t = self.torch
+        self._one_rank("set_tangents", None, 1)
+        if dz is None:
+            return self._hand("set_tangents", None, 0)
+        if isinstance(dz, np.ndarray):
+            dz = t.from_numpy(np.ascontiguousarray(dz, dtype=np.float32)).cuda()
+        assert dz.is_cuda and dz.dtype == t.float32 and dz.is_contiguous() and dz.dim() == 3 and tuple(dz.shape[1:]) == self._shape
+        self._hand("set_tangents", dz, int(dz.shape[0]))
+
+    def tangent_count(self): return self._count("tangent_count")
+
+    def _tangent_rows(self):
+        """the number of perturbations for an output's shape; with none set 1, so that the engine's own refusal is what is raised"""
+        return max(self.tangent_count(), 1)
+
+    def tangents(self):
+        """every perturbation, float32 [M, nx, ny]"""
+        out = self.torch.empty((self._tangent_rows(),) + self._shape, dtype=self.torch.float32, device="cuda")
+        self._hand("get_tangents", out)
+        return out
+
+    def _tangent_pairs(self, name, kind):
+        m = self._tangent_rows()
+        out = self.torch.empty((m, m), dtype=self.torch.float64, device="cuda")
+        self._hand(name, tangent_kind(kind), out)
+        return out
+
+    def tangent_gram(self, kind="enstrophy"):
+        """The Gram matrix of the perturbations, a float64 [M, M] tensor on the GPU: <v_i, v_j> in the inner product whose <v, v> is
+        tangent_norm(kind), summed in float64 on the GPU; symmetric bit for bit."""
+        return self._tangent_pairs("tangent_gram", kind)
+
+    def orthonormalize_tangents(self, kind="enstrophy"):
+        """Orthonormalises the perturbations in place in that inner product (modified Gram-Schmidt on the GPU, in their order) and
+        returns R, float64 [M, M] numpy, upper triangular, with v_j (before) = sum over i <= j of R[i, j] q_i.  Raises FftBaroError
+        for a rank-deficient set: R's diagonal is not finite and positive, or r_jj <= RANK_TOL |v_j (before)|, which in float32 storage
+        is what an exactly dependent v_j leaves (the rounding of its updates, not zero).  The perturbations are then not finite, or
+        noise: set them again."""
+        r = self._tangent_pairs("tangent_qr", kind).cpu().numpy()
+        d = np.diagonal(r)
+        if not (np.isfinite(r).all() and (d > RANK_TOL * np.sqrt((r * r).sum(axis=0))).all()):
+            raise FftBaroError("orthonormalize_tangents: the perturbations are not linearly independent in the %s inner product (diagonal of R: %s)" % (kind, d))
+        return r
+
+    def lyapunov_spectrum(self, steps, renorm_every, kind="enstrophy"):
+        """(exponents [M] in s^-1, log_growth [intervals, M]): steps the model, orthonormalising the perturbations every renorm_every
+        steps (lyapunov_spectrum())."""
+        return lyapunov_spectrum(self, steps, renorm_every, kind)
 
     def record_adjoint(self, depth):
         """Turns the adjoint's tape on (depth >= 1: room for depth steps; every step from now on records its four stage states, and a

@@ -168,15 +168,15 @@ static int set_tracer(const Call &k, const float *d_rows, float kappa)
 extern "C" int fb_model_set_tracer(fb_model *m, const float *d_c_real, float kappa) { return set_tracer(on_model("fb_model_set_tracer", m), d_c_real, kappa); }
 extern "C" int fb_slab_set_tracer_local(fb_slab *s, const float *d_rows, float kappa) { return set_tracer(on_slab("fb_slab_set_tracer_local", s), d_rows, kappa); }
 
-// the real field of a field stepped beside the vorticity (the model's member `f`: its base arrays, in the 3-pass layout), as the
+// the real field of a field stepped beside the vorticity (f(m): its base arrays, in the 3-pass layout), as the
 // vorticity's own record
-static int get_beside(const Call &k, unsigned needs, Beside fb_model::*f, float *d_rows)
+static int get_beside(const Call &k, unsigned needs, Beside *(*f)(fb_model *), float *d_rows)
 {
     if (!d_rows) return refuse(k, "NULL output");
     if (int rc = enter(k, needs)) return rc;
-    return record(k.m, k.s, REC_VORT, d_rows, nullptr, (k.m->*f).c0);
+    return record(k.m, k.s, REC_VORT, d_rows, nullptr, f(k.m)->c0);
 }
-static int get_tracer(const Call &k, float *d_rows) { return get_beside(k, NEED_TRANSPORT | NEED_TRACER, &fb_model::tr, d_rows); }
+static int get_tracer(const Call &k, float *d_rows) { return get_beside(k, NEED_TRANSPORT | NEED_TRACER, [](fb_model *m) { return &m->tr; }, d_rows); }
 extern "C" int fb_model_get_tracer(fb_model *m, float *d_c_real) { return get_tracer(on_model("fb_model_get_tracer", m), d_c_real); }
 extern "C" int fb_slab_get_tracer_local(fb_slab *s, float *d_rows) { return get_tracer(on_slab("fb_slab_get_tracer_local", s), d_rows); }
 
@@ -193,46 +193,56 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
 // ---- the tangent-linear model (kernels: fb_tangent.h) ----
 static void tangent_free(fb_model *m)
 {
-    beside_free(m->tg);
+    for (Beside &f : m->tg) beside_free(f);
     for (cf *&p : m->tg_j) if (p) { hipFree(p); p = nullptr; }
     if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
+    m->tg_n = 0;
     m->tangent = false;
 }
 
-// One RK stage of the perturbation, where tracer_stage runs and from the same states.  The tangent of the bilinear J is two advect
-// passes, J(dz; psi) + J(zeta; dpsi); the first pass's result is copied to tg_j before the second overwrites the record workspace;
-// then the update with both and the model's nu.
+// One RK stage of the perturbations, where tracer_stage runs and from the same states, one perturbation after the other in index
+// order.  The tangent of the bilinear J is two advect passes, J(dz; psi) + J(zeta; dpsi); the first pass's result is copied to tg_j
+// before the second overwrites the record workspace; then the update with both and the model's nu.  Nothing is shared between two
+// perturbations but the scratch: perturbation k of a set is bit for bit the single tangent started from the same field.
 static int tangent_stage(fb_model *m, fb_slab *s, int stage)
 {
     fb_ctx *c = m->c;
     int rc;
-    if ((rc = beside_advect(m, s, stage, &m->tg, nullptr))) return rc;
-    for (int g = 0; g < c->nact; ++g) {
-        const size_t n = grp_elems(c, c->grp[g]);
-        if (n) HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < m->tg_n; ++k) {
+        Beside &f = m->tg[k];
+        if ((rc = beside_advect(m, s, stage, &f, nullptr))) return rc;
+        for (int g = 0; g < c->nact; ++g) {
+            const size_t n = grp_elems(c, c->grp[g]);
+            if (n) HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        }
+        if ((rc = beside_advect(m, s, stage, nullptr, &f))) return rc;
+        if ((rc = beside_update(m, s, stage, f, m->tg_j, m->nu))) return rc;
     }
-    if ((rc = beside_advect(m, s, stage, nullptr, &m->tg))) return rc;
-    return beside_update(m, s, stage, m->tg, m->tg_j, m->nu);
+    return FB_OK;
 }
 
-// The perturbation in (beside_begin, beside_in) with the scratch of the first advect pass and the partial sums of the norm
-// ([ngroups][max_wg] float64); d_rows == NULL removes it.
-static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows)
+// `count` perturbations in, d_rows [count] real fields one after the other (beside_begin, beside_in each), with the scratch of the
+// first advect pass and the partial sums of a norm or an inner product ([ngroups][max_wg] float64); whatever set was there is
+// replaced, perturbations beyond `count` freed; d_rows == NULL removes all.
+static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
 {
     fb_ctx *c = m->c;
     int rc;
-    if ((rc = beside_begin(m, !d_rows && m->tangent))) return rc;
+    if ((rc = beside_begin(m, m->tangent && (!d_rows || count < m->tg_n)))) return rc;
     if (!d_rows) { tangent_free(m); return FB_OK; }
     for (int g = 0; g < c->nact && !rc; ++g)
         if (grp_elems(c, c->grp[g])) rc = rec_alloc((void **)&m->tg_j[g], grp_elems(c, c->grp[g]) * sizeof(cf));
     if (!rc) rc = rec_alloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double));
-    if (rc || (rc = beside_in(m, s, d_rows, m->tg))) { tangent_free(m); return rc; }
+    for (int k = 0; k < count && !rc; ++k) rc = beside_in(m, s, d_rows + (size_t)k * c->XL * c->ny, m->tg[k]);
+    if (rc) { tangent_free(m); return rc; }
+    for (int k = count; k < m->tg_n; ++k) beside_free(m->tg[k]);
+    m->tg_n = count;
     m->tangent = true;
     return FB_OK;
 }
 
 // kind 0: the enstrophy norm <dz^2> / 2, kind 1: the energy norm <|grad dpsi|^2> / 2 (means over the grid), of the resident spectrum
-// (k_tangent_norm per column group, then k_tangent_norm_final over every partial sum) into *d_out on the device
+// of perturbation 0 (k_tangent_norm per column group, then k_tangent_norm_final over every partial sum) into *d_out on the device
 static int tangent_norm(fb_model *m, int kind, double *d_out)
 {
     fb_ctx *c = m->c;
@@ -243,7 +253,7 @@ static int tangent_norm(fb_model *m, int kind, double *d_out)
         const size_t n = grp_elems(c, G);
         if (n == 0) continue;
         const int nwg = grid_for(c, n / 2);
-        if (int rc = launch(c, k_tangent_norm, dim3(nwg), dim3(256), 0, coef, (const cf *)m->tg.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
+        if (int rc = launch(c, k_tangent_norm, dim3(nwg), dim3(256), 0, coef, (const cf *)m->tg[0].c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
         np += nwg;
     }
     const double grids = (double)c->nx * c->ny;
@@ -256,7 +266,68 @@ static int tangent_scale(fb_model *m, float a)
     for (int g = 0; g < c->ngroups; ++g) {
         const size_t n = grp_elems(c, c->grp[g]);
         if (n == 0) continue;
-        if (int rc = launch_n(c, k_tangent_scale, n / 2, m->tg.c0[g], n, a)) return rc;
+        if (int rc = launch_n(c, k_tangent_scale, n / 2, m->tg[0].c0[g], n, a)) return rc;
+    }
+    return FB_OK;
+}
+
+// <a, b> of two perturbations into *d_out on the device, with tangent_norm's grids, weights and scale: <a, a> is tangent_norm's norm
+// (k_tangent_dot per column group, then k_tangent_dot_final over every partial sum, through the one tg_red: calls follow each other
+// on the one stream)
+static int tangent_dot(fb_model *m, int kind, const Beside &a, const Beside &b, double *d_out)
+{
+    fb_ctx *c = m->c;
+    const SpecCoef coef = make_coef(c);
+    int np = 0;
+    for (int g = 0; g < c->ngroups; ++g) {
+        const ColGroup &G = c->grp[g];
+        const size_t n = grp_elems(c, G);
+        if (n == 0) continue;
+        const int nwg = grid_for(c, n / 2);
+        if (int rc = launch(c, k_tangent_dot, dim3(nwg), dim3(256), 0, coef, (const cf *)a.c0[g], (const cf *)b.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
+        np += nwg;
+    }
+    const double grids = (double)c->nx * c->ny;
+    return launch(c, k_tangent_dot_final, dim3(1), dim3(256), 0, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
+}
+
+// every <v_i, v_j> into the device array d_gram, [tg_n][tg_n] float64 row-major: the upper triangle through tangent_dot, mirrored
+static int tangent_gram(fb_model *m, int kind, double *d_gram)
+{
+    const int M = m->tg_n;
+    for (int i = 0; i < M; ++i)
+        for (int j = i; j < M; ++j)
+            if (int rc = tangent_dot(m, kind, m->tg[i], m->tg[j], d_gram + (size_t)i * M + j)) return rc;
+    return launch(m->c, k_tangent_mirror, dim3(1), dim3(256), 0, d_gram, M);
+}
+
+// Modified Gram-Schmidt in place on the bases, in index order: for every j, r_ij = <q_i, v_j> of the CURRENT v_j and v_j -= r_ij q_i
+// for i < j, then r_jj = sqrt(<v_j, v_j>) and v_j /= r_jj.  d_r, a device array [tg_n][tg_n] float64 row-major, ends upper triangular
+// with v_j(old) = sum over i <= j of r_ij q_i; every coefficient is written there by one kernel and read from there by the next, so
+// the host waits for nothing.  A rank-deficient set leaves a diagonal element that is not finite and positive and vectors that are
+// not finite; nothing here tests for it.  The stage arrays hold no live data between two steps: only the bases change.
+static int tangent_qr(fb_model *m, int kind, double *d_r)
+{
+    fb_ctx *c = m->c;
+    const int M = m->tg_n;
+    int rc;
+    HIPCHK(hipMemsetAsync(d_r, 0, (size_t)M * M * sizeof(double), c->stream));
+    for (int j = 0; j < M; ++j) {
+        Beside &v = m->tg[j];
+        for (int i = 0; i < j; ++i) {
+            double *r = d_r + (size_t)i * M + j;
+            if ((rc = tangent_dot(m, kind, m->tg[i], v, r))) return rc;
+            for (int g = 0; g < c->ngroups; ++g) {
+                const size_t n = grp_elems(c, c->grp[g]);
+                if (n && (rc = launch_n(c, k_tangent_axpy, n / 2, v.c0[g], (const cf *)m->tg[i].c0[g], n, (const double *)r))) return rc;
+            }
+        }
+        double *r = d_r + (size_t)j * M + j;
+        if ((rc = tangent_dot(m, kind, v, v, r)) || (rc = launch(c, k_tangent_sqrt, dim3(1), dim3(64), 0, r))) return rc;
+        for (int g = 0; g < c->ngroups; ++g) {
+            const size_t n = grp_elems(c, c->grp[g]);
+            if (n && (rc = launch_n(c, k_tangent_scale_dev, n / 2, v.c0[g], n, (const double *)r))) return rc;
+        }
     }
     return FB_OK;
 }
@@ -267,12 +338,12 @@ constexpr unsigned TANGENT = NEED_TRANSPORT | ONE_RANK_TANGENT, TANGENT_SET = TA
 static int set_tangent(const Call &k, const float *d_dz_real)
 {
     if (int rc = enter(k, TANGENT)) return rc;
-    return tangent_in(k.m, k.s, d_dz_real);
+    return tangent_in(k.m, k.s, d_dz_real, 1);
 }
 extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real) { return set_tangent(on_model("fb_model_set_tangent", m), d_dz_real); }
 extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real) { return set_tangent(on_slab("fb_slab_set_tangent", s), d_dz_real); }
 
-static int get_tangent(const Call &k, float *d_dz_real) { return get_beside(k, TANGENT_SET, &fb_model::tg, d_dz_real); }
+static int get_tangent(const Call &k, float *d_dz_real) { return get_beside(k, TANGENT_SET, [](fb_model *m) { return &m->tg[0]; }, d_dz_real); }
 extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real) { return get_tangent(on_model("fb_model_get_tangent", m), d_dz_real); }
 extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real) { return get_tangent(on_slab("fb_slab_get_tangent", s), d_dz_real); }
 
@@ -294,6 +365,52 @@ static int tangent_scale(const Call &k, float a)
 }
 extern "C" int fb_model_tangent_scale(fb_model *m, float a) { return tangent_scale(on_model("fb_model_tangent_scale", m), a); }
 extern "C" int fb_slab_tangent_scale(fb_slab *s, float a) { return tangent_scale(on_slab("fb_slab_tangent_scale", s), a); }
+
+// the tangent subspace: [count] fields in or out, the count, and the two calls on every pair of bases
+static int set_tangents(const Call &k, const float *d_dz_real, int count)
+{
+    if (d_dz_real && (count < 1 || count > FB_TANGENTS_MAX)) return refuse(k, "count outside [1, 32]");
+    if (int rc = enter(k, TANGENT)) return rc;
+    return tangent_in(k.m, k.s, d_dz_real, count);
+}
+extern "C" int fb_model_set_tangents(fb_model *m, const float *d_dz_real, int count) { return set_tangents(on_model("fb_model_set_tangents", m), d_dz_real, count); }
+extern "C" int fb_slab_set_tangents(fb_slab *s, const float *d_dz_real, int count) { return set_tangents(on_slab("fb_slab_set_tangents", s), d_dz_real, count); }
+
+static int get_tangents(const Call &k, float *d_dz_real)
+{
+    if (!d_dz_real) return refuse(k, "NULL output");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    const fb_ctx *c = k.m->c;
+    for (int v = 0; v < k.m->tg_n; ++v)
+        if (int rc = record(k.m, k.s, REC_VORT, d_dz_real + (size_t)v * c->XL * c->ny, nullptr, k.m->tg[v].c0)) return rc;
+    return FB_OK;
+}
+extern "C" int fb_model_get_tangents(fb_model *m, float *d_dz_real) { return get_tangents(on_model("fb_model_get_tangents", m), d_dz_real); }
+extern "C" int fb_slab_get_tangents(fb_slab *s, float *d_dz_real) { return get_tangents(on_slab("fb_slab_get_tangents", s), d_dz_real); }
+
+// (0 while none is set: not a refusal)
+static int tangent_count(const Call &k, int *count)
+{
+    if (!count) return refuse(k, "NULL output");
+    if (int rc = enter(k, TANGENT)) return rc;
+    *count = k.m->tg_n;
+    return FB_OK;
+}
+extern "C" int fb_model_tangent_count(fb_model *m, int *count) { return tangent_count(on_model("fb_model_tangent_count", m), count); }
+extern "C" int fb_slab_tangent_count(fb_slab *s, int *count) { return tangent_count(on_slab("fb_slab_tangent_count", s), count); }
+
+// tangent_gram or tangent_qr behind the guards they share
+static int tangent_pairs(const Call &k, int kind, double *d_out, int (*body)(fb_model *, int, double *))
+{
+    if (kind != 0 && kind != 1) return refuse(k, "kind must be 0 (enstrophy) or 1 (energy)");
+    if (!d_out) return refuse(k, "NULL output");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    return body(k.m, kind, d_out);
+}
+extern "C" int fb_model_tangent_gram(fb_model *m, int kind, double *d_gram) { return tangent_pairs(on_model("fb_model_tangent_gram", m), kind, d_gram, tangent_gram); }
+extern "C" int fb_slab_tangent_gram(fb_slab *s, int kind, double *d_gram) { return tangent_pairs(on_slab("fb_slab_tangent_gram", s), kind, d_gram, tangent_gram); }
+extern "C" int fb_model_tangent_qr(fb_model *m, int kind, double *d_r) { return tangent_pairs(on_model("fb_model_tangent_qr", m), kind, d_r, tangent_qr); }
+extern "C" int fb_slab_tangent_qr(fb_slab *s, int kind, double *d_r) { return tangent_pairs(on_slab("fb_slab_tangent_qr", s), kind, d_r, tangent_qr); }
 
 // ---- the Lagrangian particles (kernels: fb_particles.h) ----
 #define FB_PARTICLES_MAX (1 << 24)
@@ -574,7 +691,7 @@ static int set_adjoint(const Call &k, const float *d_lambda_real)
 extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real) { return set_adjoint(on_model("fb_model_set_adjoint", m), d_lambda_real); }
 extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real) { return set_adjoint(on_slab("fb_slab_set_adjoint", s), d_lambda_real); }
 
-static int get_adjoint(const Call &k, float *d_real) { return get_beside(k, ADJOINT_SET, &fb_model::ad, d_real); }
+static int get_adjoint(const Call &k, float *d_real) { return get_beside(k, ADJOINT_SET, [](fb_model *m) { return &m->ad; }, d_real); }
 extern "C" int fb_model_get_adjoint(fb_model *m, float *d_real) { return get_adjoint(on_model("fb_model_get_adjoint", m), d_real); }
 extern "C" int fb_slab_get_adjoint(fb_slab *s, float *d_real) { return get_adjoint(on_slab("fb_slab_get_adjoint", s), d_real); }
 
