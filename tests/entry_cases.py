@@ -27,6 +27,9 @@ GETTER_BEFORE_SET = [
     ("fb_model_get_particles", ["M", "buf"], "no particles are set"),
     ("fb_model_get_adjoint", ["M", "buf"], "no adjoint is set"),
     ("fb_model_adjoint_back", ["M", 1], "no adjoint is set"),
+    ("fb_model_get_tangents", ["M", "buf"], "no tangent is set"),
+    ("fb_model_tangent_gram", ["M", 0, "buf"], "no tangent is set"),
+    ("fb_model_tangent_qr", ["M", 0, "buf"], "no tangent is set"),
 ]
 ONE_RANK_ONLY = [(fn, args, "several ranks") for fn, args in [
     ("fb_slab_set_tangent", ["S", "field"]), ("fb_slab_get_tangent", ["S", "buf"]),
@@ -34,6 +37,8 @@ ONE_RANK_ONLY = [(fn, args, "several ranks") for fn, args in [
     ("fb_slab_set_particles", ["S", "buf", 100]), ("fb_slab_get_particles", ["S", "buf"]), ("fb_slab_sample", ["S", "field", "buf", 100, "buf"]),
     ("fb_slab_adjoint_record", ["S", 1]), ("fb_slab_adjoint_recorded", ["S", "host"]), ("fb_slab_set_adjoint", ["S", "field"]),
     ("fb_slab_get_adjoint", ["S", "buf"]), ("fb_slab_adjoint_back", ["S", 1]),
+    ("fb_slab_set_tangents", ["S", "field", 1]), ("fb_slab_get_tangents", ["S", "buf"]), ("fb_slab_tangent_count", ["S", "host"]),
+    ("fb_slab_tangent_gram", ["S", 0, "buf"]), ("fb_slab_tangent_qr", ["S", 0, "buf"]),
 ]]
 NOT_CONNECTED = [(fn, args, "not connected") for fn, args in [
     ("fb_slab_set_vort_local", ["S", "field"]), ("fb_slab_step", ["S", 1]), ("fb_slab_time_steps", ["S", 1, "host"]),
@@ -69,6 +74,10 @@ RANGE_CHECKS = [
     ("fb_model_step", ["M", -1], "bad argument"),
     ("fb_model_adjoint_record", ["M", -1], "depth"),
     ("fb_model_adjoint_back", ["M", -1], "nsteps"),
+    ("fb_model_set_tangents", ["M", "field", 0], "count outside"),
+    ("fb_model_set_tangents", ["M", "field", 33], "count outside"),
+    ("fb_model_tangent_gram", ["M", 2, "buf"], "kind"),
+    ("fb_model_tangent_qr", ["M", 2, "buf"], "kind"),
     # a tape of one step, then two steps asked for; an adjoint variable, then one recorded step asked back of none
     ("fb_model_adjoint_record", ["M", 1], ""),
     ("fb_model_step", ["M", 2], "tape"),

@@ -1,7 +1,8 @@
 """The entry layer of the C ABI on the GPU (csrc/fb_entry.h): every fb_model_X / fb_slab_X[_local] pair is one body behind one guard
 layer.  Two checks at 64 x 64.
 
-The refusal table, tests/golden/entry_refusals.json, was recorded from the hand-written pairs (tests/golden/make_entry_fixture.py):
+The refusal table, tests/golden/entry_refusals.json, was recorded twice (tests/golden/make_entry_fixture.py): from the hand-written
+pairs at 321421f, and again at e2fbb09 with the five pairs of the tangent subspace added, every earlier entry unchanged.  It holds
 every paired function before its feature is set, on a slab of two ranks where it supports one, on a slab that is not connected, and
 with each numeric argument out of its range.  Every entry has one thing wrong and is refused before anything is launched.  Asserted:
 the status and the telling phrase of the recording, and that the message starts with the function's own name.
@@ -52,7 +53,8 @@ def test_refusals_are_those_of_the_hand_written_pairs():
 # the paired functions (binding.SIGNATURES) that the table has a refusal of
 PAIRED = ("set_vort", "step", "time_steps", "get_vort", "get_diag", "get_okubo_weiss", "get_eddy_diffusivity", "get_pressure", "get_spectra",
           "get_azimuthal", "set_tracer", "get_tracer", "get_tracer_eddy_diffusivity", "set_particles", "get_particles", "sample",
-          "set_tangent", "get_tangent", "tangent_norm", "tangent_scale", "adjoint_record", "adjoint_recorded", "set_adjoint", "get_adjoint",
+          "set_tangent", "get_tangent", "tangent_norm", "tangent_scale", "set_tangents", "get_tangents", "tangent_count", "tangent_gram",
+          "tangent_qr", "adjoint_record", "adjoint_recorded", "set_adjoint", "get_adjoint",
           "adjoint_back")
 
 

@@ -3,6 +3,7 @@ side csrc/fb_beside.h) against the single tangent it must reproduce bit for bit,
 the analytic spectrum of a fluid at rest.  Every bar here is fixed by reasoning or by a CPU figure (tests/test_lyapunov_cpu.py), none
 by what the GPU gave; one line of figures per case (pytest -s); DESIGN.md, "Tangent subspace and Lyapunov spectrum", has the table."""
 import functools
+import json
 import os
 import sys
 
@@ -19,6 +20,7 @@ for p in (HERE, ROOT, os.path.join(ROOT, "oracle")):
 
 import entry_cases as E                                         # noqa: E402
 import lyapunov_numpy as Y                                      # noqa: E402
+import tangent_norm_cases as N                                  # noqa: E402
 import tangent_numpy as G                                       # noqa: E402
 import tracer_numpy as T                                        # noqa: E402
 from ref_numpy import rel_l2                                    # noqa: E402
@@ -114,8 +116,8 @@ GRAM_GRIDS = ((64, 64), (192, 192), (1024, 64))
 
 @pytest.mark.parametrize("nx,ny", GRAM_GRIDS, ids=_ids(GRAM_GRIDS))
 def test_gram_matrix_against_float64(nx, ny):
-    """|G_ij - <w_i, w_j>| <= 1e-6 sqrt(<w_i, w_i> <w_j, w_j>), the bar tangent_norm is held to; G_00 is tangent_norm; two calls give
-    the same bits; G is symmetric bit for bit"""
+    """|G_ij - <w_i, w_j>| <= 1e-6 sqrt(<w_i, w_i> <w_j, w_j>), the bar tangent_norm is held to; G_00 has the bits of tangent_norm (one
+    kernel); two calls give the same bits; G is symmetric bit for bit"""
     v0, W, _ = _inputs(nx, ny)
     ref = Y.SubspaceModel64(nx, ny)
     V = Y.spectra(W)
@@ -129,11 +131,30 @@ def test_gram_matrix_against_float64(nx, ny):
         print("tangent_gram(%s) %dx%d: largest |G_ij - ref_ij| / sqrt(ref_ii ref_jj) = %.3g; G_00 / tangent_norm - 1 = %.3g" % (kind, nx, ny, err, a[0, 0] / n0 - 1))
         assert a.shape == (3, 3) and a.dtype == np.float64
         assert err <= 1e-6
-        assert abs(a[0, 0] / n0 - 1) <= 1e-12
+        assert _same(a[0, 0], np.float64(n0))
         assert _same(a, b)
         assert _same(a, np.ascontiguousarray(a.T))
         assert abs(want[0, 1]) > 0.1 * d[0] * d[1]               # (not a diagonal matrix)
     m.close()
+
+
+NORM_CASES = [(nx, ny, False) for nx, ny in N.GRIDS] + [(64, 64, True)]
+
+
+@pytest.mark.parametrize("nx,ny,slab", NORM_CASES, ids=["%dx%d%s" % (nx, ny, "-slab" if slab else "") for nx, ny, slab in NORM_CASES])
+def test_norm_and_gram_have_the_bits_of_the_two_kernel_engine(nx, ny, slab):
+    """tests/golden/tangent_norm_bits.json, recorded while the norm had a kernel of its own (tests/golden/make_tangent_norm_fixture.py):
+    tangent_norm after set_tangent, after 2 steps and after rescale_tangent(-1.75), and tangent_gram of a set of three, both kinds,
+    bit for bit; on Model at every grid and on an EngineSlab of one rank at 64^2"""
+    table = json.load(open(os.path.join(HERE, "golden", "tangent_norm_bits.json")))
+    want = {e["kind"]: {k: v for k, v in e.items() if k not in ("nx", "ny", "kind")} for e in table if (e["nx"], e["ny"]) == (nx, ny)}
+    m = N.model(nx, ny, slab)
+    got = N.bits(m, nx, ny)
+    m.close()
+    for kind in Y.KINDS:
+        print("%dx%d %s: %s, recorded %s" % (nx, ny, kind, got[kind], want[kind]))
+    assert sorted(want) == sorted(Y.KINDS) and all(("gram" in want[k]) == ((nx, ny) in N.GRAM_GRIDS) for k in want)
+    assert got == want
 
 
 # ---- 3. the orthonormalisation ----

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Times of the tangent subspace on one GPU by events on the engine's stream: a plain step, a step with M = 1, 4 and 8 perturbations,
-and one orthonormalisation (fb_model_tangent_qr) at M = 4 and 8.  Per configuration `reps` timings (of `steps` steps each, or of one
-QR), warmed, interleaved, in one process; prints median [min, max] in ms, the deviation of a step with M perturbations from
-plain + M (tangent - plain), the QR's share of renorm_every = 10 steps, and one JSON line.  DESIGN.md, "Tangent subspace and Lyapunov
-spectrum", holds the 4096^2 figures.
+one orthonormalisation (fb_model_tangent_qr) at M = 4 and 8 and one norm (fb_model_tangent_norm).  Per configuration `reps` timings (of
+`steps` steps each, or of one call), warmed, interleaved, in one process; prints median [min, max] in ms, the deviation of a step with
+M perturbations from plain + M (tangent - plain), the QR's share of renorm_every = 10 steps, and one JSON line.  DESIGN.md, "Tangent
+subspace and Lyapunov spectrum", holds the 4096^2 figures.
 
     python tools/lyapunov_time.py [--n 4096] [--steps 8] [--reps 10]
 """
@@ -57,6 +57,7 @@ def main():
         runs["step_M%d" % M] = lambda M=M: timed(lambda: models[M].step(steps), steps)
     for M in QR_COUNTS:                                         # the engine's call alone: R stays on the device
         runs["qr_M%d" % M] = lambda M=M: timed(lambda: models[M]._call("tangent_qr", 0, B._ptr(r)), 1)
+    runs["norm"] = lambda: timed(lambda: models[1]._call("tangent_norm", 0, B._ptr(r)), 1)     # of the one perturbation, as the QR's call
     for f in runs.values():
         f()
     ms = {k: [] for k in runs}
@@ -67,7 +68,7 @@ def main():
     for k, v in ms.items():
         v = sorted(v)
         out[k] = {"median_ms": float(np.median(v)), "min_ms": v[0], "max_ms": v[-1]}
-        print("%-10s %.3f [%.3f, %.3f] ms per %s" % (k, out[k]["median_ms"], v[0], v[-1], "call" if k.startswith("qr") else "step"))
+        print("%-10s %.3f [%.3f, %.3f] ms per %s" % (k, out[k]["median_ms"], v[0], v[-1], "step" if "step" in k or k == "plain" else "call"))
     plain, one = out["plain"]["median_ms"], out["step_M1"]["median_ms"]
     for M in COUNTS[1:]:
         got, want = out["step_M%d" % M]["median_ms"], plain + M * (one - plain)

@@ -70,14 +70,10 @@ _PAIRS = {
     "set_tracer_local": [_vp, _fl], "get_tracer_local": [_vp], "get_tracer_eddy_diffusivity": [_ip, _vp, _vp, _vp],
     "set_particles": [_vp, _ip], "get_particles": [_vp], "particle_count": [_pip], "sample": [_vp, _vp, _ip, _vp],
     "set_tangent": [_vp], "get_tangent": [_vp], "tangent_norm": [_ip, _vp], "tangent_scale": [_fl],
+    "set_tangents": [_vp, _ip], "get_tangents": [_vp], "tangent_count": [_pip], "tangent_gram": [_ip, _vp], "tangent_qr": [_ip, _vp],
     "adjoint_record": [_ip], "adjoint_recorded": [_pip], "set_adjoint": [_vp], "get_adjoint": [_vp], "adjoint_back": [_ip],
 }
-# the tangent subspace's pairs, in a table of their own: _PAIRS is the set that the recorded refusal table (tests/golden/entry_refusals.json)
-# covers name by name, and that recording predates these
-_SUBSPACE_PAIRS = {
-    "set_tangents": [_vp, _ip], "get_tangents": [_vp], "tangent_count": [_pip], "tangent_gram": [_ip, _vp], "tangent_qr": [_ip, _vp],
-}
-for _name, _args in list(_PAIRS.items()) + list(_SUBSPACE_PAIRS.items()):
+for _name, _args in _PAIRS.items():
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -588,9 +584,7 @@ class ModelSurface:
 
     def tangent_norm(self, kind="enstrophy"):
         """The perturbation's norm, a float: "enstrophy" <dz^2> / 2 or "energy" <|grad dpsi|^2> / 2, summed in float64 on the GPU."""
-        out = self.torch.empty(1, dtype=self.torch.float64, device="cuda")
-        self._hand("tangent_norm", tangent_kind(kind), out)
-        return float(out.item())
+        return float(self._tangent_pairs("tangent_norm", kind, 1).item())
 
     def rescale_tangent(self, a):
         """dz *= a (a finite and not zero)"""
@@ -627,8 +621,9 @@ class ModelSurface:
         self._hand("get_tangents", out)
         return out
 
-    def _tangent_pairs(self, name, kind):
-        m = self._tangent_rows()
+    def _tangent_pairs(self, name, kind, m=None):
+        """the float64 [m, m] output of fb_*_<name>(kind, out), m the number of perturbations unless given"""
+        m = m or self._tangent_rows()
         out = self.torch.empty((m, m), dtype=self.torch.float64, device="cuda")
         self._hand(name, tangent_kind(kind), out)
         return out

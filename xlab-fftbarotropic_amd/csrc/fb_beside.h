@@ -3,8 +3,9 @@
 //
 // Each is taken in between two steps and advanced at the top of every RK stage of fb_model_step and fb_slab_step, from the state the
 // vorticity's stage starts from, through the record workspace (record_advect, fb_record.h): the step's own buffers are only read.  A
-// spectral field of this kind (struct Beside, fftbaro.hip: the tracer, the perturbation) has one host path: beside_in, per stage
-// beside_advect once per advective tendency and one beside_update, beside_free.  The particles share stage_vstate and beside_begin.
+// spectral field of this kind (struct Beside, fftbaro.hip: the tracer, each perturbation of the tangent's set) has one host path:
+// beside_in, per stage beside_advect once per advective tendency and one beside_update, beside_free.  The particles share
+// stage_vstate and beside_begin.
 #pragma once
 
 static void beside_free(Beside &f)
@@ -191,19 +192,29 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
 }
 
 // ---- the tangent-linear model (kernels: fb_tangent.h) ----
+// A set of tg_n perturbations on the one trajectory; the single tangent of fb_model_set_tangent is the set of one, and its norm the
+// inner product of perturbation 0 with itself.
 static void tangent_free(fb_model *m)
 {
     for (Beside &f : m->tg) beside_free(f);
     for (cf *&p : m->tg_j) if (p) { hipFree(p); p = nullptr; }
     if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
     m->tg_n = 0;
-    m->tangent = false;
+}
+
+// f(g, n) for each of the first ngroups column groups that has elements, n (complex) of them; the first status that is not FB_OK ends it
+template <class F> static int each_group(const fb_ctx *c, int ngroups, F &&f)
+{
+    for (int g = 0; g < ngroups; ++g)
+        if (const size_t n = grp_elems(c, c->grp[g]))
+            if (int rc = f(g, n)) return rc;
+    return FB_OK;
 }
 
 // One RK stage of the perturbations, where tracer_stage runs and from the same states, one perturbation after the other in index
 // order.  The tangent of the bilinear J is two advect passes, J(dz; psi) + J(zeta; dpsi); the first pass's result is copied to tg_j
 // before the second overwrites the record workspace; then the update with both and the model's nu.  Nothing is shared between two
-// perturbations but the scratch: perturbation k of a set is bit for bit the single tangent started from the same field.
+// perturbations but the scratch: perturbation k of a set is bit for bit the set of one started from the same field.
 static int tangent_stage(fb_model *m, fb_slab *s, int stage)
 {
     fb_ctx *c = m->c;
@@ -211,85 +222,61 @@ static int tangent_stage(fb_model *m, fb_slab *s, int stage)
     for (int k = 0; k < m->tg_n; ++k) {
         Beside &f = m->tg[k];
         if ((rc = beside_advect(m, s, stage, &f, nullptr))) return rc;
-        for (int g = 0; g < c->nact; ++g) {
-            const size_t n = grp_elems(c, c->grp[g]);
-            if (n) HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-        }
-        if ((rc = beside_advect(m, s, stage, nullptr, &f))) return rc;
+        rc = each_group(c, c->nact, [&](int g, size_t n) -> int {
+            HIPCHK(hipMemcpyAsync(m->tg_j[g], advect_out(m, s, g), n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+            return FB_OK;
+        });
+        if (rc || (rc = beside_advect(m, s, stage, nullptr, &f))) return rc;
         if ((rc = beside_update(m, s, stage, f, m->tg_j, m->nu))) return rc;
     }
     return FB_OK;
 }
 
 // `count` perturbations in, d_rows [count] real fields one after the other (beside_begin, beside_in each), with the scratch of the
-// first advect pass and the partial sums of a norm or an inner product ([ngroups][max_wg] float64); whatever set was there is
-// replaced, perturbations beyond `count` freed; d_rows == NULL removes all.
+// first advect pass and the partial sums of an inner product ([ngroups][max_wg] float64); whatever set was there is replaced,
+// perturbations beyond `count` freed; d_rows == NULL removes all.
 static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
 {
     fb_ctx *c = m->c;
     int rc;
-    if ((rc = beside_begin(m, m->tangent && (!d_rows || count < m->tg_n)))) return rc;
+    if ((rc = beside_begin(m, m->tg_n && (!d_rows || count < m->tg_n)))) return rc;
     if (!d_rows) { tangent_free(m); return FB_OK; }
-    for (int g = 0; g < c->nact && !rc; ++g)
-        if (grp_elems(c, c->grp[g])) rc = rec_alloc((void **)&m->tg_j[g], grp_elems(c, c->grp[g]) * sizeof(cf));
+    rc = each_group(c, c->nact, [&](int g, size_t n) { return rec_alloc((void **)&m->tg_j[g], n * sizeof(cf)); });
     if (!rc) rc = rec_alloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double));
     for (int k = 0; k < count && !rc; ++k) rc = beside_in(m, s, d_rows + (size_t)k * c->XL * c->ny, m->tg[k]);
     if (rc) { tangent_free(m); return rc; }
     for (int k = count; k < m->tg_n; ++k) beside_free(m->tg[k]);
     m->tg_n = count;
-    m->tangent = true;
     return FB_OK;
-}
-
-// kind 0: the enstrophy norm <dz^2> / 2, kind 1: the energy norm <|grad dpsi|^2> / 2 (means over the grid), of the resident spectrum
-// of perturbation 0 (k_tangent_norm per column group, then k_tangent_norm_final over every partial sum) into *d_out on the device
-static int tangent_norm(fb_model *m, int kind, double *d_out)
-{
-    fb_ctx *c = m->c;
-    const SpecCoef coef = make_coef(c);
-    int np = 0;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        const size_t n = grp_elems(c, G);
-        if (n == 0) continue;
-        const int nwg = grid_for(c, n / 2);
-        if (int rc = launch(c, k_tangent_norm, dim3(nwg), dim3(256), 0, coef, (const cf *)m->tg[0].c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
-        np += nwg;
-    }
-    const double grids = (double)c->nx * c->ny;
-    return launch(c, k_tangent_norm_final, dim3(1), dim3(256), 0, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
 }
 
 static int tangent_scale(fb_model *m, float a)
 {
     fb_ctx *c = m->c;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const size_t n = grp_elems(c, c->grp[g]);
-        if (n == 0) continue;
-        if (int rc = launch_n(c, k_tangent_scale, n / 2, m->tg[0].c0[g], n, a)) return rc;
-    }
-    return FB_OK;
+    return each_group(c, c->ngroups, [&](int g, size_t n) { return launch_n(c, k_tangent_scale, n / 2, m->tg[0].c0[g], n, a); });
 }
 
-// <a, b> of two perturbations into *d_out on the device, with tangent_norm's grids, weights and scale: <a, a> is tangent_norm's norm
-// (k_tangent_dot per column group, then k_tangent_dot_final over every partial sum, through the one tg_red: calls follow each other
-// on the one stream)
+// <a, b> of the resident spectra of two perturbations into *d_out on the device (a may be b): kind 0 the enstrophy inner product
+// <a b> / 2, kind 1 the energy one <grad psi_a . grad psi_b> / 2, means over the grid (k_tangent_dot per column group, its partial sums
+// one group after the other in the one tg_red, then k_tangent_dot_final over all of them: calls follow each other on the one stream)
 static int tangent_dot(fb_model *m, int kind, const Beside &a, const Beside &b, double *d_out)
 {
     fb_ctx *c = m->c;
     const SpecCoef coef = make_coef(c);
     int np = 0;
-    for (int g = 0; g < c->ngroups; ++g) {
+    const int rc = each_group(c, c->ngroups, [&](int g, size_t n) {
         const ColGroup &G = c->grp[g];
-        const size_t n = grp_elems(c, G);
-        if (n == 0) continue;
-        const int nwg = grid_for(c, n / 2);
-        if (int rc = launch(c, k_tangent_dot, dim3(nwg), dim3(256), 0, coef, (const cf *)a.c0[g], (const cf *)b.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + np)) return rc;
+        const int nwg = grid_for(c, n / 2), at = np;
         np += nwg;
-    }
+        return launch(c, k_tangent_dot, dim3(nwg), dim3(256), 0, coef, (const cf *)a.c0[g], (const cf *)b.c0[g], kind, G.ncols, c->N1, c->N2, G.ky0, m->tg_red + at);
+    });
+    if (rc) return rc;
     const double grids = (double)c->nx * c->ny;
     return launch(c, k_tangent_dot_final, dim3(1), dim3(256), 0, (const double *)m->tg_red, np, 0.5 / (grids * grids), d_out);
 }
+
+// the norm of perturbation 0 into *d_out on the device: kind 0 <dz^2> / 2, kind 1 <|grad dpsi|^2> / 2
+static int tangent_norm0(fb_model *m, int kind, double *d_out) { return tangent_dot(m, kind, m->tg[0], m->tg[0], d_out); }
 
 // every <v_i, v_j> into the device array d_gram, [tg_n][tg_n] float64 row-major: the upper triangle through tangent_dot, mirrored
 static int tangent_gram(fb_model *m, int kind, double *d_gram)
@@ -317,17 +304,13 @@ static int tangent_qr(fb_model *m, int kind, double *d_r)
         for (int i = 0; i < j; ++i) {
             double *r = d_r + (size_t)i * M + j;
             if ((rc = tangent_dot(m, kind, m->tg[i], v, r))) return rc;
-            for (int g = 0; g < c->ngroups; ++g) {
-                const size_t n = grp_elems(c, c->grp[g]);
-                if (n && (rc = launch_n(c, k_tangent_axpy, n / 2, v.c0[g], (const cf *)m->tg[i].c0[g], n, (const double *)r))) return rc;
-            }
+            rc = each_group(c, c->ngroups, [&](int g, size_t n) { return launch_n(c, k_tangent_axpy, n / 2, v.c0[g], (const cf *)m->tg[i].c0[g], n, (const double *)r); });
+            if (rc) return rc;
         }
         double *r = d_r + (size_t)j * M + j;
         if ((rc = tangent_dot(m, kind, v, v, r)) || (rc = launch(c, k_tangent_sqrt, dim3(1), dim3(64), 0, r))) return rc;
-        for (int g = 0; g < c->ngroups; ++g) {
-            const size_t n = grp_elems(c, c->grp[g]);
-            if (n && (rc = launch_n(c, k_tangent_scale_dev, n / 2, v.c0[g], n, (const double *)r))) return rc;
-        }
+        rc = each_group(c, c->ngroups, [&](int g, size_t n) { return launch_n(c, k_tangent_scale_dev, n / 2, v.c0[g], n, (const double *)r); });
+        if (rc) return rc;
     }
     return FB_OK;
 }
@@ -335,46 +318,22 @@ static int tangent_qr(fb_model *m, int kind, double *d_r)
 // a slab of one rank goes through the same code; on several ranks the tangent-linear model is refused
 constexpr unsigned TANGENT = NEED_TRANSPORT | ONE_RANK_TANGENT, TANGENT_SET = TANGENT | NEED_TANGENT;
 
-static int set_tangent(const Call &k, const float *d_dz_real)
-{
-    if (int rc = enter(k, TANGENT)) return rc;
-    return tangent_in(k.m, k.s, d_dz_real, 1);
-}
-extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real) { return set_tangent(on_model("fb_model_set_tangent", m), d_dz_real); }
-extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real) { return set_tangent(on_slab("fb_slab_set_tangent", s), d_dz_real); }
-
-static int get_tangent(const Call &k, float *d_dz_real) { return get_beside(k, TANGENT_SET, [](fb_model *m) { return &m->tg[0]; }, d_dz_real); }
-extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real) { return get_tangent(on_model("fb_model_get_tangent", m), d_dz_real); }
-extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real) { return get_tangent(on_slab("fb_slab_get_tangent", s), d_dz_real); }
-
-static int tangent_norm(const Call &k, int kind, double *d_out)
-{
-    if (kind != 0 && kind != 1) return refuse(k, "kind must be 0 (enstrophy) or 1 (energy)");
-    if (!d_out) return refuse(k, "NULL output");
-    if (int rc = enter(k, TANGENT_SET)) return rc;
-    return tangent_norm(k.m, kind, d_out);
-}
-extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out) { return tangent_norm(on_model("fb_model_tangent_norm", m), kind, d_out); }
-extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out) { return tangent_norm(on_slab("fb_slab_tangent_norm", s), kind, d_out); }
-
-static int tangent_scale(const Call &k, float a)
-{
-    if (!std::isfinite(a) || a == 0.0f) return refuse(k, "the factor must be finite and not zero");
-    if (int rc = enter(k, TANGENT_SET)) return rc;
-    return tangent_scale(k.m, a);
-}
-extern "C" int fb_model_tangent_scale(fb_model *m, float a) { return tangent_scale(on_model("fb_model_tangent_scale", m), a); }
-extern "C" int fb_slab_tangent_scale(fb_slab *s, float a) { return tangent_scale(on_slab("fb_slab_tangent_scale", s), a); }
-
-// the tangent subspace: [count] fields in or out, the count, and the two calls on every pair of bases
+// [count] fields in; the single tangent's call sets one (and with NULL removes the whole set, as the set's own does)
 static int set_tangents(const Call &k, const float *d_dz_real, int count)
 {
     if (d_dz_real && (count < 1 || count > FB_TANGENTS_MAX)) return refuse(k, "count outside [1, 32]");
     if (int rc = enter(k, TANGENT)) return rc;
     return tangent_in(k.m, k.s, d_dz_real, count);
 }
+extern "C" int fb_model_set_tangent(fb_model *m, const float *d_dz_real) { return set_tangents(on_model("fb_model_set_tangent", m), d_dz_real, 1); }
+extern "C" int fb_slab_set_tangent(fb_slab *s, const float *d_dz_real) { return set_tangents(on_slab("fb_slab_set_tangent", s), d_dz_real, 1); }
 extern "C" int fb_model_set_tangents(fb_model *m, const float *d_dz_real, int count) { return set_tangents(on_model("fb_model_set_tangents", m), d_dz_real, count); }
 extern "C" int fb_slab_set_tangents(fb_slab *s, const float *d_dz_real, int count) { return set_tangents(on_slab("fb_slab_set_tangents", s), d_dz_real, count); }
+
+// (perturbation 0 only)
+static int get_tangent(const Call &k, float *d_dz_real) { return get_beside(k, TANGENT_SET, [](fb_model *m) { return &m->tg[0]; }, d_dz_real); }
+extern "C" int fb_model_get_tangent(fb_model *m, float *d_dz_real) { return get_tangent(on_model("fb_model_get_tangent", m), d_dz_real); }
+extern "C" int fb_slab_get_tangent(fb_slab *s, float *d_dz_real) { return get_tangent(on_slab("fb_slab_get_tangent", s), d_dz_real); }
 
 static int get_tangents(const Call &k, float *d_dz_real)
 {
@@ -399,7 +358,16 @@ static int tangent_count(const Call &k, int *count)
 extern "C" int fb_model_tangent_count(fb_model *m, int *count) { return tangent_count(on_model("fb_model_tangent_count", m), count); }
 extern "C" int fb_slab_tangent_count(fb_slab *s, int *count) { return tangent_count(on_slab("fb_slab_tangent_count", s), count); }
 
-// tangent_gram or tangent_qr behind the guards they share
+static int tangent_scale(const Call &k, float a)
+{
+    if (!std::isfinite(a) || a == 0.0f) return refuse(k, "the factor must be finite and not zero");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    return tangent_scale(k.m, a);
+}
+extern "C" int fb_model_tangent_scale(fb_model *m, float a) { return tangent_scale(on_model("fb_model_tangent_scale", m), a); }
+extern "C" int fb_slab_tangent_scale(fb_slab *s, float a) { return tangent_scale(on_slab("fb_slab_tangent_scale", s), a); }
+
+// tangent_norm0, tangent_gram or tangent_qr behind the guards they share
 static int tangent_pairs(const Call &k, int kind, double *d_out, int (*body)(fb_model *, int, double *))
 {
     if (kind != 0 && kind != 1) return refuse(k, "kind must be 0 (enstrophy) or 1 (energy)");
@@ -407,6 +375,8 @@ static int tangent_pairs(const Call &k, int kind, double *d_out, int (*body)(fb_
     if (int rc = enter(k, TANGENT_SET)) return rc;
     return body(k.m, kind, d_out);
 }
+extern "C" int fb_model_tangent_norm(fb_model *m, int kind, double *d_out) { return tangent_pairs(on_model("fb_model_tangent_norm", m), kind, d_out, tangent_norm0); }
+extern "C" int fb_slab_tangent_norm(fb_slab *s, int kind, double *d_out) { return tangent_pairs(on_slab("fb_slab_tangent_norm", s), kind, d_out, tangent_norm0); }
 extern "C" int fb_model_tangent_gram(fb_model *m, int kind, double *d_gram) { return tangent_pairs(on_model("fb_model_tangent_gram", m), kind, d_gram, tangent_gram); }
 extern "C" int fb_slab_tangent_gram(fb_slab *s, int kind, double *d_gram) { return tangent_pairs(on_slab("fb_slab_tangent_gram", s), kind, d_gram, tangent_gram); }
 extern "C" int fb_model_tangent_qr(fb_model *m, int kind, double *d_r) { return tangent_pairs(on_model("fb_model_tangent_qr", m), kind, d_r, tangent_qr); }
@@ -713,7 +683,7 @@ static int beside_stage(fb_model *m, fb_slab *s, int stage)
     int rc;
     if (m->tracer && (rc = tracer_stage(m, s, stage))) return rc;
     if (m->pt_n && (rc = particle_stage(m, stage))) return rc;
-    if (m->tangent && (rc = tangent_stage(m, s, stage))) return rc;
+    if (m->tg_n && (rc = tangent_stage(m, s, stage))) return rc;
     if (m->ad_depth && (rc = adjoint_stash(m, stage))) return rc;
     return FB_OK;
 }

@@ -13,11 +13,11 @@
 //   k_advect_deriv     gradx a, grady a, grady phi, gradx phi with (a, phi) = (dz, psi), then with (a, phi) = (zeta, dpsi) (fb_tracer.h)
 //   (record_advect, fb_record.h: the backward x pass, the ROW_FUSED row pass without a source, the forward x pass; twice)
 //   k_beside_update    the two tendencies summed, viscous term, mask, RK stage update (fb_tracer.h, NJ == 2)
-// The stage's kernels are the tracer's, in fb_tracer.h; this file holds what is the tangent's own, between steps: k_tangent_norm
-// (+ k_tangent_norm_final) and k_tangent_scale on the base, and what a tangent subspace (fb_model_set_tangents: several perturbations on
-// the one trajectory) adds: the inner product of two bases k_tangent_dot (+ k_tangent_dot_final) and the steps of a modified
-// Gram-Schmidt sweep whose coefficients never leave the device, k_tangent_axpy, k_tangent_sqrt, k_tangent_scale_dev (host side:
-// tangent_qr, tangent_gram in fb_beside.h).
+// The stage's kernels are the tracer's, in fb_tracer.h; this file holds what is the tangent's own, between steps, on the bases of a set
+// of perturbations on the one trajectory (fb_model_set_tangents; a single tangent, fb_model_set_tangent, is the set of one):
+// k_tangent_scale, the inner product of two bases k_tangent_dot (+ k_tangent_dot_final), whose <a, a> is the norm, and the steps of a
+// modified Gram-Schmidt sweep whose coefficients never leave the device, k_tangent_axpy, k_tangent_sqrt, k_tangent_scale_dev (host
+// side: tangent_dot, tangent_gram, tangent_qr in fb_beside.h).
 // No reference counterpart: the reference has no tangent-linear model.
 #pragma once
 
@@ -44,52 +44,12 @@ FB_DEV double tangent_block_sum(double v, double *sh)
     return sh[0];
 }
 
-// The squared norm of the perturbation over the resident half spectrum of one column group (the base, 3-pass layout), in float64:
-// sum over kx and ky <= ny/2 of w |dz_c|^2 q, with the Hermitian weight w = 1 in the columns ky = 0 and ky = ny/2 and 2 elsewhere;
+// ---- inner products and in-place orthonormalisation of the bases ----
+// The inner product of two perturbations over the resident half spectrum of one column group (the bases, 3-pass layout), in float64:
+// sum over kx and ky <= ny/2 of w q Re(a conj(b)), with the Hermitian weight w = 1 in the columns ky = 0 and ky = ny/2 and 2 elsewhere;
 // kind 0 (enstrophy): q = 1; kind 1 (energy): q = |k|^2 / laplacian_coe^2 = |grad dpsi|^2 / |dz|^2 of the mode, the (0, 0) mode left out.
-// One partial sum per workgroup into part[blockIdx.x]: no atomics, the same grid gives the same bits.
-__global__ void __launch_bounds__(256) k_tangent_norm(SpecCoef c, const cf *__restrict__ c0, int kind, int P, int N1, int N2, int ky0, double *__restrict__ part)
-{
-    __shared__ double sh[256];
-    const size_t total = (size_t)c.nx * P / 2;
-    const int hp = P >> 1;
-    double acc = 0.0;
-    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (size_t)gridDim.x * blockDim.x) {
-        const int row = (int)(p / hp), col = 2 * (int)(p - (size_t)row * hp);
-        if (ky0 + col >= c.hy) continue;
-        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d;
-        const float4 v = reinterpret_cast<const float4 *>(c0)[p];
-        const double m2[2] = {(double)v.x * v.x + (double)v.y * v.y, (double)v.z * v.z + (double)v.w * v.w};
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            const int j = ky0 + col + e;
-            if (j >= c.hy) continue;
-            double q = (j == 0 || j == c.hy - 1) ? 1.0 : 2.0;
-            if (kind == 1) {
-                const double lap = (double)coef_lap(c, i, j);
-                q = (i == 0 && j == 0) ? 0.0 : q * (c.kx2[i] + c.ky2[j]) / (lap * lap);
-            }
-            acc += q * m2[e];
-        }
-    }
-    const double s = tangent_block_sum(acc, sh);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// the partial sums of every column group, in a fixed order -> *out = scale * sum (scale = 1 / (2 GRIDS^2): half the mean square)
-__global__ void __launch_bounds__(256) k_tangent_norm_final(const double *__restrict__ part, int nparts, double scale, double *__restrict__ out)
-{
-    __shared__ double sh[256];
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += 256) acc += part[k];
-    const double s = tangent_block_sum(acc, sh);
-    if (threadIdx.x == 0) *out = s * scale;
-}
-
-// ---- the tangent subspace: inner products and in-place orthonormalisation of the bases ----
-// The inner product of two perturbations over the resident half spectrum of one column group, in float64: k_tangent_norm's walk, index
-// arithmetic, weights and kinds, with the summand q Re(a conj(b)) in the place of q |dz_c|^2; a == b is allowed.  One partial sum per
-// workgroup into part[blockIdx.x]: no atomics, the same grid gives the same bits.
+// a == b is allowed and gives the squared norm: each summand, two products of float32 values, is exact in float64 before it is
+// rounded once, fused or not.  One partial sum per workgroup into part[blockIdx.x]: no atomics, the same grid gives the same bits.
 __global__ void __launch_bounds__(256) k_tangent_dot(SpecCoef c, const cf *a0, const cf *b0, int kind, int P, int N1, int N2, int ky0, double *__restrict__ part)
 {
     __shared__ double sh[256];
@@ -118,7 +78,7 @@ __global__ void __launch_bounds__(256) k_tangent_dot(SpecCoef c, const cf *a0, c
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// the partial sums of every column group, in a fixed order -> *out = scale * sum (scale = 1 / (2 GRIDS^2): <a, a> is k_tangent_norm's norm)
+// the partial sums of every column group, in a fixed order -> *out = scale * sum (scale = 1 / (2 GRIDS^2): half the mean square)
 __global__ void __launch_bounds__(256) k_tangent_dot_final(const double *__restrict__ part, int nparts, double scale, double *__restrict__ out)
 {
     __shared__ double sh[256];

@@ -1051,13 +1051,12 @@ struct fb_model {
     float *pt_uv;
     // the tangent-linear model (fb_tangent.h; host side in fb_beside.h): tg_n perturbations on the one trajectory (a tangent subspace;
     // fb_model_set_tangent sets one), each allocated when it is set, and what they share, since they are advanced one after the other:
-    // the first advect pass's tendency of a stage (groups of active columns) and the partial sums of a norm or an inner product; NULL
-    // and 0 without
+    // the first advect pass's tendency of a stage (groups of active columns) and the partial sums of an inner product (the norm is
+    // one); NULL and tg_n == 0 without, and tg_n alone says whether a tangent is set
     Beside tg[FB_TANGENTS_MAX];
     int tg_n;
     cf *tg_j[3];
     double *tg_red;
-    bool tangent;                    // tg_n > 0
     // the adjoint model (fb_adjoint.h; host side in fb_beside.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
     // 3-pass layout, masked modes merged in from the base, ad_fill steps of it recorded; NULL and 0 while nothing is recorded.  The
     // adjoint variable lam (ad.c0) with the k-bar (ad.c1) and the accumulator (ad.acc) of a backward step, and the five real fields
@@ -1171,7 +1170,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups; ++g) n += (c->world > 1 ? (g < c->nact ? 13 : 11) : 8) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
         if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
-        for (int g = 0; g < c->ngroups && m->tangent; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
+        for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         *hbm = n;
     }
