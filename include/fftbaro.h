@@ -221,6 +221,33 @@ int fb_model_set_particles(fb_model *m, const double *d_xy, int n);        /* NU
 int fb_model_get_particles(fb_model *m, double *d_xy);
 int fb_model_particle_count(fb_model *m, int *n);
 int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n, double *d_out);
+/* The deformation gradient along the particles and the finite-time Lyapunov exponent (no reference counterpart).  Every particle
+ * carries F = dX(t) / dX(t0), float64 (F11, F12, F21, F22), advanced in every step by the linearisation of the particle's own RK4 step:
+ *   K1 = A_0(X0) F0, K2 = A_1(X0 + dt/2 k1) (F0 + dt/2 K1), K3 = A_2(X0 + dt/2 k2) (F0 + dt/2 K2), K4 = A_3(X0 + dt k3) (F0 + dt K3),
+ *   F <- F0 + dt/6 (((K1 + 2 K2) + 2 K3) + K4)
+ * with A_s(X) = [[du/dx, du/dy], [dv/dx, dv/dy]] the gradient of the INTERPOLANT of the stage's u, v at X, from the stencils the
+ * position update reads: on each axis the value weights w or their derivatives over the spacing,
+ *   w'(-1) = -(3t^2 - 6t + 2) / 6,  w'(0) = (3t^2 - 4t - 1) / 2,  w'(1) = -(3t^2 - 2t - 2) / 2,  w'(2) = (3t^2 - 1) / 6.
+ * So F is the exact Jacobian of the discrete map X0 -> X in the given flow wherever that map is differentiable: the cubic Lagrange
+ * interpolant is continuous, its derivative jumps at cell faces, and at t == 0 the derivative of the cell to the right is taken.  det F
+ * is close to 1 and not equal to it (the interpolated velocity is not exactly non-divergent): not a defect.  A particle whose
+ * position is not finite gets NaN in F.  The positions, the vorticity, a tracer and the tangent are bit for bit what they are without.
+ * fb_model_set_particle_deformation: on == 1 allocates twelve float64 arrays of n where needed, sets F = I and the elapsed time to 0
+ * (so it is the reset too: F grows like exp(lambda t)); on == 0 frees; any other value is refused.  Either way a captured step is
+ * dropped as fb_model_set_particles drops it.  fb_model_set_particles (a new set or NULL) and fb_model_destroy switch it off.
+ * fb_model_get_particle_deformation: F into d_F, device float64 [n][4]; *elapsed (host, may be NULL): (steps since the reset) x dt [s].
+ * fb_model_particle_stretching: the closed-form singular value decomposition of every matrix of d_F, device float64 [n][4], n in
+ * [1, 2^24] (ANY matrices, as fb_model_sample takes any positions), or with d_F == NULL of the model's own F and n, into d_out,
+ * device float64 [n][4] with the columns
+ *   ln sigma1, ln sigma2, theta_in, theta_out:  F = Rot(theta_out) diag(sigma1, sign(det F) sigma2) Rot(theta_in)^T up to the overall
+ * sign, sigma1 >= sigma2 >= 0, both angles folded into (-pi/2, pi/2] (they name axes): theta_in is the direction of strongest
+ * stretching at the initial time, theta_out its image, ln sigma1 / elapsed the forward finite-time Lyapunov exponent.  F is scaled by
+ * its largest |entry| first and sigma2 = |det| / sigma1; the zero matrix gives -inf, -inf, 0, 0, a singular one ln sigma2 = -inf, an
+ * entry that is not finite four NaN.  FB_EINVAL before any HIP call: a NULL model or output, on outside {0, 1}, n outside [1, 2^24],
+ * no particles set, and (get, stretching with d_F == NULL) the deformation not switched on. */
+int fb_model_set_particle_deformation(fb_model *m, int on);
+int fb_model_get_particle_deformation(fb_model *m, double *d_F, double *elapsed);
+int fb_model_particle_stretching(fb_model *m, const double *d_F, int n, double *d_out);
 /* Tangent-linear model (no reference counterpart): a perturbation dz of the vorticity, a real [nx][ny] field, carried along the
  * evolving state by the linearisation of the DISCRETE step (not of the PDE), so that M(zeta + eps dz) - M(zeta) = eps T(dz) + O(eps^2)
  * for the step M itself.  fb_model_set_tangent takes the device field d_dz_real in as fb_model_set_vort takes the vorticity and keeps
@@ -460,6 +487,10 @@ int fb_slab_set_particles(fb_slab *s, const double *d_xy, int n);          /* NU
 int fb_slab_get_particles(fb_slab *s, double *d_xy);
 int fb_slab_particle_count(fb_slab *s, int *n);
 int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out);
+/* the particles' deformation gradient (fb_model_set_particle_deformation) on a slab of ONE rank, refused on world > 1 as the particles are */
+int fb_slab_set_particle_deformation(fb_slab *s, int on);
+int fb_slab_get_particle_deformation(fb_slab *s, double *d_F, double *elapsed);
+int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n, double *d_out);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

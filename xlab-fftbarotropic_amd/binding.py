@@ -73,7 +73,13 @@ _PAIRS = {
     "set_tangents": [_vp, _ip], "get_tangents": [_vp], "tangent_count": [_pip], "tangent_gram": [_ip, _vp], "tangent_qr": [_ip, _vp],
     "adjoint_record": [_ip], "adjoint_recorded": [_pip], "set_adjoint": [_vp], "get_adjoint": [_vp], "adjoint_back": [_ip],
 }
-for _name, _args in _PAIRS.items():
+# the particle deformation's pairs, in a table of their own: _PAIRS is the set that the recorded refusal table
+# (tests/golden/entry_refusals.json) covers name by name, and that recording predates these
+_pdb = C.POINTER(_db)
+_DEFORMATION_PAIRS = {
+    "set_particle_deformation": [_ip], "get_particle_deformation": [_vp, _pdb], "particle_stretching": [_vp, _ip, _vp],
+}
+for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -181,6 +187,9 @@ def _entry(prefix, name):
 
 
 PARTICLES_MAX = 1 << 24
+# the columns of the stretching table (fb_model_particle_stretching, include/fftbaro.h), one row per particle (or matrix):
+# F = Rot(theta_out) diag(sigma1, sign(det F) sigma2) Rot(theta_in)^T up to the overall sign, the angles in (-pi/2, pi/2]
+PARTICLE_STRETCHING_COLUMNS = ("ln_sigma1", "ln_sigma2", "theta_in", "theta_out")
 TANGENTS_MAX = 32
 # orthonormalize_tangents: an update v -= r q rounds every element of v to float32, an error of up to eps32 / 2 of |v| + |r q|, about
 # eps32 |v|; what is left of a v that lay in the span of the q is that noise.  8 eps32 of its length: below this nothing but it is left.
@@ -572,6 +581,59 @@ class ModelSurface:
         out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
         self._hand("sample", f, a, int(a.shape[0]), out)
         return out
+
+    def set_particle_deformation(self, on=True):
+        """Switches the particles' deformation gradient on: every particle carries F = dX(t) / dX(t0), float64 2 x 2, advanced by the
+        exact linearisation of the particles' own RK4 step (the Jacobian of the discrete map, with the gradient of the cubic Lagrange
+        interpolant itself).  on=True sets F = I and the elapsed time to 0, so it is the reset too (F grows like exp(lambda t));
+        on=False frees it.  set_particles switches it off.  det F is close to 1, not equal: the interpolated velocity is not exactly
+        non-divergent.  One rank only, as the particles."""
+        self._call("set_particle_deformation", int(on))
+
+    def _deformation(self):
+        """(F as float64 [n, 4] on the GPU, the elapsed time in seconds)"""
+        t = self.torch
+        out = t.empty((max(self.particle_count(), 1), 4), dtype=t.float64, device="cuda")
+        el = C.c_double()
+        self._hand("get_particle_deformation", out, C.byref(el))
+        return out, el.value
+
+    def particle_deformation(self):
+        """The particles' deformation gradient, a float64 [n, 2, 2] tensor: F[p] = [[F11, F12], [F21, F22]]."""
+        return self._deformation()[0].view(-1, 2, 2)
+
+    def particle_deformation_time(self):
+        """The time F has been carried for [s]: (steps since set_particle_deformation) x dt."""
+        return self._deformation()[1]
+
+    def particle_stretching(self, F=None):
+        """The closed-form 2 x 2 singular value decomposition, on the GPU, of the particles' F (F=None) or of ANY matrices F, float64
+        [n, 2, 2] or [n, 4] (numpy or torch): a float64 [n, 4] tensor with the columns PARTICLE_STRETCHING_COLUMNS, ln sigma1,
+        ln sigma2, theta_in (the direction of strongest stretching at the initial time) and theta_out (its image), the angles folded
+        into (-pi/2, pi/2].  The zero matrix gives -inf, -inf, 0, 0; a singular one ln sigma2 = -inf; an entry that is not finite NaN."""
+        t = self.torch
+        self._one_rank("particle_stretching", None, 1, None)
+        if F is None:
+            out = t.empty((max(self.particle_count(), 1), 4), dtype=t.float64, device="cuda")
+            self._hand("particle_stretching", None, 0, out)
+            return out
+        if isinstance(F, np.ndarray):
+            F = t.from_numpy(np.ascontiguousarray(F, dtype=np.float64))
+        if F.dtype != t.float64 or F.dim() not in (2, 3) or F.shape[0] == 0 or F.shape[1:].numel() != 4:
+            raise ValueError("particle_stretching: float64 [n, 2, 2] or [n, 4], n >= 1")
+        F = F.cuda().contiguous().view(-1, 4)
+        out = t.empty((F.shape[0], 4), dtype=t.float64, device="cuda")
+        self._hand("particle_stretching", F, int(F.shape[0]), out)
+        return out
+
+    def ftle(self):
+        """The forward finite-time Lyapunov exponent of every particle [s^-1], float64 [n]: ln sigma1 / T, T the time since
+        set_particle_deformation.  Raises while T = 0."""
+        T = self.particle_deformation_time()
+        if not T > 0.0:
+            raise FftBaroError("ftle: no step since set_particle_deformation (T = 0)")
+        ln1 = self.particle_stretching()[:, 0]
+        return ln1 / self.torch.full_like(ln1, T)               # (a tensor divisor: torch multiplies by the reciprocal of a scalar one)
 
     def set_tangent(self, dz):
         """Sets the perturbation of the tangent-linear model, a field carried along the evolving vorticity by the linearisation of the

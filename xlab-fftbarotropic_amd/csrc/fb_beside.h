@@ -385,8 +385,14 @@ extern "C" int fb_slab_tangent_qr(fb_slab *s, int kind, double *d_r) { return ta
 // ---- the Lagrangian particles (kernels: fb_particles.h) ----
 #define FB_PARTICLES_MAX (1 << 24)
 
+static void deformation_free(fb_model *m)
+{
+    if (m->pd) { hipFree(m->pd); m->pd = nullptr; }
+}
+
 static void particles_free(fb_model *m)
 {
+    deformation_free(m);                                    // F belongs to the particles it was carried by
     if (m->pt) { hipFree(m->pt); m->pt = nullptr; }
     if (m->pt_uv) { hipFree(m->pt_uv); m->pt_uv = nullptr; }
     m->pt_n = 0;
@@ -426,6 +432,8 @@ static int particle_stage(fb_model *m, int stage)
     const PartGeo pg = part_geo(c);
     const float *u = m->pt_uv, *v = m->pt_uv + nr;
     const double dt = (double)m->dt;
+    if (m->pd)                                              // positions and the deformation gradient in one pass, in k_particle_stage's place
+        return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_stage_def<S()>, (size_t)m->pt_n, pg, u, v, m->pt, m->pd, m->pt_n, dt); });
     return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_stage<S()>, (size_t)m->pt_n, pg, u, v, m->pt, m->pt_n, dt); });
 }
 
@@ -512,6 +520,76 @@ extern "C" int fb_model_sample(fb_model *m, const float *d_field, const double *
 extern "C" int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, double *d_out)
 {
     return sample(on_slab("fb_slab_sample", s), d_field, d_xy, n, d_out);
+}
+
+// ---- the particles' deformation gradient and its stretching (kernels: fb_particles.h) ----
+// on: F = I for every particle and the elapsed time 0, allocating the twelve arrays where they are not there (so it is the reset
+// too: F grows like exp(lambda t)); off: freed.  As particles_in, the captured step is dropped: the step's particle kernel changes.
+static int deformation_in(fb_model *m, bool on)
+{
+    fb_ctx *c = m->c;
+    const size_t n = (size_t)m->pt_n;
+    int rc;
+    if ((rc = beside_begin(m, !on && m->pd))) return rc;
+    if (!on) { deformation_free(m); return FB_OK; }
+    if (!m->pd && hipMalloc((void **)&m->pd, 12 * n * sizeof(double)) != hipSuccess) {
+        m->pd = nullptr;
+        (void)hipGetLastError();
+        return fail(FB_ENOMEM, "particle deformation: allocation failed");
+    }
+    HIPCHK(hipMemsetAsync(m->pd, 0, 12 * n * sizeof(double), c->stream));
+    if ((rc = launch_n(c, k_particle_def_init, n, m->pd, m->pt_n))) return rc;
+    m->pd_steps0 = m->steps;
+    return FB_OK;
+}
+
+constexpr unsigned DEFORMATION = PARTICLES | NEED_PARTICLES | NEED_DEFORMATION;
+
+static int set_particle_deformation(const Call &k, int on)
+{
+    if (on != 0 && on != 1) return refuse(k, "on must be 0 or 1");
+    if (int rc = enter(k, PARTICLES | NEED_PARTICLES)) return rc;
+    return deformation_in(k.m, on == 1);
+}
+extern "C" int fb_model_set_particle_deformation(fb_model *m, int on) { return set_particle_deformation(on_model("fb_model_set_particle_deformation", m), on); }
+extern "C" int fb_slab_set_particle_deformation(fb_slab *s, int on) { return set_particle_deformation(on_slab("fb_slab_set_particle_deformation", s), on); }
+
+static int get_particle_deformation(const Call &k, double *d_F, double *elapsed)
+{
+    if (!d_F) return refuse(k, "NULL output");
+    if (int rc = enter(k, DEFORMATION)) return rc;
+    fb_model *m = k.m;
+    if (elapsed) *elapsed = (double)(m->steps - m->pd_steps0) * (double)m->dt;
+    return launch_n(m->c, k_particle_def_pack, (size_t)m->pt_n, (const double *)m->pd, d_F, m->pt_n);
+}
+extern "C" int fb_model_get_particle_deformation(fb_model *m, double *d_F, double *elapsed)
+{
+    return get_particle_deformation(on_model("fb_model_get_particle_deformation", m), d_F, elapsed);
+}
+extern "C" int fb_slab_get_particle_deformation(fb_slab *s, double *d_F, double *elapsed)
+{
+    return get_particle_deformation(on_slab("fb_slab_get_particle_deformation", s), d_F, elapsed);
+}
+
+// d_F == NULL: the model's own F, read where it lies (SoA), and its own n; else any [n][4], as sample takes any positions (and as
+// sample the handle's refusals first: ModelSurface.particle_stretching asks a slab of several ranks for its refusal before it shapes
+// any buffer)
+static int particle_stretching(const Call &k, const double *d_F, int n, double *d_out)
+{
+    if (int rc = enter(k, d_F ? PARTICLES : DEFORMATION)) return rc;
+    if (!d_out) return refuse(k, "NULL output");
+    if (d_F && !particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    fb_model *m = k.m;
+    if (!d_F) return launch_n(m->c, k_particle_stretching, (size_t)m->pt_n, (const double *)m->pd, (size_t)m->pt_n, (size_t)1, m->pt_n, d_out);
+    return launch_n(m->c, k_particle_stretching, (size_t)n, d_F, (size_t)1, (size_t)4, n, d_out);
+}
+extern "C" int fb_model_particle_stretching(fb_model *m, const double *d_F, int n, double *d_out)
+{
+    return particle_stretching(on_model("fb_model_particle_stretching", m), d_F, n, d_out);
+}
+extern "C" int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n, double *d_out)
+{
+    return particle_stretching(on_slab("fb_slab_particle_stretching", s), d_F, n, d_out);
 }
 
 // ---- the adjoint model (kernels: fb_adjoint.h) ----

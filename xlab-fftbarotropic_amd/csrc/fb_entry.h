@@ -21,6 +21,7 @@ enum : unsigned {
     NEED_TRANSPORT = 1,         // a slab: connected (fb_slab_connect_*; a slab of one rank is from creation).  A model: not a slab's own, driven phase by phase
     NEED_TRACER = 2, NEED_TANGENT = 4, NEED_ADJOINT = 8, NEED_PARTICLES = 16,       // the feature is set
     ONE_RANK_TANGENT = 32, ONE_RANK_ADJOINT = 64, ONE_RANK_PARTICLES = 128,         // refused on a slab of several ranks
+    NEED_DEFORMATION = 256,     // the particles carry their deformation gradient (after NEED_PARTICLES: no particles is the first refusal)
 };
 static const struct { unsigned need; const char *who; int code; } ONE_RANK[] = {
     {ONE_RANK_TANGENT, "the tangent-linear model is", FB_EINVAL},
@@ -33,6 +34,7 @@ static const struct { unsigned need; bool (*set)(const fb_model *); const char *
     {NEED_TANGENT, [](const fb_model *m) { return m->tg_n != 0; }, "no tangent is set"},
     {NEED_ADJOINT, [](const fb_model *m) { return m->adjoint; }, "no adjoint is set"},
     {NEED_PARTICLES, [](const fb_model *m) { return m->pt_n != 0; }, "no particles are set"},
+    {NEED_DEFORMATION, [](const fb_model *m) { return m->pd != nullptr; }, "no particle deformation is set (fb_model_set_particle_deformation)"},
 };
 
 // every refusal that depends on the handle alone

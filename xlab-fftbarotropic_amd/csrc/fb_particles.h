@@ -8,6 +8,7 @@
 //   k_particle_uv_spec   grady(psi_c), gradx(psi_c) of the stage state into two fields of the record workspace (k_psi_private<1>, <2>)
 //   (the backward x pass of the two fields and the ROW_INV row pass of each: fb_record.h, particle_stage)
 //   k_particle_stage     interpolation and the RK stage update of every particle
+//   k_particle_stage_def  the same with the deformation gradient F carried along (fb_model_set_particle_deformation), in its place
 // The state is SoA: six float64 arrays of n (base x, y; stage position x, y; accumulator x, y).
 // No reference counterpart: the reference follows no particles.
 #pragma once
@@ -16,8 +17,9 @@ struct PartGeo { double dx, dy; int nx, ny; };
 
 // The four stencil indices and weights of one axis: s = x / d, i0 = floor(s) (64-bit), t = s - i0, rows (i0 - 1 .. i0 + 2) mod n as a
 // non-negative modulus.  false: x is not finite or s lies beyond the 64-bit integers; no index is formed then and the caller reads
-// nothing.  Every index returned lies in [0, n).
-FB_DEV bool pt_axis(double x, double d, int n, int idx[4], double w[4])
+// nothing.  Every index returned lies in [0, n).  dw (optional): the weights' derivatives with respect to t; over d they are those
+// with respect to x, of the cell [i0, i0 + 1) that t lies in (at t == 0 the cell to the right).
+FB_DEV bool pt_axis(double x, double d, int n, int idx[4], double w[4], double *dw = nullptr)
 {
 #pragma clang fp contract(off)
     if (!__builtin_isfinite(x)) return false;
@@ -37,6 +39,13 @@ FB_DEV bool pt_axis(double x, double d, int n, int idx[4], double w[4])
     w[1] = (t + 1.0) * (t - 1.0) * (t - 2.0) / 2.0;
     w[2] = -(t + 1.0) * t * (t - 2.0) / 2.0;
     w[3] = (t + 1.0) * t * (t - 1.0) / 6.0;
+    if (dw) {
+        const double t3 = 3.0 * t * t;
+        dw[0] = -((t3 - 6.0 * t) + 2.0) / 6.0;
+        dw[1] = ((t3 - 4.0 * t) - 1.0) / 2.0;
+        dw[2] = -((t3 - 2.0 * t) - 2.0) / 2.0;
+        dw[3] = (t3 - 1.0) / 6.0;
+    }
     return true;
 }
 
@@ -55,6 +64,30 @@ FB_DEV double pt_gather(const float *__restrict__ f, int ny, const int ix[4], co
         const double r = ((wy[0] * (double)q0 + wy[1] * (double)q1) + wy[2] * (double)q2) + wy[3] * (double)q3;
         acc = acc + wx[a] * r;
     }
+    return acc;
+}
+
+// pt_gather's value (the same expressions in the same order: bit for bit) with both partial derivatives of the interpolant itself, from
+// the same sixteen loads: *fx = sum_a dwx[a] r_a / dx, *fy = sum_a wx[a] (sum_b dwy[b] f[ix[a]][jy[b]]) / dy
+FB_DEV double pt_gather_grad(const float *__restrict__ f, int ny, const int ix[4], const double wx[4], const double dwx[4], const int jy[4], const double wy[4],
+                             const double dwy[4], double dx, double dy, double *fx, double *fy)
+{
+#pragma clang fp contract(off)
+    const bool run = jy[3] == jy[0] + 3;
+    double acc = 0.0, gx = 0.0, gy = 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float *row = f + (size_t)ix[a] * ny;
+        float q0, q1, q2, q3;
+        if (run) { const float *p = row + jy[0]; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
+        else { q0 = row[jy[0]]; q1 = row[jy[1]]; q2 = row[jy[2]]; q3 = row[jy[3]]; }
+        const double r = ((wy[0] * (double)q0 + wy[1] * (double)q1) + wy[2] * (double)q2) + wy[3] * (double)q3;
+        const double ry = ((dwy[0] * (double)q0 + dwy[1] * (double)q1) + dwy[2] * (double)q2) + dwy[3] * (double)q3;
+        acc = acc + wx[a] * r;
+        gx = gx + dwx[a] * r;
+        gy = gy + wx[a] * ry;
+    }
+    *fx = gx / dx; *fy = gy / dy;
     return acc;
 }
 
@@ -118,6 +151,104 @@ __global__ void __launch_bounds__(256) k_particle_stage(PartGeo g, const float *
         if (STAGE == 0) { ax[p] = ku; ay[p] = kv; sx[p] = x0 + h * ku; sy[p] = y0 + h * kv; }
         else if (STAGE < 3) { ax[p] = ax[p] + 2.0 * ku; ay[p] = ay[p] + 2.0 * kv; sx[p] = x0 + h * ku; sy[p] = y0 + h * kv; }
         else { bx[p] = x0 + (dt / 6.0) * (ax[p] + ku); by[p] = y0 + (dt / 6.0) * (ay[p] + kv); }
+    }
+}
+
+// ---- the deformation gradient along the particles (fb_model_set_particle_deformation) ----
+// Every particle carries F = dX(t) / dX(t0), float64 (F11, F12, F21, F22), advanced by the linearisation of the particle's own RK4 step:
+//   K1 = A_0(X0) F0, K2 = A_1(X0 + dt/2 k1) (F0 + dt/2 K1), K3 = A_2(X0 + dt/2 k2) (F0 + dt/2 K2), K4 = A_3(X0 + dt k3) (F0 + dt K3),
+//   F <- F0 + dt/6 (((K1 + 2 K2) + 2 K3) + K4)
+// with A_s(X) = [[du/dx, du/dy], [dv/dx, dv/dy]] the gradient of the INTERPOLANT of the stage's u, v at X (pt_gather_grad): F is the
+// exact Jacobian of the discrete map X0 -> X wherever that map is differentiable (the interpolant's derivative jumps at cell faces; on
+// a face the cell to the right is taken).  det F is close to 1, not equal: the interpolated velocity is not exactly non-divergent.
+// The state is SoA beside pt: twelve float64 arrays of n (base, stage value, accumulator of F11, F12, F21, F22 each).
+
+// F = I into the four base arrays
+__global__ void __launch_bounds__(256) k_particle_def_init(double *__restrict__ pd, int n)
+{
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < (size_t)n; p += (size_t)gridDim.x * blockDim.x) {
+        pd[p] = 1.0; pd[(size_t)n + p] = 0.0; pd[2 * (size_t)n + p] = 0.0; pd[3 * (size_t)n + p] = 1.0;
+    }
+}
+// the four base arrays -> float64 [n][4] (F11, F12, F21, F22)
+__global__ void __launch_bounds__(256) k_particle_def_pack(const double *__restrict__ pd, double *__restrict__ out, int n)
+{
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < (size_t)n; p += (size_t)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[4 * p + e] = pd[e * (size_t)n + p];
+    }
+}
+
+// k_particle_stage with F carried along in the same pass: the position arithmetic is k_particle_stage's, expression for expression
+// (positions bit for bit), u, v and the four entries of A come from the same thirty-two loads.  pd: the twelve arrays of n
+// (base 0..3, stage value 4..7, accumulator 8..11).  A particle whose position is not finite gets NaN in F.
+template <int STAGE>
+__global__ void __launch_bounds__(256) k_particle_stage_def(PartGeo g, const float *__restrict__ u, const float *__restrict__ v, double *__restrict__ pt,
+                                                            double *__restrict__ pd, int n, double dt)
+{
+#pragma clang fp contract(off)
+    const size_t N = (size_t)n;
+    double *bx = pt, *by = pt + N, *sx = pt + 2 * N, *sy = pt + 3 * N, *ax = pt + 4 * N, *ay = pt + 5 * N;
+    const double h = STAGE == 2 ? dt : dt / 2.0;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (size_t)gridDim.x * blockDim.x) {
+        const double x0 = bx[p], y0 = by[p];
+        const double x = STAGE == 0 ? x0 : sx[p], y = STAGE == 0 ? y0 : sy[p];
+        int ix[4], jy[4];
+        double wx[4], wy[4], dwx[4], dwy[4];
+        double ku = __builtin_nan(""), kv = ku, a11 = ku, a12 = ku, a21 = ku, a22 = ku;
+        const bool okx = pt_axis(x, g.dx, g.nx, ix, wx, dwx), oky = pt_axis(y, g.dy, g.ny, jy, wy, dwy);
+        if (okx && oky) {
+            ku = pt_gather_grad(u, g.ny, ix, wx, dwx, jy, wy, dwy, g.dx, g.dy, &a11, &a12);
+            kv = pt_gather_grad(v, g.ny, ix, wx, dwx, jy, wy, dwy, g.dx, g.dy, &a21, &a22);
+        }
+        if (STAGE == 0) { ax[p] = ku; ay[p] = kv; sx[p] = x0 + h * ku; sy[p] = y0 + h * kv; }
+        else if (STAGE < 3) { ax[p] = ax[p] + 2.0 * ku; ay[p] = ay[p] + 2.0 * kv; sx[p] = x0 + h * ku; sy[p] = y0 + h * kv; }
+        else { bx[p] = x0 + (dt / 6.0) * (ax[p] + ku); by[p] = y0 + (dt / 6.0) * (ay[p] + kv); }
+        double f0[4], fs[4], k[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { f0[e] = pd[e * N + p]; fs[e] = STAGE == 0 ? f0[e] : pd[(4 + e) * N + p]; }
+        k[0] = a11 * fs[0] + a12 * fs[2]; k[1] = a11 * fs[1] + a12 * fs[3];
+        k[2] = a21 * fs[0] + a22 * fs[2]; k[3] = a21 * fs[1] + a22 * fs[3];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double *acc = pd + (8 + e) * N;
+            if (STAGE == 0) { acc[p] = k[e]; pd[(4 + e) * N + p] = f0[e] + h * k[e]; }
+            else if (STAGE < 3) { acc[p] = acc[p] + 2.0 * k[e]; pd[(4 + e) * N + p] = f0[e] + h * k[e]; }
+            else pd[e * N + p] = f0[e] + (dt / 6.0) * (acc[p] + k[e]);
+        }
+    }
+}
+
+// fb_model_particle_stretching: the closed-form singular value decomposition of every 2 x 2 matrix of F, float64 [n][4] (F11, F12,
+// F21, F22), into out [n][4] = ln sigma1, ln sigma2, theta_in, theta_out with
+//   F = Rot(theta_out) diag(sigma1, sign(det F) sigma2) Rot(theta_in)^T up to the overall sign (both angles name an axis, folded into
+//   (-pi/2, pi/2]): theta_in the direction of strongest stretching at the initial time, theta_out its image.
+// F is divided by its largest |entry| s first (no overflow or underflow in the products); sigma2 = |det| / sigma1, not Q - R, which
+// cancels under strong stretching.  s == 0: -inf, -inf, 0, 0; a singular F: ln sigma2 = -inf; an entry that is not finite: four NaN.
+// Entry e of particle p is read from F[e * se + p * sp]: se = 1, sp = 4 for [n][4], se = n, sp = 1 for the model's own four base arrays.
+__global__ void __launch_bounds__(256) k_particle_stretching(const double *__restrict__ F, size_t se, size_t sp, int n, double *__restrict__ out)
+{
+#pragma clang fp contract(off)
+    const double PI = 3.14159265358979323846, NINF = -__builtin_inf();
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < (size_t)n; p += (size_t)gridDim.x * blockDim.x) {
+        double a = F[p * sp], b = F[se + p * sp], c = F[2 * se + p * sp], d = F[3 * se + p * sp];
+        double l1, l2, ti, to;
+        const double s = fmax(fmax(fabs(a), fabs(b)), fmax(fabs(c), fabs(d)));
+        if (!(__builtin_isfinite(a) && __builtin_isfinite(b) && __builtin_isfinite(c) && __builtin_isfinite(d))) l1 = l2 = ti = to = __builtin_nan("");
+        else if (s == 0.0) { l1 = l2 = NINF; ti = to = 0.0; }
+        else {
+            a = a / s; b = b / s; c = c / s; d = d / s;
+            const double E = (a + d) / 2.0, Fm = (a - d) / 2.0, G = (c + b) / 2.0, H = (c - b) / 2.0;
+            const double Q = hypot(E, H), R = hypot(Fm, G);
+            const double s1 = Q + R, s2 = fabs(a * d - b * c) / s1, ls = log(s);
+            const double a1 = atan2(G, Fm), a2 = atan2(H, E);
+            l1 = log(s1) + ls;
+            l2 = s2 > 0.0 ? log(s2) + ls : NINF;
+            ti = (a1 - a2) / 2.0; to = (a2 + a1) / 2.0;
+            if (ti > PI / 2.0) ti -= PI; else if (ti <= -PI / 2.0) ti += PI;
+            if (to > PI / 2.0) to -= PI; else if (to <= -PI / 2.0) to += PI;
+        }
+        out[4 * p] = l1; out[4 * p + 1] = l2; out[4 * p + 2] = ti; out[4 * p + 3] = to;
     }
 }
 

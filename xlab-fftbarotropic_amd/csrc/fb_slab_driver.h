@@ -379,7 +379,13 @@ static int slab_steps(fb_slab *s, int nsteps)
 }
 
 // the step pair: fb_model_step (hipGraph replay where it applies, model_steps) and fb_slab_step
-static int run_steps(const Call &k, int nsteps) { return nsteps == 0 ? FB_OK : k.s ? slab_steps(k.s, nsteps) : model_steps(k.m, nsteps); }
+// (counted here, not where a step is launched: a captured step is launched once and replayed)
+static int run_steps(const Call &k, int nsteps)
+{
+    const int rc = nsteps == 0 ? FB_OK : k.s ? slab_steps(k.s, nsteps) : model_steps(k.m, nsteps);
+    if (!rc) k.m->steps += nsteps;
+    return rc;
+}
 static int step(const Call &k, int nsteps)
 {
     if (int rc = step_refusals(k, nsteps)) return rc;

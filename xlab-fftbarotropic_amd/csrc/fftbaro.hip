@@ -1049,6 +1049,10 @@ struct fb_model {
     // accumulator, x then y of each) and the stage velocity u, v as two real fields [2][nx][ny]; NULL and 0 without particles
     double *pt; int pt_n;
     float *pt_uv;
+    // the particles' deformation gradient (fb_model_set_particle_deformation): twelve float64 arrays of pt_n (base, stage value, RK
+    // accumulator of F11, F12, F21, F22 each), NULL while it is off; steps: the model's steps so far, pd_steps0: at the last reset
+    double *pd;
+    long long steps, pd_steps0;
     // the tangent-linear model (fb_tangent.h; host side in fb_beside.h): tg_n perturbations on the one trajectory (a tangent subspace;
     // fb_model_set_tangent sets one), each allocated when it is set, and what they share, since they are advanced one after the other:
     // the first advect pass's tendency of a stage (groups of active columns) and the partial sums of an inner product (the norm is
@@ -1170,6 +1174,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups; ++g) n += (c->world > 1 ? (g < c->nact ? 13 : 11) : 8) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
         if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
+        if (m->pd) n += 12 * (size_t)m->pt_n * sizeof(double);                                                             // and their deformation gradient
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         *hbm = n;
@@ -1413,6 +1418,7 @@ extern "C" int fb_model_profile_steps(fb_model *m, int nsteps, float *ms_sum, in
     if ((rc = step_refusals(k, nsteps))) return rc;
     StepProf prof; prof.stream = m->c->stream;
     rc = model_step_impl(m, nsteps, &prof);
+    if (!rc) m->steps += nsteps;
     HIPCHK(hipStreamSynchronize(m->c->stream));
     for (int cls = 0; cls < 4; ++cls) {
         ms_sum[cls] = 0.f; launches[cls] = (int)prof.ev0[cls].size();

@@ -49,6 +49,10 @@
 // with n from the file's size, and sets them as the model's Lagrangian particles (fb_model_set_particles); every record gains
 // particles_step_N.bin in the same format, the unwrapped positions, the last file of a record in ./log.  One GPU only: --world P > 1,
 // a file whose size is no positive multiple of 16 bytes and n above 2^24 are refused (exit status 2).
+// --particle-deformation (with --particles; no reference counterpart) lets the particles carry their deformation gradient F
+// (fb_model_set_particle_deformation, F = I at the start); every record gains particle_deformation_step_N.bin, raw float64 [n][4]
+// (F11, F12, F21, F22), and particle_stretching_step_N.bin, [n][4] (ln sigma1, ln sigma2, theta_in, theta_out:
+// fb_model_particle_stretching), right after particles_step_N.bin in ./log.  Without --particles or with --world P > 1: exit status 2.
 // --tangent FILE [--tangent-renorm K] (no reference counterpart, K >= 0, default 0) reads FILE from the input directory as the initial
 // field is read and sets it as the perturbation of the model's tangent-linear model (fb_model_set_tangent); every record gains
 // tangent_step_N.bin and tangent_growth_step_N.bin, three float64: the time, the perturbation's enstrophy norm <dz^2> / 2 and the sum
@@ -101,6 +105,7 @@ struct Config {
     bool dump_azim = false; int azim_mode = FB_CENTER_PSI_MIN; double azim_xc = 0.0, azim_yc = 0.0;   // azimuthal means about a vortex centre (no reference counterpart)
     int azim_bins = 0, azim_modes = 4; double azim_dr = 0.0;                       // 0: the default number of bins / bin width
     std::string tangent_file; int tangent_renorm = 0;                              // the tangent-linear model's initial perturbation; renormalise every K steps (no reference counterpart)
+    bool particle_deformation = false;                                             // --particle-deformation: the particles carry F, recorded with its stretching table
     std::string particles_file; int n_particles = 0;                               // the Lagrangian particles' initial positions and their number (no reference counterpart)
 };
 
@@ -251,8 +256,9 @@ struct RecordWriter {
     double *ha[2] = {nullptr, nullptr}; size_t azim_bytes = 0;                         // the azimuthal-mean table (item buffer AZIM_TABLE), rank 0 only
     double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
     double *hp[2] = {nullptr, nullptr}; size_t part_bytes = 0;                         // the particles' positions (item buffer PARTICLES), one GPU only
+    double *hd[2] = {nullptr, nullptr}, *hst[2] = {nullptr, nullptr}; size_t def_bytes = 0;   // their deformation gradient and its stretching table (item buffers DEFORMATION, STRETCHING), one GPU only
     double hg[2][3] = {};                                                              // the tangent's time, norm and sum of ln(growth) (item buffer TANGENT_GROWTH), filled by the step loop
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8 };
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8, DEFORMATION = -9, STRETCHING = -10 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -285,6 +291,8 @@ struct RecordWriter {
                     case SPECTRA_TABLE: tab = hs[job.set]; tb = spectra_bytes; break;
                     case AZIM_TABLE: tab = ha[job.set]; tb = azim_bytes; break;
                     case PARTICLES: tab = hp[job.set]; tb = part_bytes; break;
+                    case DEFORMATION: tab = hd[job.set]; tb = def_bytes; break;
+                    case STRETCHING: tab = hst[job.set]; tb = def_bytes; break;
                     case TANGENT_GROWTH: tab = hg[job.set]; tb = 3 * sizeof(double); break;
                     default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
                     }
@@ -356,6 +364,8 @@ struct Engine {
     virtual void get_azimuthal(const Config &cfg, double *d_table, double *d_center) = 0;     // --dump-azimuthal, on the compute stream (collective)
     virtual void set_particles(const double *d_xy, int n) = 0;                        // --particles (one GPU)
     virtual void get_particles(double *d_xy) = 0;
+    virtual void set_particle_deformation() = 0;                                      // --particle-deformation (one GPU)
+    virtual void get_particle_deformation(double *d_F, double *d_table) = 0;          // F and its stretching table, [n][4] each
     virtual void set_tangent(const float *d) = 0;                                     // --tangent (one GPU)
     virtual void get_tangent(float *d) = 0;
     virtual double tangent_norm(double *d_scratch) = 0;                               // the enstrophy norm, on the host: waits for the compute stream
@@ -422,6 +432,12 @@ struct SingleEngine : Engine {
     }
     void set_particles(const double *d_xy, int n) override { must(fb_model_set_particles(model, d_xy, n), "fb_model_set_particles"); }
     void get_particles(double *d_xy) override { must(fb_model_get_particles(model, d_xy), "fb_model_get_particles"); }
+    void set_particle_deformation() override { must(fb_model_set_particle_deformation(model, 1), "fb_model_set_particle_deformation"); }
+    void get_particle_deformation(double *d_F, double *d_table) override
+    {
+        must(fb_model_get_particle_deformation(model, d_F, nullptr), "fb_model_get_particle_deformation");
+        must(fb_model_particle_stretching(model, nullptr, 0, d_table), "fb_model_particle_stretching");
+    }
     void set_tangent(const float *d) override { must(fb_model_set_tangent(model, d), "fb_model_set_tangent"); }
     void get_tangent(float *d) override { must(fb_model_get_tangent(model, d), "fb_model_get_tangent"); }
     double tangent_norm(double *d_scratch) override
@@ -489,6 +505,12 @@ struct SlabEngine : Engine {
     }
     void set_particles(const double *d_xy, int n) override { must(fb_slab_set_particles(sl, d_xy, n), "fb_slab_set_particles"); }     // (refused in main() already)
     void get_particles(double *d_xy) override { must(fb_slab_get_particles(sl, d_xy), "fb_slab_get_particles"); }
+    void set_particle_deformation() override { must(fb_slab_set_particle_deformation(sl, 1), "fb_slab_set_particle_deformation"); }   // (refused in main() already)
+    void get_particle_deformation(double *d_F, double *d_table) override
+    {
+        must(fb_slab_get_particle_deformation(sl, d_F, nullptr), "fb_slab_get_particle_deformation");
+        must(fb_slab_particle_stretching(sl, nullptr, 0, d_table), "fb_slab_particle_stretching");
+    }
     void set_tangent(const float *d) override { must(fb_slab_set_tangent(sl, d), "fb_slab_set_tangent"); }                             // (refused in main() already)
     void get_tangent(float *d) override { must(fb_slab_get_tangent(sl, d), "fb_slab_get_tangent"); }
     double tangent_norm(double *) override { std::fprintf(stderr, "--tangent: one GPU only\n"); std::exit(2); }
@@ -534,6 +556,10 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t part_bytes = (size_t)cfg.n_particles * 2 * sizeof(double);
     double *d_part = nullptr;
     if (part_bytes) must(fb_malloc((void **)&d_part, part_bytes), "fb_malloc");
+    // their deformation gradient and its stretching table (--particle-deformation): [n][4] float64 each, out at every record
+    const size_t def_bytes = cfg.particle_deformation ? (size_t)cfg.n_particles * 4 * sizeof(double) : 0;
+    double *d_def = nullptr, *d_stretch = nullptr;
+    if (def_bytes) { must(fb_malloc((void **)&d_def, def_bytes), "fb_malloc"); must(fb_malloc((void **)&d_stretch, def_bytes), "fb_malloc"); }
     // the tangent's norm (--tangent): one float64 on the device; its norm at the start, at the last renormalisation, and the sum of
     // ln(growth) over the renormalisations so far
     double *d_norm = nullptr, tg_norm0 = 0.0, tg_norm_ref = 0.0, tg_sum = 0.0;
@@ -551,6 +577,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
         if (cfg.dump_azim && lead) { must(fb_malloc_host((void **)&writer.ha[b], azim_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hc[b], 4 * sizeof(double)), "fb_malloc_host"); }
         if (part_bytes && lead) must(fb_malloc_host((void **)&writer.hp[b], part_bytes), "fb_malloc_host");
+        if (def_bytes && lead) { must(fb_malloc_host((void **)&writer.hd[b], def_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hst[b], def_bytes), "fb_malloc_host"); }
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
@@ -564,8 +591,9 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
     if (cfg.dump_azim) { writer.items.push_back({"azimuthal", RecordWriter::AZIM_TABLE}); writer.items.push_back({"azimuthal_center", RecordWriter::AZIM_CENTER}); }
     if (part_bytes) writer.items.push_back({"particles", RecordWriter::PARTICLES});
+    if (def_bytes) { writer.items.push_back({"particle_deformation", RecordWriter::DEFORMATION}); writer.items.push_back({"particle_stretching", RecordWriter::STRETCHING}); }
     if (tangent) { writer.items.push_back({"tangent", 11}); writer.items.push_back({"tangent_growth", RecordWriter::TANGENT_GROWTH}); }
-    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes;
+    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes; writer.def_bytes = def_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
@@ -616,6 +644,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         must(fb_event_record(e_h2d, copy), "record");
         eng->wait(e_h2d);
         eng->set_particles(d_part, cfg.n_particles);
+        if (def_bytes) eng->set_particle_deformation();
         must(fb_event_synchronize(e_h2d), "sync");
     }
     if (tangent) {                                                                     // the perturbation's field, as the initial field was read
@@ -673,6 +702,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
             if (cfg.dump_azim) eng->get_azimuthal(cfg, d_azim, d_azim_center);
             if (d_part) eng->get_particles(d_part);
+            if (d_def) eng->get_particle_deformation(d_def, d_stretch);
             if (tangent) {
                 eng->get_tangent(d_out[11]);
                 const double now = eng->tangent_norm(d_norm);                          // (waits for the compute stream: one host round trip per record)
@@ -688,6 +718,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (writer.ha[set]) must(fb_memcpy_d2h_async(copy, writer.ha[set], d_azim, azim_bytes), "d2h");
             if (writer.hc[set]) must(fb_memcpy_d2h_async(copy, writer.hc[set], d_azim_center, 4 * sizeof(double)), "d2h");
             if (writer.hp[set]) must(fb_memcpy_d2h_async(copy, writer.hp[set], d_part, part_bytes), "d2h");
+            if (writer.hd[set]) { must(fb_memcpy_d2h_async(copy, writer.hd[set], d_def, def_bytes), "d2h"); must(fb_memcpy_d2h_async(copy, writer.hst[set], d_stretch, def_bytes), "d2h"); }
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -760,6 +791,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (d_azim) fb_free(d_azim);
     if (d_azim_center) fb_free(d_azim_center);
     if (d_part) fb_free(d_part);
+    if (d_def) { fb_free(d_def); fb_free(d_stretch); }
     if (d_norm) fb_free(d_norm);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
@@ -769,6 +801,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (writer.ha[b]) fb_free_host(writer.ha[b]);
         if (writer.hc[b]) fb_free_host(writer.hc[b]);
         if (writer.hp[b]) fb_free_host(writer.hp[b]);
+        if (writer.hd[b]) { fb_free_host(writer.hd[b]); fb_free_host(writer.hst[b]); }
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -790,6 +823,7 @@ int main(int argc, char *args[])
                                     {"dump-spectra", 0, 0, 29}, {"tracer", 1, 0, 30}, {"tracer-kappa", 1, 0, 31},
                                     {"dump-azimuthal", 0, 0, 32}, {"azim-center", 1, 0, 33}, {"azim-bins", 1, 0, 34}, {"azim-dr", 1, 0, 35}, {"azim-modes", 1, 0, 36},
                                     {"particles", 1, 0, 37}, {"tangent", 1, 0, 38}, {"tangent-renorm", 1, 0, 39},
+                                    {"particle-deformation", 0, 0, 40},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -867,6 +901,7 @@ int main(int argc, char *args[])
             break;
         }
         case 37: cfg.particles_file = optarg; break;    // particles_step_N.bin (one GPU only)
+        case 40: cfg.particle_deformation = true; break; // particle_deformation_step_N.bin, particle_stretching_step_N.bin (with --particles)
         case 38: cfg.tangent_file = optarg; break;      // tangent_step_N.bin, tangent_growth_step_N.bin (one GPU only)
         case 39: {
             char *end = nullptr;
@@ -908,6 +943,10 @@ int main(int argc, char *args[])
         if (cfg.azim_mode == FB_CENTER_FIXED && !(cfg.azim_xc >= 0.0 && cfg.azim_xc < lx && cfg.azim_yc >= 0.0 && cfg.azim_yc < ly)) {
             fprintf(stderr, "--azim-center: X,Y must lie inside the domain, 0 <= X < Lx and 0 <= Y < Ly\n"); return 2;
         }
+    }
+    if (cfg.particle_deformation) {                                                    // what fb_model_set_particle_deformation would refuse
+        if (cfg.particles_file.empty()) { fprintf(stderr, "--particle-deformation: needs --particles FILE\n"); return 2; }
+        if (cfg.world > 1) { fprintf(stderr, "--particle-deformation: one GPU only (particles are not supported with --world P > 1)\n"); return 2; }
     }
     if (!cfg.particles_file.empty()) {                                                 // what fb_model_set_particles would refuse
         if (cfg.world > 1) { fprintf(stderr, "--particles: one GPU only (particles are not supported with --world P > 1)\n"); return 2; }
