@@ -384,6 +384,38 @@ int fb_model_get_azimuthal(fb_model *m, int center_mode, double xc, double yc, i
                            double *d_center);
 /* host logic, no GPU needed: the columns of the table, 12 + 2 nmodes; FB_EINVAL for nmodes outside [0, 8] or a NULL pointer */
 int fb_azimuthal_cols(int nmodes, int *ncols);
+/* Vortex census (no reference counterpart; McWilliams 1990): the coherent structures of a thresholded field, labelled and measured.
+ * d_field (the mask field f) and d_weight (the weight w; NULL: w = f) are ANY device [nx][ny] float32 fields, as fb_model_sample takes
+ * any field: zeta, W, the tracer ...  Cell c is in the mask iff f[c] > threshold (FB_CENSUS_ABOVE) or f[c] < threshold
+ * (FB_CENSUS_BELOW); a NaN in f is never in the mask.  A structure is a 4-connected component of the mask on the doubly periodic
+ * grid: cell (i, j) neighbours ((i +- 1) mod nx, j) and (i, (j +- 1) mod ny).  Its label is the smallest flat index ny i + j of its
+ * cells, and that cell is its anchor (i0, j0).  Structures with fewer than min_cells cells are dropped; the kept ones, in ascending
+ * label order, get the dense ids 0, 1, 2, ...  d_table: device float64 [max_structures][FB_CENSUS_COLS], row = dense id:
+ *   0 label (a whole number)   1 n (cells)   2 S_w = sum w   3 S_wx = sum (w ex)   4 S_wy = sum (w ey)   5 S_wxx = sum ((w ex) ex)
+ *   6 S_wyy = sum ((w ey) ey)   7 S_wxy = sum ((w ex) ey)   8 S_x = sum ex   9 S_y = sum ey
+ *   10 peak: the w of largest |w| among the structure's cells (a NaN never wins, ties go to the smallest flat index; NaN where every
+ *   w of the structure is a NaN)   11 peak_index: the flat index of that cell (-1 likewise)
+ * with ex = (double)((i - i0 + nx/2) mod nx - nx/2) dx, ey = (double)((j - j0 + ny/2) mod ny - ny/2) dy (a non-negative modulus: the
+ * minimum-image offset from the anchor [m]), dx = (double)Lx / nx, dy = (double)Ly / ny (the context's float32 lengths widened, as
+ * the particles and the azimuthal record take them).  Everything is float64 without contraction, w widened exactly and every product
+ * one correctly rounded multiply in the order of the brackets above: every TERM is reproducible bit for bit, and only the order of
+ * the sums (float64 atomics) differs, from call to call too; label, n, peak and peak_index are exact.  The table keeps the raw
+ * moments and subtracts nothing, as the azimuthal table does (centroid: anchor + (S_wx, S_wy) / S_w; the central second moments
+ * follow).  The moments are meaningful for a structure that spans less than half the domain on each axis: beyond that the minimum
+ * image misfolds.  label, n, S_w, peak and peak_index stay right for any structure, a percolating one included.  Rows from
+ * min(found, max_structures) on hold label = -1 and zeros.  d_count: device int32 [2]: found, the number of kept structures (it may
+ * exceed max_structures: the table then holds the first max_structures of them), and the number of all structures before min_cells.
+ * d_labels (may be NULL): device int32 [nx][ny], the dense id of every kept structure's cells, ids >= max_structures too, and -1
+ * elsewhere.  Memory of the model's own, allocated at the first call and kept: two int32 [nx][ny] arrays and nx ny / 128 bytes; the
+ * record workspace, the state, the step's buffers and a captured step are untouched.  FB_EINVAL before any HIP call: a NULL model,
+ * then a NULL field, table or count, a threshold that is not finite, a mode outside {0, 1}, min_cells outside [1, 2^30],
+ * max_structures outside [1, FB_CENSUS_MAX = 65536].  Enqueued on the context stream, no synchronisation, no host round trip. */
+#define FB_CENSUS_ABOVE 0      /* f > threshold */
+#define FB_CENSUS_BELOW 1      /* f < threshold */
+#define FB_CENSUS_COLS  12
+#define FB_CENSUS_MAX   65536
+int fb_model_census(fb_model *m, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
+                    double *d_table, int *d_count, int *d_labels);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -491,6 +523,10 @@ int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, 
 int fb_slab_set_particle_deformation(fb_slab *s, int on);
 int fb_slab_get_particle_deformation(fb_slab *s, double *d_F, double *elapsed);
 int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n, double *d_out);
+/* the vortex census (fb_model_census) on a slab of ONE rank: the same code, bit-equal labels.  On world > 1 it returns
+ * FB_EUNSUPPORTED: a structure that crosses the ranks' row slabs needs a border merge over the ranks. */
+int fb_slab_census(fb_slab *s, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
+                   double *d_table, int *d_count, int *d_labels);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

@@ -79,7 +79,9 @@ _pdb = C.POINTER(_db)
 _DEFORMATION_PAIRS = {
     "set_particle_deformation": [_ip], "get_particle_deformation": [_vp, _pdb], "particle_stretching": [_vp, _ip, _vp],
 }
-for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()):
+# the vortex census's pair, likewise
+_CENSUS_PAIRS = {"census": [_vp, _vp, _ip, _fl, _ip, _ip, _vp, _vp, _vp]}
+for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -166,6 +168,46 @@ def azimuthal_args(nx, ny, Lx, Ly, center, nbins, dr):
         while nbins > 2 and nbins * dr > min(lx, ly) / 2:
             nbins -= 1
     return mode, float(xc), float(yc), int(nbins), float(dr)
+
+
+# the columns of the vortex census table (fb_model_census, include/fftbaro.h), one row per structure
+CENSUS_COLUMNS = ("label", "n", "S_w", "S_wx", "S_wy", "S_wxx", "S_wyy", "S_wxy", "S_x", "S_y", "peak", "peak_index")
+CENSUS_MAX = 65536
+# what census_shapes derives from a row
+CENSUS_SHAPE_COLUMNS = ("area", "circulation", "xc", "yc", "xg", "yg", "a", "b", "phi", "aspect")
+
+
+def census_shapes(table, nx, ny, Lx, Ly):
+    """The shapes of the structures of a census table (numpy float64 [rows, 12], columns CENSUS_COLUMNS): float64 [rows, 10] with the
+    columns CENSUS_SHAPE_COLUMNS.  area = n dx dy [m^2]; circulation = S_w dx dy; (xc, yc) the weighted centroid, anchor + (S_wx,
+    S_wy) / S_w folded into [0, Lx) x [0, Ly), NaN where S_w = 0; (xg, yg) the geometric centroid, anchor + (S_x, S_y) / n; a >= b
+    the semi-axes 2 sqrt(lambda) of the central weighted second-moment matrix M (exact for a uniform elliptic patch; NaN where M is
+    not positive semi-definite, as a weight of mixed sign can make it); phi = atan2(2 M_xy, M_xx - M_yy) / 2 in (-pi/2, pi/2], the
+    angle of the major axis from the x axis (the first index); aspect = a / b.  A row with label -1 gives NaN.  dx, dy from the
+    float32 lengths widened, as the engine takes them.  Meaningful for structures that span less than half the domain per axis.
+    Host logic, no GPU."""
+    t = np.asarray(table, dtype=np.float64).reshape(-1, len(CENSUS_COLUMNS))
+    lx, ly = float(np.float32(Lx)), float(np.float32(Ly))
+    dx, dy = lx / nx, ly / ny
+    out = np.full((t.shape[0], len(CENSUS_SHAPE_COLUMNS)), np.nan)
+    ok = t[:, 0] >= 0
+    label = np.where(ok, t[:, 0], 0.0).astype(np.int64)
+    x0, y0 = (label // ny) * dx, (label % ny) * dy
+    n, sw = t[:, 1], t[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mx, my = t[:, 3] / sw, t[:, 4] / sw
+        mxx, myy, mxy = t[:, 5] / sw - mx * mx, t[:, 6] / sw - my * my, t[:, 7] / sw - mx * my
+        half, mean = np.hypot((mxx - myy) / 2, mxy), (mxx + myy) / 2
+        a, b = 2 * np.sqrt(mean + half), 2 * np.sqrt(mean - half)
+        phi = 0.5 * np.arctan2(2 * mxy, mxx - myy)
+        phi = np.where(phi <= -np.pi / 2, np.pi / 2, phi)
+        cols = (n * dx * dy, sw * dx * dy, np.mod(x0 + mx, lx), np.mod(y0 + my, ly), np.mod(x0 + t[:, 8] / n, lx), np.mod(y0 + t[:, 9] / n, ly),
+                a, b, phi, a / b)
+    for k, v in enumerate(cols):
+        out[ok, k] = v[ok]
+    for k, L in ((2, lx), (3, ly), (4, lx), (5, ly)):           # (a tiny negative offset folds to L itself in rounding)
+        out[out[:, k] >= L, k] = 0.0
+    return out
 
 
 def _torch():
@@ -542,6 +584,26 @@ class ModelSurface:
         cen = t.empty(4, dtype=t.float64, device="cuda")
         self._hand("get_azimuthal", mode, xc, yc, nbins, dr, int(nmodes), table, cen)
         return table, cen
+
+    def census(self, field=None, threshold=0.0, below=False, weight=None, min_cells=1, max_structures=1024, labels=False):
+        """(table, found): the vortex census (fb_model_census) of `field`, an [nx, ny] float32 field (numpy or torch; None: the model's
+        vorticity): the 4-connected structures of field > threshold (below=True: < threshold) on the doubly periodic grid with at
+        least min_cells cells, in the order of their smallest flat index.  table: float64 [min(found, max_structures), 12] on the GPU
+        (columns CENSUS_COLUMNS: label, cells, the raw moments of `weight` (None: the field itself) about the anchor cell, the peak);
+        found: the number of structures kept, which may exceed max_structures.  labels=True adds the int32 [nx, ny] map of dense
+        ids (-1 off the structures).  census_shapes turns the table into areas, circulations, centroids and axes.  One rank only."""
+        t = self.torch
+        self._one_rank("census", None, None, 0, 0.0, 1, 1, None, None, None)
+        f = self.vort() if field is None else self._dev(field)
+        w = self._dev(weight)
+        m = int(max_structures)
+        table = t.empty((min(max(m, 1), CENSUS_MAX), len(CENSUS_COLUMNS)), dtype=t.float64, device="cuda")
+        count = t.empty(2, dtype=t.int32, device="cuda")
+        ids = t.empty(self._shape, dtype=t.int32, device="cuda") if labels else None
+        self._hand("census", f, w, 1 if below else 0, float(threshold), int(min_cells), m, table, count, ids)
+        found = int(count[0].item())
+        table = table[:min(found, m)]
+        return (table, found, ids) if labels else (table, found)
 
     def set_tracer(self, c, kappa=0.0):
         """Sets the passive tracer, a field advected by the model's flow with the diffusivity kappa [m^2 s^-1] (it is stepped beside

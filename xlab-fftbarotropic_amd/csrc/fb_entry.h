@@ -22,12 +22,15 @@ enum : unsigned {
     NEED_TRACER = 2, NEED_TANGENT = 4, NEED_ADJOINT = 8, NEED_PARTICLES = 16,       // the feature is set
     ONE_RANK_TANGENT = 32, ONE_RANK_ADJOINT = 64, ONE_RANK_PARTICLES = 128,         // refused on a slab of several ranks
     NEED_DEFORMATION = 256,     // the particles carry their deformation gradient (after NEED_PARTICLES: no particles is the first refusal)
+    ONE_RANK_CENSUS = 512,      // refused on a slab of several ranks
 };
 static const struct { unsigned need; const char *who; int code; } ONE_RANK[] = {
     {ONE_RANK_TANGENT, "the tangent-linear model is", FB_EINVAL},
     {ONE_RANK_ADJOINT, "the adjoint model is", FB_EINVAL},
     // particles distributed over row slabs would need neighbour halo rows that the all-to-all transport does not provide
     {ONE_RANK_PARTICLES, "particles are", FB_EUNSUPPORTED},
+    // a structure that crosses the ranks' row slabs would need a border merge over the ranks
+    {ONE_RANK_CENSUS, "the vortex census is", FB_EUNSUPPORTED},
 };
 static const struct { unsigned need; bool (*set)(const fb_model *); const char *refusal; } FEATURE[] = {
     {NEED_TRACER, [](const fb_model *m) { return m->tracer; }, "no tracer is set"},

@@ -603,3 +603,59 @@ static int get_spectra(const Call &k, double *d_table)
 }
 extern "C" int fb_model_get_spectra(fb_model *m, double *d_table) { return get_spectra(on_model("fb_model_get_spectra", m), d_table); }
 extern "C" int fb_slab_get_spectra(fb_slab *s, double *d_table) { return get_spectra(on_slab("fb_slab_get_spectra", s), d_table); }
+
+// ---- the vortex census (fb_census.h): structures of a thresholded field labelled and measured ----
+// The census's own buffers (cs_label, cs_ids [nx][ny] int32; cs_part, the scan's partials per tile of 1024 cells) are allocated at the
+// first call and kept: not the record workspace, which a captured step reads.  In stream order: the table and the counts zeroed;
+// labels by runs; the unions; the roots and their cell counts; the scan of the kept roots (tile counts, one workgroup over them,
+// the ids); the sums; the table's last columns.  The caller's field and weight are read where they lie.
+static int record_census(fb_model *m, const float *f, const float *w, int mode, float thr, int min_cells, int max_structures, double *d_table, int *d_count,
+                         int *d_labels)
+{
+    fb_ctx *c = m->c;
+    const size_t n = (size_t)c->nx * c->ny;
+    const int ntiles = (int)(n / CENSUS_TILE), tile_grid = std::min(ntiles, c->max_wg);
+    int rc;
+    if ((rc = rec_alloc((void **)&m->cs_label, n * sizeof(int))) || (rc = rec_alloc((void **)&m->cs_ids, n * sizeof(int))) ||
+        (rc = rec_alloc((void **)&m->cs_part, (size_t)ntiles * sizeof(int2))))
+        return rc;
+    if (!w) w = f;
+    CensusGeo g;
+    g.dx = (double)c->lx / c->nx; g.dy = (double)c->ly / c->ny; g.nx = c->nx; g.ny = c->ny; g.n = n;
+    int *label = m->cs_label, *ids = m->cs_ids;
+    HIPCHK(hipMemsetAsync(ids, 0, n * sizeof(int), c->stream));
+    HIPCHK(hipMemsetAsync(d_table, 0, (size_t)max_structures * CENSUS_COLS * sizeof(double), c->stream));
+    if ((rc = launch_n(c, k_census_init, n, f, thr, mode, n, label)) || (rc = launch_n(c, k_census_merge, n, g, label)) ||
+        (rc = launch_n(c, k_census_flatten, n, n, label, ids)))
+        return rc;
+    if ((rc = launch(c, k_census_tile_counts, dim3(tile_grid), dim3(256), 0, (const int *)label, (const int *)ids, ntiles, min_cells, m->cs_part)) ||
+        (rc = launch(c, k_census_scan_tiles, dim3(1), dim3(1024), 0, m->cs_part, ntiles, d_count)) ||
+        (rc = launch(c, k_census_ids, dim3(tile_grid), dim3(256), 0, (const int *)label, ids, (const int2 *)m->cs_part, ntiles, min_cells, max_structures, d_table)))
+        return rc;
+    const bool v4 = (((size_t)w | (size_t)d_labels) & 15) == 0;
+    if ((rc = launch_n(c, v4 ? k_census_sums<true> : k_census_sums<false>, n / 4, g, (const int *)label, (const int *)ids, w, max_structures, d_table, d_labels))) return rc;
+    return launch(c, k_census_table, dim3((max_structures + 255) / 256), dim3(256), 0, (const int *)d_count, w, max_structures, d_table);
+}
+
+// (the handle's refusals first, as sample: EngineSlab.census asks a slab of several ranks for its refusal before it shapes any buffer)
+static int census(const Call &k, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures, double *d_table,
+                  int *d_count, int *d_labels)
+{
+    if (int rc = enter(k, NEED_TRANSPORT | ONE_RANK_CENSUS)) return rc;
+    if (!d_field || !d_table || !d_count) return refuse(k, "NULL field, table or count");
+    if (!std::isfinite(threshold)) return refuse(k, "the threshold is not finite");
+    if (mode != FB_CENSUS_ABOVE && mode != FB_CENSUS_BELOW) return refuse(k, "mode outside {0, 1}");
+    if (min_cells < 1 || min_cells > (1 << 30)) return refuse(k, "min_cells outside [1, 2^30]");
+    if (max_structures < 1 || max_structures > FB_CENSUS_MAX) return refuse(k, "max_structures outside [1, 65536]");
+    return record_census(k.m, d_field, d_weight, mode, threshold, min_cells, max_structures, d_table, d_count, d_labels);
+}
+extern "C" int fb_model_census(fb_model *m, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
+                               double *d_table, int *d_count, int *d_labels)
+{
+    return census(on_model("fb_model_census", m), d_field, d_weight, mode, threshold, min_cells, max_structures, d_table, d_count, d_labels);
+}
+extern "C" int fb_slab_census(fb_slab *s, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
+                              double *d_table, int *d_count, int *d_labels)
+{
+    return census(on_slab("fb_slab_census", s), d_field, d_weight, mode, threshold, min_cells, max_structures, d_table, d_count, d_labels);
+}

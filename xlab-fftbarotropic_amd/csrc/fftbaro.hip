@@ -17,6 +17,7 @@
 #include "fb_kernels.h"
 #include "fb_keff.h"
 #include "fb_azim.h"
+#include "fb_census.h"
 #include "fb_spectra.h"
 #include "fb_tracer.h"
 #include "fb_particles.h"
@@ -1032,6 +1033,11 @@ struct fb_model {
     // to the largest request)
     float *azim_fields;
     void *azim_red; size_t azim_red_cap;
+    // the vortex census (fb_census.h; host side: fb_record.h, record_census): the labels and the cells per root, then the dense ids
+    // ([nx][ny] int32 each), and the scan's per-tile partials (nx ny / 1024 int2); allocated at the first census, then kept.  Not the
+    // record workspace: a census of the caller's own field between two steps must not move what a captured step reads
+    int *cs_label, *cs_ids;
+    int2 *cs_part;
     // the pressure record's reference-point value: [world] floats to send, [world] received (fb_record.h, record_pres)
     float *pres_ref;
     // the spectra record: fields the record workspace holds where this kind has grown it (0: the three of the other kinds), and the
@@ -1158,6 +1164,9 @@ extern "C" int fb_model_destroy(fb_model *m)
     if (m->keff_red) hipFree(m->keff_red);
     if (m->azim_fields) hipFree(m->azim_fields);
     if (m->azim_red) hipFree(m->azim_red);
+    if (m->cs_label) hipFree(m->cs_label);
+    if (m->cs_ids) hipFree(m->cs_ids);
+    if (m->cs_part) hipFree(m->cs_part);
     if (m->pres_ref) hipFree(m->pres_ref);
     if (m->spec_red) hipFree(m->spec_red);
     beside_free_all(m);
@@ -1177,6 +1186,8 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         if (m->pd) n += 12 * (size_t)m->pt_n * sizeof(double);                                                             // and their deformation gradient
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
+        if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
+        if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
         *hbm = n;
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;

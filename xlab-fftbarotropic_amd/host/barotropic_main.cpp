@@ -59,6 +59,12 @@
 // of ln(growth) since the start (half the log of the norm's ratios, over every renormalisation), the last two files of a record in
 // ./log.  With K > 0 the perturbation is rescaled to its initial norm after every K steps.  One GPU only: --world P > 1 is refused
 // (exit status 2).
+// --dump-census --census-threshold T [--census-field vort|okubo-weiss] [--census-below] [--census-min-cells K] [--census-max M] (no
+// reference counterpart; defaults vort, above, K = 4, M = 256) adds census_step_N.bin to every record: the vortex census table of
+// fb_model_census, raw little-endian float64 [M][12] at a fixed size (rows beyond the structures found hold label -1 and zeros), of
+// the structures of zeta (or of the Okubo-Weiss parameter W) above (or below) T with at least K cells, always weighted by zeta.  The
+// last file of a record in ./log.  One GPU only: --world P > 1, a missing --census-threshold and arguments that the C ABI would
+// refuse are refused here (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -106,6 +112,8 @@ struct Config {
     int azim_bins = 0, azim_modes = 4; double azim_dr = 0.0;                       // 0: the default number of bins / bin width
     std::string tangent_file; int tangent_renorm = 0;                              // the tangent-linear model's initial perturbation; renormalise every K steps (no reference counterpart)
     bool particle_deformation = false;                                             // --particle-deformation: the particles carry F, recorded with its stretching table
+    bool dump_census = false, census_have_thr = false, census_ow = false, census_below = false;       // the vortex census (no reference counterpart)
+    float census_thr = 0.0f; int census_min = 4, census_max = 256;
     std::string particles_file; int n_particles = 0;                               // the Lagrangian particles' initial positions and their number (no reference counterpart)
 };
 
@@ -257,8 +265,9 @@ struct RecordWriter {
     double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
     double *hp[2] = {nullptr, nullptr}; size_t part_bytes = 0;                         // the particles' positions (item buffer PARTICLES), one GPU only
     double *hd[2] = {nullptr, nullptr}, *hst[2] = {nullptr, nullptr}; size_t def_bytes = 0;   // their deformation gradient and its stretching table (item buffers DEFORMATION, STRETCHING), one GPU only
+    double *hcs[2] = {nullptr, nullptr}; size_t census_bytes = 0;                      // the vortex census table (item buffer CENSUS), one GPU only
     double hg[2][3] = {};                                                              // the tangent's time, norm and sum of ln(growth) (item buffer TANGENT_GROWTH), filled by the step loop
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8, DEFORMATION = -9, STRETCHING = -10 };
+    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8, DEFORMATION = -9, STRETCHING = -10, CENSUS = -11 };
     // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
     // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
     std::vector<std::pair<const char *, int> > items;
@@ -293,6 +302,7 @@ struct RecordWriter {
                     case PARTICLES: tab = hp[job.set]; tb = part_bytes; break;
                     case DEFORMATION: tab = hd[job.set]; tb = def_bytes; break;
                     case STRETCHING: tab = hst[job.set]; tb = def_bytes; break;
+                    case CENSUS: tab = hcs[job.set]; tb = census_bytes; break;
                     case TANGENT_GROWTH: tab = hg[job.set]; tb = 3 * sizeof(double); break;
                     default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
                     }
@@ -370,6 +380,8 @@ struct Engine {
     virtual void get_tangent(float *d) = 0;
     virtual double tangent_norm(double *d_scratch) = 0;                               // the enstrophy norm, on the host: waits for the compute stream
     virtual void tangent_scale(float a) = 0;
+    // --dump-census (one GPU): the census of d_field weighted by d_zeta, on the compute stream
+    virtual void census(const Config &cfg, const float *d_field, const float *d_zeta, double *d_table, int *d_count) = 0;
 };
 struct SingleEngine : Engine {
     fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
@@ -448,6 +460,11 @@ struct SingleEngine : Engine {
         return v;
     }
     void tangent_scale(float a) override { must(fb_model_tangent_scale(model, a), "fb_model_tangent_scale"); }
+    void census(const Config &cfg, const float *d_field, const float *d_zeta, double *d_table, int *d_count) override
+    {
+        must(fb_model_census(model, d_field, d_zeta, cfg.census_below ? FB_CENSUS_BELOW : FB_CENSUS_ABOVE, cfg.census_thr, cfg.census_min, cfg.census_max, d_table, d_count, nullptr),
+             "fb_model_census");
+    }
     int npts = 0;
 };
 struct SlabEngine : Engine {
@@ -515,6 +532,7 @@ struct SlabEngine : Engine {
     void get_tangent(float *d) override { must(fb_slab_get_tangent(sl, d), "fb_slab_get_tangent"); }
     double tangent_norm(double *) override { std::fprintf(stderr, "--tangent: one GPU only\n"); std::exit(2); }
     void tangent_scale(float a) override { must(fb_slab_tangent_scale(sl, a), "fb_slab_tangent_scale"); }
+    void census(const Config &, const float *, const float *, double *, int *) override { std::fprintf(stderr, "--dump-census: one GPU only\n"); std::exit(2); }   // (refused in main() already)
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -560,6 +578,13 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const size_t def_bytes = cfg.particle_deformation ? (size_t)cfg.n_particles * 4 * sizeof(double) : 0;
     double *d_def = nullptr, *d_stretch = nullptr;
     if (def_bytes) { must(fb_malloc((void **)&d_def, def_bytes), "fb_malloc"); must(fb_malloc((void **)&d_stretch, def_bytes), "fb_malloc"); }
+    // the vortex census table and its two counts (--dump-census); W where the census is of W and no record buffer holds it
+    const size_t census_bytes = cfg.dump_census ? (size_t)cfg.census_max * FB_CENSUS_COLS * sizeof(double) : 0;
+    double *d_census = nullptr; int *d_census_count = nullptr; float *d_census_w = nullptr;
+    if (cfg.dump_census) {
+        must(fb_malloc((void **)&d_census, census_bytes), "fb_malloc"); must(fb_malloc((void **)&d_census_count, 2 * sizeof(int)), "fb_malloc");
+        if (cfg.census_ow && !cfg.dump_ow) must(fb_malloc((void **)&d_census_w, floats * sizeof(float)), "fb_malloc");
+    }
     // the tangent's norm (--tangent): one float64 on the device; its norm at the start, at the last renormalisation, and the sum of
     // ln(growth) over the renormalisations so far
     double *d_norm = nullptr, tg_norm0 = 0.0, tg_norm_ref = 0.0, tg_sum = 0.0;
@@ -578,6 +603,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (cfg.dump_azim && lead) { must(fb_malloc_host((void **)&writer.ha[b], azim_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hc[b], 4 * sizeof(double)), "fb_malloc_host"); }
         if (part_bytes && lead) must(fb_malloc_host((void **)&writer.hp[b], part_bytes), "fb_malloc_host");
         if (def_bytes && lead) { must(fb_malloc_host((void **)&writer.hd[b], def_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hst[b], def_bytes), "fb_malloc_host"); }
+        if (census_bytes && lead) must(fb_malloc_host((void **)&writer.hcs[b], census_bytes), "fb_malloc_host");
     }
     writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
     if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
@@ -593,6 +619,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (part_bytes) writer.items.push_back({"particles", RecordWriter::PARTICLES});
     if (def_bytes) { writer.items.push_back({"particle_deformation", RecordWriter::DEFORMATION}); writer.items.push_back({"particle_stretching", RecordWriter::STRETCHING}); }
     if (tangent) { writer.items.push_back({"tangent", 11}); writer.items.push_back({"tangent_growth", RecordWriter::TANGENT_GROWTH}); }
+    if (census_bytes) writer.items.push_back({"census", RecordWriter::CENSUS});
+    writer.census_bytes = census_bytes;
     writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes; writer.def_bytes = def_bytes;
     writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
@@ -708,6 +736,11 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 const double now = eng->tangent_norm(d_norm);                          // (waits for the compute stream: one host round trip per record)
                 writer.hg[set][0] = (double)step * cfg.dt; writer.hg[set][1] = now; writer.hg[set][2] = tg_sum + 0.5 * std::log(now / tg_norm_ref);
             }
+            if (d_census) {
+                const float *w = !cfg.census_ow ? d_out[0] : cfg.dump_ow ? d_out[7] : d_census_w;
+                if (d_census_w) eng->get_okubo_weiss(d_census_w, nullptr);
+                eng->census(cfg, w, d_out[0], d_census, d_census_count);
+            }
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
@@ -719,6 +752,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             if (writer.hc[set]) must(fb_memcpy_d2h_async(copy, writer.hc[set], d_azim_center, 4 * sizeof(double)), "d2h");
             if (writer.hp[set]) must(fb_memcpy_d2h_async(copy, writer.hp[set], d_part, part_bytes), "d2h");
             if (writer.hd[set]) { must(fb_memcpy_d2h_async(copy, writer.hd[set], d_def, def_bytes), "d2h"); must(fb_memcpy_d2h_async(copy, writer.hst[set], d_stretch, def_bytes), "d2h"); }
+            if (writer.hcs[set]) must(fb_memcpy_d2h_async(copy, writer.hcs[set], d_census, census_bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -793,6 +827,8 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (d_part) fb_free(d_part);
     if (d_def) { fb_free(d_def); fb_free(d_stretch); }
     if (d_norm) fb_free(d_norm);
+    if (d_census) { fb_free(d_census); fb_free(d_census_count); }
+    if (d_census_w) fb_free(d_census_w);
     for (int b = 0; b < 2; ++b) {
         for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
         if (writer.ht[b]) fb_free_host(writer.ht[b]);
@@ -802,6 +838,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (writer.hc[b]) fb_free_host(writer.hc[b]);
         if (writer.hp[b]) fb_free_host(writer.hp[b]);
         if (writer.hd[b]) { fb_free_host(writer.hd[b]); fb_free_host(writer.hst[b]); }
+        if (writer.hcs[b]) fb_free_host(writer.hcs[b]);
         if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
     }
     delete eng;
@@ -824,6 +861,8 @@ int main(int argc, char *args[])
                                     {"dump-azimuthal", 0, 0, 32}, {"azim-center", 1, 0, 33}, {"azim-bins", 1, 0, 34}, {"azim-dr", 1, 0, 35}, {"azim-modes", 1, 0, 36},
                                     {"particles", 1, 0, 37}, {"tangent", 1, 0, 38}, {"tangent-renorm", 1, 0, 39},
                                     {"particle-deformation", 0, 0, 40},
+                                    {"dump-census", 0, 0, 41}, {"census-threshold", 1, 0, 42}, {"census-field", 1, 0, 43}, {"census-below", 0, 0, 44},
+                                    {"census-min-cells", 1, 0, 45}, {"census-max", 1, 0, 46},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -910,6 +949,29 @@ int main(int argc, char *args[])
             cfg.tangent_renorm = (int)v;
             break;
         }
+        case 41: cfg.dump_census = true; break;          // census_step_N.bin (one GPU only)
+        case 42: {
+            char *end = nullptr;
+            cfg.census_thr = strtof(optarg, &end);
+            if (!*optarg || *end || !std::isfinite(cfg.census_thr)) { fprintf(stderr, "--census-threshold: a finite number\n"); return 2; }
+            cfg.census_have_thr = true;
+            break;
+        }
+        case 43: {
+            const std::string a = optarg;
+            if (a != "vort" && a != "okubo-weiss") { fprintf(stderr, "--census-field: vort or okubo-weiss\n"); return 2; }
+            cfg.census_ow = a == "okubo-weiss";
+            break;
+        }
+        case 44: cfg.census_below = true; break;
+        case 45: case 46: {
+            char *end = nullptr;
+            const long v = strtol(optarg, &end, 10);
+            if (opt == 45 && (!*optarg || *end || v < 1 || v > (1L << 30))) { fprintf(stderr, "--census-min-cells: an integer in [1, 2^30]\n"); return 2; }
+            if (opt == 46 && (!*optarg || *end || v < 1 || v > FB_CENSUS_MAX)) { fprintf(stderr, "--census-max: an integer in [1, 65536]\n"); return 2; }
+            (opt == 45 ? cfg.census_min : cfg.census_max) = (int)v;
+            break;
+        }
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
@@ -957,6 +1019,10 @@ int main(int argc, char *args[])
         }
         if (st.st_size / 16 > (off_t)(1 << 24)) { fprintf(stderr, "--particles: more than 2^24 particles\n"); return 2; }
         cfg.n_particles = (int)(st.st_size / 16);
+    }
+    if (cfg.dump_census) {                                                             // what fb_model_census would refuse
+        if (!cfg.census_have_thr) { fprintf(stderr, "--dump-census: needs --census-threshold T\n"); return 2; }
+        if (cfg.world > 1) { fprintf(stderr, "--dump-census: one GPU only (the vortex census is not supported with --world P > 1)\n"); return 2; }
     }
     if (!cfg.tangent_file.empty() && cfg.world > 1) { fprintf(stderr, "--tangent: one GPU only (the tangent-linear model is not supported with --world P > 1)\n"); return 2; }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
