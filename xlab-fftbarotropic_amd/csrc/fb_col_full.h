@@ -44,6 +44,14 @@
 #define CF_GX_CF 2048                    /* gradx_coe[4096] as floats                               */
 #define CF_LDS_CF (CF_X2_CF + 512 + CF_GX_CF)  /* + tabB[256] (W256^m) + tabA[256] (W4096^m, m < 256) + gradx_coe */
 #define CF_LDS_BYTES (CF_LDS_CF * 8)
+// how many of a thread's sixteen k3 keep their new stage state in registers across the derivative fields (k_col_full's KEEP), at
+// nx = 4096 and at nx = 8192; FB_FULL_KEEP=0 selects the KEEP = 0 kernels at run time (DESIGN.md section 7 has the measurements)
+#ifndef CF_KEEP1
+#define CF_KEEP1 5
+#endif
+#ifndef CF_KEEP2
+#define CF_KEEP2 5
+#endif
 
 struct FullArgs {
     const cf *Tin;        // tendency after the row pass, mixed layout [x][P]
@@ -126,9 +134,13 @@ template <int DIR> FB_DEV void cf_bfly16(cf *v)
     t = v[11]; v[11] = v[14]; v[14] = t;
 }
 
-template <int DIR>
-FB_DEV void cf_fft4096(cf *lds, const cf *tabA, const cf *tabB, cf (*v)[16], int w, int l, int c, int lane)
+// FRESH (inverse direction): every column works from its own opaque copy of l.  The fifteen W256^{lr l} table addresses are the same
+// for both columns and for every field, so the compiler otherwise computes them once and holds them in registers through the whole
+// derivative loop -- registers that a kernel keeping part of the state (KEEP > 0) needs for the state.
+template <int DIR, bool FRESH = false>
+FB_DEV void cf_fft4096(cf *lds, const cf *tabA, const cf *tabB, cf (*v)[16], int w, int l_, int c, int lane)
 {
+    const int l = l_;
     if (DIR < 0) {
         // mixed -> spectral
 #pragma unroll
@@ -155,6 +167,7 @@ FB_DEV void cf_fft4096(cf *lds, const cf *tabA, const cf *tabB, cf (*v)[16], int
         // spectral -> mixed (thread: k1 = w, k2 = l, reg = k3)
 #pragma unroll
         for (int col = 0; col < 2; ++col) {
+            const int l = FRESH ? launder(l_) : l_;
             cf_bfly16<+1>(v[col]);                                       // over k3 -> l (in reg)
 #pragma unroll
             for (int lr = 1; lr < 16; ++lr) { v[col][lr] = cf_mulc(v[col][lr], cf_mul(tabA[lr * w], tabB[lr * l])); if ((lr & 3) == 3) CF_FENCE(); }
@@ -186,9 +199,13 @@ FB_DEV void cf_st4(void *ubase, unsigned voff, float4 x) { *reinterpret_cast<flo
 // touched a whole stage later.  vort_c0, the previous stage state and the re-reads of the new state stay cached (nt: no gain).
 FB_DEV void cf_st4_w4(void *ubase, unsigned voff, float4 x) { st4<true>(static_cast<char *>(ubase) + voff, x); }
 
-template <int STAGE, int NSUB>
+// KEEP: the new stage state of k3 < KEEP (both columns, 4 registers per k3) stays in registers across the four derivative fields
+// instead of being fetched again for fields 1-3; the other k3 are re-read as before.  Same values through the same operations:
+// bit-identical for every KEEP; KEEP = 0 is the kernel without the copy.
+template <int STAGE, int NSUB, int KEEP>
 __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
 {
+    static_assert(KEEP >= 0 && KEEP <= 16, "KEEP counts k3 indices");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     cf *lds = reinterpret_cast<cf *>(smem_raw);
     cf *tabB = lds + CF_X2_CF, *tabA = tabB + 256;
@@ -264,6 +281,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
 #endif
     constexpr bool REMAKE_ZC = CF_REMAKE_ZC && STAGE == 1;
     float4 q0[DEPTH], q1[DEPTH], q2[DEPTH];
+    float4 zkeep[KEEP > 0 ? KEEP : 1];                  // the new state of k3 < KEEP, as stored (unused at KEEP = 0)
     auto load_k3 = [&](int k3) {
         const int sl = k3 % DEPTH;
         q0[sl] = ld4<false>(Z0 + k3 * sstep + voff_s);
@@ -306,6 +324,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
                              z0.z + (ac.z + k.z) * dt / 6.0f, z0.w + (ac.w + k.w) * dt / 6.0f);
         }
         v[0][k3] = cf_make(zn.x, zn.y); v[1][k3] = cf_make(zn.z, zn.w);
+        if (k3 < KEEP) zkeep[k3] = zn;
         if (k3 + DEPTH < 16) load_k3(k3 + DEPTH);
         if (stage < 3) { st4<true>(AC + k3 * sstep + voff_s, acc); cf_st4(ZC + k3 * sstep, voff_s, zn); }
         else cf_st4(ZO + k3 * sstep, voff_s, zn);
@@ -314,13 +333,17 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
 
     // ---- four derivatives of the new state, each transformed back and stored (fftwfop.cpp:87-117)
     const char *ZN = PRIME ? Z0 : (stage < 3 ? ZC : ZO);
+    if (PRIME) {                                      // no update loop: the kept part comes from one load of the state that was set
+#pragma unroll
+        for (int k3 = 0; k3 < KEEP; ++k3) zkeep[k3] = cf_ld4(ZN + k3 * sstep, voff_s);
+    }
 #pragma unroll 1
     for (int f = 0; f < 4; ++f) {
-        if (f > 0 || PRIME) {                         // registers were consumed: fetch the state again (own writes, L2/MALL)
+        if (f > 0 || PRIME) {                         // registers were consumed: fetch the state again (own writes, L2/MALL), but for the kept k3
             const unsigned vs = (unsigned)launder((int)voff_s);
 #pragma unroll
             for (int k3 = 0; k3 < 16; ++k3) {
-                const float4 z = cf_ld4(ZN + k3 * sstep, vs);
+                const float4 z = k3 < KEEP ? zkeep[k3] : cf_ld4(ZN + k3 * sstep, vs);
                 v[0][k3] = cf_make(z.x, z.y); v[1][k3] = cf_make(z.z, z.w);
             }
         }
@@ -342,7 +365,7 @@ __global__ void __launch_bounds__(CF_THREADS) k_col_full(FullArgs a)
             v[1][k3] = cf_make(-zb.y * kb, zb.x * kb);
             CF_FENCE();
         }
-        cf_fft4096<+1>(lds, tabA, tabB, v, w, l, c, lane);
+        cf_fft4096<+1, (KEEP > 0)>(lds, tabA, tabB, v, w, KEEP > 0 ? lkx : l, c, lane);
         char *dst = reinterpret_cast<char *>(a.W4) + (size_t)f * a.fstride * sizeof(cf) + ubase_m;
         const unsigned vm = (unsigned)launder((int)voff_m);
 #pragma unroll

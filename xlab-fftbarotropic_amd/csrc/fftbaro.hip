@@ -124,6 +124,7 @@ struct fb_ctx {
     bool rowq_off, no_row8, no_rowh;                  // FB_ROWQ=0, FB_NO_ROW8, FB_NO_ROWH
     bool full_pass_off, full_noskip;                  // FB_FULL_PASS=0, FB_FULL_NOSKIP
     bool no_column_skip, no_prescale;                 // FB_NO_COLUMN_SKIP, FB_NO_PRESCALE
+    bool full_keep_off;                               // FB_FULL_KEEP=0
     int pitch_extra;                                  // FB_PITCH_EXTRA (0 if unset)
     bool no_pitch_tune, pitch_tune, tune_verbose;     // FB_NO_PITCH_TUNE or FB_PITCH_EXTRA set, FB_PITCH_TUNE, FB_TUNE_VERBOSE
     bool nyq_frozen;            // the ky = ny/2 column lies outside the dealiasing circle (always on square grids)
@@ -241,7 +242,7 @@ static int autotune_pitch(fb_ctx *c);
 static void read_switches(fb_ctx *c)
 {
     auto set = [](const char *name) { return getenv(name) != nullptr; };
-    const char *rowq = getenv("FB_ROWQ"), *full = getenv("FB_FULL_PASS"), *extra = getenv("FB_PITCH_EXTRA");
+    const char *rowq = getenv("FB_ROWQ"), *full = getenv("FB_FULL_PASS"), *extra = getenv("FB_PITCH_EXTRA"), *keep = getenv("FB_FULL_KEEP");
     c->rowq_off = rowq && rowq[0] == '0';
     c->no_row8 = set("FB_NO_ROW8");
     c->no_rowh = set("FB_NO_ROWH");
@@ -249,6 +250,7 @@ static void read_switches(fb_ctx *c)
     c->full_noskip = set("FB_FULL_NOSKIP");
     c->no_column_skip = set("FB_NO_COLUMN_SKIP");
     c->no_prescale = set("FB_NO_PRESCALE");
+    c->full_keep_off = keep && keep[0] == '0';
     c->pitch_extra = extra ? atoi(extra) : 0;
     c->no_pitch_tune = extra || set("FB_NO_PITCH_TUNE");          // a fixed pitch (FB_PITCH_EXTRA) disables the autotuner too
     c->pitch_tune = set("FB_PITCH_TUNE");
@@ -799,13 +801,15 @@ static XPass choose_xpass(const fb_ctx *c)
     return XP_COLS;
 }
 
-// k_col_full<a.stage, a.nsub>: stage 0..3 forward x transform of the tendency + RK update + derivatives, 4 PRIME (fb_col_full.h)
+// k_col_full<a.stage, a.nsub, KEEP>: stage 0..3 forward x transform of the tendency + RK update + derivatives, 4 PRIME (fb_col_full.h)
 static int launch_full(const fb_ctx *c, const FullArgs &a)
 {
     using K = void (*)(FullArgs);
-    static const K ks[2][5] = {{k_col_full<0, 1>, k_col_full<1, 1>, k_col_full<2, 1>, k_col_full<3, 1>, k_col_full<4, 1>},
-                               {k_col_full<0, 2>, k_col_full<1, 2>, k_col_full<2, 2>, k_col_full<3, 2>, k_col_full<4, 2>}};
-    return launch_lds(c, ks[a.nsub - 1][a.stage], a.nsub * (a.stage == 4 ? a.ntiles + 1 : a.ntiles), CF_THREADS, CF_LDS_BYTES, a);
+#define CF_ROW(N, KP) {k_col_full<0, N, KP>, k_col_full<1, N, KP>, k_col_full<2, N, KP>, k_col_full<3, N, KP>, k_col_full<4, N, KP>}
+    static const K ks[2][2][5] = {{CF_ROW(1, 0), CF_ROW(2, 0)},                      // FB_FULL_KEEP=0: no part of the state kept
+                                  {CF_ROW(1, CF_KEEP1), CF_ROW(2, CF_KEEP2)}};       // the default
+#undef CF_ROW
+    return launch_lds(c, ks[c->full_keep_off ? 0 : 1][a.nsub - 1][a.stage], a.nsub * (a.stage == 4 ? a.ntiles + 1 : a.ntiles), CF_THREADS, CF_LDS_BYTES, a);
 }
 
 // The strided x sub-pass reads rows N2*P*8 bytes apart; how well that stride spreads over the HBM channels
