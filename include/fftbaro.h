@@ -301,6 +301,25 @@ int fb_model_get_tangents(fb_model *m, float *d_dz_real);                   /* [
 int fb_model_tangent_count(fb_model *m, int *count);                        /* 0 when none is set */
 int fb_model_tangent_gram(fb_model *m, int kind, double *d_gram);           /* [count][count] */
 int fb_model_tangent_qr(fb_model *m, int kind, double *d_r);                /* [count][count], upper triangular */
+/* Covariant Lyapunov vectors (no reference counterpart): what Ginelli's algorithm needs of the engine on top of fb_model_tangent_qr.
+ * The basis tape keeps the orthonormal bases Q_n of a window of QR intervals on the device: fb_model_tangent_tape(depth) allocates
+ * depth slots, each the bases of all `count` perturbations of the current set (count half spectra; no stage state, no accumulator),
+ * and leaves the tape empty; depth 0 frees it.  fb_model_tangent_tape_push copies the live bases into the next slot, device to device
+ * on the context stream; it allocates nothing and the captured step stays.  fb_model_tangent_tape_count: slots pushed and slots
+ * allocated, 0 and 0 while there is no tape.  The tape is freed with the model, by fb_model_set_tangents with NULL or another count
+ * (a set of the same count keeps it); fb_model_set_vort and fb_model_set_spectrum leave it alone.  fb_model_info counts its bytes.
+ * fb_model_tangent_combine: the live set becomes V = Q C, v_j = sum over i of c_ij q_i for all j at once, with Q the bases of tape slot
+ * `slot` or, slot = -1, the live set itself (in place), and d_c a device array [count][count] float64, row-major.  Each source is
+ * read once and each perturbation written once, whatever C holds.  Every element is summed in float64 in ascending i, not contracted,
+ * and rounded once to float32: C = I returns the bits of Q, a permutation permutes them, a power of two scales them exactly.  The
+ * vorticity, a tracer, particles and the adjoint are not touched by any of the four.  FB_EINVAL before any HIP call: depth outside
+ * [0, 2^20], a NULL output, NULL coefficients, a NULL model, a tape of depth >= 1, a push or a combination without a tangent set, a
+ * push without a tape or into a full one, slot outside [-1, slots pushed).  FB_ENOMEM: the tape does not fit (none is left).  Enqueued
+ * on the context stream, no synchronisation (fb_model_tangent_tape waits for the stream where a tape is freed). */
+int fb_model_tangent_tape(fb_model *m, int depth);                          /* 0: free the tape */
+int fb_model_tangent_tape_push(fb_model *m);
+int fb_model_tangent_tape_count(fb_model *m, int *count, int *depth);       /* 0, 0 while there is none */
+int fb_model_tangent_combine(fb_model *m, int slot, const double *d_c);     /* -1: the live set in place; d_c [count][count] */
 /* Adjoint model (no reference counterpart): the transpose T^T of the tangent-linear step above under the inner product
  * <a, b> = sum over the grid of a b, so that <T dz, lam> = <dz, T^T lam> for the DISCRETE step: sensitivities of a scalar of the
  * final state to the initial vorticity, singular vectors of T, gradients for fitting an initial state to later data.  It runs
@@ -505,6 +524,11 @@ int fb_slab_get_tangents(fb_slab *s, float *d_dz_real);
 int fb_slab_tangent_count(fb_slab *s, int *count);
 int fb_slab_tangent_gram(fb_slab *s, int kind, double *d_gram);
 int fb_slab_tangent_qr(fb_slab *s, int kind, double *d_r);
+/* the basis tape and the combination (fb_model_tangent_tape) of a slab of ONE rank, likewise */
+int fb_slab_tangent_tape(fb_slab *s, int depth);
+int fb_slab_tangent_tape_push(fb_slab *s);
+int fb_slab_tangent_tape_count(fb_slab *s, int *count, int *depth);
+int fb_slab_tangent_combine(fb_slab *s, int slot, const double *d_c);
 /* the adjoint model (fb_model_adjoint_record) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EINVAL with a message. */
 int fb_slab_adjoint_record(fb_slab *s, int depth);

@@ -6,6 +6,7 @@ main.cpp RK4 driver.  Arrays on the GPU are torch tensors (device memory + strea
 the compute is entirely in libfftbaro.so.  There is no CPU fallback: a missing library or a
 missing GPU raises.
 """
+import collections
 import ctypes as C
 import functools
 import os
@@ -81,7 +82,9 @@ _DEFORMATION_PAIRS = {
 }
 # the vortex census's pair, likewise
 _CENSUS_PAIRS = {"census": [_vp, _vp, _ip, _fl, _ip, _ip, _vp, _vp, _vp]}
-for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()):
+# the covariant Lyapunov vectors' pairs, likewise: the basis tape and the combination
+_CLV_PAIRS = {"tangent_tape": [_ip], "tangent_tape_push": [], "tangent_tape_count": [_pip, _pip], "tangent_combine": [_ip, _vp]}
+for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items()):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -288,6 +291,86 @@ def lyapunov_spectrum(model, steps, renorm_every, kind="enstrophy"):
         rows.append(np.log(np.diagonal(model.orthonormalize_tangents(kind))))
     log_growth = np.array(rows, dtype=np.float64)
     return log_growth.sum(axis=0) / (steps * model.dt), log_growth
+
+
+def _solve_upper(r, b):
+    """x with r x = b for an upper triangular r, by back substitution over all columns of b at once (no inverse is formed)"""
+    m = r.shape[0]
+    x = np.zeros_like(b)
+    for i in range(m - 1, -1, -1):
+        x[i] = (b[i] - r[i, i + 1:] @ x[i + 1:]) / r[i, i]
+    return x
+
+
+def clv_coefficients(R, C_end=None, seed=0):
+    """The backward recursion of Ginelli's algorithm on the factors of N consecutive QR intervals.  R: float64 [N, M, M], R[n - 1] the
+    upper triangular factor R_n of interval n, T Q_(n-1) = Q_n R_n with T the tangent step over the interval and Q_n the orthonormal
+    bases after it.  C_end: the coefficients C_N after the last interval (default: a random upper triangular matrix from `seed`);
+    its columns are scaled to unit length.  C_(n-1) = R_n^-1 C_n D_n by triangular solve, D_n diagonal so that every column of
+    C_(n-1) has unit Euclidean length.  The columns of V_n = Q_n C_n are the covariant Lyapunov vectors at slot n, as far as the
+    recursion has converged: T V_(n-1) = V_n D_n^-1 holds for ANY C_end.  Returns (C float64 [N + 1, M, M], log_growth float64 [N, M]):
+    log_growth[n - 1, j] = -ln |R_n^-1 c_j| is ln of the factor by which covariant vector j grows over interval n.  Raises ValueError
+    for a factor that is not finite, not upper triangular or has a diagonal element that is not positive.  Host logic, no GPU."""
+    R = np.asarray(R, dtype=np.float64)
+    if R.ndim != 3 or R.shape[1] != R.shape[2] or R.shape[1] < 1:
+        raise ValueError("clv_coefficients: R must be [N, M, M]")
+    N, M = R.shape[0], R.shape[1]
+    for n in range(N):
+        if not np.isfinite(R[n]).all():
+            raise ValueError("clv_coefficients: factor %d is not finite" % n)
+        if not np.array_equal(R[n], np.triu(R[n])):
+            raise ValueError("clv_coefficients: factor %d is not upper triangular" % n)
+        if not (np.diagonal(R[n]) > 0.0).all():
+            raise ValueError("clv_coefficients: factor %d has a diagonal element that is not positive" % n)
+    if C_end is None:
+        C_end = np.triu(np.random.default_rng(seed).standard_normal((M, M)))
+        C_end[np.diag_indices(M)] += np.sign(np.diagonal(C_end)) + (np.diagonal(C_end) == 0.0)   # (no column close to the span of the ones before)
+    C_end = np.array(C_end, dtype=np.float64)
+    if C_end.shape != (M, M) or not np.isfinite(C_end).all() or not np.array_equal(C_end, np.triu(C_end)) or (np.diagonal(C_end) == 0.0).any():
+        raise ValueError("clv_coefficients: C_end must be a finite upper triangular [M, M] matrix with a non-zero diagonal")
+    C = np.empty((N + 1, M, M))
+    log_growth = np.empty((N, M))
+    C[N] = C_end / np.sqrt((C_end * C_end).sum(axis=0))
+    for n in range(N, 0, -1):
+        x = _solve_upper(R[n - 1], C[n])
+        length = np.sqrt((x * x).sum(axis=0))
+        C[n - 1] = x / length
+        log_growth[n - 1] = -np.log(length)
+    return C, log_growth
+
+
+ClvResult = collections.namedtuple("ClvResult", "C log_growth log_r cosines kind")
+ClvResult.__doc__ = """What clv() returns.  With K window intervals, `settle` further ones and M perturbations: C float64 [K + 1, M, M], the
+coefficients of the covariant Lyapunov vectors V_n = Q_n C_n in the bases of tape slot n; log_growth [K, M], ln of the growth of vector
+j over window interval n; log_r [K + settle, M], ln r_ii of every QR (what lyapunov_spectrum accumulates); cosines [K + 1, M, M] =
+C_n^T C_n, the cosines of the angles between the vectors of slot n in the inner product of `kind` (Q_n is orthonormal in it)."""
+
+
+def clv(model, steps, renorm_every, settle, kind="enstrophy", seed=0, C_end=None):
+    """Ginelli's algorithm on the tangent subspace of `model` (anything with step, orthonormalize_tangents, tangent_tape and
+    push_tangents).  One QR (its R discarded) and the bases pushed as slot 0; then K = ceil(steps / renorm_every) window intervals of
+    step, QR, push; then `settle` further intervals of step and QR whose R alone is kept (the recursion needs no fields there, only
+    room to converge before it reaches the window); then clv_coefficients over all K + settle factors from C_end (default: random from
+    `seed`).  Returns a ClvResult.  The model is left at the end of the run with the tape full: clv_vectors(result, n) puts the vectors
+    of slot n into the live set."""
+    if steps < 1 or renorm_every < 1 or settle < 0:
+        raise ValueError("clv: steps and renorm_every must be >= 1, settle >= 0")
+    K = -(-steps // renorm_every)
+    model.orthonormalize_tangents(kind)
+    model.tangent_tape(K + 1)
+    model.push_tangents()
+    factors, done = [], 0
+    for n in range(K + settle):
+        k = min(renorm_every, steps - done) if n < K else renorm_every
+        model.step(k)
+        done += k
+        factors.append(model.orthonormalize_tangents(kind))
+        if n < K:
+            model.push_tangents()
+    R = np.array(factors, dtype=np.float64)
+    C, log_growth = clv_coefficients(R, C_end, seed)
+    C = C[:K + 1]
+    return ClvResult(C, log_growth[:K], np.log(np.diagonal(R, axis1=1, axis2=2)), np.einsum("nki,nkj->nij", C, C), kind)
 
 
 def kaplan_yorke(exponents):
@@ -773,6 +856,58 @@ class ModelSurface:
         """(exponents [M] in s^-1, log_growth [intervals, M]): steps the model, orthonormalising the perturbations every renorm_every
         steps (lyapunov_spectrum())."""
         return lyapunov_spectrum(self, steps, renorm_every, kind)
+
+    def tangent_tape(self, depth):
+        """Allocates the basis tape: depth >= 1 slots, each the bases of every perturbation of the current set (M half spectra; info()
+        counts them), and leaves it empty; depth = 0 frees it.  set_tangents with another count, or with None, frees it too; set_vort
+        and set_spectrum leave it alone.  One rank only, as set_tangent."""
+        self._call("tangent_tape", int(depth))
+
+    def push_tangents(self):
+        """Copies the perturbations' bases into the next slot of the tape, on the GPU; a full tape raises.  Nothing is allocated, and
+        the captured step (use_graph) stays."""
+        self._call("tangent_tape_push")
+
+    def tangent_tape_count(self):
+        """(slots pushed, slots allocated); (0, 0) while there is no tape"""
+        n, d = C.c_int(), C.c_int()
+        self._call("tangent_tape_count", C.byref(n), C.byref(d))
+        return n.value, d.value
+
+    _COMBINE_KEEP = 64
+
+    def combine_tangents(self, Cm, slot=None):
+        """The perturbations become V = Q C on the GPU: v_j = sum over i of C[i, j] q_i for all j in one pass, with Q the bases of
+        tape slot `slot`, or the live set itself (slot=None, in place).  Cm: float64 [M, M], numpy or torch; it is uploaded to the GPU,
+        and nothing is waited for beyond that upload (the engine works on its stream; the uploaded coefficients are kept until it has
+        read them).  Every element is summed in float64 in the order of i and rounded once to float32."""
+        t = self.torch
+        m = self._tangent_rows()
+        if isinstance(Cm, np.ndarray):
+            Cm = t.from_numpy(np.ascontiguousarray(Cm, dtype=np.float64))
+        if Cm.dtype != t.float64 or tuple(Cm.shape) != (m, m):
+            raise ValueError("combine_tangents: float64 [%d, %d]" % (m, m))
+        Cm = Cm.cuda().contiguous()
+        t.cuda.current_stream().synchronize()                   # the engine reads them on ITS stream
+        keep = self.__dict__.setdefault("_combine_kept", [])
+        if len(keep) >= self._COMBINE_KEEP:                     # (a wait once in _COMBINE_KEEP calls: what is dropped here has been read)
+            self._wait()
+            del keep[:]
+        keep.append(Cm)
+        self._call("tangent_combine", -1 if slot is None else int(slot), _ptr(Cm))
+
+    def clv(self, steps, renorm_every, settle, kind="enstrophy", seed=0, C_end=None):
+        """The covariant Lyapunov vectors over the next `steps` steps by Ginelli's algorithm (clv()): a ClvResult with the coefficients
+        C [K + 1, M, M], log_growth [K, M], log_r [K + settle, M] and cosines [K + 1, M, M], K = ceil(steps / renorm_every).  Needs a
+        set of at most TANGENTS_MAX perturbations and room for a tape of K + 1 slots (it allocates the tape and raises FftBaroError
+        where that fails).  The model is left at the end of the run, steps + settle * renorm_every steps on, with the tape full."""
+        return clv(self, steps, renorm_every, settle, kind, seed, C_end)
+
+    def clv_vectors(self, result, n):
+        """The covariant Lyapunov vectors at slot n of a clv() result, float32 [M, nx, ny]: combine_tangents(result.C[n], slot=n), then
+        tangents().  It REPLACES the live set of perturbations by these vectors (the tape keeps the bases)."""
+        self.combine_tangents(result.C[n], slot=n)
+        return self.tangents()
 
     def record_adjoint(self, depth):
         """Turns the adjoint's tape on (depth >= 1: room for depth steps; every step from now on records its four stage states, and a

@@ -1,5 +1,5 @@
 // fb_beside.h -- the fields stepped beside the vorticity: the passive tracer, the tangent-linear model and the Lagrangian particles
-// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_particles.h; C ABI: include/fftbaro.h).
+// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h; C ABI: include/fftbaro.h).
 //
 // Each is taken in between two steps and advanced at the top of every RK stage of fb_model_step and fb_slab_step, from the state the
 // vorticity's stage starts from, through the record workspace (record_advect, fb_record.h): the step's own buffers are only read.  A
@@ -194,8 +194,16 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
 // ---- the tangent-linear model (kernels: fb_tangent.h) ----
 // A set of tg_n perturbations on the one trajectory; the single tangent of fb_model_set_tangent is the set of one, and its norm the
 // inner product of perturbation 0 with itself.
+static void tangent_tape_free(fb_model *m)
+{
+    for (cf *&p : m->tt) if (p) { hipFree(p); p = nullptr; }
+    m->tt_depth = m->tt_fill = 0;
+}
+
+// (the basis tape holds copies of this set's bases in this set's count: it goes with the set)
 static void tangent_free(fb_model *m)
 {
+    tangent_tape_free(m);
     for (Beside &f : m->tg) beside_free(f);
     for (cf *&p : m->tg_j) if (p) { hipFree(p); p = nullptr; }
     if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
@@ -234,12 +242,15 @@ static int tangent_stage(fb_model *m, fb_slab *s, int stage)
 
 // `count` perturbations in, d_rows [count] real fields one after the other (beside_begin, beside_in each), with the scratch of the
 // first advect pass and the partial sums of an inner product ([ngroups][max_wg] float64); whatever set was there is replaced,
-// perturbations beyond `count` freed; d_rows == NULL removes all.
+// perturbations beyond `count` freed; d_rows == NULL removes all.  The basis tape is freed with a set that goes or changes its count
+// (its slots are laid out for that count); a set of the same count keeps it.
 static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
 {
     fb_ctx *c = m->c;
     int rc;
-    if ((rc = beside_begin(m, m->tg_n && (!d_rows || count < m->tg_n)))) return rc;
+    const bool tape_goes = m->tt_depth && (!d_rows || count != m->tg_n);
+    if ((rc = beside_begin(m, (m->tg_n && (!d_rows || count < m->tg_n)) || tape_goes))) return rc;
+    if (tape_goes) tangent_tape_free(m);
     if (!d_rows) { tangent_free(m); return FB_OK; }
     rc = each_group(c, c->nact, [&](int g, size_t n) { return rec_alloc((void **)&m->tg_j[g], n * sizeof(cf)); });
     if (!rc) rc = rec_alloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double));
@@ -315,8 +326,70 @@ static int tangent_qr(fb_model *m, int kind, double *d_r)
     return FB_OK;
 }
 
+// ---- the basis tape and the combination of the covariant Lyapunov vectors (kernel: fb_clv.h) ----
+// base k of slot `slot` of column group g (n = grp_elems of the group)
+static cf *tangent_tape_at(const fb_model *m, int g, size_t n, int slot, int k) { return m->tt[g] + ((size_t)slot * m->tg_n + k) * n; }
+
+// The tape on (depth >= 1 slots for the current set) or off (depth == 0); either way it starts empty.  The step reads no pointer of
+// it: the captured step stays.  A tape that goes may still be read or written by queued work.
+static int tangent_tape(fb_model *m, int depth)
+{
+    fb_ctx *c = m->c;
+    if (m->tt_depth) HIPCHK(hipStreamSynchronize(c->stream));
+    tangent_tape_free(m);
+    if (depth == 0) return FB_OK;
+    const int rc = each_group(c, c->ngroups, [&](int g, size_t n) -> int {
+        if (hipMalloc((void **)&m->tt[g], (size_t)depth * m->tg_n * n * sizeof(cf)) == hipSuccess) return FB_OK;
+        m->tt[g] = nullptr;
+        (void)hipGetLastError();
+        return fail(FB_ENOMEM, "the tangent's basis tape: allocation failed");
+    });
+    if (rc) { tangent_tape_free(m); return rc; }
+    m->tt_depth = depth;
+    return FB_OK;
+}
+
+// the bases of the live set into the next slot: device to device on the context's stream, nothing allocated
+static int tangent_tape_push(fb_model *m)
+{
+    fb_ctx *c = m->c;
+    for (int k = 0; k < m->tg_n; ++k) {
+        const int rc = each_group(c, c->ngroups, [&](int g, size_t n) -> int {
+            HIPCHK(hipMemcpyAsync(tangent_tape_at(m, g, n, m->tt_fill, k), m->tg[k].c0[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+            return FB_OK;
+        });
+        if (rc) return rc;
+    }
+    ++m->tt_fill;
+    return FB_OK;
+}
+
+// live set <- (slot >= 0: the bases of tape slot `slot`; slot == -1: the live set itself, in place) C, d_c a device array [tg_n][tg_n]
+// float64 row-major: v_j = sum over i of c_ij q_i, one k_tangent_combine per column group with the smallest compile-time bound that
+// holds the count.  The stage arrays hold no live data between two steps: only the bases change.
+template <int MB> static int tangent_combine_mb(fb_model *m, int slot, const double *d_c)
+{
+    fb_ctx *c = m->c;
+    const int M = m->tg_n;
+    return each_group(c, c->ngroups, [&](int g, size_t n) {
+        CombineArrays<MB> a = {};
+        for (int k = 0; k < M; ++k) {
+            a.dst[k] = m->tg[k].c0[g];
+            a.src[k] = slot < 0 ? a.dst[k] : tangent_tape_at(m, g, n, slot, k);
+        }
+        return launch_n(c, k_tangent_combine<MB>, n / 2, a, n, M, d_c);
+    });
+}
+static int tangent_combine(fb_model *m, int slot, const double *d_c)
+{
+    const int M = m->tg_n;
+    return M <= 4 ? tangent_combine_mb<4>(m, slot, d_c) : M <= 8 ? tangent_combine_mb<8>(m, slot, d_c)
+         : M <= 16 ? tangent_combine_mb<16>(m, slot, d_c) : tangent_combine_mb<32>(m, slot, d_c);
+}
+static_assert(FB_TANGENTS_MAX <= 32, "k_tangent_combine's largest instance holds 32 perturbations");
+
 // a slab of one rank goes through the same code; on several ranks the tangent-linear model is refused
-constexpr unsigned TANGENT = NEED_TRANSPORT | ONE_RANK_TANGENT, TANGENT_SET = TANGENT | NEED_TANGENT;
+constexpr unsigned TANGENT =NEED_TRANSPORT | ONE_RANK_TANGENT, TANGENT_SET = TANGENT | NEED_TANGENT;
 
 // [count] fields in; the single tangent's call sets one (and with NULL removes the whole set, as the set's own does)
 static int set_tangents(const Call &k, const float *d_dz_real, int count)
@@ -381,6 +454,50 @@ extern "C" int fb_model_tangent_gram(fb_model *m, int kind, double *d_gram) { re
 extern "C" int fb_slab_tangent_gram(fb_slab *s, int kind, double *d_gram) { return tangent_pairs(on_slab("fb_slab_tangent_gram", s), kind, d_gram, tangent_gram); }
 extern "C" int fb_model_tangent_qr(fb_model *m, int kind, double *d_r) { return tangent_pairs(on_model("fb_model_tangent_qr", m), kind, d_r, tangent_qr); }
 extern "C" int fb_slab_tangent_qr(fb_slab *s, int kind, double *d_r) { return tangent_pairs(on_slab("fb_slab_tangent_qr", s), kind, d_r, tangent_qr); }
+
+// the basis tape: a set is needed unless the tape is only freed
+static int tangent_tape(const Call &k, int depth)
+{
+    if (depth < 0 || depth > (1 << 20)) return refuse(k, "depth outside [0, 2^20]");
+    if (int rc = enter(k, depth ? TANGENT_SET : TANGENT)) return rc;
+    return tangent_tape(k.m, depth);
+}
+extern "C" int fb_model_tangent_tape(fb_model *m, int depth) { return tangent_tape(on_model("fb_model_tangent_tape", m), depth); }
+extern "C" int fb_slab_tangent_tape(fb_slab *s, int depth) { return tangent_tape(on_slab("fb_slab_tangent_tape", s), depth); }
+
+// (a full tape, and no tape at all, are refused before anything is launched)
+static int tangent_tape_push(const Call &k)
+{
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    if (!k.m->tt_depth) return refuse(k, "no basis tape (fb_model_tangent_tape)");
+    if (k.m->tt_fill >= k.m->tt_depth) return refuse(k, "the basis tape is full: " + std::to_string(k.m->tt_depth) + " slots (fb_model_tangent_tape)");
+    return tangent_tape_push(k.m);
+}
+extern "C" int fb_model_tangent_tape_push(fb_model *m) { return tangent_tape_push(on_model("fb_model_tangent_tape_push", m)); }
+extern "C" int fb_slab_tangent_tape_push(fb_slab *s) { return tangent_tape_push(on_slab("fb_slab_tangent_tape_push", s)); }
+
+// (0, 0 while there is none: not a refusal)
+static int tangent_tape_count(const Call &k, int *count, int *depth)
+{
+    if (!count || !depth) return refuse(k, "NULL output");
+    if (int rc = enter(k, TANGENT)) return rc;
+    *count = k.m->tt_fill;
+    *depth = k.m->tt_depth;
+    return FB_OK;
+}
+extern "C" int fb_model_tangent_tape_count(fb_model *m, int *count, int *depth) { return tangent_tape_count(on_model("fb_model_tangent_tape_count", m), count, depth); }
+extern "C" int fb_slab_tangent_tape_count(fb_slab *s, int *count, int *depth) { return tangent_tape_count(on_slab("fb_slab_tangent_tape_count", s), count, depth); }
+
+// (the slot's range needs the model's state: after the handle)
+static int tangent_combine(const Call &k, int slot, const double *d_c)
+{
+    if (!d_c) return refuse(k, "NULL coefficients");
+    if (int rc = enter(k, TANGENT_SET)) return rc;
+    if (slot < -1 || slot >= k.m->tt_fill) return refuse(k, "slot " + std::to_string(slot) + " outside [-1, " + std::to_string(k.m->tt_fill) + "): -1 the live set, else a pushed slot of the basis tape");
+    return tangent_combine(k.m, slot, d_c);
+}
+extern "C" int fb_model_tangent_combine(fb_model *m, int slot, const double *d_c) { return tangent_combine(on_model("fb_model_tangent_combine", m), slot, d_c); }
+extern "C" int fb_slab_tangent_combine(fb_slab *s, int slot, const double *d_c) { return tangent_combine(on_slab("fb_slab_tangent_combine", s), slot, d_c); }
 
 // ---- the Lagrangian particles (kernels: fb_particles.h) ----
 #define FB_PARTICLES_MAX (1 << 24)

@@ -22,6 +22,7 @@
 #include "fb_tracer.h"
 #include "fb_particles.h"
 #include "fb_tangent.h"
+#include "fb_clv.h"
 #include "fb_adjoint.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
@@ -1071,6 +1072,10 @@ struct fb_model {
     int tg_n;
     cf *tg_j[3];
     double *tg_red;
+    // the basis tape of the covariant Lyapunov vectors (fb_clv.h; host side in fb_beside.h): per column group tt_depth slots of the tg_n
+    // bases tg[k].c0[g], [tt_depth][tg_n] arrays of grp_elems each in c0's own layout, tt_fill slots of it pushed; NULL and 0 while
+    // there is none.  Bases only: stage states and accumulators carry nothing between two steps.  The step never reads it
+    cf *tt[3]; int tt_depth, tt_fill;
     // the adjoint model (fb_adjoint.h; host side in fb_beside.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
     // 3-pass layout, masked modes merged in from the base, ad_fill steps of it recorded; NULL and 0 while nothing is recorded.  The
     // adjoint variable lam (ad.c0) with the k-bar (ad.c1) and the accumulator (ad.acc) of a backward step, and the five real fields
@@ -1190,6 +1195,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         if (m->pd) n += 12 * (size_t)m->pt_n * sizeof(double);                                                             // and their deformation gradient
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
+        for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
         if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
         *hbm = n;
