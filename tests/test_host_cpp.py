@@ -139,6 +139,64 @@ def test_driver_optional_debug_dumps(tmp_path):
 
 
 @pytest.mark.gpu
+def test_driver_every_output_in_one_run(tmp_path):
+    """Every record output of the driver at once, 256^2 Gaussian vortex, 21 steps, a record every 10: (a) one GPU with every option --
+    ./log lists the files of steps 0, 10 and 20 in the one fixed order, every optional group present, and every file has its size;
+    (b) the same input with no option -- vort, psi, u and v are run (a)'s byte for byte, the added outputs only read the step's buffers;
+    (c) --world 2 --ranks-as-threads with the options a slab supports -- the same relative order and sizes.  What the files hold is
+    compared per output by each output's own driver test."""
+    import xlab_fftbarotropic_amd as X
+    _build()
+    n, bins, M, npart = 256, 16, 8, 8
+    order = ("vort_src_input", "vort", "dvortdx", "dvortdy", "psi", "u", "v", "dvortdt", "okubo_weiss", "tau_fil", "pres", "spectra",
+             "eddy_diffusivity", "tracer", "tracer_eddy_diffusivity", "azimuthal", "azimuthal_center", "particles", "particle_deformation",
+             "particle_stretching", "tangent", "tangent_growth", "census")
+    size = dict.fromkeys(order, n * n * 4)
+    size.update({"spectra": X.spectra_shells(n) * 10 * 8, "eddy_diffusivity": bins * 9 * 8, "tracer_eddy_diffusivity": bins * 9 * 8,
+                 "azimuthal": 8 * (12 + 4) * 8, "azimuthal_center": 32, "particles": npart * 16, "particle_deformation": npart * 32,
+                 "particle_stretching": npart * 32, "tangent_growth": 24, "census": M * 12 * 8})
+    rng = np.random.default_rng(5)
+    x0 = rng.uniform(1e5, 5e5, (npart, 2))
+
+    def run(tag, extra):
+        d = tmp_path / tag
+        (d / "input").mkdir(parents=True)
+        (d / "output").mkdir()
+        for kind, name in (("gaussian", "initial_vorticity.bin"), ("elliptic", "second.bin")):
+            subprocess.check_call([os.path.join(HOST, "makefield.out"), "--kind", kind, "--npts", str(n), "-i", name], cwd=str(d),
+                                  stderr=subprocess.DEVNULL)
+        x0.astype("<f8").tofile(str(d / "input" / "p.bin"))
+        r = subprocess.run([os.path.join(HOST, "barotropic_main.out"), "--npts", str(n), "--steps", "21", "--record-step", "10", "--no-timing"] + extra,
+                           cwd=str(d), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert r.returncode == 0, (tag, r.returncode, r.stderr[-1500:])
+        return d, (d / "log").read_text().split()
+
+    def check(d, log, names):
+        assert log == ["output/%s_step_%d.bin" % (name, s) for s in (0, 10, 20) for name in names]
+        for s in (0, 10, 20):
+            for name in names:
+                assert (d / "output" / ("%s_step_%d.bin" % (name, s))).stat().st_size == size[name], (name, s)
+
+    v0 = np.fromfile(str(run("plain", [])[0] / "input" / "initial_vorticity.bin"), dtype="<f4")
+    thr = float(np.float32(0.1 * float(v0.max())))               # as test_driver_census takes it: a float32 value
+    slab = ["--dump-okubo-weiss", "--dump-pressure", "--dump-spectra", "--dump-eddy-diffusivity", "--keff-bins", str(bins), "--tracer", "second.bin",
+            "--dump-azimuthal", "--azim-bins", "8", "--azim-modes", "2"]
+    one = ["--dump-grad-vort", "--dump-dvortdt", "--particles", "p.bin", "--particle-deformation", "--tangent", "second.bin", "--tangent-renorm", "5",
+           "--dump-census", "--census-threshold", repr(thr), "--census-max", str(M)]
+    da, log = run("all", slab + one)                             # (a)
+    check(da, log, order)
+    dp = tmp_path / "plain"                                      # (b)
+    check(dp, (dp / "log").read_text().split(), ("vort_src_input", "vort", "psi", "u", "v"))
+    for s in (0, 10, 20):
+        for name in ("vort", "psi", "u", "v"):
+            f = "%s_step_%d.bin" % (name, s)
+            assert (dp / "output" / f).read_bytes() == (da / "output" / f).read_bytes(), f
+    dc, log = run("slab", slab + ["--world", "2", "--ranks-as-threads"])          # (c)
+    check(dc, log, ("vort_src_input", "vort", "psi", "u", "v", "okubo_weiss", "tau_fil", "pres", "spectra", "eddy_diffusivity", "tracer",
+                    "tracer_eddy_diffusivity", "azimuthal", "azimuthal_center"))
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("sets", ["1", "2"])
 def test_driver_fifo_source_every_step_with_records_in_flight(tmp_path, sets):
     """The FIFO source's three pinned buffers (SourceFeed) against a writer that holds sources for the records it has queued: a NEW source

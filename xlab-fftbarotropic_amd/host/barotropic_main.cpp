@@ -70,6 +70,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -247,6 +248,24 @@ struct SourceFeed {
     }
 };
 
+// ---- the table of record outputs --------------------------------------------------------------------------------------------
+// What a record step writes, one entry per file, in the order of ./log: the reference's (main.cpp:266-282, then the stage-0 dumps
+// :156-235), followed by the outputs that have no reference counterpart.  run_rank builds the table once from Config; device and pinned
+// allocation, the D2H copies of a record, the writer's file loop, the byte count and the frees are loops over it.
+//   ROWS   a float32 field of which this rank holds `bytes`: fb_write_field on one GPU, pwrite at the rank's offset on several;
+//          pinned on every rank
+//   WHOLE  raw bytes, one whole file by fopen/fwrite: written, and pinned, on the lead rank alone; the device buffer exists on every
+//          rank, because the record calls are collective.  Without a device buffer the step loop fills the host bytes itself.
+//   SOURCE vort_src as of the record step: no buffer of its own, it comes from Job::src
+// Adding an output takes its option in Config and main(), one line in run_rank's table at its place in ./log, and the engine call that
+// fills its device buffer in the record branch: nothing else.
+struct Output {
+    enum Kind { ROWS, WHOLE, SOURCE };
+    const char *stem; Kind kind; size_t bytes;
+    void *dev;                                                                         // NULL: none
+    void *host[2];                                                                     // per set of record buffers; NULL: not on this rank
+};
+
 // ---- the record path: main.cpp:266-282 and the stage-0 dumps :181-222, written by a thread of its own ---------------------------
 struct RecordWriter {
     // Up to TWO sets of pinned buffers, each with the event behind its D2H copies: the step loop hands a record over and goes on; it has
@@ -257,22 +276,10 @@ struct RecordWriter {
     std::thread th; std::mutex mu; std::condition_variable cv;
     std::deque<Job> jobs; bool writing = false, quit = false;
     int nsets = 1; bool set_free[2] = {true, true};
-    void *e_copy[2] = {nullptr, nullptr}; float *h[2][12] = {};
-    double *ht[2] = {nullptr, nullptr}; size_t table_bytes = 0;                        // the eddy diffusivity table (item buffer KEFF_TABLE), rank 0 only
-    double *hs[2] = {nullptr, nullptr}; size_t spectra_bytes = 0;                      // the spectra table (item buffer SPECTRA_TABLE), rank 0 only
-    double *hk[2] = {nullptr, nullptr};                                                // the tracer's eddy diffusivity table (item buffer TRACER_KEFF_TABLE, table_bytes), rank 0 only
-    double *ha[2] = {nullptr, nullptr}; size_t azim_bytes = 0;                         // the azimuthal-mean table (item buffer AZIM_TABLE), rank 0 only
-    double *hc[2] = {nullptr, nullptr};                                                // its centre, four doubles (item buffer AZIM_CENTER), rank 0 only
-    double *hp[2] = {nullptr, nullptr}; size_t part_bytes = 0;                         // the particles' positions (item buffer PARTICLES), one GPU only
-    double *hd[2] = {nullptr, nullptr}, *hst[2] = {nullptr, nullptr}; size_t def_bytes = 0;   // their deformation gradient and its stretching table (item buffers DEFORMATION, STRETCHING), one GPU only
-    double *hcs[2] = {nullptr, nullptr}; size_t census_bytes = 0;                      // the vortex census table (item buffer CENSUS), one GPU only
-    double hg[2][3] = {};                                                              // the tangent's time, norm and sum of ln(growth) (item buffer TANGENT_GROWTH), filled by the step loop
-    enum { KEFF_TABLE = -2, SPECTRA_TABLE = -3, TRACER_KEFF_TABLE = -4, AZIM_TABLE = -5, AZIM_CENTER = -6, PARTICLES = -7, TANGENT_GROWTH = -8, DEFORMATION = -9, STRETCHING = -10, CENSUS = -11 };
-    // what a record step writes, in the reference's order (main.cpp:266-282, then the stage-0 dumps :156-235): name and buffer (-1 = vort_src,
-    // KEFF_TABLE = the eddy diffusivity table, SPECTRA_TABLE = the spectra table: one whole file each, written by the lead rank alone)
-    std::vector<std::pair<const char *, int> > items;
+    void *e_copy[2] = {nullptr, nullptr};
+    const std::vector<Output> *outs = nullptr;                                         // the table; fixed before start()
     SourceFeed *feed = nullptr;                                                        // vort_src as of the record step is held until written
-    std::string output; FILE *log_fd = nullptr; size_t floats = 0;
+    std::string output; FILE *log_fd = nullptr;
     bool whole = true, lead = true; off_t off = 0;                                     // whole file (writeField) or this rank's byte range
     double busy_s = 0.0, slowest_s = 0.0; size_t bytes = 0;                            // time spent writing (total, slowest record) and what was written ([timing] summary)
     void start() { th = std::thread([this] { run(); }); }
@@ -289,48 +296,35 @@ struct RecordWriter {
             must(fb_event_synchronize(e_copy[job.set]), "record: wait for copies");
             const auto w0 = std::chrono::steady_clock::now();
             char fn[1024];
-            for (size_t i = 0; i < items.size(); ++i) {                                // main.cpp:268-278, :156-235
-                snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), items[i].first, job.step);
-                if (items[i].second <= KEFF_TABLE) {
+            for (const Output &o : *outs) {                                            // main.cpp:268-278, :156-235
+                snprintf(fn, sizeof fn, "%s/%s_step_%d.bin", output.c_str(), o.stem, job.step);
+                if (o.kind == Output::WHOLE) {
                     if (!lead) continue;
-                    const double *tab = nullptr; size_t tb = 0;
-                    switch (items[i].second) {
-                    case KEFF_TABLE: tab = ht[job.set]; tb = table_bytes; break;
-                    case TRACER_KEFF_TABLE: tab = hk[job.set]; tb = table_bytes; break;
-                    case SPECTRA_TABLE: tab = hs[job.set]; tb = spectra_bytes; break;
-                    case AZIM_TABLE: tab = ha[job.set]; tb = azim_bytes; break;
-                    case PARTICLES: tab = hp[job.set]; tb = part_bytes; break;
-                    case DEFORMATION: tab = hd[job.set]; tb = def_bytes; break;
-                    case STRETCHING: tab = hst[job.set]; tb = def_bytes; break;
-                    case CENSUS: tab = hcs[job.set]; tb = census_bytes; break;
-                    case TANGENT_GROWTH: tab = hg[job.set]; tb = 3 * sizeof(double); break;
-                    default: tab = hc[job.set]; tb = 4 * sizeof(double); break;
-                    }
                     FILE *f = fopen(fn, "wb");
-                    if (!f || fwrite(tab, 1, tb, f) != tb) { perror("Write field."); std::exit(1); }
+                    if (!f || fwrite(o.host[job.set], 1, o.bytes, f) != o.bytes) { perror("Write field."); std::exit(1); }
                     fclose(f);
                     if (!whole) fprintf(stderr, "Output %s\n", fn);
                     fprintf(log_fd, "%s\n", fn); fflush(log_fd);
-                    bytes += tb;
+                    bytes += o.bytes;
                     continue;
                 }
-                const float *data = items[i].second < 0 ? job.src : h[job.set][items[i].second];
-                if (whole) must(fb_write_field(fn, data, floats), "writeField");
+                const float *data = o.kind == Output::SOURCE ? job.src : (const float *)o.host[job.set];
+                if (whole) must(fb_write_field(fn, data, o.bytes / sizeof(float)), "writeField");
                 else {
                     const int fd = open(fn, O_WRONLY | O_CREAT, 0644);
-                    const char *p = (const char *)data; size_t left = floats * sizeof(float); off_t o = off;
-                    while (fd >= 0 && left) { const ssize_t k = pwrite(fd, p, left, o); if (k <= 0) break; p += k; left -= (size_t)k; o += k; }
+                    const char *p = (const char *)data; size_t left = o.bytes; off_t at = off;
+                    while (fd >= 0 && left) { const ssize_t k = pwrite(fd, p, left, at); if (k <= 0) break; p += k; left -= (size_t)k; at += k; }
                     if (fd < 0 || left) { perror("Write field."); std::exit(1); }
                     close(fd);
                     if (lead) fprintf(stderr, "Output %s\n", fn);
                 }
                 if (lead) { fprintf(log_fd, "%s\n", fn); fflush(log_fd); }
+                bytes += o.bytes;
             }
             if (feed) feed->release(job.src_buf);
             const double this_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
             busy_s += this_s;
             if (this_s > slowest_s) slowest_s = this_s;
-            for (const auto &it : items) if (it.second > KEFF_TABLE) bytes += floats * sizeof(float);
             lk.lock();
             writing = false;
             set_free[job.set] = true;
@@ -351,126 +345,25 @@ struct RecordWriter {
     void stop() { wait_idle(); { std::lock_guard<std::mutex> lk(mu); quit = true; } cv.notify_all(); if (th.joinable()) th.join(); }
 };
 
-// ---- what the step loop needs from either model ------------------------------------------------------------------------------
+// ---- the engine: one GPU (fb_model) or this rank's slab of several (fb_slab) -----------------------------------------------------
+// The C ABI pairs fb_model_X with fb_slab_Y (Y = X, or X_local where the slab call takes this rank's rows): same arguments behind the
+// handle, one body in the library, and what needs one GPU is refused there on several ranks.  ENGINE_CALL calls the member of the pair
+// that applies; must() names it.
+#define ENGINE_CALL(eng, X, Y, ...) \
+    must((eng).sl ? fb_slab_##Y((eng).sl, __VA_ARGS__) : fb_model_##X((eng).model, __VA_ARGS__), (eng).sl ? "fb_slab_" #Y : "fb_model_" #X)
 struct Engine {
-    virtual ~Engine() {}
-    virtual void set_vort(const float *d) = 0;                                        // main.cpp:256
-    virtual void get(float *d_vort, float *d_psi, float *d_u, float *d_v) = 0;        // record kernels, on the compute stream
-    virtual void record(void *event) = 0;                                             // event behind what the compute stream holds
-    virtual void wait(void *event) = 0;                                               // compute stream waits for it
-    virtual void set_source(const float *d) = 0;                                      // main-shallow-water.cpp:304
-    virtual void step() = 0;                                                          // main.cpp:286-317
-    virtual void sync() = 0;
-    // the optional stage-0 dumps of getDvortdt(debug) (main.cpp:156-162,170-176,229-235): dvortdx, dvortdy and
-    // dvortdt = -u dvortdx - v dvortdy + vort_src of the CURRENT state (u, v as get() returned them; src NULL = zeros); any output may be NULL
-    virtual void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src) = 0;
-    virtual void get_okubo_weiss(float *d_w, float *d_tau) = 0;                       // --dump-okubo-weiss, on the compute stream
-    virtual void get_eddy_diffusivity(int nbins, double *d_table) = 0;                // --dump-eddy-diffusivity, on the compute stream (collective)
-    virtual void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) = 0;   // --dump-pressure, on the compute stream (collective)
-    virtual void get_spectra(double *d_table) = 0;                                    // --dump-spectra, on the compute stream (collective)
-    virtual void set_tracer(const float *d, float kappa) = 0;                         // --tracer (collective)
-    virtual void get_tracer(float *d) = 0;
-    virtual void get_tracer_eddy_diffusivity(int nbins, double *d_table) = 0;         // --tracer with --dump-eddy-diffusivity (collective)
-    virtual void get_azimuthal(const Config &cfg, double *d_table, double *d_center) = 0;     // --dump-azimuthal, on the compute stream (collective)
-    virtual void set_particles(const double *d_xy, int n) = 0;                        // --particles (one GPU)
-    virtual void get_particles(double *d_xy) = 0;
-    virtual void set_particle_deformation() = 0;                                      // --particle-deformation (one GPU)
-    virtual void get_particle_deformation(double *d_F, double *d_table) = 0;          // F and its stretching table, [n][4] each
-    virtual void set_tangent(const float *d) = 0;                                     // --tangent (one GPU)
-    virtual void get_tangent(float *d) = 0;
-    virtual double tangent_norm(double *d_scratch) = 0;                               // the enstrophy norm, on the host: waits for the compute stream
-    virtual void tangent_scale(float a) = 0;
-    // --dump-census (one GPU): the census of d_field weighted by d_zeta, on the compute stream
-    virtual void census(const Config &cfg, const float *d_field, const float *d_zeta, double *d_table, int *d_count) = 0;
-};
-struct SingleEngine : Engine {
-    fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;
-    SingleEngine(const Config &cfg)
-    {
-        must(fb_create(&fop, cfg.npts, cfg.npts, cfg.LX, cfg.LY), "fb_create");
-        must(fb_stream_create(&compute), "stream");
-        must(fb_set_stream(fop, compute), "fb_set_stream");
-        must(fb_model_create(&model, fop, cfg.NU, cfg.dt), "fb_model_create");
-        npts = cfg.npts;
-    }
-    ~SingleEngine() { for (float *p : {d_spec, d_tmp, d_gx, d_gy}) if (p) fb_free(p); fb_model_destroy(model); fb_destroy(fop); fb_stream_destroy(compute); }
-    void set_vort(const float *d) override { must(fb_model_set_vort(model, d), "fb_model_set_vort"); }
-    void get(float *a, float *b, float *c, float *d) override
-    {
-        must(fb_model_get_vort(model, a), "fb_model_get_vort");
-        must(fb_model_get_diag(model, b, c, d), "fb_model_get_diag");                   // functions of vort_c only: the reference's stage-0 values
-    }
-    void record(void *e) override { must(fb_event_record(e, compute), "record"); }
-    void wait(void *e) override { must(fb_stream_wait_event(compute, e), "wait"); }
-    void set_source(const float *d) override { must(fb_model_set_source(model, d), "fb_model_set_source"); }
-    void step() override { must(fb_model_step(model, 1), "fb_model_step"); }
-    void sync() override { must(fb_synchronize(fop), "sync"); }
-    float *d_spec = nullptr, *d_tmp = nullptr, *d_gx = nullptr, *d_gy = nullptr; size_t nreal = 0;
-    void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src) override
-    {
-        // the reference's own operator sequence on vort_c (main.cpp:151-168,225-227) through the operator entry points of the C ABI
-        // (bit-exact standalone kernels): off the hot path, only on record steps and only when asked for
-        if (!d_spec) {
-            nreal = (size_t)npts * npts;
-            const size_t spec = (size_t)npts * (npts / 2 + 1) * 2 * sizeof(float);
-            must(fb_malloc((void **)&d_spec, spec), "fb_malloc"); must(fb_malloc((void **)&d_tmp, spec), "fb_malloc");
-            must(fb_malloc((void **)&d_gx, nreal * sizeof(float)), "fb_malloc"); must(fb_malloc((void **)&d_gy, nreal * sizeof(float)), "fb_malloc");
-        }
-        must(fb_model_get_spectrum(model, d_spec), "fb_model_get_spectrum");
-        float *gx = d_dzdx ? d_dzdx : d_gx, *gy = d_dzdy ? d_dzdy : d_gy;
-        must(fb_gradx(fop, d_spec, d_tmp), "gradx"); must(fb_c2r(fop, d_tmp, gx, 1), "c2r");          // main.cpp:151,154
-        must(fb_grady(fop, d_spec, d_tmp), "grady"); must(fb_c2r(fop, d_tmp, gy, 1), "c2r");          // main.cpp:165,168
-        if (d_dzdt) must(fb_jacobian(fop, d_u, d_v, gx, gy, d_src, d_dzdt), "jacobian");               // main.cpp:225-227
-    }
-    void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_model_get_okubo_weiss(model, d_w, d_tau), "fb_model_get_okubo_weiss"); }
-    void get_eddy_diffusivity(int nbins, double *d_table) override
-    {
-        must(fb_model_get_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_eddy_diffusivity");
-    }
-    void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) override
-    {
-        must(fb_model_get_pressure(model, rho, f, ref_x, ref_y, d_pres), "fb_model_get_pressure");
-    }
-    void get_spectra(double *d_table) override { must(fb_model_get_spectra(model, d_table), "fb_model_get_spectra"); }
-    void set_tracer(const float *d, float kappa) override { must(fb_model_set_tracer(model, d, kappa), "fb_model_set_tracer"); }
-    void get_tracer(float *d) override { must(fb_model_get_tracer(model, d), "fb_model_get_tracer"); }
-    void get_tracer_eddy_diffusivity(int nbins, double *d_table) override
-    {
-        must(fb_model_get_tracer_eddy_diffusivity(model, nbins, d_table, nullptr, nullptr), "fb_model_get_tracer_eddy_diffusivity");
-    }
-    void get_azimuthal(const Config &cfg, double *d_table, double *d_center) override
-    {
-        must(fb_model_get_azimuthal(model, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_model_get_azimuthal");
-    }
-    void set_particles(const double *d_xy, int n) override { must(fb_model_set_particles(model, d_xy, n), "fb_model_set_particles"); }
-    void get_particles(double *d_xy) override { must(fb_model_get_particles(model, d_xy), "fb_model_get_particles"); }
-    void set_particle_deformation() override { must(fb_model_set_particle_deformation(model, 1), "fb_model_set_particle_deformation"); }
-    void get_particle_deformation(double *d_F, double *d_table) override
-    {
-        must(fb_model_get_particle_deformation(model, d_F, nullptr), "fb_model_get_particle_deformation");
-        must(fb_model_particle_stretching(model, nullptr, 0, d_table), "fb_model_particle_stretching");
-    }
-    void set_tangent(const float *d) override { must(fb_model_set_tangent(model, d), "fb_model_set_tangent"); }
-    void get_tangent(float *d) override { must(fb_model_get_tangent(model, d), "fb_model_get_tangent"); }
-    double tangent_norm(double *d_scratch) override
-    {
-        double v = 0.0;
-        must(fb_model_tangent_norm(model, 0, d_scratch), "fb_model_tangent_norm");
-        must(fb_memcpy_d2h(fop, &v, d_scratch, sizeof v), "d2h");
-        return v;
-    }
-    void tangent_scale(float a) override { must(fb_model_tangent_scale(model, a), "fb_model_tangent_scale"); }
-    void census(const Config &cfg, const float *d_field, const float *d_zeta, double *d_table, int *d_count) override
-    {
-        must(fb_model_census(model, d_field, d_zeta, cfg.census_below ? FB_CENSUS_BELOW : FB_CENSUS_ABOVE, cfg.census_thr, cfg.census_min, cfg.census_max, d_table, d_count, nullptr),
-             "fb_model_census");
-    }
+    fb_ctx *fop = nullptr; fb_model *model = nullptr; void *compute = nullptr;         // one GPU: the record kernels run on `compute`
+    fb_slab *sl = nullptr;                                                             // several: the slab owns its stream
     int npts = 0;
-};
-struct SlabEngine : Engine {
-    fb_slab *sl = nullptr;
-    SlabEngine(const Config &cfg, int rank, void *hub)
+    Engine(const Config &cfg, int rank, void *hub) : npts(cfg.npts)
     {
+        if (cfg.world == 1) {
+            must(fb_create(&fop, cfg.npts, cfg.npts, cfg.LX, cfg.LY), "fb_create");
+            must(fb_stream_create(&compute), "stream");
+            must(fb_set_stream(fop, compute), "fb_set_stream");
+            must(fb_model_create(&model, fop, cfg.NU, cfg.dt), "fb_model_create");
+            return;
+        }
         if (!hub && rank == 0) fbcomm::prepare(cfg.comm_file);                         // before anything else: no rank may find a leftover
         must(fb_slab_create(&sl, cfg.npts, cfg.npts, cfg.LX, cfg.LY, cfg.NU, cfg.dt, rank, cfg.world), "fb_slab_create");
         if (hub) { must(fb_slab_connect_local(sl, hub), "fb_slab_connect_local"); return; }
@@ -484,55 +377,42 @@ struct SlabEngine : Engine {
         }
         must(fb_slab_connect_rccl(sl, id), "fb_slab_connect_rccl");
     }
-    ~SlabEngine() { fb_slab_destroy(sl); }
-    void set_vort(const float *d) override { must(fb_slab_set_vort_local(sl, d), "fb_slab_set_vort_local"); }
-    void get(float *a, float *b, float *c, float *d) override
+    ~Engine()
     {
-        must(fb_slab_get_vort_local(sl, a), "fb_slab_get_vort_local");
-        must(fb_slab_get_diag_local(sl, b, c, d), "fb_slab_get_diag_local");
+        if (sl) { fb_slab_destroy(sl); return; }
+        for (float *p : {d_spec, d_tmp, d_gx, d_gy}) if (p) fb_free(p);
+        fb_model_destroy(model); fb_destroy(fop); fb_stream_destroy(compute);
     }
-    void record(void *e) override { must(fb_slab_record_event(sl, e), "record"); }
-    void wait(void *e) override { must(fb_slab_wait_event(sl, e), "wait"); }
-    void set_source(const float *d) override { must(fb_slab_set_source_local(sl, d), "fb_slab_set_source_local"); }
-    void step() override { must(fb_slab_step(sl, 1), "fb_slab_step"); }
-    void sync() override { must(fb_slab_synchronize(sl), "sync"); }
-    void get_debug(float *, float *, float *, const float *, const float *, const float *) override
+    void record(void *e) { must(sl ? fb_slab_record_event(sl, e) : fb_event_record(e, compute), "record"); }      // event behind what the compute stream holds
+    void wait(void *e) { must(sl ? fb_slab_wait_event(sl, e) : fb_stream_wait_event(compute, e), "wait"); }       // compute stream waits for it
+    void step() { must(sl ? fb_slab_step(sl, 1) : fb_model_step(model, 1), sl ? "fb_slab_step" : "fb_model_step"); }   // main.cpp:286-317
+    void sync() { must(sl ? fb_slab_synchronize(sl) : fb_synchronize(fop), "sync"); }
+    // the optional stage-0 dumps of getDvortdt(debug) (main.cpp:156-162,170-176,229-235), one GPU only: dvortdx, dvortdy and
+    // dvortdt = -u dvortdx - v dvortdy + vort_src of the CURRENT state (u, v as the record branch got them; src NULL = zeros); any output may be NULL
+    float *d_spec = nullptr, *d_tmp = nullptr, *d_gx = nullptr, *d_gy = nullptr;
+    void get_debug(float *d_dzdx, float *d_dzdy, float *d_dzdt, const float *d_u, const float *d_v, const float *d_src)
     {
-        std::fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); std::exit(2);      // (refused in main() already)
+        // the reference's own operator sequence on vort_c (main.cpp:151-168,225-227) through the operator entry points of the C ABI
+        // (bit-exact standalone kernels): off the hot path, only on record steps and only when asked for
+        if (!d_spec) {
+            const size_t nreal = (size_t)npts * npts;
+            const size_t spec = (size_t)npts * (npts / 2 + 1) * 2 * sizeof(float);
+            must(fb_malloc((void **)&d_spec, spec), "fb_malloc"); must(fb_malloc((void **)&d_tmp, spec), "fb_malloc");
+            must(fb_malloc((void **)&d_gx, nreal * sizeof(float)), "fb_malloc"); must(fb_malloc((void **)&d_gy, nreal * sizeof(float)), "fb_malloc");
+        }
+        must(fb_model_get_spectrum(model, d_spec), "fb_model_get_spectrum");
+        float *gx = d_dzdx ? d_dzdx : d_gx, *gy = d_dzdy ? d_dzdy : d_gy;
+        must(fb_gradx(fop, d_spec, d_tmp), "gradx"); must(fb_c2r(fop, d_tmp, gx, 1), "c2r");          // main.cpp:151,154
+        must(fb_grady(fop, d_spec, d_tmp), "grady"); must(fb_c2r(fop, d_tmp, gy, 1), "c2r");          // main.cpp:165,168
+        if (d_dzdt) must(fb_jacobian(fop, d_u, d_v, gx, gy, d_src, d_dzdt), "jacobian");               // main.cpp:225-227
     }
-    void get_okubo_weiss(float *d_w, float *d_tau) override { must(fb_slab_get_okubo_weiss_local(sl, d_w, d_tau), "fb_slab_get_okubo_weiss_local"); }
-    void get_eddy_diffusivity(int nbins, double *d_table) override
+    double tangent_norm(double *d_scratch)                                             // the enstrophy norm, on the host, one GPU only: waits for the compute stream
     {
-        must(fb_slab_get_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_eddy_diffusivity");
+        double v = 0.0;
+        must(fb_model_tangent_norm(model, 0, d_scratch), "fb_model_tangent_norm");
+        must(fb_memcpy_d2h(fop, &v, d_scratch, sizeof v), "d2h");
+        return v;
     }
-    void get_pressure(float rho, float f, int ref_x, int ref_y, float *d_pres) override
-    {
-        must(fb_slab_get_pressure_local(sl, rho, f, ref_x, ref_y, d_pres), "fb_slab_get_pressure_local");
-    }
-    void get_spectra(double *d_table) override { must(fb_slab_get_spectra(sl, d_table), "fb_slab_get_spectra"); }
-    void set_tracer(const float *d, float kappa) override { must(fb_slab_set_tracer_local(sl, d, kappa), "fb_slab_set_tracer_local"); }
-    void get_tracer(float *d) override { must(fb_slab_get_tracer_local(sl, d), "fb_slab_get_tracer_local"); }
-    void get_tracer_eddy_diffusivity(int nbins, double *d_table) override
-    {
-        must(fb_slab_get_tracer_eddy_diffusivity(sl, nbins, d_table, nullptr, nullptr), "fb_slab_get_tracer_eddy_diffusivity");
-    }
-    void get_azimuthal(const Config &cfg, double *d_table, double *d_center) override
-    {
-        must(fb_slab_get_azimuthal(sl, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, d_table, d_center), "fb_slab_get_azimuthal");
-    }
-    void set_particles(const double *d_xy, int n) override { must(fb_slab_set_particles(sl, d_xy, n), "fb_slab_set_particles"); }     // (refused in main() already)
-    void get_particles(double *d_xy) override { must(fb_slab_get_particles(sl, d_xy), "fb_slab_get_particles"); }
-    void set_particle_deformation() override { must(fb_slab_set_particle_deformation(sl, 1), "fb_slab_set_particle_deformation"); }   // (refused in main() already)
-    void get_particle_deformation(double *d_F, double *d_table) override
-    {
-        must(fb_slab_get_particle_deformation(sl, d_F, nullptr), "fb_slab_get_particle_deformation");
-        must(fb_slab_particle_stretching(sl, nullptr, 0, d_table), "fb_slab_particle_stretching");
-    }
-    void set_tangent(const float *d) override { must(fb_slab_set_tangent(sl, d), "fb_slab_set_tangent"); }                             // (refused in main() already)
-    void get_tangent(float *d) override { must(fb_slab_get_tangent(sl, d), "fb_slab_get_tangent"); }
-    double tangent_norm(double *) override { std::fprintf(stderr, "--tangent: one GPU only\n"); std::exit(2); }
-    void tangent_scale(float a) override { must(fb_slab_tangent_scale(sl, a), "fb_slab_tangent_scale"); }
-    void census(const Config &, const float *, const float *, double *, int *) override { std::fprintf(stderr, "--dump-census: one GPU only\n"); std::exit(2); }   // (refused in main() already)
 };
 
 // ---- one rank's run: the whole program when world == 1 --------------------------------------------------------------------------
@@ -541,48 +421,53 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const int N = cfg.npts, P = cfg.world;
     const size_t floats = (size_t)(N / P) * N;                                         // this rank's share of a field (all of it on one GPU)
     const off_t off = (off_t)rank * floats * sizeof(float);
-    Engine *eng = P == 1 ? (Engine *)new SingleEngine(cfg) : (Engine *)new SlabEngine(cfg, rank, hub);
+    Engine *eng = new Engine(cfg, rank, hub);
     void *copy = nullptr, *e_rec = nullptr, *e_h2d = nullptr, *e_src = nullptr;
     must(fb_stream_create(&copy), "stream");
     for (void **e : {&e_rec, &e_h2d, &e_src}) must(fb_event_create(e), "event");
-    // record buffers 0..3 = vort, psi, u, v; 4, 5 = dvortdx, dvortdy (--dump-grad-vort); 6 = dvortdt (--dump-dvortdt);
-    // 7, 8 = Okubo-Weiss parameter, filamentation time (--dump-okubo-weiss); 9 = balanced pressure (--dump-pressure); 10 = tracer (--tracer);
-    // 11 = the tangent-linear model's perturbation (--tangent)
-    constexpr int NB = 12;
     const bool tracer = !cfg.tracer_file.empty(), tangent = !cfg.tangent_file.empty();
-    const bool use[NB] = {true, true, true, true, cfg.dump_grad, cfg.dump_grad, cfg.dump_dvortdt, cfg.dump_ow, cfg.dump_ow, cfg.dump_pres, tracer, tangent};
-    float *d_in = nullptr, *d_out[NB] = {};
+    float *d_in = nullptr;
     must(fb_malloc((void **)&d_in, floats * sizeof(float)), "fb_malloc");
-    for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc((void **)&d_out[i], floats * sizeof(float)), "fb_malloc");
-    // the eddy diffusivity table (--dump-eddy-diffusivity): every rank computes it (collective), the lead rank copies it out and writes it
-    const size_t table_bytes = cfg.dump_keff ? (size_t)cfg.keff_bins * 9 * sizeof(double) : 0;
-    double *d_table = nullptr;
-    if (cfg.dump_keff) must(fb_malloc((void **)&d_table, table_bytes), "fb_malloc");
-    double *d_ttable = nullptr;                                                        // the tracer's table (--tracer with --dump-eddy-diffusivity)
-    if (cfg.dump_keff && tracer) must(fb_malloc((void **)&d_ttable, table_bytes), "fb_malloc");
-    // the spectra table (--dump-spectra): likewise
+
+    // the table of outputs, in the order of ./log; a handle is the entry's index, -1 where the option is off
+    std::vector<Output> outs;
+    auto add = [&](const char *stem, Output::Kind kind, size_t bytes, bool on_device) -> int {
+        Output o = {stem, kind, bytes, nullptr, {nullptr, nullptr}};
+        if (on_device) must(fb_malloc(&o.dev, bytes), "fb_malloc");
+        outs.push_back(o);
+        return (int)outs.size() - 1;
+    };
+    auto rows = [&](bool on, const char *stem) { return on ? add(stem, Output::ROWS, floats * sizeof(float), true) : -1; };
+    auto whole = [&](bool on, const char *stem, size_t bytes) { return on ? add(stem, Output::WHOLE, bytes, true) : -1; };
     int nshells = 0;
     if (cfg.dump_spectra) must(fb_spectra_shells(N, N, cfg.LX, cfg.LY, &nshells), "fb_spectra_shells");
-    const size_t spectra_bytes = (size_t)nshells * 10 * sizeof(double);
-    double *d_spectra = nullptr;
-    if (cfg.dump_spectra) must(fb_malloc((void **)&d_spectra, spectra_bytes), "fb_malloc");
-    // the azimuthal-mean table and its centre (--dump-azimuthal): likewise
-    const size_t azim_bytes = cfg.dump_azim ? (size_t)cfg.azim_bins * (12 + 2 * cfg.azim_modes) * sizeof(double) : 0;
-    double *d_azim = nullptr, *d_azim_center = nullptr;
-    if (cfg.dump_azim) { must(fb_malloc((void **)&d_azim, azim_bytes), "fb_malloc"); must(fb_malloc((void **)&d_azim_center, 4 * sizeof(double)), "fb_malloc"); }
-    // the particles' positions (--particles): in once, out at every record
-    const size_t part_bytes = (size_t)cfg.n_particles * 2 * sizeof(double);
-    double *d_part = nullptr;
-    if (part_bytes) must(fb_malloc((void **)&d_part, part_bytes), "fb_malloc");
-    // their deformation gradient and its stretching table (--particle-deformation): [n][4] float64 each, out at every record
-    const size_t def_bytes = cfg.particle_deformation ? (size_t)cfg.n_particles * 4 * sizeof(double) : 0;
-    double *d_def = nullptr, *d_stretch = nullptr;
-    if (def_bytes) { must(fb_malloc((void **)&d_def, def_bytes), "fb_malloc"); must(fb_malloc((void **)&d_stretch, def_bytes), "fb_malloc"); }
-    // the vortex census table and its two counts (--dump-census); W where the census is of W and no record buffer holds it
-    const size_t census_bytes = cfg.dump_census ? (size_t)cfg.census_max * FB_CENSUS_COLS * sizeof(double) : 0;
-    double *d_census = nullptr; int *d_census_count = nullptr; float *d_census_w = nullptr;
+    const size_t keff_bytes = (size_t)cfg.keff_bins * 9 * sizeof(double), np = (size_t)cfg.n_particles;
+    add("vort_src_input", Output::SOURCE, floats * sizeof(float), false);              // main.cpp:268-278
+    const int o_vort = rows(true, "vort");
+    const int o_dzdx = rows(cfg.dump_grad, "dvortdx"), o_dzdy = rows(cfg.dump_grad, "dvortdy");                   // main.cpp:156-162,170-176
+    const int o_psi = rows(true, "psi"), o_u = rows(true, "u"), o_v = rows(true, "v");                            // main.cpp:181-222
+    const int o_dzdt = rows(cfg.dump_dvortdt, "dvortdt");                              // main.cpp:229-235
+    const int o_ow = rows(cfg.dump_ow, "okubo_weiss"), o_tau = rows(cfg.dump_ow, "tau_fil");
+    const int o_pres = rows(cfg.dump_pres, "pres");                                    // invert_pres.cpp:187
+    const int o_spectra = whole(cfg.dump_spectra, "spectra", (size_t)nshells * 10 * sizeof(double));
+    const int o_keff = whole(cfg.dump_keff, "eddy_diffusivity", keff_bytes);
+    const int o_tracer = rows(tracer, "tracer");
+    const int o_tkeff = whole(tracer && cfg.dump_keff, "tracer_eddy_diffusivity", keff_bytes);
+    const int o_azim = whole(cfg.dump_azim, "azimuthal", (size_t)cfg.azim_bins * (12 + 2 * cfg.azim_modes) * sizeof(double));
+    const int o_center = whole(cfg.dump_azim, "azimuthal_center", 4 * sizeof(double));
+    const int o_part = whole(np > 0, "particles", np * 2 * sizeof(double));            // in once, out at every record
+    const int o_def = whole(cfg.particle_deformation, "particle_deformation", np * 4 * sizeof(double));
+    const int o_stretch = whole(cfg.particle_deformation, "particle_stretching", np * 4 * sizeof(double));
+    const int o_tangent = rows(tangent, "tangent");
+    const int o_growth = tangent ? add("tangent_growth", Output::WHOLE, 3 * sizeof(double), false) : -1;          // time, norm, sum of ln(growth): filled by the step loop
+    const int o_census = whole(cfg.dump_census, "census", (size_t)cfg.census_max * FB_CENSUS_COLS * sizeof(double));
+    auto F = [&](int o) { return o < 0 ? (float *)nullptr : (float *)outs[o].dev; };   // an entry's device buffer; NULL where the option is off
+    auto D = [&](int o) { return o < 0 ? (double *)nullptr : (double *)outs[o].dev; };
+
+    // device buffers that are no output: the census's two counts, and W where the census is of W and no record buffer holds it
+    int *d_census_count = nullptr; float *d_census_w = nullptr;
     if (cfg.dump_census) {
-        must(fb_malloc((void **)&d_census, census_bytes), "fb_malloc"); must(fb_malloc((void **)&d_census_count, 2 * sizeof(int)), "fb_malloc");
+        must(fb_malloc((void **)&d_census_count, 2 * sizeof(int)), "fb_malloc");
         if (cfg.census_ow && !cfg.dump_ow) must(fb_malloc((void **)&d_census_w, floats * sizeof(float)), "fb_malloc");
     }
     // the tangent's norm (--tangent): one float64 on the device; its norm at the start, at the last renormalisation, and the sum of
@@ -591,38 +476,16 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     if (tangent) must(fb_malloc((void **)&d_norm, sizeof(double)), "fb_malloc");
 
     RecordWriter writer;
-    size_t set_bytes = 0;
-    for (int i = 0; i < NB; ++i) if (use[i]) set_bytes += floats * sizeof(float);
+    size_t set_bytes = 0;                                                              // of the fields: the tables do not count towards the choice
+    for (const Output &o : outs) if (o.kind == Output::ROWS) set_bytes += o.bytes;
     writer.nsets = cfg.record_buffers == 1 || cfg.record_buffers == 2 ? cfg.record_buffers : (set_bytes <= ((size_t)1 << 30) ? 2 : 1);
     for (int b = 0; b < writer.nsets; ++b) {
         must(fb_event_create(&writer.e_copy[b]), "event");
-        for (int i = 0; i < NB; ++i) if (use[i]) must(fb_malloc_host((void **)&writer.h[b][i], floats * sizeof(float)), "fb_malloc_host");
-        if (cfg.dump_keff && lead) must(fb_malloc_host((void **)&writer.ht[b], table_bytes), "fb_malloc_host");
-        if (cfg.dump_keff && tracer && lead) must(fb_malloc_host((void **)&writer.hk[b], table_bytes), "fb_malloc_host");
-        if (cfg.dump_spectra && lead) must(fb_malloc_host((void **)&writer.hs[b], spectra_bytes), "fb_malloc_host");
-        if (cfg.dump_azim && lead) { must(fb_malloc_host((void **)&writer.ha[b], azim_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hc[b], 4 * sizeof(double)), "fb_malloc_host"); }
-        if (part_bytes && lead) must(fb_malloc_host((void **)&writer.hp[b], part_bytes), "fb_malloc_host");
-        if (def_bytes && lead) { must(fb_malloc_host((void **)&writer.hd[b], def_bytes), "fb_malloc_host"); must(fb_malloc_host((void **)&writer.hst[b], def_bytes), "fb_malloc_host"); }
-        if (census_bytes && lead) must(fb_malloc_host((void **)&writer.hcs[b], census_bytes), "fb_malloc_host");
+        for (Output &o : outs)
+            if (o.kind == Output::ROWS || (o.kind == Output::WHOLE && lead)) must(fb_malloc_host(&o.host[b], o.bytes), "fb_malloc_host");
     }
-    writer.items = {{"vort_src_input", -1}, {"vort", 0}};                              // main.cpp:268-278
-    if (cfg.dump_grad) { writer.items.push_back({"dvortdx", 4}); writer.items.push_back({"dvortdy", 5}); }   // main.cpp:156-162,170-176
-    writer.items.push_back({"psi", 1}); writer.items.push_back({"u", 2}); writer.items.push_back({"v", 3});   // main.cpp:181-222
-    if (cfg.dump_dvortdt) writer.items.push_back({"dvortdt", 6});                      // main.cpp:229-235
-    if (cfg.dump_ow) { writer.items.push_back({"okubo_weiss", 7}); writer.items.push_back({"tau_fil", 8}); }
-    if (cfg.dump_pres) writer.items.push_back({"pres", 9});                            // invert_pres.cpp:187
-    if (cfg.dump_spectra) writer.items.push_back({"spectra", RecordWriter::SPECTRA_TABLE});
-    if (cfg.dump_keff) writer.items.push_back({"eddy_diffusivity", RecordWriter::KEFF_TABLE});
-    if (tracer) writer.items.push_back({"tracer", 10});
-    if (tracer && cfg.dump_keff) writer.items.push_back({"tracer_eddy_diffusivity", RecordWriter::TRACER_KEFF_TABLE});
-    if (cfg.dump_azim) { writer.items.push_back({"azimuthal", RecordWriter::AZIM_TABLE}); writer.items.push_back({"azimuthal_center", RecordWriter::AZIM_CENTER}); }
-    if (part_bytes) writer.items.push_back({"particles", RecordWriter::PARTICLES});
-    if (def_bytes) { writer.items.push_back({"particle_deformation", RecordWriter::DEFORMATION}); writer.items.push_back({"particle_stretching", RecordWriter::STRETCHING}); }
-    if (tangent) { writer.items.push_back({"tangent", 11}); writer.items.push_back({"tangent_growth", RecordWriter::TANGENT_GROWTH}); }
-    if (census_bytes) writer.items.push_back({"census", RecordWriter::CENSUS});
-    writer.census_bytes = census_bytes;
-    writer.table_bytes = table_bytes; writer.spectra_bytes = spectra_bytes; writer.azim_bytes = azim_bytes; writer.part_bytes = part_bytes; writer.def_bytes = def_bytes;
-    writer.output = cfg.output; writer.log_fd = log_fd; writer.floats = floats;
+    writer.outs = &outs;
+    writer.output = cfg.output; writer.log_fd = log_fd;
     writer.whole = P == 1; writer.lead = lead; writer.off = off;
     writer.start();
     int last_set = -1;                                                                 // the set the previous record's D2H copies went into
@@ -645,41 +508,42 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         eng->wait(e_h2d);
     };
     snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.init_file.c_str());
-    read_rows(writer.h[0][0]);
+    read_rows((float *)outs[o_vort].host[0]);
     SourceFeed *feedp = new SourceFeed;
     SourceFeed &feed = *feedp;
     const std::string fifo = (P == 1 || cfg.vort_src_filename.empty()) ? cfg.vort_src_filename : cfg.vort_src_filename + "." + std::to_string(rank);
     feed.init(cfg.recipe_type, fifo, floats);                                          // main-shallow-water.cpp:151-152
     writer.feed = &feed;
     if (lead) printf("Initialization complete.\n");
-    eng->set_vort(d_in);                                                               // main.cpp:256
+    ENGINE_CALL(*eng, set_vort, set_vort_local, d_in);                                                               // main.cpp:256
     eng->record(e_src);                                                                // d_in is free again behind this
     must(fb_event_synchronize(e_h2d), "sync");                                         // the pinned buffer goes back to the record path
     if (tracer) {                                                                      // the tracer's field, as the initial field was read
         snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.tracer_file.c_str());
         must(fb_stream_wait_event(copy, e_src), "wait");                               // set_vort has read d_in
-        read_rows(writer.h[0][10]);
-        eng->set_tracer(d_in, cfg.tracer_kappa);
+        read_rows((float *)outs[o_tracer].host[0]);
+        ENGINE_CALL(*eng, set_tracer, set_tracer_local, d_in, cfg.tracer_kappa);
         eng->record(e_src);
         must(fb_event_synchronize(e_h2d), "sync");
     }
-    if (part_bytes) {                                                                  // the particles' positions, through a pinned record buffer
+    if (o_part >= 0) {                                                                 // the particles' positions, through a pinned record buffer
+        const Output &part = outs[o_part];
         snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.particles_file.c_str());
         FILE *f = fopen(filename, "rb");
-        if (!f || fread(writer.hp[0], 1, part_bytes, f) != part_bytes) { perror("Read particles."); std::exit(1); }
+        if (!f || fread(part.host[0], 1, part.bytes, f) != part.bytes) { perror("Read particles."); std::exit(1); }
         fclose(f);
-        must(fb_memcpy_h2d_async(copy, d_part, writer.hp[0], part_bytes), "h2d");
+        must(fb_memcpy_h2d_async(copy, part.dev, part.host[0], part.bytes), "h2d");
         must(fb_event_record(e_h2d, copy), "record");
         eng->wait(e_h2d);
-        eng->set_particles(d_part, cfg.n_particles);
-        if (def_bytes) eng->set_particle_deformation();
+        ENGINE_CALL(*eng, set_particles, set_particles, D(o_part), cfg.n_particles);
+        if (o_def >= 0) ENGINE_CALL(*eng, set_particle_deformation, set_particle_deformation, 1);
         must(fb_event_synchronize(e_h2d), "sync");
     }
     if (tangent) {                                                                     // the perturbation's field, as the initial field was read
         snprintf(filename, sizeof filename, "%s/%s", cfg.input.c_str(), cfg.tangent_file.c_str());
         must(fb_stream_wait_event(copy, e_src), "wait");                               // set_vort / set_tracer has read d_in
-        read_rows(writer.h[0][11]);
-        eng->set_tangent(d_in);
+        read_rows((float *)outs[o_tangent].host[0]);
+        ENGINE_CALL(*eng, set_tangent, set_tangent, d_in);
         eng->record(e_src);
         must(fb_event_synchronize(e_h2d), "sync");
         tg_norm0 = tg_norm_ref = eng->tangent_norm(d_norm);
@@ -715,44 +579,44 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
             feed.hold(feed.cur);                                                       // vort_src as of this step (dumped BEFORE this step's read)
             RecordWriter::Job job{step, set, feed.cur >= 0 ? feed.pin[feed.cur] : zeros.data(), feed.cur};
             h0 = std::chrono::steady_clock::now();
-            eng->get(d_out[0], d_out[1], d_out[2], d_out[3]);
+            // the record kernels, on the compute stream, in the order of the data flow (not of ./log)
+            ENGINE_CALL(*eng, get_vort, get_vort_local, F(o_vort));
+            ENGINE_CALL(*eng, get_diag, get_diag_local, F(o_psi), F(o_u), F(o_v));      // functions of vort_c only: the reference's stage-0 values
             host_get_s += since(h0);
             if (cfg.dump_grad || cfg.dump_dvortdt) {
                 // vort_src on the device: d_in holds the source in force once one has been uploaded (before that: zeros = NULL)
-                eng->get_debug(d_out[4], d_out[5], d_out[6], d_out[2], d_out[3], feed.cur >= 0 ? d_in : nullptr);
+                eng->get_debug(F(o_dzdx), F(o_dzdy), F(o_dzdt), F(o_u), F(o_v), feed.cur >= 0 ? d_in : nullptr);
                 eng->record(e_src);                                                    // d_in may be overwritten behind this
             }
-            if (cfg.dump_ow) eng->get_okubo_weiss(d_out[7], d_out[8]);
-            if (cfg.dump_pres) eng->get_pressure(cfg.pres_rho, cfg.pres_f, cfg.pres_ref_x, cfg.pres_ref_y, d_out[9]);
-            if (cfg.dump_spectra) eng->get_spectra(d_spectra);
-            if (cfg.dump_keff) eng->get_eddy_diffusivity(cfg.keff_bins, d_table);
-            if (tracer) eng->get_tracer(d_out[10]);
-            if (d_ttable) eng->get_tracer_eddy_diffusivity(cfg.keff_bins, d_ttable);
-            if (cfg.dump_azim) eng->get_azimuthal(cfg, d_azim, d_azim_center);
-            if (d_part) eng->get_particles(d_part);
-            if (d_def) eng->get_particle_deformation(d_def, d_stretch);
-            if (tangent) {
-                eng->get_tangent(d_out[11]);
-                const double now = eng->tangent_norm(d_norm);                          // (waits for the compute stream: one host round trip per record)
-                writer.hg[set][0] = (double)step * cfg.dt; writer.hg[set][1] = now; writer.hg[set][2] = tg_sum + 0.5 * std::log(now / tg_norm_ref);
+            if (cfg.dump_ow) ENGINE_CALL(*eng, get_okubo_weiss, get_okubo_weiss_local, F(o_ow), F(o_tau));
+            if (cfg.dump_pres) ENGINE_CALL(*eng, get_pressure, get_pressure_local, cfg.pres_rho, cfg.pres_f, cfg.pres_ref_x, cfg.pres_ref_y, F(o_pres));
+            if (cfg.dump_spectra) ENGINE_CALL(*eng, get_spectra, get_spectra, D(o_spectra));
+            if (cfg.dump_keff) ENGINE_CALL(*eng, get_eddy_diffusivity, get_eddy_diffusivity, cfg.keff_bins, D(o_keff), nullptr, nullptr);
+            if (tracer) ENGINE_CALL(*eng, get_tracer, get_tracer_local, F(o_tracer));
+            if (o_tkeff >= 0) ENGINE_CALL(*eng, get_tracer_eddy_diffusivity, get_tracer_eddy_diffusivity, cfg.keff_bins, D(o_tkeff), nullptr, nullptr);
+            if (cfg.dump_azim)
+                ENGINE_CALL(*eng, get_azimuthal, get_azimuthal, cfg.azim_mode, cfg.azim_xc, cfg.azim_yc, cfg.azim_bins, cfg.azim_dr, cfg.azim_modes, D(o_azim), D(o_center));
+            if (o_part >= 0) ENGINE_CALL(*eng, get_particles, get_particles, D(o_part));
+            if (o_def >= 0) {
+                ENGINE_CALL(*eng, get_particle_deformation, get_particle_deformation, D(o_def), nullptr);
+                ENGINE_CALL(*eng, particle_stretching, particle_stretching, nullptr, 0, D(o_stretch));
             }
-            if (d_census) {
-                const float *w = !cfg.census_ow ? d_out[0] : cfg.dump_ow ? d_out[7] : d_census_w;
-                if (d_census_w) eng->get_okubo_weiss(d_census_w, nullptr);
-                eng->census(cfg, w, d_out[0], d_census, d_census_count);
+            if (tangent) {
+                ENGINE_CALL(*eng, get_tangent, get_tangent, F(o_tangent));
+                const double now = eng->tangent_norm(d_norm);                          // (waits for the compute stream: one host round trip per record)
+                double *growth = (double *)outs[o_growth].host[set];
+                growth[0] = (double)step * cfg.dt; growth[1] = now; growth[2] = tg_sum + 0.5 * std::log(now / tg_norm_ref);
+            }
+            if (cfg.dump_census) {
+                const float *w = !cfg.census_ow ? F(o_vort) : cfg.dump_ow ? F(o_ow) : d_census_w;
+                if (d_census_w) ENGINE_CALL(*eng, get_okubo_weiss, get_okubo_weiss_local, d_census_w, nullptr);
+                ENGINE_CALL(*eng, census, census, w, F(o_vort), cfg.census_below ? FB_CENSUS_BELOW : FB_CENSUS_ABOVE, cfg.census_thr, cfg.census_min, cfg.census_max,
+                            D(o_census), d_census_count, nullptr);
             }
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
-            for (int i = 0; i < NB; ++i) if (use[i]) must(fb_memcpy_d2h_async(copy, writer.h[set][i], d_out[i], floats * sizeof(float)), "d2h");
-            if (writer.ht[set]) must(fb_memcpy_d2h_async(copy, writer.ht[set], d_table, table_bytes), "d2h");
-            if (writer.hs[set]) must(fb_memcpy_d2h_async(copy, writer.hs[set], d_spectra, spectra_bytes), "d2h");
-            if (writer.hk[set]) must(fb_memcpy_d2h_async(copy, writer.hk[set], d_ttable, table_bytes), "d2h");
-            if (writer.ha[set]) must(fb_memcpy_d2h_async(copy, writer.ha[set], d_azim, azim_bytes), "d2h");
-            if (writer.hc[set]) must(fb_memcpy_d2h_async(copy, writer.hc[set], d_azim_center, 4 * sizeof(double)), "d2h");
-            if (writer.hp[set]) must(fb_memcpy_d2h_async(copy, writer.hp[set], d_part, part_bytes), "d2h");
-            if (writer.hd[set]) { must(fb_memcpy_d2h_async(copy, writer.hd[set], d_def, def_bytes), "d2h"); must(fb_memcpy_d2h_async(copy, writer.hst[set], d_stretch, def_bytes), "d2h"); }
-            if (writer.hcs[set]) must(fb_memcpy_d2h_async(copy, writer.hcs[set], d_census, census_bytes), "d2h");
+            for (const Output &o : outs) if (o.dev && o.host[set]) must(fb_memcpy_d2h_async(copy, o.host[set], o.dev, o.bytes), "d2h");
             host_copy_s += since(h0);
             must(fb_event_record(writer.e_copy[set], copy), "record");
             last_set = set;
@@ -768,7 +632,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 must(fb_memcpy_h2d_async(copy, d_in, feed.pin[e.buf], floats * sizeof(float)), "h2d");
                 must(fb_event_record(e_h2d, copy), "record");
                 eng->wait(e_h2d);
-                eng->set_source(d_in);
+                ENGINE_CALL(*eng, set_source, set_source_local, d_in);
                 eng->record(e_src);
             }
         }
@@ -776,7 +640,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (tangent && cfg.tangent_renorm > 0 && (step + 1 - cfg.start_step) % cfg.tangent_renorm == 0) {       // back to the initial norm
             const double now = eng->tangent_norm(d_norm);
             tg_sum += 0.5 * std::log(now / tg_norm_ref);
-            eng->tangent_scale((float)std::sqrt(tg_norm0 / now));
+            ENGINE_CALL(*eng, tangent_scale, tangent_scale, (float)std::sqrt(tg_norm0 / now));
             tg_norm_ref = eng->tangent_norm(d_norm);
         }
     }
@@ -818,32 +682,32 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         }
     }
     if (feed_done) delete feedp;
-    fb_free(d_in); for (auto p : d_out) if (p) fb_free(p);
-    if (d_table) fb_free(d_table);
-    if (d_ttable) fb_free(d_ttable);
-    if (d_spectra) fb_free(d_spectra);
-    if (d_azim) fb_free(d_azim);
-    if (d_azim_center) fb_free(d_azim_center);
-    if (d_part) fb_free(d_part);
-    if (d_def) { fb_free(d_def); fb_free(d_stretch); }
-    if (d_norm) fb_free(d_norm);
-    if (d_census) { fb_free(d_census); fb_free(d_census_count); }
-    if (d_census_w) fb_free(d_census_w);
-    for (int b = 0; b < 2; ++b) {
-        for (int i = 0; i < NB; ++i) if (writer.h[b][i]) fb_free_host(writer.h[b][i]);
-        if (writer.ht[b]) fb_free_host(writer.ht[b]);
-        if (writer.hs[b]) fb_free_host(writer.hs[b]);
-        if (writer.hk[b]) fb_free_host(writer.hk[b]);
-        if (writer.ha[b]) fb_free_host(writer.ha[b]);
-        if (writer.hc[b]) fb_free_host(writer.hc[b]);
-        if (writer.hp[b]) fb_free_host(writer.hp[b]);
-        if (writer.hd[b]) { fb_free_host(writer.hd[b]); fb_free_host(writer.hst[b]); }
-        if (writer.hcs[b]) fb_free_host(writer.hcs[b]);
-        if (writer.e_copy[b]) fb_event_destroy(writer.e_copy[b]);
+    for (void *p : {(void *)d_in, (void *)d_census_count, (void *)d_census_w, (void *)d_norm}) if (p) fb_free(p);
+    for (const Output &o : outs) {
+        if (o.dev) fb_free(o.dev);
+        for (int b = 0; b < writer.nsets; ++b) if (o.host[b]) fb_free_host(o.host[b]);
     }
+    for (int b = 0; b < writer.nsets; ++b) fb_event_destroy(writer.e_copy[b]);
     delete eng;
     for (void *e : {e_rec, e_h2d, e_src}) fb_event_destroy(e);
     fb_stream_destroy(copy);
+}
+
+// the value of the option getopt_long has just returned (optarg): an integer in [lo, hi], or a number between lo (itself allowed where
+// lo_ok) and hi, parsed as float where `single`; anything else, trailing characters included, ends the run with `msg` and exit status 2
+static int int_option(long lo, long hi, const char *msg)
+{
+    char *end = nullptr;
+    const long v = strtol(optarg, &end, 10);
+    if (!*optarg || *end || v < lo || v > hi) { fprintf(stderr, "%s\n", msg); std::exit(2); }
+    return (int)v;
+}
+static double real_option(bool single, double lo, bool lo_ok, double hi, const char *msg)
+{
+    char *end = nullptr;
+    const double v = single ? (double)strtof(optarg, &end) : strtod(optarg, &end);
+    if (!*optarg || *end || !(lo_ok ? v >= lo : v > lo) || v > hi) { fprintf(stderr, "%s\n", msg); std::exit(2); }
+    return v;
 }
 
 int main(int argc, char *args[])
@@ -894,23 +758,11 @@ int main(int argc, char *args[])
         case 20: cfg.record_buffers = atoi(optarg); break;         // main.cpp:229-235 (#ifdef OUTPUT_DVORTDT)
         case 21: cfg.dump_ow = true; break;              // okubo_weiss_step_N.bin, tau_fil_step_N.bin (also with --world P)
         case 22: cfg.dump_keff = true; break;            // eddy_diffusivity_step_N.bin (also with --world P)
-        case 23: {
-            char *end = nullptr;
-            const long v = strtol(optarg, &end, 10);
-            if (!*optarg || *end || v < 2 || v > 4096) { fprintf(stderr, "--keff-bins: an integer in [2, 4096]\n"); return 2; }
-            cfg.keff_bins = (int)v;
-            break;
-        }
+        case 23: cfg.keff_bins = int_option(2, 4096, "--keff-bins: an integer in [2, 4096]"); break;
         case 24: cfg.dump_pres = true; break;            // pres_step_N.bin (also with --world P)
         case 29: cfg.dump_spectra = true; break;         // spectra_step_N.bin (also with --world P)
         case 30: cfg.tracer_file = optarg; break;       // tracer_step_N.bin (also with --world P)
-        case 31: {
-            char *end = nullptr;
-            const float v = strtof(optarg, &end);
-            if (!*optarg || *end || !(v >= 0.0f) || v > 3.0e38f) { fprintf(stderr, "--tracer-kappa: a finite number >= 0\n"); return 2; }
-            cfg.tracer_kappa = v;
-            break;
-        }
+        case 31: cfg.tracer_kappa = (float)real_option(true, 0.0, true, 3.0e38f, "--tracer-kappa: a finite number >= 0"); break;
         case 32: cfg.dump_azim = true; break;            // azimuthal_step_N.bin, azimuthal_center_step_N.bin (also with --world P)
         case 33: {
             const std::string a = optarg;
@@ -925,38 +777,15 @@ int main(int argc, char *args[])
             }
             break;
         }
-        case 34: case 36: {
-            char *end = nullptr;
-            const long v = strtol(optarg, &end, 10);
-            if (opt == 34 && (!*optarg || *end || v < 2 || v > 4096)) { fprintf(stderr, "--azim-bins: an integer in [2, 4096]\n"); return 2; }
-            if (opt == 36 && (!*optarg || *end || v < 0 || v > 8)) { fprintf(stderr, "--azim-modes: an integer in [0, 8]\n"); return 2; }
-            (opt == 34 ? cfg.azim_bins : cfg.azim_modes) = (int)v;
-            break;
-        }
-        case 35: {
-            char *end = nullptr;
-            cfg.azim_dr = strtod(optarg, &end);
-            if (!*optarg || *end || !(cfg.azim_dr > 0.0) || cfg.azim_dr > 1.0e300) { fprintf(stderr, "--azim-dr: a finite number > 0\n"); return 2; }
-            break;
-        }
+        case 34: cfg.azim_bins = int_option(2, 4096, "--azim-bins: an integer in [2, 4096]"); break;
+        case 36: cfg.azim_modes = int_option(0, 8, "--azim-modes: an integer in [0, 8]"); break;
+        case 35: cfg.azim_dr = real_option(false, 0.0, false, 1.0e300, "--azim-dr: a finite number > 0"); break;
         case 37: cfg.particles_file = optarg; break;    // particles_step_N.bin (one GPU only)
         case 40: cfg.particle_deformation = true; break; // particle_deformation_step_N.bin, particle_stretching_step_N.bin (with --particles)
         case 38: cfg.tangent_file = optarg; break;      // tangent_step_N.bin, tangent_growth_step_N.bin (one GPU only)
-        case 39: {
-            char *end = nullptr;
-            const long v = strtol(optarg, &end, 10);
-            if (!*optarg || *end || v < 0 || v > 0x7fffffffL) { fprintf(stderr, "--tangent-renorm: an integer >= 0\n"); return 2; }
-            cfg.tangent_renorm = (int)v;
-            break;
-        }
+        case 39: cfg.tangent_renorm = int_option(0, 0x7fffffffL, "--tangent-renorm: an integer >= 0"); break;
         case 41: cfg.dump_census = true; break;          // census_step_N.bin (one GPU only)
-        case 42: {
-            char *end = nullptr;
-            cfg.census_thr = strtof(optarg, &end);
-            if (!*optarg || *end || !std::isfinite(cfg.census_thr)) { fprintf(stderr, "--census-threshold: a finite number\n"); return 2; }
-            cfg.census_have_thr = true;
-            break;
-        }
+        case 42: cfg.census_thr = (float)real_option(true, -FLT_MAX, true, FLT_MAX, "--census-threshold: a finite number"); cfg.census_have_thr = true; break;
         case 43: {
             const std::string a = optarg;
             if (a != "vort" && a != "okubo-weiss") { fprintf(stderr, "--census-field: vort or okubo-weiss\n"); return 2; }
@@ -964,23 +793,13 @@ int main(int argc, char *args[])
             break;
         }
         case 44: cfg.census_below = true; break;
-        case 45: case 46: {
-            char *end = nullptr;
-            const long v = strtol(optarg, &end, 10);
-            if (opt == 45 && (!*optarg || *end || v < 1 || v > (1L << 30))) { fprintf(stderr, "--census-min-cells: an integer in [1, 2^30]\n"); return 2; }
-            if (opt == 46 && (!*optarg || *end || v < 1 || v > FB_CENSUS_MAX)) { fprintf(stderr, "--census-max: an integer in [1, 65536]\n"); return 2; }
-            (opt == 45 ? cfg.census_min : cfg.census_max) = (int)v;
-            break;
-        }
+        case 45: cfg.census_min = int_option(1, 1L << 30, "--census-min-cells: an integer in [1, 2^30]"); break;
+        case 46: cfg.census_max = int_option(1, FB_CENSUS_MAX, "--census-max: an integer in [1, 65536]"); break;
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
-        case 27: case 28: {                              // invert_pres.cpp:71-79 (-x, -y)
-            char *end = nullptr;
-            const long v = strtol(optarg, &end, 10);
-            if (!*optarg || *end || v < 0 || v > 0x7fffffffL) { fprintf(stderr, "--pres-ref-x / --pres-ref-y: a non-negative integer\n"); return 2; }
-            (opt == 27 ? cfg.pres_ref_x : cfg.pres_ref_y) = (int)v;
+        case 27: case 28:                                // invert_pres.cpp:71-79 (-x, -y)
+            (opt == 27 ? cfg.pres_ref_x : cfg.pres_ref_y) = int_option(0, 0x7fffffffL, "--pres-ref-x / --pres-ref-y: a non-negative integer");
             break;
-        }
         }
     }
     if (cfg.world < 1 || cfg.rank < 0 || cfg.rank >= cfg.world || (cfg.world > 1 && !cfg.threads && cfg.comm_file.empty()) ||
