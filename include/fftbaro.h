@@ -344,6 +344,38 @@ int fb_model_adjoint_recorded(fb_model *m, int *n);
 int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real);         /* NULL: remove the adjoint variable */
 int fb_model_get_adjoint(fb_model *m, float *d_real);
 int fb_model_adjoint_back(fb_model *m, int nsteps);
+/* Point observations and the forcing of the adjoint by their misfits (no reference counterpart): what a 4D-Var cost
+ *   J(zeta_0) = 1/2 sum over times k and points p of (H_k zeta_k - y_k)_p^2 / sigma_p^2
+ * and its gradient need of the engine on top of the adjoint sweep.  All four act between two steps only: the step, the tape, a
+ * tracer, particles, a tangent and the sweep itself are bit for bit what they are without them.  kind: 0 zeta, 1 u, 2 v, 3 psi.
+ * Positions are device float64 [n][2], unwrapped, n in [1, 2^24], on the grid and with the stencil and weights of fb_model_sample.
+ * fb_model_observe: h = H zeta of the resident state into d_out, float64 [n]: the field of that kind formed as fb_model_get_vort and
+ * fb_model_get_diag form it (their kernels, their rounding) and interpolated as fb_model_sample interpolates, bit for bit
+ * fb_model_sample of that record; NaN where a position is not finite.  It changes nothing.
+ * fb_model_scatter: the transpose of fb_model_sample, field[i][j] = sum over p of w_p wx_a(p) wy_b(p) over the sixteen stencil cells
+ * of every point, into d_field, ANY device [nx][ny] float32 field, so that <sample(f, xy), w> = <f, scatter(xy, w)> (indices and
+ * weights come from the one routine both use).  It needs nothing set; it is also how a quantity carried by particles is deposited
+ * on the grid.  A point whose position or weight is not finite deposits nothing.  The result is bitwise reproducible, in any order
+ * of execution and for any permutation of the points: every contribution is added by integer atomics into a fixed-point
+ * accumulator of two 64-bit limbs per cell, in units of 2^-(e+39), e the largest integer with n_2 wmax_2 2^e <= 2^62, n_2 and wmax_2
+ * the powers of two at or above n and above max |w| (found on the device), and each cell is then rounded to float32.  Error per
+ * cell: half a float32 ulp of the cell's value (times 1 + 2^-28) plus at most 2^-(e+40) <= n max |w| 2^-101 per contribution.
+ * fb_model_adjoint_add_obs: lam += H^T w for the adjoint variable set by fb_model_set_adjoint: the scatter of w, its r2c as
+ * fb_model_set_adjoint takes a field, times the complex conjugate of the kind's spectral multiplier (1; -i ky / lap for u; i kx / lap
+ * for v; 1 / lap for psi, the (0, 0) mode divided by 1 as the record divides it).  A cost term at an intermediate time is this call
+ * between two sweeps.  It leaves the tape alone.
+ * fb_model_obs_misfit: d_r[p] = (d_h[p] - d_y[p]) / sigma_p^2 and *d_cost += 1/2 sum over p of (d_h[p] - d_y[p])^2 / sigma_p^2, all
+ * device float64, summed in a fixed order (two calls give the same bits); *d_cost is a device scalar that the caller zeroes.
+ * d_sigma == NULL means sigma = 1; every sigma must be positive and finite, which is the caller's contract (checking it would need
+ * a read of device memory).
+ * One GPU or a slab of one rank, as the adjoint.  FB_EINVAL before any HIP call: kind outside [0, 3], a NULL pointer (but d_sigma),
+ * n outside [1, 2^24], a NULL model, a slab of several ranks, fb_model_adjoint_add_obs without an adjoint set.  Enqueued on the
+ * context stream, no synchronisation, no host round trip; each allocates its workspace at its first use (the accumulator, 2 nx ny
+ * 64-bit words; one real field) and keeps it until fb_model_destroy. */
+int fb_model_scatter(fb_model *m, const double *d_xy, const double *d_w, int n, float *d_field);
+int fb_model_observe(fb_model *m, int kind, const double *d_xy, int n, double *d_out);      /* 0 zeta, 1 u, 2 v, 3 psi */
+int fb_model_obs_misfit(fb_model *m, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost);
+int fb_model_adjoint_add_obs(fb_model *m, int kind, const double *d_xy, const double *d_w, int n);
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -536,6 +568,11 @@ int fb_slab_adjoint_recorded(fb_slab *s, int *n);
 int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real);           /* NULL: remove the adjoint variable */
 int fb_slab_get_adjoint(fb_slab *s, float *d_real);
 int fb_slab_adjoint_back(fb_slab *s, int nsteps);
+/* the point observations (fb_model_scatter) of a slab of ONE rank, likewise */
+int fb_slab_scatter(fb_slab *s, const double *d_xy, const double *d_w, int n, float *d_field);
+int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out);
+int fb_slab_obs_misfit(fb_slab *s, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost);
+int fb_slab_adjoint_add_obs(fb_slab *s, int kind, const double *d_xy, const double *d_w, int n);
 /* the Lagrangian particles (fb_model_set_particles) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EUNSUPPORTED: particles distributed over row slabs need neighbour halo rows that the all-to-all transport
  * does not provide. */

@@ -84,7 +84,11 @@ _DEFORMATION_PAIRS = {
 _CENSUS_PAIRS = {"census": [_vp, _vp, _ip, _fl, _ip, _ip, _vp, _vp, _vp]}
 # the covariant Lyapunov vectors' pairs, likewise: the basis tape and the combination
 _CLV_PAIRS = {"tangent_tape": [_ip], "tangent_tape_push": [], "tangent_tape_count": [_pip, _pip], "tangent_combine": [_ip, _vp]}
-for _name, _args in list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items()):
+# the point observations' pairs, likewise: the scatter, the observation operator, the misfit and the adjoint's forcing
+_OBS_PAIRS = {"scatter": [_vp, _vp, _ip, _vp], "observe": [_ip, _vp, _ip, _vp], "obs_misfit": [_vp, _vp, _vp, _ip, _vp, _vp],
+              "adjoint_add_obs": [_ip, _vp, _vp, _ip]}
+for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
+                     + list(_OBS_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -422,6 +426,181 @@ def singular_values(model, steps, iters, start, save=None, restore=None):
     finally:
         model.record_adjoint(0)
     return sig, v.float()
+
+
+OBS_KINDS = {"vort": 0, "u": 1, "v": 2, "psi": 3}
+# a host address that is not NULL, for asking a slab of several ranks for its refusal: the engine refuses before it reads anything
+_SOME = (C.c_double * 2)()
+
+
+def obs_kind(kind):
+    """the C ABI's number of an observed quantity: "vort" | "u" | "v" | "psi" (an int is passed on for the engine to judge)"""
+    if isinstance(kind, str):
+        if kind not in OBS_KINDS:
+            raise ValueError("kind: 'vort', 'u', 'v' or 'psi'")
+        return OBS_KINDS[kind]
+    return int(kind)
+
+
+def values_dev(torch, a, n, what="values"):
+    """n point values, numpy or torch, as a contiguous float64 [n] tensor on the GPU that has landed there"""
+    if isinstance(a, np.ndarray):
+        a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+    if a.dtype != torch.float64 or a.dim() != 1 or a.shape[0] != n:
+        raise ValueError("%s: float64 [%d]" % (what, n))
+    a = a.cuda().contiguous()
+    torch.cuda.current_stream().synchronize()                   # the engine reads them on ITS stream
+    return a
+
+
+def sigma_ok(sigma):
+    """every sigma positive and finite (one read of a flag from the GPU): the engine itself does not look"""
+    return bool(((sigma > 0) & sigma.isfinite()).all().item())
+
+
+class Observations:
+    """One set of point observations of one kind at one time: `step` (int >= 0, counted from the start of the window), `kind` ("vort",
+    "u", "v" or "psi"), `xy` float64 [n, 2] positions [m] (unwrapped), `y` float64 [n] the observed values, `sigma` their standard
+    errors (None: 1; a number; or float64 [n]), every one positive and finite.  Numpy or torch in; everything held is a tensor on the
+    GPU after construction."""
+
+    def __init__(self, step, kind, xy, y, sigma=None):
+        t = _torch()
+        if int(step) != step or step < 0:
+            raise ValueError("Observations: step must be an int >= 0")
+        obs_kind(kind)
+        self.step, self.kind = int(step), kind
+        self.xy = particles_dev(t, xy)
+        n = int(self.xy.shape[0])
+        if n < 1 or n > PARTICLES_MAX:
+            raise ValueError("Observations: 1 to 2^24 points")
+        self.y = values_dev(t, y, n, "y")
+        if sigma is None or np.isscalar(sigma):
+            self.sigma = t.full((n,), 1.0 if sigma is None else float(sigma), dtype=t.float64, device="cuda")
+        else:
+            self.sigma = values_dev(t, sigma, n, "sigma")
+        if not sigma_ok(self.sigma):
+            raise ValueError("Observations: every sigma must be positive and finite")
+
+    def __len__(self):
+        return int(self.xy.shape[0])
+
+
+def fourdvar(model, z0, obs, background=None):
+    """(J, grad) of the 4D-Var cost of the initial vorticity z0 (an [nx, ny] field, numpy or torch; it is set as float32) on `model`
+    (anything with set_vort, record_adjoint, step, observe, obs_misfit, set_adjoint, adjoint_add_obs, adjoint_back, adjoint):
+      J = 1/2 sum over the sets of obs and their points of (H zeta(step) - y)^2 / sigma^2   (+ 1/2 |z0 - zb|^2 / sigma_b^2),
+    obs a sequence of Observations, background = (zb, sigma_b) with zb an [nx, ny] field and sigma_b a number.  The model is set to z0
+    and stepped with the adjoint's tape on to the last observation step T, from one observation time to the next; at each, observe and
+    obs_misfit keep h, the residuals r = (h - y) / sigma^2 and J on the GPU.  Then lam = 0 and the times are walked backward:
+    adjoint_add_obs for every set of that time, adjoint_back to the time before, sets at step 0 included; grad is what is left in lam,
+    float64 [nx, ny] on the GPU.  No field crosses to the host; J, a float, is read once at the end.  Tape memory: T x 4 half spectra
+    (4 nx (ny/2 + 1) 8 bytes per step, 271 MB per step at 4096^2); where record_adjoint cannot allocate it, its FftBaroError is raised
+    and nothing stays allocated (windows that do not fit would need checkpointing, which this does not do).  The tape is freed at the
+    end, whatever happens; a tape that was on before is gone.  The model is left at step T of the run from z0, with lam = grad's
+    float32 form set."""
+    t = model.torch
+    obs = list(obs)
+    if not obs:
+        raise ValueError("fourdvar: no observations")
+    if isinstance(z0, np.ndarray):
+        z0 = t.from_numpy(np.ascontiguousarray(z0))
+    z0 = z0.cuda()
+    times = sorted(set(o.step for o in obs))
+    cost = t.zeros(1, dtype=t.float64, device="cuda")
+    res = {}
+    try:
+        model.set_vort(z0.float().contiguous())
+        if times[-1]:
+            model.record_adjoint(times[-1])
+        at = 0
+        for when in times:
+            model.step(when - at)
+            at = when
+            for k, o in enumerate(obs):
+                if o.step == when:
+                    res[k] = model.obs_misfit(model.observe(o.kind, o.xy), o.y, o.sigma, cost, check=False)
+        model.set_adjoint(t.zeros(tuple(z0.shape), dtype=t.float32, device="cuda"))
+        for when, before in zip(times[::-1], times[-2::-1] + [0]):
+            for k, o in enumerate(obs):
+                if o.step == when:
+                    model.adjoint_add_obs(o.kind, o.xy, res[k])
+            model.adjoint_back(when - before)
+        grad = model.adjoint().double()
+    finally:
+        model.record_adjoint(0)
+    if background is not None:
+        zb, sb = background
+        if isinstance(zb, np.ndarray):
+            zb = t.from_numpy(np.ascontiguousarray(zb))
+        d = z0.double() - zb.cuda().double()
+        cost += 0.5 * (d * d).sum() / float(sb) ** 2
+        grad = grad + d / float(sb) ** 2
+    return float(cost.item()), grad
+
+
+def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, shrink=0.5, max_backtracks=25):
+    """Minimises model.fourdvar(z, obs, background) -> (J, grad) over the initial field z from z0 by L-BFGS (the two-loop recursion over
+    the last `history` pairs) with a backtracking Armijo line search: a step t d is accepted when J(z + t d) <= J(z) + armijo t <grad, d>,
+    t from 1 (the first iteration: from the step 2 J / |grad|^2 along -grad, the exact minimiser of a one-dimensional quadratic
+    that touches zero), times `shrink` per rejection, at most max_backtracks times.  Host logic on float64 tensors wherever z0 lives
+    (the GPU for the engine; anything with a fourdvar will do).  It stops after `iters` accepted iterations, or at the first whose
+    line search finds no acceptable step, or when the gradient is zero.  Returns (z, J_history, evaluations): the final field, float64;
+    J at the start and after every accepted iteration (it falls at every one); the number of fourdvar calls."""
+    t = model.torch
+    if iters < 0 or history < 1:
+        raise ValueError("fit_initial: iters must be >= 0, history >= 1")
+    if isinstance(z0, np.ndarray):
+        z0 = t.from_numpy(np.ascontiguousarray(z0))
+    x = z0.double().clone()
+
+    def evaluate(z):
+        J, g = model.fourdvar(z, obs, background)
+        return float(J), g.double().to(x.device)
+
+    def dot(a, b):
+        return float((a * b).sum())
+    J, g = evaluate(x)
+    hist, evals, pairs = [J], 1, []                             # pairs: (s, y, 1 / <s, y>), oldest first
+    for _ in range(iters):
+        gg = dot(g, g)
+        if not gg > 0.0:
+            break
+        q, alphas = g.clone(), []
+        for s, y, rho in reversed(pairs):
+            a = rho * dot(s, q)
+            alphas.append(a)
+            q -= a * y
+        if pairs:
+            s, y, _ = pairs[-1]
+            q *= dot(s, y) / dot(y, y)
+        else:
+            q *= 2.0 * J / gg
+        for (s, y, rho), a in zip(pairs, reversed(alphas)):
+            q += (a - rho * dot(y, q)) * s
+        d = -q
+        slope = dot(g, d)
+        if not slope < 0.0:                                     # not a descent direction: steepest descent, the memory dropped
+            pairs, d, slope = [], -g * (2.0 * J / gg), -2.0 * J
+        step, found = 1.0, None
+        for _ in range(max_backtracks):
+            xn = x + step * d
+            Jn, gn = evaluate(xn)
+            evals += 1
+            if np.isfinite(Jn) and Jn <= J + armijo * step * slope:
+                found = (xn, Jn, gn)
+                break
+            step *= shrink
+        if found is None:
+            break
+        xn, Jn, gn = found
+        s, y = xn - x, gn - g
+        sy = dot(s, y)
+        if sy > 1e-12 * np.sqrt(dot(s, s) * dot(y, y)):         # curvature condition: keep the memory positive definite
+            pairs = (pairs + [(s, y, 1.0 / sy)])[-history:]
+        x, J, g = xn, Jn, gn
+        hist.append(J)
+    return x, hist, evals
 
 
 def particles_dev(torch, xy):
@@ -934,6 +1113,69 @@ class ModelSurface:
         state is kept and put back through _STATE."""
         self._one_rank("adjoint_record", int(steps))
         return singular_values(self, steps, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]))
+
+
+    def scatter(self, w, xy):
+        """The transpose of sample(): n point values w, float64 [n], at the positions xy, float64 [n, 2], spread onto the grid with the
+        cubic Lagrange weights of sample(), field[i, j] = sum over the points of w wx wy: a float32 [nx, ny] tensor with
+        <sample(f, xy), w> = <f, scatter(w, xy)>.  Bitwise reproducible, in any order of the points (fixed-point accumulation,
+        include/fftbaro.h); a point whose position or weight is not finite deposits nothing.  It needs nothing set: it is also how a
+        quantity carried by particles is deposited on the grid.  One rank only: on several ranks this and the three methods below raise
+        FftBaroError with the engine's message."""
+        t = self.torch
+        self._one_rank("scatter", _SOME, _SOME, 1, _SOME)
+        a = particles_dev(t, xy)
+        out = t.empty(self._shape, dtype=t.float32, device="cuda")
+        self._hand("scatter", a, values_dev(t, w, int(a.shape[0]), "w"), int(a.shape[0]), out)
+        return out
+
+    def observe(self, kind, xy):
+        """h = H zeta: the resident state's "vort", "u", "v" or "psi" at the positions xy, float64 [n, 2]: a float64 [n] tensor, bit for
+        bit sample(vort(), xy) or sample(diag()[k], xy), without the field leaving the engine.  It changes nothing."""
+        t = self.torch
+        self._one_rank("observe", 0, _SOME, 1, _SOME)
+        a = particles_dev(t, xy)
+        out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
+        self._hand("observe", obs_kind(kind), a, int(a.shape[0]), out)
+        return out
+
+    def obs_misfit(self, h, y, sigma, cost, check=True):
+        """r = (h - y) / sigma^2, a float64 [n] tensor, and cost += 1/2 sum (h - y)^2 / sigma^2 on the GPU, summed in a fixed order;
+        h, y float64 [n], sigma float64 [n] or None (1), cost a float64 tensor of one element on the GPU.  Every sigma must be positive
+        and finite: checked here on the tensor unless check=False (the engine does not look)."""
+        t = self.torch
+        self._one_rank("obs_misfit", _SOME, _SOME, None, 1, _SOME, _SOME)
+        n = int(h.shape[0])
+        h, y = values_dev(t, h, n, "h"), values_dev(t, y, n, "y")
+        sigma = None if sigma is None else values_dev(t, sigma, n, "sigma")
+        if check and sigma is not None and not sigma_ok(sigma):
+            raise ValueError("obs_misfit: every sigma must be positive and finite")
+        assert cost.is_cuda and cost.dtype == t.float64 and cost.numel() == 1 and cost.is_contiguous()
+        r = t.empty(n, dtype=t.float64, device="cuda")
+        self._hand("obs_misfit", h, y, sigma, n, r, cost)
+        return r
+
+    def adjoint_add_obs(self, kind, xy, w):
+        """lam += H^T w for the adjoint variable set by set_adjoint: the forcing of the backward sweep by n point values w (the misfits
+        r of obs_misfit) of the kind observed at xy.  Between two adjoint_back calls it is a cost term at an intermediate time."""
+        t = self.torch
+        self._one_rank("adjoint_add_obs", 0, _SOME, _SOME, 1)
+        a = particles_dev(t, xy)
+        self._hand("adjoint_add_obs", obs_kind(kind), a, values_dev(t, w, int(a.shape[0]), "w"), int(a.shape[0]))
+
+    def fourdvar(self, z0, obs, background=None):
+        """(J, grad): the 4D-Var cost of the initial vorticity z0 against the Observations in obs, and its gradient with respect to z0,
+        float64 [nx, ny] on the GPU (fourdvar()).  The tape takes T x 4 half spectra, T the last observation step."""
+        self._one_rank("adjoint_record", 1)
+        return fourdvar(self, z0, obs, background)
+
+    def fit_initial(self, z0, obs, iters, background=None, history=8):
+        """(z, J_history, evaluations): L-BFGS on fourdvar from the first guess z0 (fit_initial()); z0 goes to the GPU first, so the
+        iterate, the gradients and the memory of the recursion stay there."""
+        self._one_rank("adjoint_record", 1)
+        if isinstance(z0, np.ndarray):
+            z0 = self.torch.from_numpy(np.ascontiguousarray(z0))
+        return fit_initial(self, z0.cuda(), obs, iters, background, history)
 
 
 class Model(ModelSurface):

@@ -1,5 +1,6 @@
 // fb_beside.h -- the fields stepped beside the vorticity: the passive tracer, the tangent-linear model and the Lagrangian particles
-// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h; C ABI: include/fftbaro.h).
+// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h, fb_adjoint.h, fb_obs.h; C ABI:
+// include/fftbaro.h).
 //
 // Each is taken in between two steps and advanced at the top of every RK stage of fb_model_step and fb_slab_step, from the state the
 // vorticity's stage starts from, through the record workspace (record_advect, fb_record.h): the step's own buffers are only read.  A
@@ -91,13 +92,47 @@ static int beside_update(fb_model *m, fb_slab *s, int stage, Beside &f, cf *cons
     return j1 ? beside_update_nj<2>(m, s, stage, f, j1, kappa) : beside_update_nj<1>(m, s, stage, f, j1, kappa);
 }
 
+// f(g, n) for each of the first ngroups column groups that has elements, n (complex) of them; the first status that is not FB_OK ends it
+template <class F> static int each_group(const fb_ctx *c, int ngroups, F &&f)
+{
+    for (int g = 0; g < ngroups; ++g)
+        if (const size_t n = grp_elems(c, c->grp[g]))
+            if (int rc = f(g, n)) return rc;
+    return FB_OK;
+}
+
 // readField + r2c of a second real field as state_in takes the vorticity (ROW_FWD, the transpose on a slab, the forward x pass),
-// through the record workspace into the field's own arrays in the 3-pass layout: the base c0 of every column group, and for the
+// through the record workspace: the half spectrum of column group g is left in rec_work[g], in the 3-pass layout, pad columns zero.
+static int beside_r2c(fb_model *m, fb_slab *s, const float *d_rows)
+{
+    fb_ctx *c = m->c;
+    const bool xchg = s && c->world > 1;
+    int rc;
+    if ((rc = advect_workspace(m, s))) return rc;
+    RowArgs a = row_args_base(c);
+    a.rin = d_rows;
+    if (xchg) {
+        const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
+        a.T = view_slab(c, ts, 1);
+    } else {
+        HIPCHK(hipMemsetAsync(m->rec_work[0], 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
+        a.T = view_single(c, m->rec_work[0], 0);
+    }
+    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+    if (xchg && (rc = slab_rows_to_cols(s, m->rec_send, m->rec_work, c->ngroups))) return rc;
+    return each_group(c, c->ngroups, [&](int g, size_t) -> int {
+        const ColGroup &G = c->grp[g];
+        cf *t = m->rec_work[g];
+        if (int r = launch_col_strided<-1>(c, G, t, 1, 0)) return r;
+        return launch_col_block<-1>(c, G, t, 1, 0);
+    });
+}
+
+// beside_r2c of a real field into the field's own arrays in the 3-pass layout: the base c0 of every column group, and for the
 // groups of active columns the stage state c1 and the accumulator acc, zeroed.
 static int beside_in(fb_model *m, fb_slab *s, const float *d_rows, Beside &f)
 {
     fb_ctx *c = m->c;
-    const bool xchg = s && c->world > 1;
     int rc;
     if ((rc = advect_workspace(m, s))) return rc;
     for (int g = 0; g < c->ngroups; ++g) {
@@ -110,26 +145,11 @@ static int beside_in(fb_model *m, fb_slab *s, const float *d_rows, Beside &f)
             HIPCHK(hipMemsetAsync(f.acc[g], 0, n * sizeof(cf), c->stream));
         }
     }
-    RowArgs a = row_args_base(c);
-    a.rin = d_rows;
-    if (xchg) {
-        const cf *ts[3] = {m->rec_send[0], m->rec_send[1], m->rec_send[2]};
-        a.T = view_slab(c, ts, 1);
-    } else {
-        HIPCHK(hipMemsetAsync(m->rec_work[0], 0, priv_elems(c) * sizeof(cf), c->stream));      // pad columns zero
-        a.T = view_single(c, m->rec_work[0], 0);
-    }
-    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
-    if (xchg && (rc = slab_rows_to_cols(s, m->rec_send, m->rec_work, c->ngroups))) return rc;
-    for (int g = 0; g < c->ngroups; ++g) {
-        const ColGroup &G = c->grp[g];
-        const size_t n = grp_elems(c, G);
-        if (n == 0) continue;
-        cf *t = m->rec_work[g];
-        if ((rc = launch_col_strided<-1>(c, G, t, 1, 0)) || (rc = launch_col_block<-1>(c, G, t, 1, 0))) return rc;
-        HIPCHK(hipMemcpyAsync(f.c0[g], t, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
-    }
-    return FB_OK;
+    if ((rc = beside_r2c(m, s, d_rows))) return rc;
+    return each_group(c, c->ngroups, [&](int g, size_t n) -> int {
+        HIPCHK(hipMemcpyAsync(f.c0[g], m->rec_work[g], n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        return FB_OK;
+    });
 }
 
 // ---- the passive tracer (kernels: fb_tracer.h) ----
@@ -208,15 +228,6 @@ static void tangent_free(fb_model *m)
     for (cf *&p : m->tg_j) if (p) { hipFree(p); p = nullptr; }
     if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
     m->tg_n = 0;
-}
-
-// f(g, n) for each of the first ngroups column groups that has elements, n (complex) of them; the first status that is not FB_OK ends it
-template <class F> static int each_group(const fb_ctx *c, int ngroups, F &&f)
-{
-    for (int g = 0; g < ngroups; ++g)
-        if (const size_t n = grp_elems(c, c->grp[g]))
-            if (int rc = f(g, n)) return rc;
-    return FB_OK;
 }
 
 // One RK stage of the perturbations, where tracer_stage runs and from the same states, one perturbation after the other in index
@@ -870,6 +881,130 @@ static int adjoint_back(const Call &k, int nsteps)
 extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps) { return adjoint_back(on_model("fb_model_adjoint_back", m), nsteps); }
 extern "C" int fb_slab_adjoint_back(fb_slab *s, int nsteps) { return adjoint_back(on_slab("fb_slab_adjoint_back", s), nsteps); }
 
+// ---- point observations and the forcing of the adjoint by their misfits (kernels: fb_obs.h) ----
+// Between two steps only: the step, the tape, the tangent and the sweep never see any of it.  One GPU or a slab of one rank, as the adjoint.
+static void obs_free(fb_model *m)
+{
+    if (m->ob_acc) { hipFree(m->ob_acc); m->ob_acc = nullptr; }
+    if (m->ob_real) { hipFree(m->ob_real); m->ob_real = nullptr; }
+    if (m->ob_red) { hipFree(m->ob_red); m->ob_red = nullptr; }
+}
+
+// field[i][j] = sum over the points of w wx_a wy_b, the transpose of sample(): the accumulator (two limbs per cell) and its head
+// zeroed, max |w|, the integer atomics, the rounding of every cell (fb_obs.h).  d_field: any device [nx][ny] float32 field.
+static int obs_scatter(fb_model *m, const double *d_xy, const double *d_w, int n, float *d_field)
+{
+    fb_ctx *c = m->c;
+    const size_t cells = (size_t)c->nx * c->ny;
+    int rc;
+    if ((rc = rec_alloc((void **)&m->ob_acc, (2 * cells + 2) * sizeof(unsigned long long)))) return rc;
+    unsigned long long *acc = m->ob_acc, *head = acc + 2 * cells;
+    HIPCHK(hipMemsetAsync(acc, 0, (2 * cells + 2) * sizeof(unsigned long long), c->stream));
+    if ((rc = launch_n(c, k_obs_wmax, (size_t)n, d_w, n, head))) return rc;
+    if ((rc = launch_n(c, k_scatter, (size_t)n, part_geo(c), d_xy, d_w, n, acc, cells, (const unsigned long long *)head))) return rc;
+    return launch_n(c, k_scatter_round, cells, (const unsigned long long *)acc, (const unsigned long long *)head, n, d_field, cells);
+}
+
+// kind 0 zeta, 1 u, 2 v, 3 psi of the resident state as the record of that kind forms it (record(): fb_model_get_vort,
+// fb_model_get_diag), into the observations' own real field, then sample(): bit for bit sample() of that record
+static const RecKind OBS_REC[4] = {REC_VORT, REC_U, REC_V, REC_PSI};
+static int obs_observe(fb_model *m, fb_slab *s, int kind, const double *d_xy, int n, double *d_out)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if ((rc = rec_alloc((void **)&m->ob_real, (size_t)c->nx * c->ny * sizeof(float)))) return rc;
+    if ((rc = record(m, s, OBS_REC[kind], m->ob_real))) return rc;
+    return sample(c, m->ob_real, d_xy, n, d_out);
+}
+
+// lam += H^T w: the scatter into the observations' real field, its r2c as set_adjoint takes lam (beside_r2c: every grid class through
+// the row and column dispatch), and the conjugate multiplier of the kind added into lam (k_obs_adjoint).  The k-bar and the
+// accumulator hold nothing between two sweeps; the tape is not touched.
+static int obs_adjoint_add(fb_model *m, fb_slab *s, int kind, const double *d_xy, const double *d_w, int n)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    int rc;
+    if ((rc = rec_alloc((void **)&m->ob_real, (size_t)c->nx * c->ny * sizeof(float)))) return rc;
+    if ((rc = obs_scatter(m, d_xy, d_w, n, m->ob_real)) || (rc = beside_r2c(m, s, m->ob_real))) return rc;
+    return launch_n(c, k_obs_adjoint, grp_elems(c, G), make_coef(c), (const cf *)m->rec_work[0], m->ad.c0[0], kind, G.ncols, c->N1, c->N2, G.ky0);
+}
+
+// r = (h - y) / sigma^2 and *d_cost += 1/2 sum (h - y)^2 / sigma^2: the workgroups' partial sums, then one workgroup over them
+static int obs_misfit(fb_model *m, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if ((rc = rec_alloc((void **)&m->ob_red, (size_t)c->max_wg * sizeof(double)))) return rc;
+    const int nwg = grid_for(c, (size_t)n);
+    if ((rc = launch(c, k_obs_misfit, dim3(nwg), dim3(256), 0, d_h, d_y, d_sigma, n, d_r, m->ob_red))) return rc;
+    return launch(c, k_obs_cost_final, dim3(1), dim3(256), 0, (const double *)m->ob_red, nwg, d_cost);
+}
+
+static bool obs_kind_ok(int kind) { return kind >= 0 && kind <= 3; }
+static const char *const OBS_KIND = "kind must be 0 (zeta), 1 (u), 2 (v) or 3 (psi)";
+
+static int scatter(const Call &k, const double *d_xy, const double *d_w, int n, float *d_field)
+{
+    if (!d_xy || !d_w || !d_field) return refuse(k, "NULL positions, weights or output");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return obs_scatter(k.m, d_xy, d_w, n, d_field);
+}
+extern "C" int fb_model_scatter(fb_model *m, const double *d_xy, const double *d_w, int n, float *d_field)
+{
+    return scatter(on_model("fb_model_scatter", m), d_xy, d_w, n, d_field);
+}
+extern "C" int fb_slab_scatter(fb_slab *s, const double *d_xy, const double *d_w, int n, float *d_field)
+{
+    return scatter(on_slab("fb_slab_scatter", s), d_xy, d_w, n, d_field);
+}
+
+static int observe(const Call &k, int kind, const double *d_xy, int n, double *d_out)
+{
+    if (!obs_kind_ok(kind)) return refuse(k, OBS_KIND);
+    if (!d_xy || !d_out) return refuse(k, "NULL positions or output");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return obs_observe(k.m, k.s, kind, d_xy, n, d_out);
+}
+extern "C" int fb_model_observe(fb_model *m, int kind, const double *d_xy, int n, double *d_out) { return observe(on_model("fb_model_observe", m), kind, d_xy, n, d_out); }
+extern "C" int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out) { return observe(on_slab("fb_slab_observe", s), kind, d_xy, n, d_out); }
+
+// (d_sigma may be NULL: sigma = 1)
+static int obs_misfit(const Call &k, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost)
+{
+    if (!d_h || !d_y || !d_r || !d_cost) return refuse(k, "NULL values, observations, residual or cost");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return obs_misfit(k.m, d_h, d_y, d_sigma, n, d_r, d_cost);
+}
+extern "C" int fb_model_obs_misfit(fb_model *m, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost)
+{
+    return obs_misfit(on_model("fb_model_obs_misfit", m), d_h, d_y, d_sigma, n, d_r, d_cost);
+}
+extern "C" int fb_slab_obs_misfit(fb_slab *s, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost)
+{
+    return obs_misfit(on_slab("fb_slab_obs_misfit", s), d_h, d_y, d_sigma, n, d_r, d_cost);
+}
+
+static int adjoint_add_obs(const Call &k, int kind, const double *d_xy, const double *d_w, int n)
+{
+    if (!obs_kind_ok(kind)) return refuse(k, OBS_KIND);
+    if (!d_xy || !d_w) return refuse(k, "NULL positions or weights");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (int rc = enter(k, ADJOINT_SET)) return rc;
+    return obs_adjoint_add(k.m, k.s, kind, d_xy, d_w, n);
+}
+extern "C" int fb_model_adjoint_add_obs(fb_model *m, int kind, const double *d_xy, const double *d_w, int n)
+{
+    return adjoint_add_obs(on_model("fb_model_adjoint_add_obs", m), kind, d_xy, d_w, n);
+}
+extern "C" int fb_slab_adjoint_add_obs(fb_slab *s, int kind, const double *d_xy, const double *d_w, int n)
+{
+    return adjoint_add_obs(on_slab("fb_slab_adjoint_add_obs", s), kind, d_xy, d_w, n);
+}
+
 // ---- what the step and the model's end know of all of them (declared in fftbaro.hip) ----
 // At the top of RK stage `stage`, from the state the vorticity's stage starts from: the tracer's stage, the particles', the
 // tangent-linear model's, and the state into the adjoint's tape (the last three on one rank only: their set calls refuse more).
@@ -895,4 +1030,5 @@ static void beside_free_all(fb_model *m)
     tangent_free(m);
     adjoint_free(m);
     adjoint_tape_free(m);
+    obs_free(m);
 }

@@ -24,6 +24,7 @@
 #include "fb_tangent.h"
 #include "fb_clv.h"
 #include "fb_adjoint.h"
+#include "fb_obs.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1084,6 +1085,12 @@ struct fb_model {
     Beside ad;
     float *ad_real;
     bool adjoint;
+    // the point observations (fb_obs.h; host side in fb_beside.h): the fixed-point accumulator of a scatter (two 64-bit limbs for
+    // each of the nx * ny cells, and its head), the real field that is observed from or scattered into, the partial sums of a misfit ([max_wg]
+    // float64); each allocated at its first use, then kept
+    unsigned long long *ob_acc;
+    float *ob_real;
+    double *ob_red;
 };
 
 // one rank of the multi-GPU model (fb_slab_driver.h)
