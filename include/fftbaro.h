@@ -344,6 +344,28 @@ int fb_model_adjoint_recorded(fb_model *m, int *n);
 int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real);         /* NULL: remove the adjoint variable */
 int fb_model_get_adjoint(fb_model *m, float *d_real);
 int fb_model_adjoint_back(fb_model *m, int nsteps);
+/* Adjoint subspace (no reference counterpart): up to FB_ADJOINTS_MAX = 32 adjoint variables swept back over the ONE tape, for the
+ * leading singular vectors of T (Model.singular_vectors: block power iteration with a tangent subspace) and for the gradients of
+ * several functionals of the final state in one sweep.  fb_model_set_adjoints takes `count` device fields [count][nx][ny] in, each as
+ * fb_model_set_adjoint takes its one (never dealiased), and replaces whatever set was there; NULL removes all.
+ * fb_model_set_adjoint(lam) is fb_model_set_adjoints(lam, 1): it REPLACES a set of several by the one, and fb_model_get_adjoint
+ * returns variable 0 of a set, as fb_model_set_tangent and fb_model_get_tangent do with a tangent set.  fb_model_get_adjoints: all of
+ * them, [count][nx][ny].  fb_model_adjoint_count: 0 while none is set (not an error).  fb_model_adjoint_back sweeps every variable of
+ * the set: per stage the four fields that depend on the recorded state alone (u, v, zeta_x, zeta_y) go back to physical space ONCE,
+ * each variable adds its own mu~, and the products of a chunk of up to 8 variables are formed in one pass that reads the four base
+ * fields once: 4 + 5 count transformed fields per stage where count single sweeps take 9 count.  Variable k of a set is bit for bit
+ * what fb_model_set_adjoint of the same field and the same sweep give; the set of one runs the single variable's own launches.
+ * fb_model_adjoint_add_obs acts on a single variable and is refused (FB_EINVAL) while a set of several is there: forcing one
+ * variable of a set at an intermediate time is get, add, set.  The step, the tape, a tracer, particles and a tangent never see the
+ * set, and the captured step stays when it comes or goes.  Memory, counted by fb_model_info: per variable 3 half spectra on the
+ * active columns and 1 on the frozen ones; shared, with C = min(count, 8), 4 + 5 C real fields and C half spectra (the one: 5 real
+ * fields); at 4096^2 and count = 8 that is 1.6 GB + 3.0 GB + 0.5 GB.  FB_EINVAL before any HIP call: count outside [1, 32] with a
+ * non-NULL field, a NULL output, a NULL model, a slab of several ranks, get without an adjoint set.  FB_ENOMEM: nothing of the adjoint
+ * stays allocated.  Enqueued on the context stream; a set that goes or changes its count waits for the stream first. */
+#define FB_ADJOINTS_MAX 32
+int fb_model_set_adjoints(fb_model *m, const float *d_lambda_real, int count);  /* [count][nx][ny]; NULL: remove all */
+int fb_model_get_adjoints(fb_model *m, float *d_real);                          /* [count][nx][ny] */
+int fb_model_adjoint_count(fb_model *m, int *count);                            /* 0 when none is set */
 /* Point observations and the forcing of the adjoint by their misfits (no reference counterpart): what a 4D-Var cost
  *   J(zeta_0) = 1/2 sum over times k and points p of (H_k zeta_k - y_k)_p^2 / sigma_p^2
  * and its gradient need of the engine on top of the adjoint sweep.  All four act between two steps only: the step, the tape, a
@@ -568,6 +590,10 @@ int fb_slab_adjoint_recorded(fb_slab *s, int *n);
 int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real);           /* NULL: remove the adjoint variable */
 int fb_slab_get_adjoint(fb_slab *s, float *d_real);
 int fb_slab_adjoint_back(fb_slab *s, int nsteps);
+/* the adjoint subspace (fb_model_set_adjoints) of a slab of ONE rank, likewise */
+int fb_slab_set_adjoints(fb_slab *s, const float *d_lambda_real, int count); /* NULL: remove all */
+int fb_slab_get_adjoints(fb_slab *s, float *d_real);
+int fb_slab_adjoint_count(fb_slab *s, int *count);
 /* the point observations (fb_model_scatter) of a slab of ONE rank, likewise */
 int fb_slab_scatter(fb_slab *s, const double *d_xy, const double *d_w, int n, float *d_field);
 int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out);

@@ -87,8 +87,10 @@ _CLV_PAIRS = {"tangent_tape": [_ip], "tangent_tape_push": [], "tangent_tape_coun
 # the point observations' pairs, likewise: the scatter, the observation operator, the misfit and the adjoint's forcing
 _OBS_PAIRS = {"scatter": [_vp, _vp, _ip, _vp], "observe": [_ip, _vp, _ip, _vp], "obs_misfit": [_vp, _vp, _vp, _ip, _vp, _vp],
               "adjoint_add_obs": [_ip, _vp, _vp, _ip]}
+# the adjoint subspace's pairs, likewise: the set in and out and its count
+_ADJOINTS_PAIRS = {"set_adjoints": [_vp, _ip], "get_adjoints": [_vp], "adjoint_count": [_pip]}
 for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
-                     + list(_OBS_PAIRS.items())):
+                     + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -426,6 +428,93 @@ def singular_values(model, steps, iters, start, save=None, restore=None):
     finally:
         model.record_adjoint(0)
     return sig, v.float()
+
+
+ADJOINTS_MAX = 32
+SV_SEED = 20240229          # singular_vectors(start=None): the seed of its start vectors
+
+
+def fields_arg(a, shape, what, most):
+    """Checks a set of M real fields, numpy or torch, [M, *shape] with 1 <= M <= most, float32 (numpy: float32 or float64, converted);
+    raises ValueError, before anything is handed to the engine.  Returns M."""
+    if isinstance(a, np.ndarray):
+        ok_dtype = a.dtype in (np.float32, np.float64)
+    else:
+        ok_dtype = str(getattr(a, "dtype", None)) == "torch.float32"
+    if not hasattr(a, "shape") or len(a.shape) != 1 + len(shape) or tuple(a.shape[1:]) != tuple(shape):
+        raise ValueError("%s: [M, %s] fields" % (what, ", ".join(str(n) for n in shape)))
+    if not ok_dtype:
+        raise ValueError("%s: float32 fields (numpy: float32 or float64)" % what)
+    if not 1 <= int(a.shape[0]) <= most:
+        raise ValueError("%s: 1 to %d fields, not %d" % (what, most, int(a.shape[0])))
+    return int(a.shape[0])
+
+
+def _orthonormal_rows(t, w):
+    """The rows of w, float64 [k, n] on any device, orthonormalised in their order: a QR by modified Gram-Schmidt, run twice (the
+    second pass removes what the rounding of the first left), on the tensor where it lives."""
+    q = w.clone()
+    for _ in range(2):
+        for j in range(q.shape[0]):
+            for i in range(j):
+                q[j] -= (q[i] @ q[j]) * q[i]
+            q[j] /= q[j].norm()
+    return q
+
+
+def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None):
+    """Orthogonal (block power) iteration on T^T T in the L2 norm on `model` (anything with set_tangents, tangents, record_adjoint,
+    step, set_adjoints, adjoint_back, adjoints; save / restore as in singular_values), T the tangent of `steps` steps from the model's
+    current state: the k leading singular values and right singular vectors from one tangent subspace and one adjoint set of k.  V,
+    [k, nx, ny], starts as the orthonormalised `start` ([k, nx, ny], numpy or torch; None: normal deviates from a fixed seed, drawn on
+    the GPU, so that two calls agree).  Per iteration: the state is restored bit for bit and set_tangents(V); `steps` steps with the
+    tape on and U = tangents(); Rayleigh-Ritz on the k x k Gram matrix of U in float64 gives sigma_i, sorted descending, and the
+    rotation E; set_adjoints(U), adjoint_back(steps), W = adjoints() rotated by E; W orthonormalised in float64 (a QR by Gram-Schmidt
+    on the device tensors) is the next V.  No field crosses to the host: the Gram matrix alone is read, once per iteration.  Returns
+    (sigma float64 [iters, k] numpy, the final V float32 [k, nx, ny] tensor, row i converging to the i-th right singular vector).
+    The model is left as singular_values leaves it: at its starting state, the tape freed; the tangent set holds the last V it
+    stepped and the adjoint set the last sweep.  Convergence of sigma_i goes like (sigma_(k+1) / sigma_i)^(2 iters)."""
+    if steps < 1 or iters < 1:
+        raise ValueError("singular_vectors: steps and iters must be >= 1")
+    if int(k) != k or not 1 <= k <= min(TANGENTS_MAX, ADJOINTS_MAX):
+        raise ValueError("singular_vectors: k must be in [1, %d]" % min(TANGENTS_MAX, ADJOINTS_MAX))
+    k = int(k)
+    if start is not None:
+        if not hasattr(start, "shape") or len(start.shape) != 3 or int(start.shape[0]) != k:
+            raise ValueError("singular_vectors: start must be [k, nx, ny]")
+    t = model.torch
+    save, restore = save or model.spectrum, restore or model.set_spectrum
+    if start is None:
+        gen = t.Generator(device="cuda")
+        gen.manual_seed(SV_SEED)
+        v = t.randn((k,) + tuple(model._shape), generator=gen, dtype=t.float64, device="cuda")
+    else:
+        if isinstance(start, np.ndarray):
+            start = t.from_numpy(np.ascontiguousarray(start, dtype=np.float64))
+        v = start.cuda().double()
+    shape = tuple(v.shape)
+    v = _orthonormal_rows(t, v.reshape(k, -1))
+    z0 = save()
+    sig = np.empty((iters, k))
+    model.record_adjoint(steps)
+    try:
+        for it in range(iters):
+            restore(z0)
+            model.set_tangents(v.float().reshape(shape).contiguous())
+            model.step(steps)
+            u32 = model.tangents()
+            u = u32.double().reshape(k, -1)
+            w, e = np.linalg.eigh((u @ u.T).cpu().numpy())
+            order = np.argsort(w)[::-1]
+            sig[it] = np.sqrt(np.maximum(w[order], 0.0))
+            rot = t.from_numpy(np.ascontiguousarray(e[:, order].T)).cuda()
+            model.set_adjoints(u32)
+            model.adjoint_back(steps)
+            v = _orthonormal_rows(t, rot @ model.adjoints().double().reshape(k, -1))
+        restore(z0)
+    finally:
+        model.record_adjoint(0)
+    return sig, v.float().reshape(shape)
 
 
 OBS_KINDS = {"vort": 0, "u": 1, "v": 2, "psi": 3}
@@ -1114,6 +1203,34 @@ class ModelSurface:
         self._one_rank("adjoint_record", int(steps))
         return singular_values(self, steps, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]))
 
+    def set_adjoints(self, lam):
+        """Sets an adjoint subspace: M adjoint variables, [M, nx, ny] (numpy or torch, 1 <= M <= ADJOINTS_MAX), swept back over the ONE
+        tape by adjoint_back, each as set_adjoint's one (variable k is bit for bit what set_adjoint of lam[k] and the same sweep give);
+        whatever set was there is replaced, set_adjoint's one too; lam=None removes all.  set_adjoint replaces a set by its one, and
+        adjoint() returns variable 0.  adjoint_add_obs is refused while a set of several is there.  One rank only, as set_adjoint."""
+        t = self.torch
+        self._one_rank("set_adjoints", None, 1)
+        if lam is None:
+            return self._hand("set_adjoints", None, 0)
+        m = fields_arg(lam, self._shape, "set_adjoints", ADJOINTS_MAX)
+        if isinstance(lam, np.ndarray):
+            lam = t.from_numpy(np.ascontiguousarray(lam, dtype=np.float32))
+        self._hand("set_adjoints", lam.cuda().contiguous(), m)
+
+    def adjoint_count(self): return self._count("adjoint_count")
+
+    def adjoints(self):
+        """every adjoint variable, float32 [M, nx, ny] (with none set the engine's refusal is raised)"""
+        out = self.torch.empty((max(self.adjoint_count(), 1),) + self._shape, dtype=self.torch.float32, device="cuda")
+        self._hand("get_adjoints", out)
+        return out
+
+    def singular_vectors(self, steps, k, iters, start=None):
+        """(sigma [iters, k], V [k, nx, ny]): the k leading singular values and right singular vectors of the tangent over `steps`
+        steps from the current state, by block power iteration with a tangent subspace and an adjoint set of k (singular_vectors());
+        the state is kept and put back through _STATE."""
+        self._one_rank("adjoint_record", int(steps))
+        return singular_vectors(self, steps, k, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]))
 
     def scatter(self, w, xy):
         """The transpose of sample(): n point values w, float64 [n], at the positions xy, float64 [n, 2], spread onto the grid with the

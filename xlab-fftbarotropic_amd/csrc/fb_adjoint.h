@@ -161,3 +161,100 @@ __global__ void __launch_bounds__(256) k_adjoint_update(SpecCoef c, const cf *__
         else reinterpret_cast<float4 *>(lam)[p] = out_l;
     }
 }
+
+// ---- a set of adjoint variables on the one trajectory (fb_model_set_adjoints; host side: fb_beside.h, adjoint_stage_set) ----
+// Four of the five fields a stage takes back to physical space are functions of the recorded stage state alone, so a set of M
+// variables forms them once per stage and each variable adds its own mu~:
+//   k_adjoint_base     grady psi, gradx psi, gradx zeta, grady zeta into the fields 0..3 of the record workspace, once per stage
+//   (their backward x pass and four ROW_INV row passes into real fields that the stage does not overwrite)
+//   k_adjoint_mu       mu~_k = mask ks kb_k of a chunk of up to ADJOINT_CHUNK variables, one launch, into the set's own spectra
+//   (the backward x pass of the chunk, one ROW_INV row pass per variable)
+//   k_adjoint_prod_set u mu~_k, v mu~_k, zeta_x mu~_k, zeta_y mu~_k of the chunk out of place, the base fields read once
+//   (per variable, as for the one: four ROW_FWD row passes, their forward x pass, k_adjoint_update)
+// Every element is formed by the expression k_adjoint_deriv and k_adjoint_prod form it by: variable k of a set has the bits of the
+// single variable started from the same field.
+#define ADJOINT_CHUNK 8
+struct AdjointKbars { const cf *kb[ADJOINT_CHUNK]; };
+
+// zs: the stage state; z: field f at z + f * fstride: 0 grady psi, 1 gradx psi, 2 gradx zeta, 3 grady zeta, the fields 1..4 of
+// k_adjoint_deriv in its float32 forms (no contraction).  Two modes per lane and access; pad columns zero.
+__global__ void __launch_bounds__(256) k_adjoint_base(SpecCoef c, const cf *__restrict__ zs, cf *__restrict__ z, long fstride, int P, int N1, int N2, int ky0)
+{
+#pragma clang fp contract(off)
+    const size_t total = (size_t)c.nx * P / 2;
+    const int hp = P >> 1;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)(p / hp), col = 2 * (int)(p - (size_t)row * hp);
+        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d;
+        const size_t idx = 2 * p;
+        float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ky0 + col < c.hy) zv = reinterpret_cast<const float4 *>(zs)[p];
+        cf o[4][2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int j = ky0 + col + e;
+            o[0][e] = o[1][e] = o[2][e] = o[3][e] = cf_make(0.f, 0.f);
+            if (j < c.hy) {
+                const cf a = e ? cf_make(zv.z, zv.w) : cf_make(zv.x, zv.y);
+                const float kx = c.gx[i], ky = c.gy[j];
+                const float li = (i == 0 && j == 0) ? 1.0f : coef_lap(c, i, j);
+                const cf ph = cf_make(a.x / li, a.y / li);
+                o[0][e] = tr_grad(ph, ky);
+                o[1][e] = tr_grad(ph, kx);
+                o[2][e] = tr_grad(a, kx);
+                o[3][e] = tr_grad(a, ky);
+            }
+        }
+#pragma unroll
+        for (int f = 0; f < 4; ++f)
+            *reinterpret_cast<float4 *>(z + (size_t)f * fstride + idx) = make_float4(o[f][0].x, o[f][0].y, o[f][1].x, o[f][1].y);
+    }
+}
+
+// a.kb[k]: the k-bar of variable k of the chunk, taken times ks; z: mu~_k = mask ks kb_k at z + k * fstride, field 0 of
+// k_adjoint_deriv in its float32 form.  The mask of a pair of modes is formed once for the cnt variables.  Pad columns zero.
+__global__ void __launch_bounds__(256) k_adjoint_mu(SpecCoef c, AdjointKbars a, int cnt, float ks, cf *__restrict__ z, long fstride, int P, int N1, int N2, int ky0)
+{
+#pragma clang fp contract(off)
+    const size_t total = (size_t)c.nx * P / 2;
+    const int hp = P >> 1;
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (size_t)gridDim.x * blockDim.x) {
+        const int row = (int)(p / hp), col = 2 * (int)(p - (size_t)row * hp);
+        const int cc = row / N2, d = row - cc * N2, i = cc + N1 * d;
+        const int j = ky0 + col;
+        const bool in0 = j < c.hy, in1 = j + 1 < c.hy;
+        const float m0 = in0 ? coef_mask(c, i, j) : 0.0f, m1 = in1 ? coef_mask(c, i, j + 1) : 0.0f;
+        for (int k = 0; k < cnt; ++k) {
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (in0) {
+                const float4 kv = reinterpret_cast<const float4 *>(a.kb[k])[p];
+                o.x = (kv.x * ks) * m0; o.y = (kv.y * ks) * m0;
+                if (in1) { o.z = (kv.z * ks) * m1; o.w = (kv.w * ks) * m1; }
+            }
+            *reinterpret_cast<float4 *>(z + (size_t)k * fstride + 2 * p) = o;
+        }
+    }
+}
+
+// base: four real fields [4][n], n = nx * ny (a multiple of 4): u, v, zeta_x, zeta_y as the ROW_INV passes left them; mu: [CNT][n], the
+// chunk's mu~_k; out: [CNT][4][n], u mu~_k, v mu~_k, zeta_x mu~_k, zeta_y mu~_k.  Each element of the base is read once and kept in
+// registers while the CNT mu~ stream past; 16 bytes per lane and access over contiguous rows, no LDS, no atomics.
+template <int CNT>
+__global__ void __launch_bounds__(256) k_adjoint_prod_set(const float *__restrict__ base, const float *__restrict__ mu, float *__restrict__ out, size_t n)
+{
+    const size_t n4 = n / 4;
+    const float4 *b = reinterpret_cast<const float4 *>(base), *q = reinterpret_cast<const float4 *>(mu);
+    float4 *o = reinterpret_cast<float4 *>(out);
+    for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n4; p += (size_t)gridDim.x * blockDim.x) {
+        float4 v[4], m[CNT];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) v[f] = b[(size_t)f * n4 + p];
+#pragma unroll
+        for (int k = 0; k < CNT; ++k) m[k] = q[(size_t)k * n4 + p];
+#pragma unroll
+        for (int k = 0; k < CNT; ++k)
+#pragma unroll
+            for (int f = 0; f < 4; ++f)
+                o[((size_t)k * 4 + f) * n4 + p] = make_float4(v[f].x * m[k].x, v[f].y * m[k].y, v[f].z * m[k].z, v[f].w * m[k].w);
+    }
+}

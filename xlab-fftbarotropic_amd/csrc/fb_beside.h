@@ -728,11 +728,33 @@ static void adjoint_tape_free(fb_model *m)
     m->ad_depth = m->ad_fill = 0;
 }
 
+// the variables of a sweep's chunk, and the real fields of the product pass, for a set of `count`: the one keeps k_adjoint_prod's five
+static int adjoint_chunk(int count) { return count < ADJOINT_CHUNK ? count : ADJOINT_CHUNK; }
+static size_t adjoint_real_fields(int count) { return count == 1 ? 5 : 4 + 5 * (size_t)adjoint_chunk(count); }
+
+// (the workspace is sized for the count: it goes with a set that changes it)
+static void adjoint_work_free(fb_model *m)
+{
+    if (m->ad_real) { hipFree(m->ad_real); m->ad_real = nullptr; }
+    if (m->ad_spec) { hipFree(m->ad_spec); m->ad_spec = nullptr; }
+}
+
 static void adjoint_free(fb_model *m)
 {
-    beside_free(m->ad);
-    if (m->ad_real) { hipFree(m->ad_real); m->ad_real = nullptr; }
-    m->adjoint = false;
+    for (Beside &f : m->ad) beside_free(f);
+    adjoint_work_free(m);
+    m->ad_n = 0;
+}
+
+// per variable 3 half spectra on the active columns and 1 on the frozen ones; the real fields; a set's chunk of mu~ spectra
+static size_t adjoint_bytes(const fb_model *m)
+{
+    const fb_ctx *c = m->c;
+    if (!m->ad_n) return 0;
+    size_t n = adjoint_real_fields(m->ad_n) * c->nx * c->ny * sizeof(float);
+    for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->ad_n * (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);
+    if (m->ad_n > 1) n += (size_t)adjoint_chunk(m->ad_n) * grp_elems(c, c->grp[0]) * sizeof(cf);
+    return n;
 }
 
 // The tape on (depth >= 1: room for depth steps x 4 stage states) or off (depth == 0); either way it starts empty.  While it is on
@@ -770,20 +792,22 @@ static int adjoint_stash(fb_model *m, int stage)
     return launch_n(c, k_adjoint_merge, n / 2, make_coef(c), v0, v1, slot, G.ncols, c->N1, c->N2, G.ky0);
 }
 
-// The adjoint variable in (beside_in: lam, with the k-bar and the accumulator of a backward step) and the real fields of the product
-// pass; d_rows == NULL removes it.  The step's launches do not depend on it: the captured step stays.
-static int adjoint_in(fb_model *m, fb_slab *s, const float *d_rows)
+// `count` adjoint variables in, d_rows [count] real fields one after the other (beside_in each: lam, with the k-bar and the
+// accumulator of a backward step), and the workspace of the product pass for that count; whatever set was there is replaced,
+// variables beyond `count` freed; d_rows == NULL removes all.  A set that goes or changes its count may still be read by a queued
+// sweep.  The step's launches do not depend on any of it: the captured step stays.  A failure leaves nothing of the adjoint allocated.
+static int adjoint_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
 {
     fb_ctx *c = m->c;
-    int rc;
-    if (!d_rows) {
-        if (m->adjoint) HIPCHK(hipStreamSynchronize(c->stream));
-        adjoint_free(m);
-        return FB_OK;
-    }
-    rc = rec_alloc((void **)&m->ad_real, 5 * (size_t)c->nx * c->ny * sizeof(float));
-    if (rc || (rc = beside_in(m, s, d_rows, m->ad))) { adjoint_free(m); return rc; }
-    m->adjoint = true;
+    if (m->ad_n && (!d_rows || count != m->ad_n)) HIPCHK(hipStreamSynchronize(c->stream));
+    if (!d_rows) { adjoint_free(m); return FB_OK; }
+    if (count != m->ad_n) adjoint_work_free(m);
+    int rc = rec_alloc((void **)&m->ad_real, adjoint_real_fields(count) * c->nx * c->ny * sizeof(float));
+    if (!rc && count > 1) rc = rec_alloc((void **)&m->ad_spec, (size_t)adjoint_chunk(count) * grp_elems(c, c->grp[0]) * sizeof(cf));
+    for (int k = 0; k < count && !rc; ++k) rc = beside_in(m, s, d_rows + (size_t)k * c->XL * c->ny, m->ad[k]);
+    if (rc) { adjoint_free(m); return rc; }
+    for (int k = count; k < m->ad_n; ++k) beside_free(m->ad[k]);
+    m->ad_n = count;
     return FB_OK;
 }
 
@@ -797,7 +821,7 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
     const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
     const SpecCoef coef = make_coef(c);
     cf *z = m->rec_work[0];
-    cf *lam = m->ad.c0[0], *kb = m->ad.c1[0], *acc = m->ad.acc[0];
+    cf *lam = m->ad[0].c0[0], *kb = m->ad[0].c1[0], *acc = m->ad[0].acc[0];
     int rc;
     if ((rc = launch_n(c, k_adjoint_deriv, n / 2, coef, zs, (const cf *)(stage == 3 ? lam : kb), stage == 3 ? m->dt / 6.0f : 1.0f, z, (long)n, G.ncols, c->N1, c->N2, G.ky0)))
         return rc;
@@ -821,7 +845,66 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
     });
 }
 
-// The last nsteps recorded steps popped, newest first, each step's transpose applied to lam (its stages in the order 3, 2, 1, 0).
+// adjoint_stage for a set of ad_n > 1 variables.  u, v, zeta_x, zeta_y depend on zs alone: their four spectra (k_adjoint_base), the
+// backward x pass and the four ROW_INV passes run once, into the real fields 0..3 of ad_real, which nothing below writes.  Then in
+// chunks of C = min(ad_n, ADJOINT_CHUNK) variables (a chunk re-reads the four base fields once, 16 nx ny bytes): the chunk's mu~ in
+// one launch into ad_spec, their backward x pass in one, a ROW_INV pass each into the real fields 4 .. 4 + C; k_adjoint_prod_set
+// out of place into the 4 C fields after them; and per variable what adjoint_stage does from its products on, through the fields
+// 0..3 of the record workspace.  Launches per stage: 7 + ceil(ad_n / C) * 4 + 9 ad_n.  The passes of distinct fields share no
+// arithmetic, so every variable gets the bits adjoint_stage gives it.
+static int adjoint_stage_set(fb_model *m, int stage, const cf *zs)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
+    const SpecCoef coef = make_coef(c);
+    const int M = m->ad_n, C = adjoint_chunk(M);
+    cf *z = m->rec_work[0], *zm = m->ad_spec;
+    float *base = m->ad_real, *mu = base + 4 * nr, *prod = mu + (size_t)C * nr;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    int rc;
+    if ((rc = launch_n(c, k_adjoint_base, n / 2, coef, zs, z, (long)n, G.ncols, c->N1, c->N2, G.ky0))) return rc;
+    if ((rc = launch_col_block<+1>(c, G, z, 4, (long)n)) || (rc = launch_col_strided<+1>(c, G, z, 4, (long)n))) return rc;
+    for (int f = 0; f < 4; ++f) {
+        RowArgs a = row_args_base(c);
+        a.M = view_single(c, z + f * n, (long)n); a.scale = f == 0 ? -g : g; a.rout = base + f * nr;               // u = -dpsi/dy (record(), REC_U)
+        if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+    }
+    for (int k0 = 0; k0 < M; k0 += C) {
+        const int cnt = M - k0 < C ? M - k0 : C;
+        AdjointKbars kbars = {};
+        for (int k = 0; k < cnt; ++k) kbars.kb[k] = stage == 3 ? m->ad[k0 + k].c0[0] : m->ad[k0 + k].c1[0];
+        if ((rc = launch_n(c, k_adjoint_mu, n / 2, coef, kbars, cnt, stage == 3 ? m->dt / 6.0f : 1.0f, zm, (long)n, G.ncols, c->N1, c->N2, G.ky0))) return rc;
+        if ((rc = launch_col_block<+1>(c, G, zm, cnt, (long)n)) || (rc = launch_col_strided<+1>(c, G, zm, cnt, (long)n))) return rc;
+        for (int k = 0; k < cnt; ++k) {
+            RowArgs a = row_args_base(c);
+            a.M = view_single(c, zm + k * n, (long)n); a.scale = g; a.rout = mu + k * nr;
+            if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+        }
+        rc = dispatch<ADJOINT_CHUNK>(cnt - 1, [&](auto K) {
+            return launch_n(c, k_adjoint_prod_set<K() + 1>, nr / 4, (const float *)base, (const float *)mu, prod, nr);
+        });
+        if (rc) return rc;
+        for (int k = 0; k < cnt; ++k) {
+            Beside &v = m->ad[k0 + k];
+            HIPCHK(hipMemsetAsync(z, 0, 4 * n * sizeof(cf), c->stream));                                            // pad columns zero
+            for (int f = 0; f < 4; ++f) {
+                RowArgs a = row_args_base(c);
+                a.rin = prod + ((size_t)k * 4 + f) * nr; a.T = view_single(c, z + f * n, 0);
+                if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+            }
+            if ((rc = launch_col_strided<-1>(c, G, z, 4, (long)n)) || (rc = launch_col_block<-1>(c, G, z, 4, (long)n))) return rc;
+            rc = dispatch<4>(stage, [&](auto S) {
+                return launch_n(c, k_adjoint_update<S()>, n / 2, coef, (const cf *)z, (long)n, v.c0[0], v.c1[0], v.acc[0], m->nu, m->dt, G.ncols, c->N1, c->N2, G.ky0);
+            });
+            if (rc) return rc;
+        }
+    }
+    return FB_OK;
+}
+
+// The last nsteps recorded steps popped, newest first, each step's transpose applied to every lam (its stages in the order 3, 2, 1, 0).
+// The set of one keeps adjoint_stage: its five-field passes are what a single variable has always run.
 static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
 {
     fb_ctx *c = m->c;
@@ -831,7 +914,7 @@ static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
     for (int k = 0; k < nsteps; ++k) {
         const cf *step = m->ad_tape + (size_t)(m->ad_fill - 1) * 4 * n;
         for (int stage = 3; stage >= 0; --stage)
-            if ((rc = adjoint_stage(m, stage, step + (size_t)stage * n))) return rc;
+            if ((rc = m->ad_n == 1 ? adjoint_stage(m, stage, step + (size_t)stage * n) : adjoint_stage_set(m, stage, step + (size_t)stage * n))) return rc;
         --m->ad_fill;
     }
     return FB_OK;
@@ -859,17 +942,46 @@ static int adjoint_recorded(const Call &k, int *n)
 extern "C" int fb_model_adjoint_recorded(fb_model *m, int *n) { return adjoint_recorded(on_model("fb_model_adjoint_recorded", m), n); }
 extern "C" int fb_slab_adjoint_recorded(fb_slab *s, int *n) { return adjoint_recorded(on_slab("fb_slab_adjoint_recorded", s), n); }
 
-static int set_adjoint(const Call &k, const float *d_lambda_real)
+// [count] fields in; the single variable's call sets one (and with NULL removes the whole set, as the set's own does)
+static int set_adjoints(const Call &k, const float *d_lambda_real, int count)
 {
+    if (d_lambda_real && (count < 1 || count > FB_ADJOINTS_MAX)) return refuse(k, "count outside [1, 32]");
     if (int rc = enter(k, ADJOINT)) return rc;
-    return adjoint_in(k.m, k.s, d_lambda_real);
+    return adjoint_in(k.m, k.s, d_lambda_real, count);
 }
-extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real) { return set_adjoint(on_model("fb_model_set_adjoint", m), d_lambda_real); }
-extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real) { return set_adjoint(on_slab("fb_slab_set_adjoint", s), d_lambda_real); }
+extern "C" int fb_model_set_adjoint(fb_model *m, const float *d_lambda_real) { return set_adjoints(on_model("fb_model_set_adjoint", m), d_lambda_real, 1); }
+extern "C" int fb_slab_set_adjoint(fb_slab *s, const float *d_lambda_real) { return set_adjoints(on_slab("fb_slab_set_adjoint", s), d_lambda_real, 1); }
+extern "C" int fb_model_set_adjoints(fb_model *m, const float *d_lambda_real, int count) { return set_adjoints(on_model("fb_model_set_adjoints", m), d_lambda_real, count); }
+extern "C" int fb_slab_set_adjoints(fb_slab *s, const float *d_lambda_real, int count) { return set_adjoints(on_slab("fb_slab_set_adjoints", s), d_lambda_real, count); }
+static_assert(FB_ADJOINTS_MAX == 32, "the refusal's text names the bound");
 
-static int get_adjoint(const Call &k, float *d_real) { return get_beside(k, ADJOINT_SET, [](fb_model *m) { return &m->ad; }, d_real); }
+// (variable 0 only)
+static int get_adjoint(const Call &k, float *d_real) { return get_beside(k, ADJOINT_SET, [](fb_model *m) { return &m->ad[0]; }, d_real); }
 extern "C" int fb_model_get_adjoint(fb_model *m, float *d_real) { return get_adjoint(on_model("fb_model_get_adjoint", m), d_real); }
 extern "C" int fb_slab_get_adjoint(fb_slab *s, float *d_real) { return get_adjoint(on_slab("fb_slab_get_adjoint", s), d_real); }
+
+static int get_adjoints(const Call &k, float *d_real)
+{
+    if (!d_real) return refuse(k, "NULL output");
+    if (int rc = enter(k, ADJOINT_SET)) return rc;
+    const fb_ctx *c = k.m->c;
+    for (int v = 0; v < k.m->ad_n; ++v)
+        if (int rc = record(k.m, k.s, REC_VORT, d_real + (size_t)v * c->XL * c->ny, nullptr, k.m->ad[v].c0)) return rc;
+    return FB_OK;
+}
+extern "C" int fb_model_get_adjoints(fb_model *m, float *d_real) { return get_adjoints(on_model("fb_model_get_adjoints", m), d_real); }
+extern "C" int fb_slab_get_adjoints(fb_slab *s, float *d_real) { return get_adjoints(on_slab("fb_slab_get_adjoints", s), d_real); }
+
+// (0 while none is set: not a refusal)
+static int adjoint_count(const Call &k, int *count)
+{
+    if (!count) return refuse(k, "NULL output");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    *count = k.m->ad_n;
+    return FB_OK;
+}
+extern "C" int fb_model_adjoint_count(fb_model *m, int *count) { return adjoint_count(on_model("fb_model_adjoint_count", m), count); }
+extern "C" int fb_slab_adjoint_count(fb_slab *s, int *count) { return adjoint_count(on_slab("fb_slab_adjoint_count", s), count); }
 
 static int adjoint_back(const Call &k, int nsteps)
 {
@@ -927,7 +1039,7 @@ static int obs_adjoint_add(fb_model *m, fb_slab *s, int kind, const double *d_xy
     int rc;
     if ((rc = rec_alloc((void **)&m->ob_real, (size_t)c->nx * c->ny * sizeof(float)))) return rc;
     if ((rc = obs_scatter(m, d_xy, d_w, n, m->ob_real)) || (rc = beside_r2c(m, s, m->ob_real))) return rc;
-    return launch_n(c, k_obs_adjoint, grp_elems(c, G), make_coef(c), (const cf *)m->rec_work[0], m->ad.c0[0], kind, G.ncols, c->N1, c->N2, G.ky0);
+    return launch_n(c, k_obs_adjoint, grp_elems(c, G), make_coef(c), (const cf *)m->rec_work[0], m->ad[0].c0[0], kind, G.ncols, c->N1, c->N2, G.ky0);
 }
 
 // r = (h - y) / sigma^2 and *d_cost += 1/2 sum (h - y)^2 / sigma^2: the workgroups' partial sums, then one workgroup over them
@@ -994,6 +1106,8 @@ static int adjoint_add_obs(const Call &k, int kind, const double *d_xy, const do
     if (!d_xy || !d_w) return refuse(k, "NULL positions or weights");
     if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
     if (int rc = enter(k, ADJOINT_SET)) return rc;
+    if (k.m->ad_n > 1)
+        return refuse(k, "a set of " + std::to_string(k.m->ad_n) + " adjoint variables is set: the forcing acts on a single variable (get, add, set for one of a set)");
     return obs_adjoint_add(k.m, k.s, kind, d_xy, d_w, n);
 }
 extern "C" int fb_model_adjoint_add_obs(fb_model *m, int kind, const double *d_xy, const double *d_w, int n)

@@ -1079,12 +1079,16 @@ struct fb_model {
     cf *tt[3]; int tt_depth, tt_fill;
     // the adjoint model (fb_adjoint.h; host side in fb_beside.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
     // 3-pass layout, masked modes merged in from the base, ad_fill steps of it recorded; NULL and 0 while nothing is recorded.  The
-    // adjoint variable lam (ad.c0) with the k-bar (ad.c1) and the accumulator (ad.acc) of a backward step, and the five real fields
-    // [5][nx][ny] of its product pass; NULL without
+    // ad_n adjoint variables on the one tape (an adjoint subspace; fb_model_set_adjoint sets one), each lam (ad[k].c0) with the k-bar
+    // (c1) and the accumulator (acc) of a backward step, and what they share: the real fields of the product pass, [5][nx][ny] for
+    // the one, [4 + 5 C][nx][ny] for a set swept in chunks of C = min(ad_n, ADJOINT_CHUNK) variables (the four base fields, C mu~,
+    // 4 C products), and for a set the C spectra of the chunk's mu~ (ad_spec); NULL and ad_n == 0 without, and ad_n alone says
+    // whether an adjoint is set
     cf *ad_tape; int ad_depth, ad_fill;
-    Beside ad;
+    Beside ad[FB_ADJOINTS_MAX];
+    int ad_n;
     float *ad_real;
-    bool adjoint;
+    cf *ad_spec;
     // the point observations (fb_obs.h; host side in fb_beside.h): the fixed-point accumulator of a scatter (two 64-bit limbs for
     // each of the nx * ny cells, and its head), the real field that is observed from or scattered into, the partial sums of a misfit ([max_wg]
     // float64); each allocated at its first use, then kept
@@ -1147,6 +1151,7 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
 static int beside_stage(fb_model *m, fb_slab *s, int stage);            // at the top of RK stage `stage` of fb_model_step and fb_slab_step
 static void beside_step_done(fb_model *m);                              // after the step's fourth stage
 static void beside_free_all(fb_model *m);
+static size_t adjoint_bytes(const fb_model *m);                         // what fb_model_info counts for the adjoint variables
 
 static void model_drop_graph(fb_model *m)
 {
@@ -1203,6 +1208,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
+        n += adjoint_bytes(m);                                                                                              // the adjoint variables and their workspace
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
         if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
         *hbm = n;
