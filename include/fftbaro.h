@@ -366,6 +366,32 @@ int fb_model_adjoint_back(fb_model *m, int nsteps);
 int fb_model_set_adjoints(fb_model *m, const float *d_lambda_real, int count);  /* [count][nx][ny]; NULL: remove all */
 int fb_model_get_adjoints(fb_model *m, float *d_real);                          /* [count][nx][ny] */
 int fb_model_adjoint_count(fb_model *m, int *count);                            /* 0 when none is set */
+/* Adjoint checkpointing (no reference counterpart): a second way to keep the adjoint's record, for windows whose full tape does not
+ * fit.  fb_model_adjoint_checkpoint(m, every, max_steps): every >= 1 allocates a tape SEGMENT of `every` steps (x 4 half spectra),
+ * room for ceil(max_steps / every) checkpoints of one state each and one more state for the live one: ceil(T / K) + 4 K + 1 half
+ * spectra for a window of T steps where the full tape takes 4 T; K ~ sqrt(T) / 2 (binding.checkpoint_every) makes that
+ * about 4 sqrt(T).  every == 0 frees all of it; either way the window starts empty.  This call and fb_model_adjoint_record replace
+ * each other: turning one on frees what the other held.  Forward: fb_model_step counts the window's steps and, before every step
+ * whose index in the window is a multiple of `every`, copies the state into the next checkpoint (device to device on the context
+ * stream); it writes no tape slot, so the captured step is replayed between two checkpoints; a call that would pass max_steps is
+ * refused before anything is launched.  Backward: fb_model_adjoint_back works as on the full tape, for one variable or a set, and
+ * fills the segment again whenever it is empty: the live state is put aside (once per call), the checkpoint of the segment that
+ * holds the newest unswept step is put back, and that segment's steps are taken again with the recording on.  These steps advance
+ * the vorticity alone: no tracer, particles, deformation, tangent set, basis tape or step count moves.  Before the call returns the
+ * live state is back.  A state that is put back gets its derivative fields from the priming pass and continues bit for bit like the
+ * state that was stepped to, so lam is bit for bit what the full tape gives, and the vorticity and everything stepped beside it are
+ * what they are with the mode off.  What is left of a segment stays on the tape between two calls: a window swept completely, in
+ * whatever pieces, has taken exactly its own length in steps again (replayed).  fb_model_adjoint_recorded: the window's steps not
+ * yet swept.  The window: fb_model_set_vort, fb_model_set_spectrum, fb_model_adjoint_checkpoint and fb_model_adjoint_record empty
+ * it; once a sweep has popped a step, fb_model_step is refused until then; fb_model_set_source is refused while the window holds
+ * unswept steps (they would be run again under another source; the model has no clock, so a source fixed over the window is run
+ * again exactly); fb_model_profile_steps is refused while the mode is on.  fb_model_adjoint_checkpoint_info: every, max_steps, the
+ * checkpoints the window holds and the steps run again since it began (each output may be NULL; all 0 while the mode is off).
+ * fb_model_info counts the segment, the checkpoints and the live copy (and the full tape of fb_model_adjoint_record).  FB_EINVAL
+ * before any HIP call: every outside [0, 2^20], max_steps < 1 or more than 2^20 checkpoints with every >= 1, a NULL model, a slab
+ * of several ranks.  FB_ENOMEM: nothing of it stays allocated. */
+int fb_model_adjoint_checkpoint(fb_model *m, int every, int max_steps);    /* every == 0: off, everything freed */
+int fb_model_adjoint_checkpoint_info(fb_model *m, int *every, int *max_steps, int *checkpoints, long long *replayed);
 /* Point observations and the forcing of the adjoint by their misfits (no reference counterpart): what a 4D-Var cost
  *   J(zeta_0) = 1/2 sum over times k and points p of (H_k zeta_k - y_k)_p^2 / sigma_p^2
  * and its gradient need of the engine on top of the adjoint sweep.  All four act between two steps only: the step, the tape, a
@@ -594,6 +620,9 @@ int fb_slab_adjoint_back(fb_slab *s, int nsteps);
 int fb_slab_set_adjoints(fb_slab *s, const float *d_lambda_real, int count); /* NULL: remove all */
 int fb_slab_get_adjoints(fb_slab *s, float *d_real);
 int fb_slab_adjoint_count(fb_slab *s, int *count);
+/* adjoint checkpointing (fb_model_adjoint_checkpoint) of a slab of ONE rank, likewise */
+int fb_slab_adjoint_checkpoint(fb_slab *s, int every, int max_steps);
+int fb_slab_adjoint_checkpoint_info(fb_slab *s, int *every, int *max_steps, int *checkpoints, long long *replayed);
 /* the point observations (fb_model_scatter) of a slab of ONE rank, likewise */
 int fb_slab_scatter(fb_slab *s, const double *d_xy, const double *d_w, int n, float *d_field);
 int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out);

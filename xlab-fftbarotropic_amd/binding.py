@@ -89,8 +89,10 @@ _OBS_PAIRS = {"scatter": [_vp, _vp, _ip, _vp], "observe": [_ip, _vp, _ip, _vp], 
               "adjoint_add_obs": [_ip, _vp, _vp, _ip]}
 # the adjoint subspace's pairs, likewise: the set in and out and its count
 _ADJOINTS_PAIRS = {"set_adjoints": [_vp, _ip], "get_adjoints": [_vp], "adjoint_count": [_pip]}
+# adjoint checkpointing's pairs, likewise: the mode on and off, and what the window holds
+_CHECKPOINT_PAIRS = {"adjoint_checkpoint": [_ip, _ip], "adjoint_checkpoint_info": [_pip, _pip, _pip, C.POINTER(C.c_longlong)]}
 for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
-                     + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items())):
+                     + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items()) + list(_CHECKPOINT_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -393,6 +395,40 @@ def kaplan_yorke(exponents):
     return j + float(sums[j - 1]) / abs(float(lam[j]))
 
 
+def checkpoint_every(steps):
+    """The checkpoint spacing K >= 1 that minimises the half spectra a checkpointed window of `steps` steps holds, ceil(steps / K)
+    checkpoints + 4 K of the tape segment (about sqrt(steps) / 2, for about 4 sqrt(steps)); of equal ones the smallest K."""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("checkpoint_every: steps must be >= 1")
+    best, k = (steps + 4, 1), 2
+    while 4 * k < best[0]:                                      # beyond that the segment alone takes more
+        best = min(best, (-(-steps // k) + 4 * k, k))
+        k += 1
+    return best[1]
+
+
+_checkpoint_every = checkpoint_every                            # (the helpers below have a keyword of that name)
+
+
+def _device(model):
+    """where a helper keeps its tensors: the GPU, or what a stand-in for the engine (a float64 model on the CPU) names as .device"""
+    return getattr(model, "device", "cuda")
+
+
+def adjoint_window(model, every):
+    """(on, off): how a helper keeps the adjoint's record on `model`.  on(steps) turns it on for a window of `steps` steps: every=None
+    the full tape (record_adjoint(steps)); an int K >= 1 checkpointing with a checkpoint every K steps (checkpoint_adjoint(K, steps));
+    "sqrt" that with K = checkpoint_every(steps).  off() turns off that mode (and with it whichever was on before)."""
+    if every is None:
+        return model.record_adjoint, lambda: model.record_adjoint(0)
+    if isinstance(every, str) and every == "sqrt":
+        return lambda steps: model.checkpoint_adjoint(_checkpoint_every(steps), steps), lambda: model.checkpoint_adjoint(0, 0)
+    if isinstance(every, str) or int(every) != every or every < 1:
+        raise ValueError("checkpoint_every: None, an int >= 1 or 'sqrt'")
+    return lambda steps: model.checkpoint_adjoint(int(every), steps), lambda: model.checkpoint_adjoint(0, 0)
+
+
 def singular_values(model, steps, iters, start, save=None, restore=None):
     """Power iteration on T^T T in the L2 (enstrophy) norm on `model` (anything with set_tangent, tangent, record_adjoint, step,
     set_adjoint, adjoint_back, adjoint; save / restore: how its state is kept and put back, by default spectrum / set_spectrum,
@@ -462,7 +498,7 @@ def _orthonormal_rows(t, w):
     return q
 
 
-def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None):
+def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None, checkpoint_every=None):
     """Orthogonal (block power) iteration on T^T T in the L2 norm on `model` (anything with set_tangents, tangents, record_adjoint,
     step, set_adjoints, adjoint_back, adjoints; save / restore as in singular_values), T the tangent of `steps` steps from the model's
     current state: the k leading singular values and right singular vectors from one tangent subspace and one adjoint set of k.  V,
@@ -473,7 +509,9 @@ def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None
     on the device tensors) is the next V.  No field crosses to the host: the Gram matrix alone is read, once per iteration.  Returns
     (sigma float64 [iters, k] numpy, the final V float32 [k, nx, ny] tensor, row i converging to the i-th right singular vector).
     The model is left as singular_values leaves it: at its starting state, the tape freed; the tangent set holds the last V it
-    stepped and the adjoint set the last sweep.  Convergence of sigma_i goes like (sigma_(k+1) / sigma_i)^(2 iters)."""
+    stepped and the adjoint set the last sweep.  Convergence of sigma_i goes like (sigma_(k+1) / sigma_i)^(2 iters).  checkpoint_every:
+    None keeps the full tape of `steps` steps; an int K or "sqrt" keeps checkpoints instead (adjoint_window; checkpoint_adjoint on the
+    model): the tangent subspace rides the forward run and not the steps a sweep takes again, and sigma and V are the same bits."""
     if steps < 1 or iters < 1:
         raise ValueError("singular_vectors: steps and iters must be >= 1")
     if int(k) != k or not 1 <= k <= min(TANGENTS_MAX, ADJOINTS_MAX):
@@ -482,21 +520,22 @@ def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None
     if start is not None:
         if not hasattr(start, "shape") or len(start.shape) != 3 or int(start.shape[0]) != k:
             raise ValueError("singular_vectors: start must be [k, nx, ny]")
-    t = model.torch
+    t, dev = model.torch, _device(model)
     save, restore = save or model.spectrum, restore or model.set_spectrum
+    record_on, record_off = adjoint_window(model, checkpoint_every)
     if start is None:
-        gen = t.Generator(device="cuda")
+        gen = t.Generator(device=dev)
         gen.manual_seed(SV_SEED)
-        v = t.randn((k,) + tuple(model._shape), generator=gen, dtype=t.float64, device="cuda")
+        v = t.randn((k,) + tuple(model._shape), generator=gen, dtype=t.float64, device=dev)
     else:
         if isinstance(start, np.ndarray):
             start = t.from_numpy(np.ascontiguousarray(start, dtype=np.float64))
-        v = start.cuda().double()
+        v = start.to(dev).double()
     shape = tuple(v.shape)
     v = _orthonormal_rows(t, v.reshape(k, -1))
     z0 = save()
     sig = np.empty((iters, k))
-    model.record_adjoint(steps)
+    record_on(steps)
     try:
         for it in range(iters):
             restore(z0)
@@ -507,13 +546,13 @@ def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None
             w, e = np.linalg.eigh((u @ u.T).cpu().numpy())
             order = np.argsort(w)[::-1]
             sig[it] = np.sqrt(np.maximum(w[order], 0.0))
-            rot = t.from_numpy(np.ascontiguousarray(e[:, order].T)).cuda()
+            rot = t.from_numpy(np.ascontiguousarray(e[:, order].T)).to(dev)
             model.set_adjoints(u32)
             model.adjoint_back(steps)
             v = _orthonormal_rows(t, rot @ model.adjoints().double().reshape(k, -1))
         restore(z0)
     finally:
-        model.record_adjoint(0)
+        record_off()
     return sig, v.float().reshape(shape)
 
 
@@ -575,7 +614,7 @@ class Observations:
         return int(self.xy.shape[0])
 
 
-def fourdvar(model, z0, obs, background=None):
+def fourdvar(model, z0, obs, background=None, checkpoint_every=None):
     """(J, grad) of the 4D-Var cost of the initial vorticity z0 (an [nx, ny] field, numpy or torch; it is set as float32) on `model`
     (anything with set_vort, record_adjoint, step, observe, obs_misfit, set_adjoint, adjoint_add_obs, adjoint_back, adjoint):
       J = 1/2 sum over the sets of obs and their points of (H zeta(step) - y)^2 / sigma^2   (+ 1/2 |z0 - zb|^2 / sigma_b^2),
@@ -585,23 +624,27 @@ def fourdvar(model, z0, obs, background=None):
     adjoint_add_obs for every set of that time, adjoint_back to the time before, sets at step 0 included; grad is what is left in lam,
     float64 [nx, ny] on the GPU.  No field crosses to the host; J, a float, is read once at the end.  Tape memory: T x 4 half spectra
     (4 nx (ny/2 + 1) 8 bytes per step, 271 MB per step at 4096^2); where record_adjoint cannot allocate it, its FftBaroError is raised
-    and nothing stays allocated (windows that do not fit would need checkpointing, which this does not do).  The tape is freed at the
-    end, whatever happens; a tape that was on before is gone.  The model is left at step T of the run from z0, with lam = grad's
-    float32 form set."""
-    t = model.torch
+    and nothing stays allocated.  A window that does not fit is what checkpoint_every is for: an int K keeps a checkpoint every K
+    steps and a tape segment of K steps instead (checkpoint_adjoint(K, T): ceil(T / K) + 4 K + 1 half spectra), "sqrt" takes K =
+    checkpoint_every(T), about 4 sqrt(T) half spectra; the piecewise sweeps between the observation times fill the segment again
+    from the checkpoints, one more forward step per backward step, and J and grad are the same bits as with the full tape.  The record
+    is freed at the end, whatever happens; one that was on before is gone.  The model is left at step T of the run from z0, with
+    lam = grad's float32 form set."""
+    t, dev = model.torch, _device(model)
     obs = list(obs)
     if not obs:
         raise ValueError("fourdvar: no observations")
+    record_on, record_off = adjoint_window(model, checkpoint_every)
     if isinstance(z0, np.ndarray):
         z0 = t.from_numpy(np.ascontiguousarray(z0))
-    z0 = z0.cuda()
+    z0 = z0.to(dev)
     times = sorted(set(o.step for o in obs))
-    cost = t.zeros(1, dtype=t.float64, device="cuda")
+    cost = t.zeros(1, dtype=t.float64, device=dev)
     res = {}
     try:
         model.set_vort(z0.float().contiguous())
         if times[-1]:
-            model.record_adjoint(times[-1])
+            record_on(times[-1])
         at = 0
         for when in times:
             model.step(when - at)
@@ -609,7 +652,7 @@ def fourdvar(model, z0, obs, background=None):
             for k, o in enumerate(obs):
                 if o.step == when:
                     res[k] = model.obs_misfit(model.observe(o.kind, o.xy), o.y, o.sigma, cost, check=False)
-        model.set_adjoint(t.zeros(tuple(z0.shape), dtype=t.float32, device="cuda"))
+        model.set_adjoint(t.zeros(tuple(z0.shape), dtype=t.float32, device=dev))
         for when, before in zip(times[::-1], times[-2::-1] + [0]):
             for k, o in enumerate(obs):
                 if o.step == when:
@@ -617,34 +660,36 @@ def fourdvar(model, z0, obs, background=None):
             model.adjoint_back(when - before)
         grad = model.adjoint().double()
     finally:
-        model.record_adjoint(0)
+        record_off()
     if background is not None:
         zb, sb = background
         if isinstance(zb, np.ndarray):
             zb = t.from_numpy(np.ascontiguousarray(zb))
-        d = z0.double() - zb.cuda().double()
+        d = z0.double() - zb.to(dev).double()
         cost += 0.5 * (d * d).sum() / float(sb) ** 2
         grad = grad + d / float(sb) ** 2
     return float(cost.item()), grad
 
 
-def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, shrink=0.5, max_backtracks=25):
+def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, shrink=0.5, max_backtracks=25, checkpoint_every=None):
     """Minimises model.fourdvar(z, obs, background) -> (J, grad) over the initial field z from z0 by L-BFGS (the two-loop recursion over
     the last `history` pairs) with a backtracking Armijo line search: a step t d is accepted when J(z + t d) <= J(z) + armijo t <grad, d>,
     t from 1 (the first iteration: from the step 2 J / |grad|^2 along -grad, the exact minimiser of a one-dimensional quadratic
     that touches zero), times `shrink` per rejection, at most max_backtracks times.  Host logic on float64 tensors wherever z0 lives
     (the GPU for the engine; anything with a fourdvar will do).  It stops after `iters` accepted iterations, or at the first whose
     line search finds no acceptable step, or when the gradient is zero.  Returns (z, J_history, evaluations): the final field, float64;
-    J at the start and after every accepted iteration (it falls at every one); the number of fourdvar calls."""
+    J at the start and after every accepted iteration (it falls at every one); the number of fourdvar calls.  checkpoint_every, where
+    it is not None, is handed to every model.fourdvar call (fourdvar(): windows whose full tape does not fit)."""
     t = model.torch
     if iters < 0 or history < 1:
         raise ValueError("fit_initial: iters must be >= 0, history >= 1")
     if isinstance(z0, np.ndarray):
         z0 = t.from_numpy(np.ascontiguousarray(z0))
     x = z0.double().clone()
+    how = {} if checkpoint_every is None else {"checkpoint_every": checkpoint_every}
 
     def evaluate(z):
-        J, g = model.fourdvar(z, obs, background)
+        J, g = model.fourdvar(z, obs, background, **how)
         return float(J), g.double().to(x.device)
 
     def dot(a, b):
@@ -1185,6 +1230,22 @@ class ModelSurface:
 
     def adjoint_recorded(self): return self._count("adjoint_recorded")
 
+    def checkpoint_adjoint(self, every, max_steps=0):
+        """Adjoint checkpointing on (every >= 1: a checkpoint of the state before every step of the window whose index is a multiple of
+        `every`, a tape segment of `every` steps, a window of at most max_steps steps) or off (every = 0, everything freed); it and
+        record_adjoint replace each other, and either way the window starts empty.  The forward run writes no tape; adjoint_back fills
+        the segment again from the checkpoints, one more forward step per backward step, and gives the bits of the full tape.  Memory:
+        ceil(max_steps / every) + 4 every + 1 half spectra (checkpoint_every(max_steps) minimises it) where record_adjoint takes
+        4 max_steps.  One rank only, as record_adjoint."""
+        self._call("adjoint_checkpoint", int(every), int(max_steps))
+
+    def adjoint_checkpoints(self):
+        """(every, max_steps, checkpoints, replayed): the mode's two settings, the checkpoints the window holds and the steps taken
+        again by sweeps since it began (a window swept completely has replayed its own length); all 0 while the mode is off."""
+        a, b, c, d = C.c_int(), C.c_int(), C.c_int(), C.c_longlong()
+        self._call("adjoint_checkpoint_info", C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+        return a.value, b.value, c.value, d.value
+
     def set_adjoint(self, lam):
         """Sets the adjoint variable, a field (the gradient of a scalar of the state with respect to the vorticity, at the time of the
         newest recorded step); lam=None removes it."""
@@ -1225,12 +1286,13 @@ class ModelSurface:
         self._hand("get_adjoints", out)
         return out
 
-    def singular_vectors(self, steps, k, iters, start=None):
+    def singular_vectors(self, steps, k, iters, start=None, checkpoint_every=None):
         """(sigma [iters, k], V [k, nx, ny]): the k leading singular values and right singular vectors of the tangent over `steps`
         steps from the current state, by block power iteration with a tangent subspace and an adjoint set of k (singular_vectors());
-        the state is kept and put back through _STATE."""
+        the state is kept and put back through _STATE.  checkpoint_every: None the full tape, an int K or "sqrt" checkpoints."""
         self._one_rank("adjoint_record", int(steps))
-        return singular_vectors(self, steps, k, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]))
+        return singular_vectors(self, steps, k, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]),
+                                checkpoint_every=checkpoint_every)
 
     def scatter(self, w, xy):
         """The transpose of sample(): n point values w, float64 [n], at the positions xy, float64 [n, 2], spread onto the grid with the
@@ -1280,19 +1342,20 @@ class ModelSurface:
         a = particles_dev(t, xy)
         self._hand("adjoint_add_obs", obs_kind(kind), a, values_dev(t, w, int(a.shape[0]), "w"), int(a.shape[0]))
 
-    def fourdvar(self, z0, obs, background=None):
+    def fourdvar(self, z0, obs, background=None, checkpoint_every=None):
         """(J, grad): the 4D-Var cost of the initial vorticity z0 against the Observations in obs, and its gradient with respect to z0,
-        float64 [nx, ny] on the GPU (fourdvar()).  The tape takes T x 4 half spectra, T the last observation step."""
+        float64 [nx, ny] on the GPU (fourdvar()).  The tape takes T x 4 half spectra, T the last observation step; with
+        checkpoint_every = K (or "sqrt": checkpoint_every(T)) ceil(T / K) + 4 K + 1 of them, for windows whose tape does not fit."""
         self._one_rank("adjoint_record", 1)
-        return fourdvar(self, z0, obs, background)
+        return fourdvar(self, z0, obs, background, checkpoint_every)
 
-    def fit_initial(self, z0, obs, iters, background=None, history=8):
+    def fit_initial(self, z0, obs, iters, background=None, history=8, checkpoint_every=None):
         """(z, J_history, evaluations): L-BFGS on fourdvar from the first guess z0 (fit_initial()); z0 goes to the GPU first, so the
-        iterate, the gradients and the memory of the recursion stay there."""
+        iterate, the gradients and the memory of the recursion stay there.  checkpoint_every: as fourdvar's."""
         self._one_rank("adjoint_record", 1)
         if isinstance(z0, np.ndarray):
             z0 = self.torch.from_numpy(np.ascontiguousarray(z0))
-        return fit_initial(self, z0.cuda(), obs, iters, background, history)
+        return fit_initial(self, z0.cuda(), obs, iters, background, history, checkpoint_every=checkpoint_every)
 
 
 class Model(ModelSurface):

@@ -722,10 +722,24 @@ extern "C" int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n,
 
 // ---- the adjoint model (kernels: fb_adjoint.h) ----
 // One GPU or a slab of one rank: one column group, no exchange (as the particles).
+// (the full tape of fb_model_adjoint_record, or the segment, the checkpoints and the live copy of fb_model_adjoint_checkpoint: one
+// mode at a time, and either call frees what the other held)
 static void adjoint_tape_free(fb_model *m)
 {
-    if (m->ad_tape) { hipFree(m->ad_tape); m->ad_tape = nullptr; }
-    m->ad_depth = m->ad_fill = 0;
+    cf **arr[] = {&m->ad_tape, &m->ck_store, &m->ck_live};
+    for (cf **p : arr) if (*p) { hipFree(*p); *p = nullptr; }
+    m->ad_depth = m->ck_every = m->ck_max = 0;
+    m->ad_on = m->ck_replay = false;
+    adjoint_window_empty(m);
+}
+
+static size_t checkpoint_slots(const fb_model *m) { return m->ck_every ? ((size_t)m->ck_max + m->ck_every - 1) / m->ck_every : 0; }
+
+// the tape (4 half spectra per step of its depth), and under checkpointing the checkpoints and the live copy (one each)
+static size_t adjoint_tape_bytes(const fb_model *m)
+{
+    const size_t n = grp_elems(m->c, m->c->grp[0]);
+    return ((size_t)m->ad_depth * 4 + (m->ck_every ? checkpoint_slots(m) + 1 : 0)) * n * sizeof(cf);
 }
 
 // the variables of a sweep's chunk, and the real fields of the product pass, for a set of `count`: the one keeps k_adjoint_prod's five
@@ -773,6 +787,88 @@ static int adjoint_record(fb_model *m, int depth)
         return fail(FB_ENOMEM, "the adjoint's tape: allocation failed");
     }
     m->ad_depth = depth;
+    m->ad_on = true;
+    return FB_OK;
+}
+
+// Checkpointing on (every >= 1: a tape segment of `every` steps, room for ceil(max_steps / every) checkpoints and the live copy) or
+// off (every == 0); either way the window starts empty, and a full tape that was on is gone.  A checkpoint is the state arrays of
+// column group 0 as they are (ZA: the 3-pass layout, the tile-major one or k_col_full's, pad columns and frozen columns included):
+// a state put back by a copy and the priming pass continues bit for bit like the state that was stepped to ("Adjoint
+// checkpointing"), so the derivative fields need not be kept.  The forward run stashes nothing, so the captured step stays valid;
+// it is dropped all the same, as fb_model_adjoint_record does, so that both modes start from one place.
+static int adjoint_checkpoint(fb_model *m, int every, int max_steps)
+{
+    fb_ctx *c = m->c;
+    int rc;
+    if ((rc = beside_begin(m, m->ad_tape != nullptr))) return rc;
+    adjoint_tape_free(m);
+    if (every == 0) return FB_OK;
+    const size_t n = grp_elems(c, c->grp[0]);
+    m->ck_every = every; m->ck_max = max_steps;
+    if (hipMalloc((void **)&m->ad_tape, (size_t)every * 4 * n * sizeof(cf)) != hipSuccess) m->ad_tape = nullptr;
+    else if (hipMalloc((void **)&m->ck_store, checkpoint_slots(m) * n * sizeof(cf)) != hipSuccess) m->ck_store = nullptr;
+    else if (hipMalloc((void **)&m->ck_live, n * sizeof(cf)) != hipSuccess) m->ck_live = nullptr;
+    if (!m->ck_live) {
+        (void)hipGetLastError();
+        adjoint_tape_free(m);
+        return fail(FB_ENOMEM, "the adjoint's tape segment, checkpoints and live copy: allocation failed");
+    }
+    m->ad_depth = every;
+    return FB_OK;
+}
+
+// run_steps, before a piece of at most *nsteps steps of a checkpointed window: where the piece starts on a multiple of ck_every the
+// state goes into the next checkpoint (device to device on the context stream; the host waits for nothing), and the piece is cut at
+// the next multiple.  step_refusals has seen to it that the window has room.
+static int checkpoint_take(fb_model *m, int *nsteps)
+{
+    fb_ctx *c = m->c;
+    const size_t n = grp_elems(c, c->grp[0]);
+    const int into = m->ck_done % m->ck_every;
+    if (into == 0) {
+        HIPCHK(hipMemcpyAsync(m->ck_store + (size_t)(m->ck_done / m->ck_every) * n, m->gb[0].ZA, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        m->ck_n = m->ck_done / m->ck_every + 1;
+    }
+    if (*nsteps > m->ck_every - into) *nsteps = m->ck_every - into;
+    return FB_OK;
+}
+
+// A kept state (a checkpoint, the live copy) back into the state arrays, as fb_model_set_spectrum puts one back after its relayout:
+// the derivative fields come from the priming pass (k_col_full: the PRIME launch here; the three-kernel path: model_prime at the next
+// step), and that step is an eager one.  The window stays as it is.
+static int checkpoint_restore(fb_model *m, const cf *from)
+{
+    fb_ctx *c = m->c;
+    HIPCHK(hipMemcpyAsync(m->gb[0].ZA, from, grp_elems(c, c->grp[0]) * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+    m->warmed = false;
+    m->primed = 0;
+    if (m->xpass == XP_COLS) return FB_OK;
+    if (int rc = launch_col_full(m, 4)) return rc;
+    m->primed = 2;
+    return FB_OK;
+}
+
+// The tape segment filled again for the sweep: the segment that holds the newest unswept step, from its checkpoint to that step, with
+// the recording on.  The steps are the eager ones of either flow and advance the vorticity alone (beside_stage, ck_replay): no
+// tracer, particles, tangent; m->steps is run_steps' to count.  *saved: the live state has been put aside (the first refill of a call).
+static int checkpoint_refill(fb_model *m, fb_slab *s, bool *saved)
+{
+    fb_ctx *c = m->c;
+    const size_t n = grp_elems(c, c->grp[0]);
+    int rc;
+    if (!*saved) {
+        HIPCHK(hipMemcpyAsync(m->ck_live, m->gb[0].ZA, n * sizeof(cf), hipMemcpyDeviceToDevice, c->stream));
+        *saved = true;
+    }
+    const int seg = (m->ck_left - 1) / m->ck_every, count = m->ck_left - seg * m->ck_every;
+    if ((rc = checkpoint_restore(m, m->ck_store + (size_t)seg * n))) return rc;
+    m->ad_fill = 0;
+    m->ad_on = m->ck_replay = true;
+    rc = s ? slab_steps(s, count) : model_step_impl(m, count, nullptr);
+    m->ad_on = m->ck_replay = false;
+    if (rc) { m->ad_fill = 0; return rc; }
+    m->ck_replayed += count;
     return FB_OK;
 }
 
@@ -910,14 +1006,20 @@ static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
     fb_ctx *c = m->c;
     const size_t n = grp_elems(c, c->grp[0]);
     int rc;
+    bool saved = false;
     if ((rc = advect_workspace(m, s))) return rc;
-    for (int k = 0; k < nsteps; ++k) {
+    for (int k = 0; k < nsteps && !rc; ++k) {
+        // a checkpointed window: an empty tape segment is filled again first; what is left of one stays for the next call
+        if (m->ck_every && !m->ad_fill && (rc = checkpoint_refill(m, s, &saved))) break;
         const cf *step = m->ad_tape + (size_t)(m->ad_fill - 1) * 4 * n;
-        for (int stage = 3; stage >= 0; --stage)
-            if ((rc = m->ad_n == 1 ? adjoint_stage(m, stage, step + (size_t)stage * n) : adjoint_stage_set(m, stage, step + (size_t)stage * n))) return rc;
+        for (int stage = 3; stage >= 0 && !rc; --stage)
+            rc = m->ad_n == 1 ? adjoint_stage(m, stage, step + (size_t)stage * n) : adjoint_stage_set(m, stage, step + (size_t)stage * n);
+        if (rc) break;
         --m->ad_fill;
+        if (m->ck_every) { --m->ck_left; m->ck_swept = true; }
     }
-    return FB_OK;
+    if (saved) { const int back = checkpoint_restore(m, m->ck_live); if (!rc) rc = back; }    // the live state is back before the call returns, failed or not
+    return rc;
 }
 
 // a slab of one rank goes through the same code; on several ranks the adjoint model is refused
@@ -932,11 +1034,50 @@ static int adjoint_record(const Call &k, int depth)
 extern "C" int fb_model_adjoint_record(fb_model *m, int depth) { return adjoint_record(on_model("fb_model_adjoint_record", m), depth); }
 extern "C" int fb_slab_adjoint_record(fb_slab *s, int depth) { return adjoint_record(on_slab("fb_slab_adjoint_record", s), depth); }
 
+static int adjoint_checkpoint(const Call &k, int every, int max_steps)
+{
+    if (every < 0 || every > (1 << 20)) return refuse(k, "every outside [0, 2^20]");
+    if (every && max_steps < 1) return refuse(k, "max_steps < 1");
+    if (every && ((long long)max_steps + every - 1) / every > (1 << 20)) return refuse(k, "more than 2^20 checkpoints (ceil(max_steps / every))");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    return adjoint_checkpoint(k.m, every, max_steps);
+}
+extern "C" int fb_model_adjoint_checkpoint(fb_model *m, int every, int max_steps)
+{
+    return adjoint_checkpoint(on_model("fb_model_adjoint_checkpoint", m), every, max_steps);
+}
+extern "C" int fb_slab_adjoint_checkpoint(fb_slab *s, int every, int max_steps)
+{
+    return adjoint_checkpoint(on_slab("fb_slab_adjoint_checkpoint", s), every, max_steps);
+}
+
+// (each output may be NULL; all 0 while checkpointing is off: not a refusal)
+static int adjoint_checkpoint_info(const Call &k, int *every, int *max_steps, int *checkpoints, long long *replayed)
+{
+    if (int rc = enter(k, ADJOINT)) return rc;
+    if (every) *every = k.m->ck_every;
+    if (max_steps) *max_steps = k.m->ck_max;
+    if (checkpoints) *checkpoints = k.m->ck_n;
+    if (replayed) *replayed = k.m->ck_replayed;
+    return FB_OK;
+}
+extern "C" int fb_model_adjoint_checkpoint_info(fb_model *m, int *every, int *max_steps, int *checkpoints, long long *replayed)
+{
+    return adjoint_checkpoint_info(on_model("fb_model_adjoint_checkpoint_info", m), every, max_steps, checkpoints, replayed);
+}
+extern "C" int fb_slab_adjoint_checkpoint_info(fb_slab *s, int *every, int *max_steps, int *checkpoints, long long *replayed)
+{
+    return adjoint_checkpoint_info(on_slab("fb_slab_adjoint_checkpoint_info", s), every, max_steps, checkpoints, replayed);
+}
+
+// the steps that a sweep can still pop: those on the tape, or under checkpointing the window's steps not yet swept
+static int adjoint_unswept(const fb_model *m) { return m->ck_every ? m->ck_left : m->ad_fill; }
+
 static int adjoint_recorded(const Call &k, int *n)
 {
     if (!n) return refuse(k, "NULL output");
     if (int rc = enter(k, ADJOINT)) return rc;
-    *n = k.m->ad_fill;
+    *n = adjoint_unswept(k.m);
     return FB_OK;
 }
 extern "C" int fb_model_adjoint_recorded(fb_model *m, int *n) { return adjoint_recorded(on_model("fb_model_adjoint_recorded", m), n); }
@@ -987,7 +1128,7 @@ static int adjoint_back(const Call &k, int nsteps)
 {
     if (nsteps < 0) return refuse(k, "nsteps < 0");
     if (int rc = enter(k, ADJOINT_SET)) return rc;
-    if (nsteps > k.m->ad_fill) return refuse(k, std::to_string(nsteps) + " steps asked for, " + std::to_string(k.m->ad_fill) + " recorded");
+    if (nsteps > adjoint_unswept(k.m)) return refuse(k, std::to_string(nsteps) + " steps asked for, " + std::to_string(adjoint_unswept(k.m)) + " recorded");
     return adjoint_back(k.m, k.s, nsteps);
 }
 extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps) { return adjoint_back(on_model("fb_model_adjoint_back", m), nsteps); }
@@ -1125,16 +1266,17 @@ extern "C" int fb_slab_adjoint_add_obs(fb_slab *s, int kind, const double *d_xy,
 static int beside_stage(fb_model *m, fb_slab *s, int stage)
 {
     int rc;
+    if (m->ck_replay) return adjoint_stash(m, stage);       // a segment of a checkpointed window run again: the vorticity alone moves
     if (m->tracer && (rc = tracer_stage(m, s, stage))) return rc;
     if (m->pt_n && (rc = particle_stage(m, stage))) return rc;
     if (m->tg_n && (rc = tangent_stage(m, s, stage))) return rc;
-    if (m->ad_depth && (rc = adjoint_stash(m, stage))) return rc;
+    if (m->ad_on && (rc = adjoint_stash(m, stage))) return rc;
     return FB_OK;
 }
 
 static void beside_step_done(fb_model *m)
 {
-    if (m->ad_depth) ++m->ad_fill;                          // the four stage states of this step are on the tape
+    if (m->ad_on) ++m->ad_fill;                             // the four stage states of this step are on the tape
 }
 
 static void beside_free_all(fb_model *m)

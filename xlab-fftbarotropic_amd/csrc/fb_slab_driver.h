@@ -380,11 +380,20 @@ static int slab_steps(fb_slab *s, int nsteps)
 
 // the step pair: fb_model_step (hipGraph replay where it applies, model_steps) and fb_slab_step
 // (counted here, not where a step is launched: a captured step is launched once and replayed)
+// Under adjoint checkpointing the call is split at the checkpoint boundaries: checkpoint_take (fb_beside.h) copies the state where a
+// piece starts on one and cuts the piece at the next, and each piece is stepped as any call is, the captured step replayed.
 static int run_steps(const Call &k, int nsteps)
 {
-    const int rc = nsteps == 0 ? FB_OK : k.s ? slab_steps(k.s, nsteps) : model_steps(k.m, nsteps);
-    if (!rc) k.m->steps += nsteps;
-    return rc;
+    fb_model *m = k.m;
+    for (int left = nsteps; left > 0; ) {
+        int n = left;
+        if (m->ck_every) if (int rc = checkpoint_take(m, &n)) return rc;
+        if (int rc = k.s ? slab_steps(k.s, n) : model_steps(m, n)) return rc;
+        m->steps += n;
+        if (m->ck_every) { m->ck_done += n; m->ck_left += n; }
+        left -= n;
+    }
+    return FB_OK;
 }
 static int step(const Call &k, int nsteps)
 {

@@ -1085,6 +1085,16 @@ struct fb_model {
     // 4 C products), and for a set the C spectra of the chunk's mu~ (ad_spec); NULL and ad_n == 0 without, and ad_n alone says
     // whether an adjoint is set
     cf *ad_tape; int ad_depth, ad_fill;
+    // ad_on: the steps taken now stash their stage states (always while fb_model_adjoint_record's tape is on; under checkpointing only
+    // while a segment is run again).  Adjoint checkpointing (fb_model_adjoint_checkpoint; host side in fb_beside.h): the tape is one
+    // segment of ck_every steps, ck_store holds room for ceil(ck_max / ck_every) states of column group 0 as the state arrays hold them
+    // (ZA), ck_n of them taken, ck_live one more for the live state during a sweep.  The window: ck_done steps taken forward, ck_left
+    // of them not yet swept (ad_fill of those are on the tape), ck_swept once a sweep has popped one, ck_replayed steps run again
+    // since it began; ck_replay: the step under way is such a run, and advances the vorticity alone.  All 0 / NULL while it is off
+    bool ad_on, ck_swept, ck_replay;
+    int ck_every, ck_max, ck_n, ck_done, ck_left;
+    long long ck_replayed;
+    cf *ck_store, *ck_live;
     Beside ad[FB_ADJOINTS_MAX];
     int ad_n;
     float *ad_real;
@@ -1152,19 +1162,30 @@ static int beside_stage(fb_model *m, fb_slab *s, int stage);            // at th
 static void beside_step_done(fb_model *m);                              // after the step's fourth stage
 static void beside_free_all(fb_model *m);
 static size_t adjoint_bytes(const fb_model *m);                         // what fb_model_info counts for the adjoint variables
+static size_t adjoint_tape_bytes(const fb_model *m);                    // and for the tape, or the tape segment, the checkpoints and the live copy
+static int checkpoint_take(fb_model *m, int *nsteps);                   // run_steps under checkpointing, before every piece of a step call
 
 static void model_drop_graph(fb_model *m)
 {
     if (m->graph_exec) { hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
 }
 
+// nothing recorded, no checkpoint taken, no step of a checkpointed window counted or swept (the arrays stay)
+static void adjoint_window_empty(fb_model *m)
+{
+    m->ad_fill = 0;
+    m->ck_n = m->ck_done = m->ck_left = 0;
+    m->ck_swept = false;
+    m->ck_replayed = 0;
+}
+
 // the vorticity is replaced (state_in, fb_model_set_spectrum): the next fb_model_step starts with an eager (priming) step, and the
-// adjoint's tape belonged to the state that went
+// adjoint's tape, or its checkpointed window, belonged to the state that went
 static void state_replaced(fb_model *m)
 {
     m->warmed = false;
     m->primed = 0;
-    m->ad_fill = 0;
+    adjoint_window_empty(m);
 }
 
 extern "C" int fb_model_destroy(fb_model *m)
@@ -1208,7 +1229,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
-        n += adjoint_bytes(m);                                                                                              // the adjoint variables and their workspace
+        n += adjoint_bytes(m) + adjoint_tape_bytes(m);                                                                      // the adjoint variables and their workspace; the tape
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
         if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
         *hbm = n;
@@ -1223,6 +1244,9 @@ static int set_source(const Call &k, const float *d_src)
     if (int rc = enter(k)) return rc;
     fb_model *m = k.m;
     fb_ctx *c = m->c;
+    // (the model has no clock: a source fixed over the window is run again exactly, another one is not)
+    if (m->ck_every && m->ck_left)
+        return refuse(k, "the checkpointed window holds " + std::to_string(m->ck_left) + " steps that would be run again under another source: sweep them or start a new window");
     const size_t n = (size_t)c->XL * c->ny * sizeof(float);       // the caller's local rows
     // NULL: no source.  The row kernels test m->src alone, so the row flags (XL ints) are kept for the next source.
     if (!d_src) { if (m->src) { HIPCHK(hipStreamSynchronize(c->stream)); hipFree(m->src); m->src = nullptr; } return FB_OK; }
@@ -1358,13 +1382,18 @@ struct StepProf {
 #define PROF_BEGIN(cls) do { if (prof && prof->begin(cls)) return fail(FB_EHIP, "event record failed"); } while (0)
 #define PROF_END(cls) do { if (prof && prof->end(cls)) return fail(FB_EHIP, "event record failed"); } while (0)
 
-// what a step call refuses before anything is launched: a bad count, the handle (enter), a call that would overrun the adjoint's tape
+// what a step call refuses before anything is launched: a bad count, the handle (enter), a call that would overrun the adjoint's tape,
+// or under checkpointing pass the window's max_steps or follow a sweep of it
 static int step_refusals(const Call &k, int nsteps)
 {
     if (nsteps < 0) return refuse(k, "bad argument: nsteps < 0");
     if (int rc = enter(k, NEED_TRANSPORT)) return rc;
     const fb_model *m = k.m;
-    if (m->ad_depth && nsteps > m->ad_depth - m->ad_fill)
+    if (m->ck_every) {
+        if (nsteps > 0 && m->ck_swept) return refuse(k, "the window has been swept: start a new one (fb_model_set_vort, fb_model_set_spectrum, fb_model_adjoint_checkpoint)");
+        if (nsteps > m->ck_max - m->ck_done)
+            return refuse(k, "the checkpointed window has room for " + std::to_string(m->ck_max - m->ck_done) + " more steps (fb_model_adjoint_checkpoint)");
+    } else if (m->ad_on && nsteps > m->ad_depth - m->ad_fill)
         return refuse(k, "the adjoint's tape has room for " + std::to_string(m->ad_depth - m->ad_fill) + " more steps (fb_model_adjoint_record)");
     return FB_OK;
 }
@@ -1422,8 +1451,9 @@ static int model_steps(fb_model *m, int nsteps)
     fb_ctx *c = m->c;
     // graph replay needs a capturable (non-null) stream, a primed pipeline and at least one eager step behind
     // us (kernel attributes are set on first launch); anything else runs eagerly.  So does a model that records the adjoint's tape:
-    // every step writes another slot, which a captured step would bake in
-    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2 || m->ad_depth) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
+    // every step writes another slot, which a captured step would bake in (ad_on: recording now; under checkpointing the forward
+    // run writes no slot, so the tape segment that is allocated does not keep it from replaying the captured step)
+    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2 || m->ad_on) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
     int rc;
     if (!m->warmed) { if ((rc = model_step_impl(m, 1, nullptr))) return rc; m->warmed = true; --nsteps; }
     if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream)) model_drop_graph(m);
@@ -1450,6 +1480,7 @@ extern "C" int fb_model_profile_steps(fb_model *m, int nsteps, float *ms_sum, in
     if (!ms_sum || !launches) return refuse(k, "NULL output");
     int rc;
     if ((rc = step_refusals(k, nsteps))) return rc;
+    if (m->ck_every) return refuse(k, "not while adjoint checkpointing is on: the profiled steps would take no checkpoint (fb_model_adjoint_checkpoint)");
     StepProf prof; prof.stream = m->c->stream;
     rc = model_step_impl(m, nsteps, &prof);
     if (!rc) m->steps += nsteps;
