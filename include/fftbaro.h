@@ -248,6 +248,34 @@ int fb_model_sample(fb_model *m, const float *d_field, const double *d_xy, int n
 int fb_model_set_particle_deformation(fb_model *m, int on);
 int fb_model_get_particle_deformation(fb_model *m, double *d_F, double *elapsed);
 int fb_model_particle_stretching(fb_model *m, const double *d_F, int n, double *d_out);
+/* Lagrangian observations: the adjoint of the particle step (no reference counterpart).  With Xb the gradient of a scalar with respect
+ * to the particles' positions at the time of the newest recorded step, and lam the adjoint variable of fb_model_set_adjoint,
+ * fb_model_adjoint_back applies, while a particle adjoint is set, the transpose of the COUPLED discrete step (vorticity and particles):
+ * per step, with x_s the position stage s started from and A_s = [[u_x, u_y], [v_x, v_y]] the gradient of the interpolant of the stage's
+ * velocity at x_s (as the deformation gradient takes it; on a cell face the cell to the right), the stages in the order 3, 2, 1, 0:
+ *   p = dt/6 Xb;           q = A_3^T p; acc = Xb + q        p = dt/3 Xb + dt q;     q = A_2^T p; acc += q
+ *   p = dt/3 Xb + dt/2 q;  q = A_1^T p; acc += q            p = dt/6 Xb + dt/2 q;   q = A_0^T p; Xb <- acc + q
+ * and the stage's transpose tendency of lam gains ( i ky r2c(S_u) - i kx r2c(S_v) ) / lap ((0, 0): / 1), S_u and S_v the transposes of
+ * the interpolation applied to p_x and p_y at x_s (fb_model_scatter's fixed-point scheme: lam and Xb are the same bits in any order
+ * of the particles).  The particles do not act on the flow, so Xb never depends on lam.  At the start of the window Xb equals F^T Xb(T)
+ * for lam(T) = 0, F the deformation gradient.  A particle whose position or Xb is not finite deposits nothing and ends with NaN in Xb.
+ * fb_model_particle_tape: depth >= 1 allocates room for depth steps x 4 stage positions (64 bytes per particle and step) and every
+ * step from then on records the positions its stages start from; depth == 0 frees it; either way it starts empty.  The positions, F,
+ * the vorticity, a tracer and the tangent are bit for bit what they are without.  While it is on fb_model_step steps eagerly (as
+ * while fb_model_adjoint_record's tape is on) and a call that would overrun it is refused before anything is launched.
+ * fb_model_set_vort, fb_model_set_spectrum and fb_model_set_particles empty it (another particle count, or NULL, frees it); it
+ * needs particles.  FB_ENOMEM leaves nothing allocated.  Under fb_model_adjoint_checkpoint it still holds the whole window: the
+ * segments that a sweep runs again move the vorticity alone.  fb_model_particle_tape_count: the steps on it and its depth (0, 0: none).
+ * fb_model_set_particle_adjoint: Xb from d_xbar, device float64 [n][2]; NULL removes it; fb_model_set_particles (a new set or NULL)
+ * removes it too.  fb_model_get_particle_adjoint: Xb into d_xbar.  While none is set fb_model_adjoint_back launches what it always has.
+ * One GPU or a slab of one rank, as the particles.  FB_EINVAL before any HIP call: depth outside [0, 2^20], a NULL output, a NULL
+ * model, no particles set, fb_model_get_particle_adjoint with none set; and for fb_model_adjoint_back while one is set: more steps
+ * than the particle tape holds, a set of several adjoint variables, a particle tape and an adjoint window that hold different
+ * numbers of steps. */
+int fb_model_particle_tape(fb_model *m, int depth);
+int fb_model_particle_tape_count(fb_model *m, int *count, int *depth);
+int fb_model_set_particle_adjoint(fb_model *m, const double *d_xbar);      /* NULL: remove it */
+int fb_model_get_particle_adjoint(fb_model *m, double *d_xbar);
 /* Tangent-linear model (no reference counterpart): a perturbation dz of the vorticity, a real [nx][ny] field, carried along the
  * evolving state by the linearisation of the DISCRETE step (not of the PDE), so that M(zeta + eps dz) - M(zeta) = eps T(dz) + O(eps^2)
  * for the step M itself.  fb_model_set_tangent takes the device field d_dz_real in as fb_model_set_vort takes the vorticity and keeps
@@ -639,6 +667,11 @@ int fb_slab_sample(fb_slab *s, const float *d_field, const double *d_xy, int n, 
 int fb_slab_set_particle_deformation(fb_slab *s, int on);
 int fb_slab_get_particle_deformation(fb_slab *s, double *d_F, double *elapsed);
 int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n, double *d_out);
+/* the particle tape and the particle adjoint (fb_model_particle_tape) on a slab of ONE rank, refused on world > 1 as the particles are */
+int fb_slab_particle_tape(fb_slab *s, int depth);
+int fb_slab_particle_tape_count(fb_slab *s, int *count, int *depth);
+int fb_slab_set_particle_adjoint(fb_slab *s, const double *d_xbar);
+int fb_slab_get_particle_adjoint(fb_slab *s, double *d_xbar);
 /* the vortex census (fb_model_census) on a slab of ONE rank: the same code, bit-equal labels.  On world > 1 it returns
  * FB_EUNSUPPORTED: a structure that crosses the ranks' row slabs needs a border merge over the ranks. */
 int fb_slab_census(fb_slab *s, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,

@@ -91,8 +91,11 @@ _OBS_PAIRS = {"scatter": [_vp, _vp, _ip, _vp], "observe": [_ip, _vp, _ip, _vp], 
 _ADJOINTS_PAIRS = {"set_adjoints": [_vp, _ip], "get_adjoints": [_vp], "adjoint_count": [_pip]}
 # adjoint checkpointing's pairs, likewise: the mode on and off, and what the window holds
 _CHECKPOINT_PAIRS = {"adjoint_checkpoint": [_ip, _ip], "adjoint_checkpoint_info": [_pip, _pip, _pip, C.POINTER(C.c_longlong)]}
+# the Lagrangian observations' pairs, likewise: the particle tape and the particle adjoint
+_LAGRANGIAN_PAIRS = {"particle_tape": [_ip], "particle_tape_count": [_pip, _pip], "set_particle_adjoint": [_vp], "get_particle_adjoint": [_vp]}
 for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
-                     + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items()) + list(_CHECKPOINT_PAIRS.items())):
+                     + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items()) + list(_CHECKPOINT_PAIRS.items())
+                     + list(_LAGRANGIAN_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -561,6 +564,10 @@ OBS_KINDS = {"vort": 0, "u": 1, "v": 2, "psi": 3}
 _SOME = (C.c_double * 2)()
 
 
+# the kind of an Observations set that holds drifter positions: no number of the C ABI, it never reaches observe or adjoint_add_obs
+POSITION = "position"
+
+
 def obs_kind(kind):
     """the C ABI's number of an observed quantity: "vort" | "u" | "v" | "psi" (an int is passed on for the engine to judge)"""
     if isinstance(kind, str):
@@ -590,31 +597,44 @@ class Observations:
     """One set of point observations of one kind at one time: `step` (int >= 0, counted from the start of the window), `kind` ("vort",
     "u", "v" or "psi"), `xy` float64 [n, 2] positions [m] (unwrapped), `y` float64 [n] the observed values, `sigma` their standard
     errors (None: 1; a number; or float64 [n]), every one positive and finite.  Numpy or torch in; everything held is a tensor on the
-    GPU after construction."""
+    GPU after construction.
+    kind "position" is Lagrangian data: `y` float64 [n, 2], the observed unwrapped positions of the n drifters that fourdvar is given as
+    `particles`, in their order; `xy` must be None; `sigma` None, a number or float64 [n], one per drifter for both components.  Held as
+    y flattened to [2 n] (x0, y0, x1, y1, ...) with sigma repeated per component: what obs_misfit takes."""
 
     def __init__(self, step, kind, xy, y, sigma=None):
         t = _torch()
         if int(step) != step or step < 0:
             raise ValueError("Observations: step must be an int >= 0")
-        obs_kind(kind)
         self.step, self.kind = int(step), kind
-        self.xy = particles_dev(t, xy)
-        n = int(self.xy.shape[0])
+        if kind == POSITION:
+            if xy is not None:
+                raise ValueError("Observations: kind 'position' takes xy=None (the drifters are fourdvar's particles)")
+            self.xy = None
+            y = particles_dev(t, y)
+            n = int(y.shape[0])
+        else:
+            obs_kind(kind)
+            self.xy = particles_dev(t, xy)
+            n = int(self.xy.shape[0])
         if n < 1 or n > PARTICLES_MAX:
             raise ValueError("Observations: 1 to 2^24 points")
-        self.y = values_dev(t, y, n, "y")
+        self.n = n
+        self.y = y.reshape(-1) if kind == POSITION else values_dev(t, y, n, "y")
         if sigma is None or np.isscalar(sigma):
             self.sigma = t.full((n,), 1.0 if sigma is None else float(sigma), dtype=t.float64, device="cuda")
         else:
             self.sigma = values_dev(t, sigma, n, "sigma")
         if not sigma_ok(self.sigma):
             raise ValueError("Observations: every sigma must be positive and finite")
+        if kind == POSITION:
+            self.sigma = self.sigma.repeat_interleave(2).contiguous()
 
     def __len__(self):
-        return int(self.xy.shape[0])
+        return self.n
 
 
-def fourdvar(model, z0, obs, background=None, checkpoint_every=None):
+def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=None):
     """(J, grad) of the 4D-Var cost of the initial vorticity z0 (an [nx, ny] field, numpy or torch; it is set as float32) on `model`
     (anything with set_vort, record_adjoint, step, observe, obs_misfit, set_adjoint, adjoint_add_obs, adjoint_back, adjoint):
       J = 1/2 sum over the sets of obs and their points of (H zeta(step) - y)^2 / sigma^2   (+ 1/2 |z0 - zb|^2 / sigma_b^2),
@@ -629,11 +649,25 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None):
     checkpoint_every(T), about 4 sqrt(T) half spectra; the piecewise sweeps between the observation times fill the segment again
     from the checkpoints, one more forward step per backward step, and J and grad are the same bits as with the full tape.  The record
     is freed at the end, whatever happens; one that was on before is gone.  The model is left at step T of the run from z0, with
-    lam = grad's float32 form set."""
+    lam = grad's float32 form set.
+    particles = xy0, float64 [n, 2]: the drifters' initial positions, set by set_particles after set_vort; sets of kind "position" then
+    add 1/2 sum |X(step) - y|^2 / sigma^2 over the drifters to J (obs_misfit on the flattened positions).  With such a set the particle
+    tape is on over the window (record_particles(T), 64 bytes per drifter and step, freed at the end with the field's), Xb starts at 0,
+    gains r at every set's time (get, add, set on the GPU) and is swept back with lam by adjoint_back; what is left in
+    model.particle_adjoint() is dJ/dX0, float64 [n, 2], as grad's float32 form is left in lam.  A "position" set without particles is a
+    ValueError.  With particles=None and no such set nothing here differs from what it was."""
     t, dev = model.torch, _device(model)
     obs = list(obs)
     if not obs:
         raise ValueError("fourdvar: no observations")
+    drift = any(o.kind == POSITION for o in obs)
+    if drift and particles is None:
+        raise ValueError("fourdvar: a 'position' set needs particles (the drifters' initial positions)")
+    if particles is not None:
+        particles = particles_dev(t, particles) if dev != "cpu" else particles
+        for o in obs:
+            if o.kind == POSITION and len(o) != int(particles.shape[0]):
+                raise ValueError("fourdvar: a 'position' set of %d drifters, %d particles" % (len(o), int(particles.shape[0])))
     record_on, record_off = adjoint_window(model, checkpoint_every)
     if isinstance(z0, np.ndarray):
         z0 = t.from_numpy(np.ascontiguousarray(z0))
@@ -643,24 +677,37 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None):
     res = {}
     try:
         model.set_vort(z0.float().contiguous())
+        if particles is not None:
+            model.set_particles(particles)
         if times[-1]:
             record_on(times[-1])
+            if drift:
+                model.record_particles(times[-1])
         at = 0
         for when in times:
             model.step(when - at)
             at = when
             for k, o in enumerate(obs):
                 if o.step == when:
-                    res[k] = model.obs_misfit(model.observe(o.kind, o.xy), o.y, o.sigma, cost, check=False)
+                    h = model.particles().reshape(-1) if o.kind == POSITION else model.observe(o.kind, o.xy)
+                    res[k] = model.obs_misfit(h, o.y, o.sigma, cost, check=False)
         model.set_adjoint(t.zeros(tuple(z0.shape), dtype=t.float32, device=dev))
+        if drift:
+            model.set_particle_adjoint(t.zeros(tuple(particles.shape), dtype=t.float64, device=dev))
         for when, before in zip(times[::-1], times[-2::-1] + [0]):
             for k, o in enumerate(obs):
-                if o.step == when:
+                if o.step == when and o.kind == POSITION:
+                    model.set_particle_adjoint(model.particle_adjoint() + res[k].reshape(-1, 2))
+                elif o.step == when:
                     model.adjoint_add_obs(o.kind, o.xy, res[k])
             model.adjoint_back(when - before)
         grad = model.adjoint().double()
     finally:
-        record_off()
+        try:
+            record_off()
+        finally:
+            if drift:
+                model.record_particles(0)
     if background is not None:
         zb, sb = background
         if isinstance(zb, np.ndarray):
@@ -671,7 +718,8 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None):
     return float(cost.item()), grad
 
 
-def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, shrink=0.5, max_backtracks=25, checkpoint_every=None):
+def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, shrink=0.5, max_backtracks=25, checkpoint_every=None,
+                particles=None):
     """Minimises model.fourdvar(z, obs, background) -> (J, grad) over the initial field z from z0 by L-BFGS (the two-loop recursion over
     the last `history` pairs) with a backtracking Armijo line search: a step t d is accepted when J(z + t d) <= J(z) + armijo t <grad, d>,
     t from 1 (the first iteration: from the step 2 J / |grad|^2 along -grad, the exact minimiser of a one-dimensional quadratic
@@ -679,7 +727,8 @@ def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, 
     (the GPU for the engine; anything with a fourdvar will do).  It stops after `iters` accepted iterations, or at the first whose
     line search finds no acceptable step, or when the gradient is zero.  Returns (z, J_history, evaluations): the final field, float64;
     J at the start and after every accepted iteration (it falls at every one); the number of fourdvar calls.  checkpoint_every, where
-    it is not None, is handed to every model.fourdvar call (fourdvar(): windows whose full tape does not fit)."""
+    it is not None, is handed to every model.fourdvar call (fourdvar(): windows whose full tape does not fit), and so is particles
+    (the drifters' initial positions, for sets of kind "position")."""
     t = model.torch
     if iters < 0 or history < 1:
         raise ValueError("fit_initial: iters must be >= 0, history >= 1")
@@ -687,6 +736,8 @@ def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, 
         z0 = t.from_numpy(np.ascontiguousarray(z0))
     x = z0.double().clone()
     how = {} if checkpoint_every is None else {"checkpoint_every": checkpoint_every}
+    if particles is not None:
+        how["particles"] = particles
 
     def evaluate(z):
         J, g = model.fourdvar(z, obs, background, **how)
@@ -1342,20 +1393,55 @@ class ModelSurface:
         a = particles_dev(t, xy)
         self._hand("adjoint_add_obs", obs_kind(kind), a, values_dev(t, w, int(a.shape[0]), "w"), int(a.shape[0]))
 
-    def fourdvar(self, z0, obs, background=None, checkpoint_every=None):
+    def fourdvar(self, z0, obs, background=None, checkpoint_every=None, particles=None):
         """(J, grad): the 4D-Var cost of the initial vorticity z0 against the Observations in obs, and its gradient with respect to z0,
         float64 [nx, ny] on the GPU (fourdvar()).  The tape takes T x 4 half spectra, T the last observation step; with
-        checkpoint_every = K (or "sqrt": checkpoint_every(T)) ceil(T / K) + 4 K + 1 of them, for windows whose tape does not fit."""
+        checkpoint_every = K (or "sqrt": checkpoint_every(T)) ceil(T / K) + 4 K + 1 of them, for windows whose tape does not fit.
+        particles: the drifters' initial positions for sets of kind "position"; dJ/dX0 is left in particle_adjoint()."""
         self._one_rank("adjoint_record", 1)
-        return fourdvar(self, z0, obs, background, checkpoint_every)
+        return fourdvar(self, z0, obs, background, checkpoint_every, particles)
 
-    def fit_initial(self, z0, obs, iters, background=None, history=8, checkpoint_every=None):
+    def fit_initial(self, z0, obs, iters, background=None, history=8, checkpoint_every=None, particles=None):
         """(z, J_history, evaluations): L-BFGS on fourdvar from the first guess z0 (fit_initial()); z0 goes to the GPU first, so the
-        iterate, the gradients and the memory of the recursion stay there.  checkpoint_every: as fourdvar's."""
+        iterate, the gradients and the memory of the recursion stay there.  checkpoint_every, particles: as fourdvar's."""
         self._one_rank("adjoint_record", 1)
         if isinstance(z0, np.ndarray):
             z0 = self.torch.from_numpy(np.ascontiguousarray(z0))
-        return fit_initial(self, z0.cuda(), obs, iters, background, history, checkpoint_every=checkpoint_every)
+        return fit_initial(self, z0.cuda(), obs, iters, background, history, checkpoint_every=checkpoint_every, particles=particles)
+
+    def record_particles(self, depth):
+        """Turns the particle tape on (depth >= 1: room for depth steps; every step from now on records the positions its four stages
+        start from, 64 bytes per particle and step, and a step call beyond depth is refused) or off (depth = 0, the tape freed).
+        Either way it starts empty.  It needs particles; set_vort and set_particles empty it.  While it is on the model steps eagerly.
+        The positions and everything else stepped are the same bits with and without.  One rank only, as the particles."""
+        self._call("particle_tape", int(depth))
+
+    def particles_recorded(self):
+        """(steps on the particle tape, its depth); (0, 0) while it is off"""
+        a, b = C.c_int(), C.c_int()
+        self._call("particle_tape_count", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def set_particle_adjoint(self, xbar):
+        """Sets the particle adjoint Xb, float64 [n, 2] (numpy or torch): the gradient of a scalar with respect to the particles'
+        positions at the time of the newest recorded step; xbar=None removes it.  While it is set adjoint_back sweeps it back with
+        lam through the transpose of the coupled step, popping the particle tape too: Xb <- its value at the earlier time, and lam
+        gains the sensitivity of the positions to the vorticity.  Bitwise reproducible, in any order of the particles."""
+        self._one_rank("set_particle_adjoint", _SOME)
+        if xbar is None:
+            return self._hand("set_particle_adjoint", None)
+        a = particles_dev(self.torch, xbar)
+        if int(a.shape[0]) != self.particle_count():
+            raise ValueError("set_particle_adjoint: float64 [%d, 2], one row per particle" % self.particle_count())
+        self._hand("set_particle_adjoint", a)
+
+    def particle_adjoint(self):
+        """The particle adjoint Xb, a float64 [n, 2] tensor."""
+        t = self.torch
+        self._one_rank("get_particle_adjoint", _SOME)
+        out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
+        self._hand("get_particle_adjoint", out)
+        return out
 
 
 class Model(ModelSurface):

@@ -1,6 +1,6 @@
 // fb_beside.h -- the fields stepped beside the vorticity: the passive tracer, the tangent-linear model and the Lagrangian particles
-// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h, fb_adjoint.h, fb_obs.h; C ABI:
-// include/fftbaro.h).
+// (included by fftbaro.hip after fb_record.h; kernels: fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h, fb_adjoint.h, fb_obs.h,
+// fb_lagrangian.h; C ABI: include/fftbaro.h).
 //
 // Each is taken in between two steps and advanced at the top of every RK stage of fb_model_step and fb_slab_step, from the state the
 // vorticity's stage starts from, through the record workspace (record_advect, fb_record.h): the step's own buffers are only read.  A
@@ -518,13 +518,19 @@ static void deformation_free(fb_model *m)
     if (m->pd) { hipFree(m->pd); m->pd = nullptr; }
 }
 
+static void lagrangian_free(fb_model *m);
+
 static void particles_free(fb_model *m)
 {
     deformation_free(m);                                    // F belongs to the particles it was carried by
+    lagrangian_free(m);                                     // and so do their tape and their adjoint
     if (m->pt) { hipFree(m->pt); m->pt = nullptr; }
     if (m->pt_uv) { hipFree(m->pt_uv); m->pt_uv = nullptr; }
     m->pt_n = 0;
 }
+
+// stage `stage` of step `step` of the particle tape: [pt_n][2] float64
+static double *particle_tape_at(const fb_model *m, int step, int stage) { return m->pt_tape + ((size_t)step * 4 + stage) * 2 * (size_t)m->pt_n; }
 
 static PartGeo part_geo(const fb_ctx *c)
 {
@@ -560,6 +566,11 @@ static int particle_stage(fb_model *m, int stage)
     const PartGeo pg = part_geo(c);
     const float *u = m->pt_uv, *v = m->pt_uv + nr;
     const double dt = (double)m->dt;
+    if (m->pt_depth) {                                      // the position this stage starts from into the particle tape's next slot
+        if (m->pt_fill >= m->pt_depth) return fail(FB_EINVAL, "fb_model_step: the particle tape is full (fb_model_particle_tape)");   // (step_refusals comes first)
+        const double *from = m->pt + (stage == 0 ? 0 : 2 * (size_t)m->pt_n);
+        if ((rc = launch_n(c, k_particle_pack, (size_t)m->pt_n, from, from + m->pt_n, particle_tape_at(m, m->pt_fill, stage), m->pt_n))) return rc;
+    }
     if (m->pd)                                              // positions and the deformation gradient in one pass, in k_particle_stage's place
         return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_stage_def<S()>, (size_t)m->pt_n, pg, u, v, m->pt, m->pd, m->pt_n, dt); });
     return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_stage<S()>, (size_t)m->pt_n, pg, u, v, m->pt, m->pt_n, dt); });
@@ -573,10 +584,15 @@ static int particles_in(fb_model *m, fb_slab *s, const double *d_xy, int n)
     fb_ctx *c = m->c;
     int rc;
     if ((rc = beside_begin(m, m->pt_n != 0))) return rc;
+    // a particle tape laid out for the same count stays, emptied: it followed the particles that go.  Another count frees it.
+    double *tape = d_xy && n == m->pt_n ? m->pt_tape : nullptr;
+    const int depth = m->pt_depth;
+    if (tape) m->pt_tape = nullptr;
     particles_free(m);
+    if (tape) { m->pt_tape = tape; m->pt_depth = depth; }
     if (!d_xy) return FB_OK;
     if ((rc = advect_workspace(m, s))) return rc;
-    if (hipMalloc((void **)&m->pt, 6 * (size_t)n * sizeof(double)) != hipSuccess) { m->pt = nullptr; return fail(FB_ENOMEM, "particle allocation failed"); }
+    if (hipMalloc((void **)&m->pt, 6 * (size_t)n * sizeof(double)) != hipSuccess) { m->pt = nullptr; particles_free(m); return fail(FB_ENOMEM, "particle allocation failed"); }
     if (hipMalloc((void **)&m->pt_uv, 2 * (size_t)c->nx * c->ny * sizeof(float)) != hipSuccess) {
         m->pt_uv = nullptr;
         particles_free(m);
@@ -719,6 +735,149 @@ extern "C" int fb_slab_particle_stretching(fb_slab *s, const double *d_F, int n,
 {
     return particle_stretching(on_slab("fb_slab_particle_stretching", s), d_F, n, d_out);
 }
+
+// ---- the particle tape and the particle adjoint (kernels: fb_lagrangian.h) ----
+static void particle_adjoint_free(fb_model *m)
+{
+    if (m->pa) { hipFree(m->pa); m->pa = nullptr; }
+    if (m->pa_acc) { hipFree(m->pa_acc); m->pa_acc = nullptr; }
+}
+
+static void particle_tape_free(fb_model *m)
+{
+    if (m->pt_tape) { hipFree(m->pt_tape); m->pt_tape = nullptr; }
+    m->pt_depth = m->pt_fill = 0;
+}
+
+static void lagrangian_free(fb_model *m)
+{
+    particle_tape_free(m);
+    particle_adjoint_free(m);
+}
+
+// the tape (64 bytes per particle and step of its depth); the adjoint's eight arrays and its two accumulators with their head
+static size_t lagrangian_bytes(const fb_model *m)
+{
+    const fb_ctx *c = m->c;
+    size_t n = (size_t)m->pt_depth * 4 * 2 * (size_t)m->pt_n * sizeof(double);
+    if (m->pa) n += 8 * (size_t)m->pt_n * sizeof(double) + (4 * (size_t)c->nx * c->ny + 2) * sizeof(unsigned long long);
+    return n;
+}
+
+// The tape on (depth >= 1: room for depth steps x 4 stage positions) or off (depth == 0); either way it starts empty.  While it is on
+// fb_model_step steps eagerly, as it does while the adjoint's tape is on: particle_stage writes another slot at every stage, which a
+// captured step would bake in.  So the captured step is dropped here (beside_begin).  A failure leaves no tape allocated.
+static int particle_tape(fb_model *m, int depth)
+{
+    int rc;
+    if ((rc = beside_begin(m, m->pt_tape != nullptr))) return rc;
+    particle_tape_free(m);
+    if (depth == 0) return FB_OK;
+    if (hipMalloc((void **)&m->pt_tape, (size_t)depth * 4 * 2 * (size_t)m->pt_n * sizeof(double)) != hipSuccess) {
+        m->pt_tape = nullptr;
+        (void)hipGetLastError();
+        return fail(FB_ENOMEM, "the particle tape: allocation failed");
+    }
+    m->pt_depth = depth;
+    return FB_OK;
+}
+
+// Xb in (d_xb: [pt_n][2] float64; NULL removes it), with the stage arrays zeroed and the accumulators of the deposit.  A particle
+// adjoint that goes may still be read by a queued sweep.  The step's launches do not depend on any of it: the captured step stays.
+static int particle_adjoint_in(fb_model *m, const double *d_xb)
+{
+    fb_ctx *c = m->c;
+    const size_t cells = (size_t)c->nx * c->ny;
+    if (!d_xb) {
+        if (m->pa) HIPCHK(hipStreamSynchronize(c->stream));
+        particle_adjoint_free(m);
+        return FB_OK;
+    }
+    int rc;
+    if ((rc = rec_alloc((void **)&m->pa, 8 * (size_t)m->pt_n * sizeof(double))) || (rc = rec_alloc((void **)&m->pa_acc, (4 * cells + 2) * sizeof(unsigned long long)))) {
+        particle_adjoint_free(m);
+        return rc;
+    }
+    return launch_n(c, k_particle_adjoint_in, (size_t)m->pt_n, d_xb, m->pa, m->pt_n);
+}
+
+// The particles' part of a backward stage, between the ROW_INV passes and k_adjoint_prod: p, q and the recurrences from u and v in
+// the fields 1 and 2 of ad_real, which k_adjoint_prod overwrites next.  xs: the stage's slot of the particle tape.
+static int lagrangian_stage(fb_model *m, int stage, const double *xs)
+{
+    fb_ctx *c = m->c;
+    const size_t nr = (size_t)c->nx * c->ny;
+    const float *u = m->ad_real + nr, *v = m->ad_real + 2 * nr;
+    const PartGeo pg = part_geo(c);
+    const double dt = (double)m->dt;
+    return dispatch<4>(stage, [&](auto S) { return launch_n(c, k_particle_adjoint<S()>, (size_t)m->pt_n, pg, u, v, xs, m->pa, m->pt_n, dt); });
+}
+
+// ... and after k_adjoint_prod, before the ROW_FWD passes: p_x and p_y spread from xs into the two accumulators (max |p| on the device,
+// the integer atomics), and the fold into the real fields zeta_x mu~ (field 3) and zeta_y mu~ (field 4).  The limbs are zero on the way
+// in (lagrangian_begin) and zero again on the way out (k_scatter_fold); the head is zeroed here.
+static int lagrangian_deposit(fb_model *m, const double *xs)
+{
+    fb_ctx *c = m->c;
+    const size_t cells = (size_t)c->nx * c->ny, N = (size_t)m->pt_n;
+    unsigned long long *acc = m->pa_acc, *head = acc + 4 * cells;
+    const double *px = m->pa + 2 * N, *py = m->pa + 3 * N;
+    int rc;
+    HIPCHK(hipMemsetAsync(head, 0, 2 * sizeof(unsigned long long), c->stream));
+    if ((rc = launch_n(c, k_obs_wmax, N, px, m->pt_n, head)) || (rc = launch_n(c, k_obs_wmax, N, py, m->pt_n, head))) return rc;
+    if ((rc = launch_n(c, k_scatter_pair, N, part_geo(c), xs, px, py, m->pt_n, acc, cells, (const unsigned long long *)head))) return rc;
+    return launch_n(c, k_scatter_fold, cells, acc, (const unsigned long long *)head, m->pt_n, m->ad_real + 3 * cells, m->ad_real + 4 * cells, cells);
+}
+
+// before the first stage of a sweep: the limbs zeroed, whatever an earlier sweep that failed half way has left in them
+static int lagrangian_begin(fb_model *m)
+{
+    fb_ctx *c = m->c;
+    HIPCHK(hipMemsetAsync(m->pa_acc, 0, (4 * (size_t)c->nx * c->ny + 2) * sizeof(unsigned long long), c->stream));
+    return FB_OK;
+}
+
+// (depth needs no handle; the tape needs particles unless it is only freed)
+static int particle_tape(const Call &k, int depth)
+{
+    if (depth < 0 || depth > (1 << 20)) return refuse(k, "depth outside [0, 2^20]");
+    if (int rc = enter(k, depth ? PARTICLES | NEED_PARTICLES : PARTICLES)) return rc;
+    return particle_tape(k.m, depth);
+}
+extern "C" int fb_model_particle_tape(fb_model *m, int depth) { return particle_tape(on_model("fb_model_particle_tape", m), depth); }
+extern "C" int fb_slab_particle_tape(fb_slab *s, int depth) { return particle_tape(on_slab("fb_slab_particle_tape", s), depth); }
+
+// (0, 0 while there is none: not a refusal)
+static int particle_tape_count(const Call &k, int *count, int *depth)
+{
+    if (!count || !depth) return refuse(k, "NULL output");
+    if (int rc = enter(k, PARTICLES)) return rc;
+    *count = k.m->pt_fill;
+    *depth = k.m->pt_depth;
+    return FB_OK;
+}
+extern "C" int fb_model_particle_tape_count(fb_model *m, int *count, int *depth) { return particle_tape_count(on_model("fb_model_particle_tape_count", m), count, depth); }
+extern "C" int fb_slab_particle_tape_count(fb_slab *s, int *count, int *depth) { return particle_tape_count(on_slab("fb_slab_particle_tape_count", s), count, depth); }
+
+// (NULL removes it; without particles there is none to remove either: the refusal is the particles')
+static int set_particle_adjoint(const Call &k, const double *d_xbar)
+{
+    if (int rc = enter(k, PARTICLES | NEED_PARTICLES)) return rc;
+    return particle_adjoint_in(k.m, d_xbar);
+}
+extern "C" int fb_model_set_particle_adjoint(fb_model *m, const double *d_xbar) { return set_particle_adjoint(on_model("fb_model_set_particle_adjoint", m), d_xbar); }
+extern "C" int fb_slab_set_particle_adjoint(fb_slab *s, const double *d_xbar) { return set_particle_adjoint(on_slab("fb_slab_set_particle_adjoint", s), d_xbar); }
+
+static int get_particle_adjoint(const Call &k, double *d_xbar)
+{
+    if (!d_xbar) return refuse(k, "NULL output");
+    if (int rc = enter(k, PARTICLES | NEED_PARTICLES)) return rc;
+    fb_model *m = k.m;
+    if (!m->pa) return refuse(k, "no particle adjoint is set (fb_model_set_particle_adjoint)");
+    return launch_n(m->c, k_particle_pack, (size_t)m->pt_n, (const double *)m->pa, (const double *)(m->pa + m->pt_n), d_xbar, m->pt_n);
+}
+extern "C" int fb_model_get_particle_adjoint(fb_model *m, double *d_xbar) { return get_particle_adjoint(on_model("fb_model_get_particle_adjoint", m), d_xbar); }
+extern "C" int fb_slab_get_particle_adjoint(fb_slab *s, double *d_xbar) { return get_particle_adjoint(on_slab("fb_slab_get_particle_adjoint", s), d_xbar); }
 
 // ---- the adjoint model (kernels: fb_adjoint.h) ----
 // One GPU or a slab of one rank: one column group, no exchange (as the particles).
@@ -909,8 +1068,10 @@ static int adjoint_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
 
 // One RK stage of a backward step: L_stage^T of the k-bar about the recorded stage state zs, then the recurrences (fb_adjoint.h).
 // Five fields back to physical space as particle_stage takes u and v, with its scales; four products forward as beside_in takes a
-// field; through the record workspace, which the step never reads.
-static int adjoint_stage(fb_model *m, int stage, const cf *zs)
+// field; through the record workspace, which the step never reads.  xs != NULL: a particle adjoint is set and xs is the stage's slot
+// of the particle tape; its stage runs while u and v are whole, and its forcing is folded into two of the products (fb_lagrangian.h).
+// With xs == NULL the launches are the ones a sweep has always made.
+static int adjoint_stage(fb_model *m, int stage, const cf *zs, const double *xs)
 {
     fb_ctx *c = m->c;
     const ColGroup &G = c->grp[0];
@@ -928,7 +1089,9 @@ static int adjoint_stage(fb_model *m, int stage, const cf *zs)
         a.M = view_single(c, z + f * n, (long)n); a.scale = f == 1 ? -g : g; a.rout = m->ad_real + f * nr;      // u = -dpsi/dy (record(), REC_U)
         if ((rc = launch_row<ROW_INV>(c, a))) return rc;
     }
+    if (xs && (rc = lagrangian_stage(m, stage, xs))) return rc;
     if ((rc = launch_n(c, k_adjoint_prod, nr / 4, m->ad_real, nr))) return rc;
+    if (xs && (rc = lagrangian_deposit(m, xs))) return rc;
     HIPCHK(hipMemsetAsync(z, 0, 4 * n * sizeof(cf), c->stream));                                                 // pad columns zero
     for (int f = 0; f < 4; ++f) {
         RowArgs a = row_args_base(c);
@@ -1000,7 +1163,9 @@ static int adjoint_stage_set(fb_model *m, int stage, const cf *zs)
 }
 
 // The last nsteps recorded steps popped, newest first, each step's transpose applied to every lam (its stages in the order 3, 2, 1, 0).
-// The set of one keeps adjoint_stage: its five-field passes are what a single variable has always run.
+// The set of one keeps adjoint_stage: its five-field passes are what a single variable has always run.  While a particle adjoint is set
+// (the entry point has seen to it that the variable is one and that both tapes hold the same steps) every step pops the particle tape
+// too; a segment of a checkpointed window that is run again never writes that tape, which always holds the whole window.
 static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
 {
     fb_ctx *c = m->c;
@@ -1008,14 +1173,17 @@ static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
     int rc;
     bool saved = false;
     if ((rc = advect_workspace(m, s))) return rc;
+    if (m->pa && nsteps > 0 && (rc = lagrangian_begin(m))) return rc;
     for (int k = 0; k < nsteps && !rc; ++k) {
         // a checkpointed window: an empty tape segment is filled again first; what is left of one stays for the next call
         if (m->ck_every && !m->ad_fill && (rc = checkpoint_refill(m, s, &saved))) break;
         const cf *step = m->ad_tape + (size_t)(m->ad_fill - 1) * 4 * n;
         for (int stage = 3; stage >= 0 && !rc; --stage)
-            rc = m->ad_n == 1 ? adjoint_stage(m, stage, step + (size_t)stage * n) : adjoint_stage_set(m, stage, step + (size_t)stage * n);
+            rc = m->ad_n == 1 ? adjoint_stage(m, stage, step + (size_t)stage * n, m->pa ? particle_tape_at(m, m->pt_fill - 1, stage) : nullptr)
+                              : adjoint_stage_set(m, stage, step + (size_t)stage * n);
         if (rc) break;
         --m->ad_fill;
+        if (m->pa) --m->pt_fill;
         if (m->ck_every) { --m->ck_left; m->ck_swept = true; }
     }
     if (saved) { const int back = checkpoint_restore(m, m->ck_live); if (!rc) rc = back; }    // the live state is back before the call returns, failed or not
@@ -1129,6 +1297,16 @@ static int adjoint_back(const Call &k, int nsteps)
     if (nsteps < 0) return refuse(k, "nsteps < 0");
     if (int rc = enter(k, ADJOINT_SET)) return rc;
     if (nsteps > adjoint_unswept(k.m)) return refuse(k, std::to_string(nsteps) + " steps asked for, " + std::to_string(adjoint_unswept(k.m)) + " recorded");
+    if (k.m->pa) {                                          // a particle adjoint is set: the sweep takes the particle tape along
+        const fb_model *m = k.m;
+        if (nsteps > m->pt_fill)
+            return refuse(k, std::to_string(nsteps) + " steps asked for, " + std::to_string(m->pt_fill) + " on the particle tape (fb_model_particle_tape)");
+        if (m->ad_n > 1)
+            return refuse(k, "a particle adjoint is set beside a set of " + std::to_string(m->ad_n) + " adjoint variables: it forces a single variable");
+        if (m->pt_fill != adjoint_unswept(m))
+            return refuse(k, "the particle tape holds " + std::to_string(m->pt_fill) + " steps, the adjoint's window " + std::to_string(adjoint_unswept(m)) +
+                          ": both must have recorded the same steps");
+    }
     return adjoint_back(k.m, k.s, nsteps);
 }
 extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps) { return adjoint_back(on_model("fb_model_adjoint_back", m), nsteps); }
@@ -1277,6 +1455,7 @@ static int beside_stage(fb_model *m, fb_slab *s, int stage)
 static void beside_step_done(fb_model *m)
 {
     if (m->ad_on) ++m->ad_fill;                             // the four stage states of this step are on the tape
+    if (m->pt_depth && m->pt_n && !m->ck_replay) ++m->pt_fill;      // and its four stage positions on the particles'
 }
 
 static void beside_free_all(fb_model *m)

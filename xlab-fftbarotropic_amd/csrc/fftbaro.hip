@@ -25,6 +25,7 @@
 #include "fb_clv.h"
 #include "fb_adjoint.h"
 #include "fb_obs.h"
+#include "fb_lagrangian.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1105,6 +1106,14 @@ struct fb_model {
     unsigned long long *ob_acc;
     float *ob_real;
     double *ob_red;
+    // the adjoint of the particle step (fb_lagrangian.h; host side in fb_beside.h).  The particle tape: pt_depth steps x 4 stage
+    // positions, float64 [pt_n][2] each, pt_fill steps of it recorded while the model stepped; NULL and 0 while it is off.  The
+    // particle adjoint: eight float64 arrays of pt_n (Xb, the stage's p and q, the accumulator; x then y of each), and the two
+    // fixed-point accumulators of a stage's deposit (2 x 2 limbs for each of the nx * ny cells, and the head); NULL while none is set.
+    // Both go with the particles they belong to
+    double *pt_tape; int pt_depth, pt_fill;
+    double *pa;
+    unsigned long long *pa_acc;
 };
 
 // one rank of the multi-GPU model (fb_slab_driver.h)
@@ -1164,6 +1173,7 @@ static void beside_free_all(fb_model *m);
 static size_t adjoint_bytes(const fb_model *m);                         // what fb_model_info counts for the adjoint variables
 static size_t adjoint_tape_bytes(const fb_model *m);                    // and for the tape, or the tape segment, the checkpoints and the live copy
 static int checkpoint_take(fb_model *m, int *nsteps);                   // run_steps under checkpointing, before every piece of a step call
+static size_t lagrangian_bytes(const fb_model *m);                      // what fb_model_info counts for the particle tape and the particle adjoint
 
 static void model_drop_graph(fb_model *m)
 {
@@ -1186,6 +1196,7 @@ static void state_replaced(fb_model *m)
     m->warmed = false;
     m->primed = 0;
     adjoint_window_empty(m);
+    m->pt_fill = 0;                                         // the particle tape followed the flow that went
 }
 
 extern "C" int fb_model_destroy(fb_model *m)
@@ -1226,6 +1237,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups && m->tracer; ++g) n += (g < c->nact ? 3 : 1) * grp_elems(c, c->grp[g]) * sizeof(cf);      // the tracer's state
         if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
         if (m->pd) n += 12 * (size_t)m->pt_n * sizeof(double);                                                             // and their deformation gradient
+        n += lagrangian_bytes(m);                                                                                           // their tape and their adjoint
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
@@ -1395,6 +1407,8 @@ static int step_refusals(const Call &k, int nsteps)
             return refuse(k, "the checkpointed window has room for " + std::to_string(m->ck_max - m->ck_done) + " more steps (fb_model_adjoint_checkpoint)");
     } else if (m->ad_on && nsteps > m->ad_depth - m->ad_fill)
         return refuse(k, "the adjoint's tape has room for " + std::to_string(m->ad_depth - m->ad_fill) + " more steps (fb_model_adjoint_record)");
+    if (m->pt_depth && nsteps > m->pt_depth - m->pt_fill)
+        return refuse(k, "the particle tape has room for " + std::to_string(m->pt_depth - m->pt_fill) + " more steps (fb_model_particle_tape)");
     return FB_OK;
 }
 
@@ -1452,8 +1466,9 @@ static int model_steps(fb_model *m, int nsteps)
     // graph replay needs a capturable (non-null) stream, a primed pipeline and at least one eager step behind
     // us (kernel attributes are set on first launch); anything else runs eagerly.  So does a model that records the adjoint's tape:
     // every step writes another slot, which a captured step would bake in (ad_on: recording now; under checkpointing the forward
-    // run writes no slot, so the tape segment that is allocated does not keep it from replaying the captured step)
-    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2 || m->ad_on) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
+    // run writes no slot, so the tape segment that is allocated does not keep it from replaying the captured step); the particle
+    // tape, whose slot the particles' stage writes, likewise
+    if (!m->use_graph || c->world != 1 || c->stream == nullptr || nsteps < 2 || m->ad_on || m->pt_depth) { if (nsteps > 0) m->warmed = true; return model_step_impl(m, nsteps, nullptr); }
     int rc;
     if (!m->warmed) { if ((rc = model_step_impl(m, 1, nullptr))) return rc; m->warmed = true; --nsteps; }
     if (m->graph_exec && (m->graph_src != m->src || m->graph_stream != c->stream)) model_drop_graph(m);
