@@ -452,6 +452,32 @@ int fb_model_scatter(fb_model *m, const double *d_xy, const double *d_w, int n, 
 int fb_model_observe(fb_model *m, int kind, const double *d_xy, int n, double *d_out);      /* 0 zeta, 1 u, 2 v, 3 psi */
 int fb_model_obs_misfit(fb_model *m, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost);
 int fb_model_adjoint_add_obs(fb_model *m, int kind, const double *d_xy, const double *d_w, int n);
+/* Tangent replay over the adjoint's tape (no reference counterpart): what a Gauss-Newton Hessian-vector product
+ *   H_GN v = B^-1 v + sum over times k of T_k^T H_k^T R_k^-1 H_k T_k v
+ * needs of the engine beside the sweep, so that no application of T steps the nonlinear model again.
+ * fb_model_tangent_replay(m, first, nsteps) applies the tangent step of the taped steps first .. first + nsteps - 1 (0: the oldest slot
+ * of fb_model_adjoint_record's tape), oldest first, to every perturbation of the tangent set, from the four recorded stage states of
+ * each step: u, v, zeta_x, zeta_y of a stage are formed once for the whole set, and each perturbation's tendency is ONE product in
+ * physical space, (((-u dz_x) - v dz_y) - du zeta_x) - dv zeta_y, then the tracer's stage update with the model's nu
+ * (csrc/fb_replay.h): 4 + 5 M fields transformed per stage where M perturbations stepped beside the vorticity take 10 M.  It is the
+ * operator fb_model_step applies to a tangent, not its bits (that one sums two spectral tendencies); perturbation k of a replayed set
+ * has the bits of the replayed set of one, and two equal replays give the same bits.  The vorticity, a tracer, particles, the step
+ * count, the tape and what fb_model_adjoint_recorded returns stay as they are.  Steps that a sweep has popped can still be replayed:
+ * the range is bounded by the slots that hold recorded steps which no later step has overwritten.  nsteps == 0 does nothing.  Its
+ * workspace, 4 + 5 min(M, 8) real fields, is allocated at the first replay of a set, counted by fb_model_info and freed with the set.
+ * fb_model_adjoint_rewind(m, n) un-pops the last n steps that fb_model_adjoint_back popped (n == -1: every one still on the tape):
+ * the sweep does not erase a slot, so a second sweep over the same steps gives the same bits.  A step recorded after a pop overwrites
+ * the slots above it, which can then no longer be rewound to.
+ * fb_model_observe_tangent(m, k, kind, d_xy, n, d_out): fb_model_observe of perturbation k of the tangent set in the place of the
+ * resident state; for kind 0 bit for bit fb_model_sample of the field fb_model_get_tangents returns for it.
+ * One GPU or a slab of one rank.  FB_EINVAL before any HIP call: a NULL model or pointer, first < 0, nsteps < 0, n < -1, kind outside
+ * [0, 3], n outside [1, 2^24], k outside the set, no tangent set (replay, observe_tangent), no tape or a range beyond the recorded
+ * slots (replay), more steps than were popped (rewind), adjoint checkpointing on (replay, rewind: the segment holds only a part of the
+ * window), a particle adjoint set (rewind: the particle tape is popped in step), a slab of several ranks.  Enqueued on the context
+ * stream, no synchronisation. */
+int fb_model_tangent_replay(fb_model *m, int first, int nsteps);
+int fb_model_adjoint_rewind(fb_model *m, int n);                            /* -1: every popped step still on the tape */
+int fb_model_observe_tangent(fb_model *m, int k, int kind, const double *d_xy, int n, double *d_out);
 /* Nonlinear-balance pressure of the current state into the device [nx][ny] field d_pres: what the reference's second program computes
  * from a psi record (invert_pres.cpp:135-185), here from the resident state with psi_c = invertLaplacian(vort_c) (fftwfop.cpp:112-117)
  * instead of readField + r2c of psi_step_N.bin (:132-135).  In the reference's float32 forms, g = 1/GRIDS:
@@ -656,6 +682,10 @@ int fb_slab_scatter(fb_slab *s, const double *d_xy, const double *d_w, int n, fl
 int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out);
 int fb_slab_obs_misfit(fb_slab *s, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost);
 int fb_slab_adjoint_add_obs(fb_slab *s, int kind, const double *d_xy, const double *d_w, int n);
+/* the tangent replay, the rewind and the observation of a perturbation (fb_model_tangent_replay) of a slab of ONE rank, likewise */
+int fb_slab_tangent_replay(fb_slab *s, int first, int nsteps);
+int fb_slab_adjoint_rewind(fb_slab *s, int n);
+int fb_slab_observe_tangent(fb_slab *s, int k, int kind, const double *d_xy, int n, double *d_out);
 /* the Lagrangian particles (fb_model_set_particles) of a slab of ONE rank: the same code, bit for bit what fb_model_* computes.  On
  * world > 1 they return FB_EUNSUPPORTED: particles distributed over row slabs need neighbour halo rows that the all-to-all transport
  * does not provide. */

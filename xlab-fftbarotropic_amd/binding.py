@@ -93,9 +93,11 @@ _ADJOINTS_PAIRS = {"set_adjoints": [_vp, _ip], "get_adjoints": [_vp], "adjoint_c
 _CHECKPOINT_PAIRS = {"adjoint_checkpoint": [_ip, _ip], "adjoint_checkpoint_info": [_pip, _pip, _pip, C.POINTER(C.c_longlong)]}
 # the Lagrangian observations' pairs, likewise: the particle tape and the particle adjoint
 _LAGRANGIAN_PAIRS = {"particle_tape": [_ip], "particle_tape_count": [_pip, _pip], "set_particle_adjoint": [_vp], "get_particle_adjoint": [_vp]}
+# the tangent replay's pairs, likewise: the replay over the adjoint's tape, the rewind of a sweep and H applied to a perturbation
+_REPLAY_PAIRS = {"tangent_replay": [_ip, _ip], "adjoint_rewind": [_ip], "observe_tangent": [_ip, _ip, _vp, _ip, _vp]}
 for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
                      + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items()) + list(_CHECKPOINT_PAIRS.items())
-                     + list(_LAGRANGIAN_PAIRS.items())):
+                     + list(_LAGRANGIAN_PAIRS.items()) + list(_REPLAY_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -501,7 +503,7 @@ def _orthonormal_rows(t, w):
     return q
 
 
-def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None, checkpoint_every=None):
+def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None, checkpoint_every=None, replay=False):
     """Orthogonal (block power) iteration on T^T T in the L2 norm on `model` (anything with set_tangents, tangents, record_adjoint,
     step, set_adjoints, adjoint_back, adjoints; save / restore as in singular_values), T the tangent of `steps` steps from the model's
     current state: the k leading singular values and right singular vectors from one tangent subspace and one adjoint set of k.  V,
@@ -514,9 +516,15 @@ def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None
     The model is left as singular_values leaves it: at its starting state, the tape freed; the tangent set holds the last V it
     stepped and the adjoint set the last sweep.  Convergence of sigma_i goes like (sigma_(k+1) / sigma_i)^(2 iters).  checkpoint_every:
     None keeps the full tape of `steps` steps; an int K or "sqrt" keeps checkpoints instead (adjoint_window; checkpoint_adjoint on the
-    model): the tangent subspace rides the forward run and not the steps a sweep takes again, and sigma and V are the same bits."""
+    model): the tangent subspace rides the forward run and not the steps a sweep takes again, and sigma and V are the same bits.
+    replay=True (the full tape only): the forward run is made once, with the tape on and no tangent set, and each iteration is
+    set_tangents(V), tangent_replay(0, steps), set_adjoints(U), adjoint_back(steps), adjoint_rewind(-1): no nonlinear step per
+    iteration, and 4 + 5 k fields transformed per stage where the stepped subspace takes 10 k.  The replayed tangent is the live
+    one's operator, not its bits: sigma and V agree with replay=False to float32 rounding.  A tangent set the user had is removed."""
     if steps < 1 or iters < 1:
         raise ValueError("singular_vectors: steps and iters must be >= 1")
+    if replay and checkpoint_every is not None:
+        raise ValueError("singular_vectors: replay needs the full tape (checkpoint_every=None)")
     if int(k) != k or not 1 <= k <= min(TANGENTS_MAX, ADJOINTS_MAX):
         raise ValueError("singular_vectors: k must be in [1, %d]" % min(TANGENTS_MAX, ADJOINTS_MAX))
     k = int(k)
@@ -540,10 +548,19 @@ def singular_vectors(model, steps, k, iters, start=None, save=None, restore=None
     sig = np.empty((iters, k))
     record_on(steps)
     try:
-        for it in range(iters):
-            restore(z0)
-            model.set_tangents(v.float().reshape(shape).contiguous())
+        if replay:                                              # the one forward run: the vorticity alone, its stage states onto the tape
+            model.set_tangents(None)
             model.step(steps)
+        for it in range(iters):
+            if replay:
+                if it:
+                    model.adjoint_rewind(-1)
+                model.set_tangents(v.float().reshape(shape).contiguous())
+                model.tangent_replay(0, steps)
+            else:
+                restore(z0)
+                model.set_tangents(v.float().reshape(shape).contiguous())
+                model.step(steps)
             u32 = model.tangents()
             u = u32.double().reshape(k, -1)
             w, e = np.linalg.eigh((u @ u.T).cpu().numpy())
@@ -634,7 +651,7 @@ class Observations:
         return self.n
 
 
-def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=None):
+def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=None, keep_tape=False):
     """(J, grad) of the 4D-Var cost of the initial vorticity z0 (an [nx, ny] field, numpy or torch; it is set as float32) on `model`
     (anything with set_vort, record_adjoint, step, observe, obs_misfit, set_adjoint, adjoint_add_obs, adjoint_back, adjoint):
       J = 1/2 sum over the sets of obs and their points of (H zeta(step) - y)^2 / sigma^2   (+ 1/2 |z0 - zb|^2 / sigma_b^2),
@@ -655,12 +672,17 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=N
     tape is on over the window (record_particles(T), 64 bytes per drifter and step, freed at the end with the field's), Xb starts at 0,
     gains r at every set's time (get, add, set on the GPU) and is swept back with lam by adjoint_back; what is left in
     model.particle_adjoint() is dJ/dX0, float64 [n, 2], as grad's float32 form is left in lam.  A "position" set without particles is a
-    ValueError.  With particles=None and no such set nothing here differs from what it was."""
+    ValueError.  With particles=None and no such set nothing here differs from what it was.
+    keep_tape=True: the tape is not freed at the end but rewound (adjoint_rewind(-1)), so the linearisation about z0 stays resident for
+    gauss_newton_hvp; J and grad are the same bits.  An error frees it all the same.  Only with the full tape and without "position"
+    sets (ValueError otherwise): checkpointed and Lagrangian Gauss-Newton are not there."""
     t, dev = model.torch, _device(model)
     obs = list(obs)
     if not obs:
         raise ValueError("fourdvar: no observations")
     drift = any(o.kind == POSITION for o in obs)
+    if keep_tape and (checkpoint_every is not None or drift):
+        raise ValueError("fourdvar: keep_tape needs the full tape (checkpoint_every=None) and no 'position' set")
     if drift and particles is None:
         raise ValueError("fourdvar: a 'position' set needs particles (the drifters' initial positions)")
     if particles is not None:
@@ -675,6 +697,7 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=N
     times = sorted(set(o.step for o in obs))
     cost = t.zeros(1, dtype=t.float64, device=dev)
     res = {}
+    kept = False                                                # keep_tape, once the sweep has gone through
     try:
         model.set_vort(z0.float().contiguous())
         if particles is not None:
@@ -702,9 +725,13 @@ def fourdvar(model, z0, obs, background=None, checkpoint_every=None, particles=N
                     model.adjoint_add_obs(o.kind, o.xy, res[k])
             model.adjoint_back(when - before)
         grad = model.adjoint().double()
+        kept = keep_tape
+        if kept:
+            model.adjoint_rewind(-1)
     finally:
         try:
-            record_off()
+            if not kept:
+                record_off()
         finally:
             if drift:
                 model.record_particles(0)
@@ -786,6 +813,130 @@ def fit_initial(model, z0, obs, iters, background=None, history=8, armijo=1e-4, 
         x, J, g = xn, Jn, gn
         hist.append(J)
     return x, hist, evals
+
+
+def gauss_newton_hvp(model, v, obs, background=None):
+    """The Gauss-Newton Hessian-vector product of the 4D-Var cost about the trajectory that model.fourdvar(z0, obs, ..., keep_tape=True)
+    has left on the tape,
+      H_GN v = v / sigma_b^2 + sum over the sets k of T_k^T H_k^T R_k^-1 H_k T_k v,
+    T_k the tangent from step 0 to the set's step, on `model` (anything with set_tangent, tangent_replay, observe_tangent, set_adjoint,
+    adjoint_add_obs, adjoint_back, adjoint, adjoint_rewind, adjoint_recorded).  v, an [nx, ny] field (numpy or torch), is set as the
+    tangent (float32) and replayed over the tape from observation time to observation time by absolute step index; at each,
+    observe_tangent gives w = h / sigma^2 on the GPU (sets at step 0 see v itself).  Then lam = 0 and the times are walked backward as
+    fourdvar walks them, adjoint_add_obs with w and adjoint_back; the tape is rewound (adjoint_rewind(-1)), so the next product finds
+    it whole.  Returns float64 [nx, ny] on the GPU.  No field crosses to the host and nothing nonlinear is stepped: one product costs a
+    replay and a sweep of the window.  It works through set_tangent and set_adjoint: a tangent set or an adjoint set that the user
+    had is REPLACED, and the tangent set is removed at the end; lam is left at the product's float32 form without the background
+    term.  'position' sets are a ValueError, and so is a tape that does not hold the window."""
+    t, dev = model.torch, _device(model)
+    obs = list(obs)
+    if not obs:
+        raise ValueError("gauss_newton_hvp: no observations")
+    if any(o.kind == POSITION for o in obs):
+        raise ValueError("gauss_newton_hvp: 'position' sets are not supported")
+    times = sorted(set(o.step for o in obs))
+    if model.adjoint_recorded() < times[-1]:
+        raise ValueError("gauss_newton_hvp: the tape holds %d steps, the window %d: call fourdvar(..., keep_tape=True) first"
+                         % (model.adjoint_recorded(), times[-1]))
+    if isinstance(v, np.ndarray):
+        v = t.from_numpy(np.ascontiguousarray(v))
+    v = v.to(dev)
+    w = {}
+    try:
+        model.set_tangent(v.float().contiguous())
+        at = 0
+        for when in times:
+            if when > at:
+                model.tangent_replay(at, when - at)
+            at = when
+            for k, o in enumerate(obs):
+                if o.step == when:
+                    w[k] = model.observe_tangent(o.kind, o.xy) / o.sigma ** 2
+        model.set_adjoint(t.zeros(tuple(v.shape), dtype=t.float32, device=dev))
+        for when, before in zip(times[::-1], times[-2::-1] + [0]):
+            for k, o in enumerate(obs):
+                if o.step == when:
+                    model.adjoint_add_obs(o.kind, o.xy, w[k])
+            model.adjoint_back(when - before)
+        hv = model.adjoint().double()
+    finally:
+        model.adjoint_rewind(-1)
+        model.set_tangent(None)
+    if background is not None:
+        hv = hv + v.double() / float(background[1]) ** 2
+    return hv
+
+
+def fit_incremental(model, z0, obs, outer, inner, background=None, cg_tol=1e-2, armijo=1e-4, shrink=0.5, max_backtracks=25):
+    """Incremental (Gauss-Newton) 4D-Var on `model` (anything with fourdvar(z, obs, background, keep_tape=True) -> (J, grad),
+    gauss_newton_hvp(v, obs, background) and record_adjoint): per outer iteration one nonlinear run gives J, g and leaves the
+    linearisation on the tape; conjugate gradients from 0 on H_GN delta = -g, stopped after `inner` products, or when
+    |r| <= cg_tol |g|, or at a direction of non-positive curvature (the first one: steepest descent); then a backtracking Armijo search
+    on the nonlinear J along delta, t from 1, times `shrink` per rejection, at most max_backtracks times, whose accepted evaluation is
+    the next outer iteration's J, g and tape.  Host logic on float64 tensors wherever z0 lives.  It stops after `outer` accepted
+    iterations, or at the first whose search finds no acceptable step, or when the gradient is zero.  Returns (z, J_history,
+    evaluations, hvps): the final field, float64; J at the start and after every accepted iteration; the numbers of fourdvar calls and
+    of Hessian-vector products.  The tape is freed at the end, whatever happens; the tangent set and the adjoint variable are
+    gauss_newton_hvp's."""
+    t = model.torch
+    if outer < 0 or inner < 1:
+        raise ValueError("fit_incremental: outer must be >= 0, inner >= 1")
+    if isinstance(z0, np.ndarray):
+        z0 = t.from_numpy(np.ascontiguousarray(z0))
+    x = z0.double().clone()
+
+    def evaluate(z):
+        J, g = model.fourdvar(z, obs, background, keep_tape=True)
+        return float(J), g.double().to(x.device)
+
+    def dot(a, b):
+        return float((a * b).sum())
+    evals = hvps = 0
+    hist = []
+    try:
+        J, g = evaluate(x)
+        evals, hist = 1, [J]
+        for _ in range(outer):
+            gg = dot(g, g)
+            if not gg > 0.0:
+                break
+            d, r = t.zeros_like(g), -g
+            p, rr = r.clone(), gg
+            for it in range(inner):
+                hp = model.gauss_newton_hvp(p, obs, background).double().to(x.device)
+                hvps += 1
+                php = dot(p, hp)
+                if not php > 0.0:
+                    if it == 0:
+                        d = r.clone()
+                    break
+                a = rr / php
+                d = d + a * p
+                r = r - a * hp
+                rn = dot(r, r)
+                if np.sqrt(rn) <= cg_tol * np.sqrt(gg):
+                    break
+                p = r + (rn / rr) * p
+                rr = rn
+            slope = dot(g, d)
+            if not slope < 0.0:
+                break
+            step, found = 1.0, None
+            for _ in range(max_backtracks):
+                xn = x + step * d
+                Jn, gn = evaluate(xn)
+                evals += 1
+                if np.isfinite(Jn) and Jn <= J + armijo * step * slope:
+                    found = (xn, Jn, gn)
+                    break
+                step *= shrink
+            if found is None:
+                break
+            x, J, g = found
+            hist.append(J)
+    finally:
+        model.record_adjoint(0)
+    return x, hist, evals, hvps
 
 
 def particles_dev(torch, xy):
@@ -1309,6 +1460,31 @@ class ModelSurface:
         """lam <- T^T lam over the last n recorded steps, newest first (the transpose of the tangent-linear step); they leave the tape."""
         self._call("adjoint_back", int(n))
 
+    def adjoint_rewind(self, n=-1):
+        """Un-pops the last n steps that adjoint_back popped (n = -1: every one still on the tape): a sweep does not erase a slot, so
+        the same steps can be swept again, with the same bits.  A step recorded after a pop overwrites the slots above it.  Refused under
+        checkpoint_adjoint and while a particle adjoint is set.  Nothing is launched."""
+        self._call("adjoint_rewind", int(n))
+
+    def tangent_replay(self, first, n):
+        """Applies the tangent step of the taped steps first .. first + n - 1 (0: the oldest step on record_adjoint's tape), oldest first,
+        to every perturbation of the tangent set, from the recorded stage states: nothing nonlinear is stepped, and the vorticity, a
+        tracer, particles, the tape and adjoint_recorded() stay as they are.  The base flow's fields are formed once per stage for the
+        whole set (4 + 5 M fields transformed per stage, where M perturbations stepped beside the vorticity take 10 M).  The operator of
+        the live tangent, not its bits; perturbation k of a set has the bits of the replayed set of one.  Steps that a sweep has popped
+        can still be replayed.  It needs a tangent set and the full tape; n = 0 does nothing."""
+        self._call("tangent_replay", int(first), int(n))
+
+    def observe_tangent(self, kind, xy, k=0):
+        """h = H dz_k: observe() of perturbation k of the tangent set in the place of the resident state, a float64 [n] tensor; for
+        "vort" bit for bit sample(tangents()[k], xy).  It changes nothing."""
+        t = self.torch
+        self._one_rank("observe_tangent", 0, 0, _SOME, 1, _SOME)
+        a = particles_dev(t, xy)
+        out = t.empty(a.shape[0], dtype=t.float64, device="cuda")
+        self._hand("observe_tangent", int(k), obs_kind(kind), a, int(a.shape[0]), out)
+        return out
+
     def singular_values(self, steps, iters, start):
         """(sigmas, v): power iteration on T^T T over `steps` steps from the current state in the L2 norm (singular_values()); the
         state is kept and put back through _STATE."""
@@ -1337,13 +1513,14 @@ class ModelSurface:
         self._hand("get_adjoints", out)
         return out
 
-    def singular_vectors(self, steps, k, iters, start=None, checkpoint_every=None):
+    def singular_vectors(self, steps, k, iters, start=None, checkpoint_every=None, replay=False):
         """(sigma [iters, k], V [k, nx, ny]): the k leading singular values and right singular vectors of the tangent over `steps`
         steps from the current state, by block power iteration with a tangent subspace and an adjoint set of k (singular_vectors());
-        the state is kept and put back through _STATE.  checkpoint_every: None the full tape, an int K or "sqrt" checkpoints."""
+        the state is kept and put back through _STATE.  checkpoint_every: None the full tape, an int K or "sqrt" checkpoints.
+        replay=True: one forward run, then tangent_replay over its tape in every iteration (no nonlinear step per iteration)."""
         self._one_rank("adjoint_record", int(steps))
         return singular_vectors(self, steps, k, iters, start, save=getattr(self, self._STATE[0]), restore=getattr(self, self._STATE[1]),
-                                checkpoint_every=checkpoint_every)
+                                checkpoint_every=checkpoint_every, replay=replay)
 
     def scatter(self, w, xy):
         """The transpose of sample(): n point values w, float64 [n], at the positions xy, float64 [n, 2], spread onto the grid with the
@@ -1393,13 +1570,29 @@ class ModelSurface:
         a = particles_dev(t, xy)
         self._hand("adjoint_add_obs", obs_kind(kind), a, values_dev(t, w, int(a.shape[0]), "w"), int(a.shape[0]))
 
-    def fourdvar(self, z0, obs, background=None, checkpoint_every=None, particles=None):
+    def fourdvar(self, z0, obs, background=None, checkpoint_every=None, particles=None, keep_tape=False):
         """(J, grad): the 4D-Var cost of the initial vorticity z0 against the Observations in obs, and its gradient with respect to z0,
         float64 [nx, ny] on the GPU (fourdvar()).  The tape takes T x 4 half spectra, T the last observation step; with
         checkpoint_every = K (or "sqrt": checkpoint_every(T)) ceil(T / K) + 4 K + 1 of them, for windows whose tape does not fit.
-        particles: the drifters' initial positions for sets of kind "position"; dJ/dX0 is left in particle_adjoint()."""
+        particles: the drifters' initial positions for sets of kind "position"; dJ/dX0 is left in particle_adjoint().
+        keep_tape=True leaves the tape, rewound, for gauss_newton_hvp (the same J and grad; the full tape only)."""
         self._one_rank("adjoint_record", 1)
-        return fourdvar(self, z0, obs, background, checkpoint_every, particles)
+        return fourdvar(self, z0, obs, background, checkpoint_every, particles, keep_tape)
+
+    def gauss_newton_hvp(self, v, obs, background=None):
+        """H_GN v, float64 [nx, ny] on the GPU: the Gauss-Newton Hessian-vector product of the 4D-Var cost about the trajectory that
+        fourdvar(..., keep_tape=True) left on the tape (gauss_newton_hvp()): one tangent replay and one sweep, nothing nonlinear stepped.
+        It REPLACES a tangent set and an adjoint set the user had, and removes the tangent set at the end."""
+        self._one_rank("tangent_replay", 0, 0)
+        return gauss_newton_hvp(self, v, obs, background)
+
+    def fit_incremental(self, z0, obs, outer, inner, background=None, cg_tol=1e-2):
+        """(z, J_history, evaluations, hvps): incremental (Gauss-Newton) 4D-Var from the first guess z0 (fit_incremental()): `outer`
+        nonlinear runs, each followed by at most `inner` conjugate-gradient steps on the quadratic model; z0 goes to the GPU first."""
+        self._one_rank("tangent_replay", 0, 0)
+        if isinstance(z0, np.ndarray):
+            z0 = self.torch.from_numpy(np.ascontiguousarray(z0))
+        return fit_incremental(self, z0.cuda(), obs, outer, inner, background, cg_tol)
 
     def fit_initial(self, z0, obs, iters, background=None, history=8, checkpoint_every=None, particles=None):
         """(z, J_history, evaluations): L-BFGS on fourdvar from the first guess z0 (fit_initial()); z0 goes to the GPU first, so the

@@ -220,10 +220,20 @@ static void tangent_tape_free(fb_model *m)
     m->tt_depth = m->tt_fill = 0;
 }
 
+// the tangent replay's real fields (tangent_replay, below): sized for the set's count, so they go with a set that goes or changes it
+static int replay_chunk(int count) { return count < REPLAY_CHUNK ? count : REPLAY_CHUNK; }
+static size_t replay_real_fields(int count) { return 4 + 5 * (size_t)replay_chunk(count); }
+static void replay_work_free(fb_model *m)
+{
+    if (m->rp_real) { hipFree(m->rp_real); m->rp_real = nullptr; }
+}
+static size_t replay_bytes(const fb_model *m) { return m->rp_real ? replay_real_fields(m->tg_n) * m->c->nx * m->c->ny * sizeof(float) : 0; }
+
 // (the basis tape holds copies of this set's bases in this set's count: it goes with the set)
 static void tangent_free(fb_model *m)
 {
     tangent_tape_free(m);
+    replay_work_free(m);
     for (Beside &f : m->tg) beside_free(f);
     for (cf *&p : m->tg_j) if (p) { hipFree(p); p = nullptr; }
     if (m->tg_red) { hipFree(m->tg_red); m->tg_red = nullptr; }
@@ -260,8 +270,10 @@ static int tangent_in(fb_model *m, fb_slab *s, const float *d_rows, int count)
     fb_ctx *c = m->c;
     int rc;
     const bool tape_goes = m->tt_depth && (!d_rows || count != m->tg_n);
-    if ((rc = beside_begin(m, (m->tg_n && (!d_rows || count < m->tg_n)) || tape_goes))) return rc;
+    const bool replay_goes = m->rp_real && (!d_rows || count != m->tg_n);     // (a queued replay may still use it)
+    if ((rc = beside_begin(m, (m->tg_n && (!d_rows || count < m->tg_n)) || tape_goes || replay_goes))) return rc;
     if (tape_goes) tangent_tape_free(m);
+    if (replay_goes) replay_work_free(m);
     if (!d_rows) { tangent_free(m); return FB_OK; }
     rc = each_group(c, c->nact, [&](int g, size_t n) { return rec_alloc((void **)&m->tg_j[g], n * sizeof(cf)); });
     if (!rc) rc = rec_alloc((void **)&m->tg_red, (size_t)c->ngroups * c->max_wg * sizeof(double));
@@ -1022,11 +1034,11 @@ static int checkpoint_refill(fb_model *m, fb_slab *s, bool *saved)
     }
     const int seg = (m->ck_left - 1) / m->ck_every, count = m->ck_left - seg * m->ck_every;
     if ((rc = checkpoint_restore(m, m->ck_store + (size_t)seg * n))) return rc;
-    m->ad_fill = 0;
+    m->ad_fill = m->ad_top = 0;
     m->ad_on = m->ck_replay = true;
     rc = s ? slab_steps(s, count) : model_step_impl(m, count, nullptr);
     m->ad_on = m->ck_replay = false;
-    if (rc) { m->ad_fill = 0; return rc; }
+    if (rc) { m->ad_fill = m->ad_top = 0; return rc; }
     m->ck_replayed += count;
     return FB_OK;
 }
@@ -1190,6 +1202,87 @@ static int adjoint_back(fb_model *m, fb_slab *s, int nsteps)
     return rc;
 }
 
+// ---- the tangent replay over the adjoint's tape (kernels: fb_replay.h) ----
+// One RK stage of the tangent step of every perturbation of the set about the recorded stage state zs, adjoint_stage_set's mirror
+// image.  The base flow once: k_adjoint_base, the backward x pass, four ROW_INV passes into the real fields 0..3 of rp_real (u, v,
+// zeta_x, zeta_y), which nothing below writes.  Then in chunks of C = min(tg_n, REPLAY_CHUNK) perturbations: per perturbation
+// k_replay_deriv from its state of this stage (tangent_stage's: the base at stage 0, the stage state afterwards), the backward x pass
+// and four ROW_INV passes into its four real fields (du, dv, dz_x, dz_y); per chunk k_replay_prod_set out of place into one field per
+// perturbation; per perturbation its product's r2c as beside_r2c takes a field (field 0 of the record workspace zeroed, ROW_FWD, the
+// forward x pass) and the tracer's k_beside_update with the model's nu, on the active column tiles only.  4 + 5 tg_n fields
+// transformed and 7 + ceil(tg_n / C) + 12 tg_n launches per stage.  The passes of distinct fields share no arithmetic.
+static int replay_stage(fb_model *m, int stage, const cf *zs)
+{
+    fb_ctx *c = m->c;
+    const ColGroup &G = c->grp[0];
+    const size_t n = grp_elems(c, G), nr = (size_t)c->nx * c->ny;
+    const SpecCoef coef = make_coef(c);
+    const int M = m->tg_n, C = replay_chunk(M);
+    cf *z = m->rec_work[0];
+    float *base = m->rp_real, *pert = base + 4 * nr, *prod = pert + (size_t)C * 4 * nr;
+    const float g = 1.0f / (float)((size_t)c->nx * c->ny);
+    const bool staged = stage > 0 && c->nact > 0;
+    const int ncr = 16 * G.nct_active;
+    int rc;
+    auto to_real = [&](float *out) -> int {                 // the fields 0..3 of the record workspace -> four real fields, the first negated
+        int r;
+        if ((r = launch_col_block<+1>(c, G, z, 4, (long)n)) || (r = launch_col_strided<+1>(c, G, z, 4, (long)n))) return r;
+        for (int f = 0; f < 4; ++f) {
+            RowArgs a = row_args_base(c);
+            a.M = view_single(c, z + f * n, (long)n); a.scale = f == 0 ? -g : g; a.rout = out + f * nr;           // u = -dpsi/dy (record(), REC_U)
+            if ((r = launch_row<ROW_INV>(c, a))) return r;
+        }
+        return FB_OK;
+    };
+    if ((rc = launch_n(c, k_adjoint_base, n / 2, coef, zs, z, (long)n, G.ncols, c->N1, c->N2, G.ky0)) || (rc = to_real(base))) return rc;
+    for (int k0 = 0; k0 < M; k0 += C) {
+        const int cnt = M - k0 < C ? M - k0 : C;
+        for (int k = 0; k < cnt; ++k) {
+            const Beside &f = m->tg[k0 + k];
+            if ((rc = launch_n(c, k_replay_deriv, n / 2, coef, (const cf *)f.c0[0], (const cf *)(staged ? f.c1[0] : f.c0[0]), z, (long)n, G.ncols, c->N1, c->N2, G.ky0)) ||
+                (rc = to_real(pert + (size_t)k * 4 * nr)))
+                return rc;
+        }
+        rc = dispatch<REPLAY_CHUNK>(cnt - 1, [&](auto K) {
+            return launch_n(c, k_replay_prod_set<K() + 1>, nr / 4, (const float *)base, (const float *)pert, prod, nr);
+        });
+        if (rc) return rc;
+        for (int k = 0; k < cnt; ++k) {
+            Beside &f = m->tg[k0 + k];
+            HIPCHK(hipMemsetAsync(z, 0, n * sizeof(cf), c->stream));                                                // pad columns zero
+            RowArgs a = row_args_base(c);
+            a.rin = prod + (size_t)k * nr; a.T = view_single(c, z, 0);
+            if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+            if ((rc = launch_col_strided<-1>(c, G, z, 1, 0)) || (rc = launch_col_block<-1>(c, G, z, 1, 0))) return rc;
+            if (ncr == 0 || c->nact == 0) continue;         // (every mode masked: nothing evolves)
+            rc = dispatch<4>(stage, [&](auto S) {
+                return launch_n(c, k_beside_update<S(), 1>, (size_t)c->nx * ncr / 2, coef, (const cf *)z, (const cf *)nullptr, f.c0[0], f.c1[0], f.acc[0], m->nu, m->dt,
+                                G.ncols, ncr, c->N1, c->N2, G.ky0);
+            });
+            if (rc) return rc;
+        }
+    }
+    return FB_OK;
+}
+
+// The tangent step of the taped steps first .. first + nsteps - 1 (0: the oldest slot) applied to every perturbation of the set, oldest
+// first, each step's stages in the order 0, 1, 2, 3.  The vorticity, a tracer, the particles, m->steps, the tape and the captured step
+// are not touched: the launches lie outside the step, as a sweep's do.  The workspace is allocated here at the first replay of a set.
+static int tangent_replay(fb_model *m, fb_slab *s, int first, int nsteps)
+{
+    fb_ctx *c = m->c;
+    const size_t n = grp_elems(c, c->grp[0]);
+    int rc;
+    if ((rc = advect_workspace(m, s))) return rc;
+    if ((rc = rec_alloc((void **)&m->rp_real, replay_real_fields(m->tg_n) * c->nx * c->ny * sizeof(float)))) return rc;
+    for (int k = 0; k < nsteps; ++k) {
+        const cf *step = m->ad_tape + (size_t)(first + k) * 4 * n;
+        for (int stage = 0; stage < 4; ++stage)
+            if ((rc = replay_stage(m, stage, step + (size_t)stage * n))) return rc;
+    }
+    return FB_OK;
+}
+
 // a slab of one rank goes through the same code; on several ranks the adjoint model is refused
 constexpr unsigned ADJOINT = NEED_TRANSPORT | ONE_RANK_ADJOINT, ADJOINT_SET = ADJOINT | NEED_ADJOINT;
 
@@ -1312,6 +1405,40 @@ static int adjoint_back(const Call &k, int nsteps)
 extern "C" int fb_model_adjoint_back(fb_model *m, int nsteps) { return adjoint_back(on_model("fb_model_adjoint_back", m), nsteps); }
 extern "C" int fb_slab_adjoint_back(fb_slab *s, int nsteps) { return adjoint_back(on_slab("fb_slab_adjoint_back", s), nsteps); }
 
+// The last n popped steps un-popped (n == -1: every one still on the tape): a sweep pops without erasing, so the slots up to ad_top
+// hold what they held.  Not under checkpointing (the segment holds ck_every steps, not the window), not while a particle adjoint is
+// set (the particle tape is popped in step with this one).  Nothing is launched.
+static int adjoint_rewind(const Call &k, int n)
+{
+    if (n < -1) return refuse(k, "n < -1 (-1: every step still on the tape)");
+    if (int rc = enter(k, ADJOINT)) return rc;
+    fb_model *m = k.m;
+    if (m->ck_every) return refuse(k, "not under adjoint checkpointing: the tape segment holds " + std::to_string(m->ck_every) + " steps, not the window (fb_model_adjoint_checkpoint)");
+    if (m->pa) return refuse(k, "a particle adjoint is set: the particle tape is popped in step with the adjoint's (fb_model_set_particle_adjoint)");
+    const int popped = m->ad_top - m->ad_fill;
+    if (n > popped) return refuse(k, std::to_string(n) + " steps asked for, " + std::to_string(popped) + " popped and still on the tape");
+    m->ad_fill += n < 0 ? popped : n;
+    return FB_OK;
+}
+extern "C" int fb_model_adjoint_rewind(fb_model *m, int n) { return adjoint_rewind(on_model("fb_model_adjoint_rewind", m), n); }
+extern "C" int fb_slab_adjoint_rewind(fb_slab *s, int n) { return adjoint_rewind(on_slab("fb_slab_adjoint_rewind", s), n); }
+
+// (the tape's range needs the model's state: after the handle; nsteps == 0 is no refusal and launches nothing)
+static int tangent_replay(const Call &k, int first, int nsteps)
+{
+    if (first < 0 || nsteps < 0) return refuse(k, "first < 0 or nsteps < 0");
+    if (int rc = enter(k, TANGENT_SET | ONE_RANK_ADJOINT)) return rc;
+    const fb_model *m = k.m;
+    if (m->ck_every) return refuse(k, "not under adjoint checkpointing: the tape segment holds " + std::to_string(m->ck_every) + " steps, not the window (fb_model_adjoint_checkpoint)");
+    if (!m->ad_tape) return refuse(k, "no tape (fb_model_adjoint_record)");
+    if ((long long)first + nsteps > m->ad_top)
+        return refuse(k, "steps " + std::to_string(first) + " .. " + std::to_string((long long)first + nsteps) + " asked for, " + std::to_string(m->ad_top) + " on the tape");
+    if (nsteps == 0) return FB_OK;
+    return tangent_replay(k.m, k.s, first, nsteps);
+}
+extern "C" int fb_model_tangent_replay(fb_model *m, int first, int nsteps) { return tangent_replay(on_model("fb_model_tangent_replay", m), first, nsteps); }
+extern "C" int fb_slab_tangent_replay(fb_slab *s, int first, int nsteps) { return tangent_replay(on_slab("fb_slab_tangent_replay", s), first, nsteps); }
+
 // ---- point observations and the forcing of the adjoint by their misfits (kernels: fb_obs.h) ----
 // Between two steps only: the step, the tape, the tangent and the sweep never see any of it.  One GPU or a slab of one rank, as the adjoint.
 static void obs_free(fb_model *m)
@@ -1339,12 +1466,13 @@ static int obs_scatter(fb_model *m, const double *d_xy, const double *d_w, int n
 // kind 0 zeta, 1 u, 2 v, 3 psi of the resident state as the record of that kind forms it (record(): fb_model_get_vort,
 // fb_model_get_diag), into the observations' own real field, then sample(): bit for bit sample() of that record
 static const RecKind OBS_REC[4] = {REC_VORT, REC_U, REC_V, REC_PSI};
-static int obs_observe(fb_model *m, fb_slab *s, int kind, const double *d_xy, int n, double *d_out)
+// (of != NULL: of a field stepped beside the vorticity in its place, as get_beside records one: H applied to a perturbation)
+static int obs_observe(fb_model *m, fb_slab *s, int kind, const double *d_xy, int n, double *d_out, cf *const *of = nullptr)
 {
     fb_ctx *c = m->c;
     int rc;
     if ((rc = rec_alloc((void **)&m->ob_real, (size_t)c->nx * c->ny * sizeof(float)))) return rc;
-    if ((rc = record(m, s, OBS_REC[kind], m->ob_real))) return rc;
+    if ((rc = record(m, s, OBS_REC[kind], m->ob_real, nullptr, of))) return rc;
     return sample(c, m->ob_real, d_xy, n, d_out);
 }
 
@@ -1402,6 +1530,27 @@ static int observe(const Call &k, int kind, const double *d_xy, int n, double *d
 extern "C" int fb_model_observe(fb_model *m, int kind, const double *d_xy, int n, double *d_out) { return observe(on_model("fb_model_observe", m), kind, d_xy, n, d_out); }
 extern "C" int fb_slab_observe(fb_slab *s, int kind, const double *d_xy, int n, double *d_out) { return observe(on_slab("fb_slab_observe", s), kind, d_xy, n, d_out); }
 
+// H applied to perturbation `which` of the tangent set: observe with the record's source set to its base (the count needs the
+// model's state: after the handle)
+static int observe_tangent(const Call &k, int which, int kind, const double *d_xy, int n, double *d_out)
+{
+    if (!obs_kind_ok(kind)) return refuse(k, OBS_KIND);
+    if (!d_xy || !d_out) return refuse(k, "NULL positions or output");
+    if (!particle_count_ok(n)) return refuse(k, "n outside [1, 2^24]");
+    if (which < 0) return refuse(k, "perturbation index < 0");
+    if (int rc = enter(k, TANGENT_SET | ONE_RANK_ADJOINT)) return rc;
+    if (which >= k.m->tg_n) return refuse(k, "perturbation " + std::to_string(which) + " of a set of " + std::to_string(k.m->tg_n));
+    return obs_observe(k.m, k.s, kind, d_xy, n, d_out, k.m->tg[which].c0);
+}
+extern "C" int fb_model_observe_tangent(fb_model *m, int k, int kind, const double *d_xy, int n, double *d_out)
+{
+    return observe_tangent(on_model("fb_model_observe_tangent", m), k, kind, d_xy, n, d_out);
+}
+extern "C" int fb_slab_observe_tangent(fb_slab *s, int k, int kind, const double *d_xy, int n, double *d_out)
+{
+    return observe_tangent(on_slab("fb_slab_observe_tangent", s), k, kind, d_xy, n, d_out);
+}
+
 // (d_sigma may be NULL: sigma = 1)
 static int obs_misfit(const Call &k, const double *d_h, const double *d_y, const double *d_sigma, int n, double *d_r, double *d_cost)
 {
@@ -1454,7 +1603,7 @@ static int beside_stage(fb_model *m, fb_slab *s, int stage)
 
 static void beside_step_done(fb_model *m)
 {
-    if (m->ad_on) ++m->ad_fill;                             // the four stage states of this step are on the tape
+    if (m->ad_on) m->ad_top = ++m->ad_fill;                 // the four stage states of this step are on the tape, and nothing above them
     if (m->pt_depth && m->pt_n && !m->ck_replay) ++m->pt_fill;      // and its four stage positions on the particles'
 }
 

@@ -26,6 +26,7 @@
 #include "fb_adjoint.h"
 #include "fb_obs.h"
 #include "fb_lagrangian.h"
+#include "fb_replay.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1074,6 +1075,10 @@ struct fb_model {
     int tg_n;
     cf *tg_j[3];
     double *tg_red;
+    // the tangent replay's real fields (fb_replay.h; host side in fb_beside.h): [4 + 5 C][nx][ny] for a set replayed in chunks of
+    // C = min(tg_n, REPLAY_CHUNK) perturbations (the four base fields, 4 C of the perturbations, C products); allocated at the first
+    // replay, sized for the count, freed with the tangent set; NULL before
+    float *rp_real;
     // the basis tape of the covariant Lyapunov vectors (fb_clv.h; host side in fb_beside.h): per column group tt_depth slots of the tg_n
     // bases tg[k].c0[g], [tt_depth][tg_n] arrays of grp_elems each in c0's own layout, tt_fill slots of it pushed; NULL and 0 while
     // there is none.  Bases only: stage states and accumulators carry nothing between two steps.  The step never reads it
@@ -1086,6 +1091,9 @@ struct fb_model {
     // 4 C products), and for a set the C spectra of the chunk's mu~ (ad_spec); NULL and ad_n == 0 without, and ad_n alone says
     // whether an adjoint is set
     cf *ad_tape; int ad_depth, ad_fill;
+    // ad_top: the slots from the oldest that hold recorded steps no later step has overwritten (>= ad_fill: a sweep pops without
+    // erasing, fb_model_adjoint_rewind un-pops up to here, fb_model_tangent_replay reads up to here); 0 wherever ad_fill is reset
+    int ad_top;
     // ad_on: the steps taken now stash their stage states (always while fb_model_adjoint_record's tape is on; under checkpointing only
     // while a segment is run again).  Adjoint checkpointing (fb_model_adjoint_checkpoint; host side in fb_beside.h): the tape is one
     // segment of ck_every steps, ck_store holds room for ceil(ck_max / ck_every) states of column group 0 as the state arrays hold them
@@ -1172,6 +1180,7 @@ static void beside_step_done(fb_model *m);                              // after
 static void beside_free_all(fb_model *m);
 static size_t adjoint_bytes(const fb_model *m);                         // what fb_model_info counts for the adjoint variables
 static size_t adjoint_tape_bytes(const fb_model *m);                    // and for the tape, or the tape segment, the checkpoints and the live copy
+static size_t replay_bytes(const fb_model *m);                          // and for the tangent replay's workspace
 static int checkpoint_take(fb_model *m, int *nsteps);                   // run_steps under checkpointing, before every piece of a step call
 static size_t lagrangian_bytes(const fb_model *m);                      // what fb_model_info counts for the particle tape and the particle adjoint
 
@@ -1183,7 +1192,7 @@ static void model_drop_graph(fb_model *m)
 // nothing recorded, no checkpoint taken, no step of a checkpointed window counted or swept (the arrays stay)
 static void adjoint_window_empty(fb_model *m)
 {
-    m->ad_fill = 0;
+    m->ad_fill = m->ad_top = 0;
     m->ck_n = m->ck_done = m->ck_left = 0;
     m->ck_swept = false;
     m->ck_replayed = 0;
@@ -1241,6 +1250,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
             n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
         for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
+        n += replay_bytes(m);                                                                                               // and its replay workspace
         n += adjoint_bytes(m) + adjoint_tape_bytes(m);                                                                      // the adjoint variables and their workspace; the tape
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
         if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
