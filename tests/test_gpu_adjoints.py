@@ -1,5 +1,5 @@
 """The adjoint subspace on the GPU (fb_model_set_adjoints, fb_model_get_adjoints, fb_model_adjoint_count; kernels csrc/fb_adjoint.h:
-k_adjoint_base, k_adjoint_mu, k_adjoint_prod_set; host side csrc/fb_beside.h, adjoint_stage_set): variable k of a set against the single
+k_adjoint_base, k_adjoint_mu, k_adjoint_prod_set; host side csrc/fb_beside_adjoint.h, adjoint_stage_set): variable k of a set against the single
 adjoint variable bit for bit on every kernel path of adjoint_numpy.PATH_CASES, the set's bounds and sweep arithmetic, its isolation
 from the step, the transpose as a matrix against the tangent subspace, Model.singular_vectors against the float64 block power iteration
 (tests/singular_numpy.py), the slab of one rank, the refusals and fb_model_info.  DESIGN.md, "Adjoint subspace", has the tables."""

@@ -1,5 +1,5 @@
 """Adjoint checkpointing on the GPU (fb_model_adjoint_checkpoint, fb_model_adjoint_checkpoint_info and what fb_model_step and
-fb_model_adjoint_back do while the mode is on; host layer csrc/fb_beside.h) against the engine's own full tape: every comparison is by
+fb_model_adjoint_back do while the mode is on; host layer csrc/fb_beside_adjoint.h) against the engine's own full tape: every comparison is by
 bits.  The inputs are adjoint_numpy.adjoint_inputs with the source set (never-dealiased noise on every field).  The grids are those of
 adjoint_numpy.PATH_CASES (the three-kernel x pass in its layouts) and 4096^2 (k_col_full); DESIGN.md, "Adjoint checkpointing", has
 the scheme, the continuity probe that a checkpoint of the state arrays alone rests on, and the memory table."""

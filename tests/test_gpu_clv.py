@@ -1,5 +1,5 @@
 """The covariant Lyapunov vectors on the GPU (fb_model_tangent_tape, fb_model_tangent_tape_push, fb_model_tangent_tape_count,
-fb_model_tangent_combine; kernel csrc/fb_clv.h, host side csrc/fb_beside.h): the combination bit for bit and against float64, the basis
+fb_model_tangent_combine; kernel csrc/fb_clv.h, host side csrc/fb_beside_tangent.h): the combination bit for bit and against float64, the basis
 tape, the covariance identity T V_n = V_(n+1) D through the engine's own tangent step, the float64 Ginelli run of tests/clv_numpy.py and
 a fluid at rest.  Every bar is fixed by reasoning or by a CPU figure (tests/test_clv_cpu.py), none by what the GPU gave; one line of
 figures per case (pytest -s); DESIGN.md, "Covariant Lyapunov vectors", has the tables."""

@@ -1,5 +1,5 @@
 """The tangent subspace on the GPU (fb_model_set_tangents, fb_model_tangent_gram, fb_model_tangent_qr; kernels csrc/fb_tangent.h, host
-side csrc/fb_beside.h) against the single tangent it must reproduce bit for bit, the float64 subspace of tests/lyapunov_numpy.py and
+side csrc/fb_beside_tangent.h) against the single tangent it must reproduce bit for bit, the float64 subspace of tests/lyapunov_numpy.py and
 the analytic spectrum of a fluid at rest.  Every bar here is fixed by reasoning or by a CPU figure (tests/test_lyapunov_cpu.py), none
 by what the GPU gave; one line of figures per case (pytest -s); DESIGN.md, "Tangent subspace and Lyapunov spectrum", has the table."""
 import functools

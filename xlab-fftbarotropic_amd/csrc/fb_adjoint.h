@@ -1,5 +1,5 @@
 // fb_adjoint.h -- kernels of the adjoint model (fb_model_adjoint_record, fb_model_set_adjoint, fb_model_adjoint_back and their fb_slab_*
-// twins on one rank; host side: fb_beside.h, adjoint_stage).
+// twins on one rank; host side: fb_beside_adjoint.h, adjoint_stage).
 //
 // The transpose of the tangent-linear step of fb_tangent.h under the inner product <a, b> = sum over the grid of a b.  With zeta the
 // vorticity's state of an RK stage (from the tape: the stage states recorded while the model stepped forward, masked modes merged in
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) k_adjoint_update(SpecCoef c, const cf *__
     }
 }
 
-// ---- a set of adjoint variables on the one trajectory (fb_model_set_adjoints; host side: fb_beside.h, adjoint_stage_set) ----
+// ---- a set of adjoint variables on the one trajectory (fb_model_set_adjoints; host side: fb_beside_adjoint.h, adjoint_stage_set) ----
 // Four of the five fields a stage takes back to physical space are functions of the recorded stage state alone, so a set of M
 // variables forms them once per stage and each variable adds its own mu~:
 //   k_adjoint_base     grady psi, gradx psi, gradx zeta, grady zeta into the fields 0..3 of the record workspace, once per stage

@@ -1,4 +1,4 @@
-// fb_clv.h -- the kernel of the covariant Lyapunov vectors (fb_model_tangent_combine, fb_slab_tangent_combine; host side: fb_beside.h,
+// fb_clv.h -- the kernel of the covariant Lyapunov vectors (fb_model_tangent_combine, fb_slab_tangent_combine; host side: fb_beside_tangent.h,
 // tangent_combine, beside tangent_qr).
 //
 // Ginelli's algorithm keeps the orthonormal bases Q_n of a window of QR intervals (the basis tape, fb_model::tt: copies of the

@@ -34,8 +34,8 @@ static const struct { unsigned need; const char *who; int code; } ONE_RANK[] = {
 };
 static const struct { unsigned need; bool (*set)(const fb_model *); const char *refusal; } FEATURE[] = {
     {NEED_TRACER, [](const fb_model *m) { return m->tracer; }, "no tracer is set"},
-    {NEED_TANGENT, [](const fb_model *m) { return m->tg_n != 0; }, "no tangent is set"},
-    {NEED_ADJOINT, [](const fb_model *m) { return m->ad_n != 0; }, "no adjoint is set"},
+    {NEED_TANGENT, [](const fb_model *m) { return m->tg.n != 0; }, "no tangent is set"},
+    {NEED_ADJOINT, [](const fb_model *m) { return m->ad.n != 0; }, "no adjoint is set"},
     {NEED_PARTICLES, [](const fb_model *m) { return m->pt_n != 0; }, "no particles are set"},
     {NEED_DEFORMATION, [](const fb_model *m) { return m->pd != nullptr; }, "no particle deformation is set (fb_model_set_particle_deformation)"},
 };

@@ -1,6 +1,6 @@
 // fb_lagrangian.h -- kernels of the adjoint of the particle step (fb_model_particle_tape, fb_model_set_particle_adjoint,
 // fb_model_get_particle_adjoint and what fb_model_adjoint_back runs while a particle adjoint is set; their fb_slab_* twins on one rank;
-// host side: fb_beside.h, lagrangian_*).
+// host side: fb_beside_particles.h, lagrangian_*).
 //
 // The particles of fb_particles.h are advanced by  x0 = X, x1 = X + dt/2 k1, x2 = X + dt/2 k2, x3 = X + dt k3,  k_{s+1} = U_s(x_s),
 // X' = X + dt/6 (k1 + 2 k2 + 2 k3 + k4), U_s the interpolated velocity of the vorticity's state of stage s.  With Xb the gradient of a

@@ -1,5 +1,5 @@
 // fb_obs.h -- kernels of the point observations (fb_model_scatter, fb_model_observe, fb_model_obs_misfit, fb_model_adjoint_add_obs and
-// their fb_slab_* twins on one rank; host side: fb_beside.h, obs_scatter, obs_observe, obs_adjoint_add).
+// their fb_slab_* twins on one rank; host side: fb_beside_adjoint.h, obs_scatter, obs_observe, obs_adjoint_add).
 //
 // The observation operator H takes a field of the resident state (zeta, u, v or psi, formed as fb_model_get_vort / fb_model_get_diag
 // form them: record(), fb_record.h) to n points by k_sample (fb_particles.h).  Its transpose spreads n point values back:

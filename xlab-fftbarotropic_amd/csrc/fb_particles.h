@@ -1,4 +1,4 @@
-// fb_particles.h -- kernels of the Lagrangian particles (fb_model_set_particles, fb_model_sample; host side: fb_record.h, particle_stage).
+// fb_particles.h -- kernels of the Lagrangian particles (fb_model_set_particles, fb_model_sample; host side: fb_beside_particles.h, particle_stage).
 //
 // Particles are points (x, y) [m] on the doubly periodic domain, float64 and UNWRAPPED; grid point (i, j) of an [nx][ny] field lies
 // at x = i dx, y = j dy.  Every RK4 step of the model advances them by the same scheme, coupled stage by stage:

@@ -43,11 +43,24 @@ extern "C" int fb_slab_set_vort_local(fb_slab *s, const float *d_rows) { return 
 // ---- the record layer ----
 enum RecKind { REC_VORT, REC_PSI, REC_U, REC_V, REC_OW, REC_KEFF, REC_PRES };
 
+// a device array: on failure *p == NULL, the runtime's last error is cleared (the next launch's check must not find it) and `what`
+// is the message of FB_ENOMEM
+static int dev_alloc(void **p, size_t bytes, const char *what)
+{
+    if (hipMalloc(p, bytes) == hipSuccess) return FB_OK;
+    *p = nullptr;
+    (void)hipGetLastError();
+    return fail(FB_ENOMEM, what);
+}
+template <class T> static void dev_free(T *&p)
+{
+    if (p) { hipFree(p); p = nullptr; }
+}
+
 // a buffer of the record path: allocated on first use, then kept
 static int rec_alloc(void **p, size_t bytes)
 {
-    if (!*p && hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return fail(FB_ENOMEM, "record-path allocation failed"); }
-    return FB_OK;
+    return *p ? FB_OK : dev_alloc(p, bytes, "record-path allocation failed");
 }
 // a scratch buffer of the record path, grown to the largest request (hipFree waits for the device)
 static int rec_reserve(void **p, size_t *cap, size_t bytes)

@@ -1,5 +1,5 @@
 // fb_replay.h -- kernels of the tangent replay over the adjoint's tape (fb_model_tangent_replay and its fb_slab_* twin on one rank; host
-// side: fb_beside.h, replay_stage).
+// side: fb_beside_adjoint.h, replay_stage).
 //
 // The tangent-linear step of fb_tangent.h applied to a set of perturbations about stage states that are already on the adjoint's tape
 // (fb_adjoint.h): nothing nonlinear is stepped.  With zeta the recorded stage state, u = -psi_y, v = psi_x its velocity and dz the

@@ -380,7 +380,7 @@ static int slab_steps(fb_slab *s, int nsteps)
 
 // the step pair: fb_model_step (hipGraph replay where it applies, model_steps) and fb_slab_step
 // (counted here, not where a step is launched: a captured step is launched once and replayed)
-// Under adjoint checkpointing the call is split at the checkpoint boundaries: checkpoint_take (fb_beside.h) copies the state where a
+// Under adjoint checkpointing the call is split at the checkpoint boundaries: checkpoint_take (fb_beside_adjoint.h) copies the state where a
 // piece starts on one and cuts the piece at the next, and each piece is stepped as any call is, the captured step replayed.
 static int run_steps(const Call &k, int nsteps)
 {

@@ -1,4 +1,4 @@
-// fb_tangent.h -- kernels of the tangent-linear model (fb_model_set_tangent, fb_slab_set_tangent; host side: fb_beside.h, tangent_stage).
+// fb_tangent.h -- kernels of the tangent-linear model (fb_model_set_tangent, fb_slab_set_tangent; host side: fb_beside_tangent.h, tangent_stage).
 //
 // A perturbation dz of the vorticity is carried along the evolving state by the linearisation of the discrete step: at every RK stage
 //   tend_dz = dealiase( r2c(-u dz_x - v dz_y  -  du zeta_x - dv zeta_y) + nu laplacian(dz_c) ),
@@ -17,7 +17,7 @@
 // of perturbations on the one trajectory (fb_model_set_tangents; a single tangent, fb_model_set_tangent, is the set of one):
 // k_tangent_scale, the inner product of two bases k_tangent_dot (+ k_tangent_dot_final), whose <a, a> is the norm, and the steps of a
 // modified Gram-Schmidt sweep whose coefficients never leave the device, k_tangent_axpy, k_tangent_sqrt, k_tangent_scale_dev (host
-// side: tangent_dot, tangent_gram, tangent_qr in fb_beside.h).
+// side: tangent_dot, tangent_gram, tangent_qr in fb_beside_tangent.h).
 // No reference counterpart: the reference has no tangent-linear model.
 #pragma once
 

@@ -940,25 +940,46 @@ static RowArgs row_args_base(const fb_ctx *c)
     return a;
 }
 
-// real [nx][ny] -> private spectral layout (dst: nx*P complex, pad columns must be zero-initialised)      [one GPU]
-static int r2c_private(fb_ctx *c, const float *d_real, cf *dst)
+// ---- the two transform passes over several fields (one GPU, or a slab of one rank: column group 0, no exchange) ----
+// nf spectra in the private layout at z + f * fstride (destroyed) -> nf real fields [nx][ny] at out + f * nx * ny, each times g, field
+// `neg` times -g (-1: none): the backward x pass over all of them in one launch each, then one ROW_INV row pass per field.
+// (nf, fstride) go to the column launches as they are: (1, 0) for a single field, (nf, nx * P) for fields one after the other.
+static int spectra_to_real(fb_ctx *c, cf *z, int nf, long fstride, float *out, float g, int neg)
 {
-    RowArgs a = row_args_base(c); a.rin = d_real; a.T = view_single(c, dst, 0);
+    const ColGroup &G = c->grp[0];
+    const size_t nr = (size_t)c->nx * c->ny;
     int rc;
-    if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
-    if ((rc = launch_col_strided<-1>(c, c->grp[0], dst, 1, 0))) return rc;
-    return launch_col_block<-1>(c, c->grp[0], dst, 1, 0);
+    if ((rc = launch_col_block<+1>(c, G, z, nf, fstride)) || (rc = launch_col_strided<+1>(c, G, z, nf, fstride))) return rc;
+    for (int f = 0; f < nf; ++f) {
+        RowArgs a = row_args_base(c);
+        a.M = view_single(c, z + f * fstride, fstride); a.scale = f == neg ? -g : g; a.rout = out + f * nr;
+        if ((rc = launch_row<ROW_INV>(c, a))) return rc;
+    }
+    return FB_OK;
 }
 
-// private spectral layout (work: destroyed) -> real [nx][ny] * scale                                       [one GPU]
-static int c2r_private(fb_ctx *c, cf *work, float *d_real, float scale)
+// nf real fields [nx][ny] at real + f * nx * ny -> nf spectra in the private layout at z + f * fstride: one ROW_FWD row pass per field,
+// then the forward x pass over all of them in one launch each.  The row pass writes the live columns only: the caller has zeroed
+// the pad columns of z (a memset of the whole destination, wherever it has always stood).
+static int real_to_spectra(fb_ctx *c, const float *real, cf *z, int nf, long fstride)
 {
+    const ColGroup &G = c->grp[0];
+    const size_t nr = (size_t)c->nx * c->ny;
     int rc;
-    if ((rc = launch_col_block<+1>(c, c->grp[0], work, 1, 0))) return rc;
-    if ((rc = launch_col_strided<+1>(c, c->grp[0], work, 1, 0))) return rc;
-    RowArgs a = row_args_base(c); a.M = view_single(c, work, 0); a.rout = d_real; a.scale = scale;
-    return launch_row<ROW_INV>(c, a);
+    for (int f = 0; f < nf; ++f) {
+        RowArgs a = row_args_base(c);
+        a.rin = real + f * nr; a.T = view_single(c, z + f * fstride, 0);
+        if ((rc = launch_row<ROW_FWD>(c, a))) return rc;
+    }
+    if ((rc = launch_col_strided<-1>(c, G, z, nf, fstride))) return rc;
+    return launch_col_block<-1>(c, G, z, nf, fstride);
 }
+
+// real [nx][ny] -> private spectral layout (dst: nx*P complex, pad columns must be zero-initialised)      [one GPU]
+static int r2c_private(fb_ctx *c, const float *d_real, cf *dst) { return real_to_spectra(c, d_real, dst, 1, 0); }
+
+// private spectral layout (work: destroyed) -> real [nx][ny] * scale                                       [one GPU]
+static int c2r_private(fb_ctx *c, cf *work, float *d_real, float scale) { return spectra_to_real(c, work, 1, 0, d_real, scale, -1); }
 
 // 3-pass row layout <-> the tile-major layout of the state arrays (out-of-place)
 static bool state_tm(const fb_ctx *c) { return c->N2 >= 32; }
@@ -1009,10 +1030,13 @@ extern "C" int fb_c2r(fb_ctx *c, const float *d_in, float *d_out, int normalize)
 //   t_recv  [nx][ncols]          block s = rows of rank s, read by the column kernels
 struct GroupBufs { cf *ZA, *ZB, *ACC, *w4_send, *w4_recv, *t_send, *t_recv; };
 
-// a spectral field stepped beside the vorticity (fb_beside.h: the tracer, the tangent-linear model's perturbation): per column group in
-// the 3-pass layout [nx][ncols] the base, and for the groups of active columns the stage state and the RK accumulator; NULL while the
-// field is not set.  Never in the record workspace: a record taken between two steps overwrites that.
+// a spectral field stepped beside the vorticity (fb_beside.h: the tracer, a perturbation of the tangent set, an adjoint variable): per
+// column group in the 3-pass layout [nx][ncols] the base, and for the groups of active columns the stage state and the RK accumulator;
+// NULL while the field is not set.  Never in the record workspace: a record taken between two steps overwrites that.
 struct Beside { cf *c0[3], *c1[3], *acc[3]; };
+// n such fields on the one trajectory, advanced one after the other: what the tangent subspace and the adjoint subspace both are
+struct BesideSet { static constexpr int MAX = 32; Beside v[MAX]; int n; };
+static_assert(FB_TANGENTS_MAX == BesideSet::MAX && FB_ADJOINTS_MAX == BesideSet::MAX, "BesideSet holds either public bound, and the refusals' text names it");
 
 struct fb_model {
     fb_ctx *c;
@@ -1059,7 +1083,7 @@ struct fb_model {
     Beside tr;
     float kappa;
     bool tracer;                     // a tracer is set
-    // the Lagrangian particles (fb_particles.h; host side in fb_beside.h): six float64 arrays of pt_n (base, stage position, RK
+    // the Lagrangian particles (fb_particles.h; host side in fb_beside_particles.h): six float64 arrays of pt_n (base, stage position, RK
     // accumulator, x then y of each) and the stage velocity u, v as two real fields [2][nx][ny]; NULL and 0 without particles
     double *pt; int pt_n;
     float *pt_uv;
@@ -1067,35 +1091,34 @@ struct fb_model {
     // accumulator of F11, F12, F21, F22 each), NULL while it is off; steps: the model's steps so far, pd_steps0: at the last reset
     double *pd;
     long long steps, pd_steps0;
-    // the tangent-linear model (fb_tangent.h; host side in fb_beside.h): tg_n perturbations on the one trajectory (a tangent subspace;
+    // the tangent-linear model (fb_tangent.h; host side in fb_beside_tangent.h): tg.n perturbations on the one trajectory (a tangent subspace;
     // fb_model_set_tangent sets one), each allocated when it is set, and what they share, since they are advanced one after the other:
     // the first advect pass's tendency of a stage (groups of active columns) and the partial sums of an inner product (the norm is
-    // one); NULL and tg_n == 0 without, and tg_n alone says whether a tangent is set
-    Beside tg[FB_TANGENTS_MAX];
-    int tg_n;
+    // one); NULL and tg.n == 0 without, and tg.n alone says whether a tangent is set
+    BesideSet tg;
     cf *tg_j[3];
     double *tg_red;
-    // the tangent replay's real fields (fb_replay.h; host side in fb_beside.h): [4 + 5 C][nx][ny] for a set replayed in chunks of
-    // C = min(tg_n, REPLAY_CHUNK) perturbations (the four base fields, 4 C of the perturbations, C products); allocated at the first
+    // the tangent replay's real fields (fb_replay.h; host side in fb_beside_adjoint.h): [4 + 5 C][nx][ny] for a set replayed in chunks of
+    // C = min(tg.n, REPLAY_CHUNK) perturbations (the four base fields, 4 C of the perturbations, C products); allocated at the first
     // replay, sized for the count, freed with the tangent set; NULL before
     float *rp_real;
-    // the basis tape of the covariant Lyapunov vectors (fb_clv.h; host side in fb_beside.h): per column group tt_depth slots of the tg_n
-    // bases tg[k].c0[g], [tt_depth][tg_n] arrays of grp_elems each in c0's own layout, tt_fill slots of it pushed; NULL and 0 while
+    // the basis tape of the covariant Lyapunov vectors (fb_clv.h; host side in fb_beside_tangent.h): per column group tt_depth slots of the tg.n
+    // bases tg.v[k].c0[g], [tt_depth][tg.n] arrays of grp_elems each in c0's own layout, tt_fill slots of it pushed; NULL and 0 while
     // there is none.  Bases only: stage states and accumulators carry nothing between two steps.  The step never reads it
     cf *tt[3]; int tt_depth, tt_fill;
-    // the adjoint model (fb_adjoint.h; host side in fb_beside.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
+    // the adjoint model (fb_adjoint.h; host side in fb_beside_adjoint.h).  The tape: ad_depth steps x 4 stage states of the vorticity in the
     // 3-pass layout, masked modes merged in from the base, ad_fill steps of it recorded; NULL and 0 while nothing is recorded.  The
-    // ad_n adjoint variables on the one tape (an adjoint subspace; fb_model_set_adjoint sets one), each lam (ad[k].c0) with the k-bar
+    // ad.n adjoint variables on the one tape (an adjoint subspace; fb_model_set_adjoint sets one), each lam (ad.v[k].c0) with the k-bar
     // (c1) and the accumulator (acc) of a backward step, and what they share: the real fields of the product pass, [5][nx][ny] for
-    // the one, [4 + 5 C][nx][ny] for a set swept in chunks of C = min(ad_n, ADJOINT_CHUNK) variables (the four base fields, C mu~,
-    // 4 C products), and for a set the C spectra of the chunk's mu~ (ad_spec); NULL and ad_n == 0 without, and ad_n alone says
+    // the one, [4 + 5 C][nx][ny] for a set swept in chunks of C = min(ad.n, ADJOINT_CHUNK) variables (the four base fields, C mu~,
+    // 4 C products), and for a set the C spectra of the chunk's mu~ (ad_spec); NULL and ad.n == 0 without, and ad.n alone says
     // whether an adjoint is set
     cf *ad_tape; int ad_depth, ad_fill;
     // ad_top: the slots from the oldest that hold recorded steps no later step has overwritten (>= ad_fill: a sweep pops without
     // erasing, fb_model_adjoint_rewind un-pops up to here, fb_model_tangent_replay reads up to here); 0 wherever ad_fill is reset
     int ad_top;
     // ad_on: the steps taken now stash their stage states (always while fb_model_adjoint_record's tape is on; under checkpointing only
-    // while a segment is run again).  Adjoint checkpointing (fb_model_adjoint_checkpoint; host side in fb_beside.h): the tape is one
+    // while a segment is run again).  Adjoint checkpointing (fb_model_adjoint_checkpoint; host side in fb_beside_adjoint.h): the tape is one
     // segment of ck_every steps, ck_store holds room for ceil(ck_max / ck_every) states of column group 0 as the state arrays hold them
     // (ZA), ck_n of them taken, ck_live one more for the live state during a sweep.  The window: ck_done steps taken forward, ck_left
     // of them not yet swept (ad_fill of those are on the tape), ck_swept once a sweep has popped one, ck_replayed steps run again
@@ -1104,17 +1127,16 @@ struct fb_model {
     int ck_every, ck_max, ck_n, ck_done, ck_left;
     long long ck_replayed;
     cf *ck_store, *ck_live;
-    Beside ad[FB_ADJOINTS_MAX];
-    int ad_n;
+    BesideSet ad;
     float *ad_real;
     cf *ad_spec;
-    // the point observations (fb_obs.h; host side in fb_beside.h): the fixed-point accumulator of a scatter (two 64-bit limbs for
+    // the point observations (fb_obs.h; host side in fb_beside_adjoint.h): the fixed-point accumulator of a scatter (two 64-bit limbs for
     // each of the nx * ny cells, and its head), the real field that is observed from or scattered into, the partial sums of a misfit ([max_wg]
     // float64); each allocated at its first use, then kept
     unsigned long long *ob_acc;
     float *ob_real;
     double *ob_red;
-    // the adjoint of the particle step (fb_lagrangian.h; host side in fb_beside.h).  The particle tape: pt_depth steps x 4 stage
+    // the adjoint of the particle step (fb_lagrangian.h; host side in fb_beside_particles.h).  The particle tape: pt_depth steps x 4 stage
     // positions, float64 [pt_n][2] each, pt_fill steps of it recorded while the model stepped; NULL and 0 while it is off.  The
     // particle adjoint: eight float64 arrays of pt_n (Xb, the stage's p and q, the accumulator; x then y of each), and the two
     // fixed-point accumulators of a stage's deposit (2 x 2 limbs for each of the nx * ny cells, and the head); NULL while none is set.
@@ -1174,7 +1196,7 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
     return model_create_impl(out, c, nu, dt, false);
 }
 
-// the fields stepped beside the vorticity (fb_beside.h): what the step and the model's end know of them
+// the fields stepped beside the vorticity (fb_beside.h and the headers it includes): what the step and the model's end know of them
 static int beside_stage(fb_model *m, fb_slab *s, int stage);            // at the top of RK stage `stage` of fb_model_step and fb_slab_step
 static void beside_step_done(fb_model *m);                              // after the step's fourth stage
 static void beside_free_all(fb_model *m);
@@ -1247,9 +1269,9 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         if (m->pt_n) n += 6 * (size_t)m->pt_n * sizeof(double) + 2 * (size_t)c->nx * c->ny * sizeof(float);               // the particles' state
         if (m->pd) n += 12 * (size_t)m->pt_n * sizeof(double);                                                             // and their deformation gradient
         n += lagrangian_bytes(m);                                                                                           // their tape and their adjoint
-        for (int g = 0; g < c->ngroups && m->tg_n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
-            n += ((size_t)m->tg_n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
-        for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg_n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
+        for (int g = 0; g < c->ngroups && m->tg.n; ++g)       // the tangent-linear model's: per perturbation, and the one shared tg_j
+            n += ((size_t)m->tg.n * (g < c->nact ? 3 : 1) + (g < c->nact ? 1 : 0)) * grp_elems(c, c->grp[g]) * sizeof(cf);
+        for (int g = 0; g < c->ngroups; ++g) n += (size_t)m->tt_depth * m->tg.n * grp_elems(c, c->grp[g]) * sizeof(cf);            // and its basis tape
         n += replay_bytes(m);                                                                                               // and its replay workspace
         n += adjoint_bytes(m) + adjoint_tape_bytes(m);                                                                      // the adjoint variables and their workspace; the tape
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
