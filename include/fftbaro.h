@@ -569,6 +569,36 @@ int fb_azimuthal_cols(int nmodes, int *ncols);
 #define FB_CENSUS_MAX   65536
 int fb_model_census(fb_model *m, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
                     double *d_table, int *d_count, int *d_labels);
+/* Stochastic ring forcing, linear drag and hyperviscosity as a split stage after every completed RK4 step (off by default).  For
+ * every stored mode (i, j) of the half spectrum inside the dealiasing circle (a masked mode keeps its bits)
+ *   zeta_new = fl32(D zeta) + Delta_n,   D = fl32(exp(-(mu + nu_p K^2p) dt)) evaluated in float64, K^2 = -laplacian_coe(i, j),
+ * an exact exponential factor, so a nabla^8 hyperviscosity puts no stability limit on dt.  The ring holds the modes with
+ * |sqrt(K^2) - k_f| <= dk [rad/m] (float64), the four self-conjugate modes (i in {0, nx/2}, j in {0, ny/2}) left out; N_ring counts
+ * them over the FULL spectrum (a stored mode with 0 < j < ny/2 twice).  On the ring
+ *   Delta_n = fl32(GRIDS sqrt(2 rate dt K^2 / N_ring) e^{i theta}),  theta = 2 pi u / 2^32,
+ * u = output word 0 of Philox4x32-10 with counter (i, j, n_lo, n_hi) and key (seed_lo, seed_hi), n the forcing clock: the split
+ * stages applied since this call, a 64-bit count in device memory (a captured step replays correctly).  On the lines j = 0 and
+ * j = ny/2 a mode with i > nx/2 takes the conjugate of mode (nx - i, j).  White in time: from rest one stage adds rate dt of energy
+ * E = sum over the full spectrum of |zeta / GRIDS|^2 / (2 K^2) exactly; rate [m^2 s^-3] is the mean energy injection rate.  The noise
+ * depends on (i, j, n, seed) alone: not on the layout, the kernel path or the launch geometry.
+ * rate = mu = nu_p = 0 removes the stage; rate = 0 alone is pure dissipation and needs no ring (k_f, dk ignored).  Every perturbation
+ * of the tangent set is multiplied by D inside the circle after each step (the forcing is additive), so the Lyapunov exponents are
+ * those of the forced-dissipative system.  The tracer, the particles and their deformation gradient are untouched.  The derivative
+ * fields are formed again after the stage, inside the step.  Memory: one half spectrum where the state arrays are not in the
+ * 3-pass layout, and a few KiB; allocated here, counted by fb_model_info.
+ * FB_EINVAL before any HIP call: rate, mu, nu_p (and with rate > 0 k_f, dk) not finite or negative, p outside [1, 8]; then a
+ * NULL model; then k_f - dk <= 0, an empty ring or a ring that holds a masked mode.  FB_EUNSUPPORTED: a slab of several
+ * ranks; while the adjoint's tape or a checkpointed window exists (and fb_model_adjoint_record / fb_model_adjoint_checkpoint are
+ * refused with FB_EUNSUPPORTED while forcing is set: the transpose through D and the replay of a window's noise are not built). */
+int fb_model_set_forcing(fb_model *m, double rate, double k_f, double dk, size_t seed, double mu, double nu_p, int p);
+/* out[6] on the HOST: the forcing clock, then the running totals since fb_model_set_forcing of dE_forc = E(zeta_new) - E(zeta'),
+ * dE_diss = E(zeta') - E(zeta) with zeta' = fl32(D zeta), dZ_forc and dZ_diss likewise with Z = sum over the full spectrum of
+ * |zeta / GRIDS|^2 / 2, then N_ring.  Summed in the stage's own pass in float64 with Hermitian weights, per workgroup and then in a
+ * fixed order: no atomics, the bits repeat.  Waits for the model's stream.  FB_EINVAL while no forcing is set. */
+int fb_model_forcing_budget(fb_model *m, double *out);
+/* Delta_n for the clock value n into d_spec, a device array [nx][ny/2+1] complex in the layout of fb_model_get_spectrum (zeros off
+ * the ring), from the device function the stage itself calls.  FB_EINVAL while no forcing is set. */
+int fb_model_forcing_increment(fb_model *m, size_t n, float *d_spec);
 /* vort_c in the reference layout */
 int fb_model_get_spectrum(fb_model *m, float *d_spec);
 int fb_model_set_spectrum(fb_model *m, const float *d_spec);
@@ -706,6 +736,11 @@ int fb_slab_get_particle_adjoint(fb_slab *s, double *d_xbar);
  * FB_EUNSUPPORTED: a structure that crosses the ranks' row slabs needs a border merge over the ranks. */
 int fb_slab_census(fb_slab *s, const float *d_field, const float *d_weight, int mode, float threshold, int min_cells, int max_structures,
                    double *d_table, int *d_count, int *d_labels);
+/* the split stage (fb_model_set_forcing) on a slab of ONE rank: the same code, the same bits.  On world > 1 they return
+ * FB_EUNSUPPORTED: the budget's sums and the re-priming after the stage are built for the one column group of one rank. */
+int fb_slab_set_forcing(fb_slab *s, double rate, double k_f, double dk, size_t seed, double mu, double nu_p, int p);
+int fb_slab_forcing_budget(fb_slab *s, double *out);
+int fb_slab_forcing_increment(fb_slab *s, size_t n, float *d_spec);
 int fb_slab_step(fb_slab *s, int nsteps);
 int fb_slab_synchronize(fb_slab *s);
 /* the rank's compute stream is the engine's own: record an event behind what has been queued on it (fb_slab_get_*_local ->

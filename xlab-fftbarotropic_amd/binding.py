@@ -95,9 +95,11 @@ _CHECKPOINT_PAIRS = {"adjoint_checkpoint": [_ip, _ip], "adjoint_checkpoint_info"
 _LAGRANGIAN_PAIRS = {"particle_tape": [_ip], "particle_tape_count": [_pip, _pip], "set_particle_adjoint": [_vp], "get_particle_adjoint": [_vp]}
 # the tangent replay's pairs, likewise: the replay over the adjoint's tape, the rewind of a sweep and H applied to a perturbation
 _REPLAY_PAIRS = {"tangent_replay": [_ip, _ip], "adjoint_rewind": [_ip], "observe_tangent": [_ip, _ip, _vp, _ip, _vp]}
+# the split stage's pairs, likewise: ring forcing, drag and hyperviscosity on and off, the budget and the increment
+_FORCING_PAIRS = {"set_forcing": [_db, _db, _db, _sz, _db, _db, _ip], "forcing_budget": [_pdb], "forcing_increment": [_sz, _vp]}
 for _name, _args in (list(_PAIRS.items()) + list(_DEFORMATION_PAIRS.items()) + list(_CENSUS_PAIRS.items()) + list(_CLV_PAIRS.items())
                      + list(_OBS_PAIRS.items()) + list(_ADJOINTS_PAIRS.items()) + list(_CHECKPOINT_PAIRS.items())
-                     + list(_LAGRANGIAN_PAIRS.items()) + list(_REPLAY_PAIRS.items())):
+                     + list(_LAGRANGIAN_PAIRS.items()) + list(_REPLAY_PAIRS.items()) + list(_FORCING_PAIRS.items())):
     SIGNATURES["fb_model_" + _name.replace("_local", "")] = SIGNATURES["fb_slab_" + _name] = ([_vp] + _args, None)
 EXPORTS = list(SIGNATURES)
 
@@ -1634,6 +1636,37 @@ class ModelSurface:
         self._one_rank("get_particle_adjoint", _SOME)
         out = t.empty((max(self.particle_count(), 1), 2), dtype=t.float64, device="cuda")
         self._hand("get_particle_adjoint", out)
+        return out
+
+    def set_forcing(self, rate=0.0, k=None, width=None, seed=0, drag=0.0, hyper_nu=0.0, hyper_order=1):
+        """Stochastic ring forcing, linear drag and hyperviscosity as a split stage after every step (include/fftbaro.h,
+        fb_model_set_forcing): zeta <- D zeta + Delta_n, D = exp(-(drag + hyper_nu K^(2 hyper_order)) dt), Delta_n white in time on
+        the ring |K - k| <= width [rad/m], injecting `rate` [m^2 s^-3] of energy per unit time, from Philox4x32-10 keyed on (mode,
+        forcing clock, seed).  rate = drag = hyper_nu = 0 (the defaults) removes the stage; rate = 0 alone is pure dissipation and
+        needs no ring.  The perturbations of the tangent set are multiplied by D.  One rank only; refused while the adjoint's tape
+        or a checkpointed window exists, and record_adjoint / checkpoint_adjoint are refused while forcing is set."""
+        none = rate == 0
+        self._call("set_forcing", float(rate), 0.0 if none and k is None else float(k), 0.0 if none and width is None else float(width),
+                   int(seed) & 0xFFFFFFFFFFFFFFFF, float(drag), float(hyper_nu), int(hyper_order))
+
+    FORCING_BUDGET = ("clock", "dE_forc", "dE_diss", "dZ_forc", "dZ_diss", "n_ring")
+
+    def forcing_budget(self):
+        """{"clock": split stages since set_forcing, "dE_forc", "dE_diss", "dZ_forc", "dZ_diss": the running totals of the energy
+        E = <|u|^2> / 2 and the enstrophy Z = <zeta^2> / 2 that the increments added and the factor D removed (float64, summed in
+        the stage's own pass in a fixed order: the bits repeat), "n_ring": the ring's modes over the full spectrum}"""
+        out = (C.c_double * 6)()
+        self._call("forcing_budget", out)
+        d = dict(zip(self.FORCING_BUDGET, out))
+        d["clock"], d["n_ring"] = int(d["clock"]), int(d["n_ring"])
+        return d
+
+    def forcing_increment(self, n):
+        """Delta_n of the forcing clock's value n, a complex64 tensor [nx, ny/2+1] in the layout of the spectrum (zeros off the ring)"""
+        t = self.torch
+        self._one_rank("forcing_increment", 0, _SOME)
+        out = t.empty((self.nx, self.ny // 2 + 1), dtype=t.complex64, device="cuda")
+        self._hand("forcing_increment", int(n), out)
         return out
 
 

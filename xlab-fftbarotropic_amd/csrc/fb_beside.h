@@ -3,7 +3,8 @@
 // included below where the shared path ends: fb_beside_tangent.h (the tangent set, its inner products and QR, the basis tape and the
 // combination), fb_beside_particles.h (the particles, their deformation gradient, their tape and their adjoint), fb_beside_adjoint.h
 // (the adjoint's tape and checkpoints, the adjoint and its set, the sweep, the tangent replay, the observations).  Kernels:
-// fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h, fb_lagrangian.h, fb_adjoint.h, fb_replay.h, fb_obs.h.
+// fb_tracer.h, fb_tangent.h, fb_clv.h, fb_particles.h, fb_lagrangian.h, fb_adjoint.h, fb_replay.h, fb_obs.h.  And the split stage that
+// follows a step once forcing, drag or hyperviscosity is set: fb_beside_forcing.h (kernels: fb_forcing.h).
 //
 // Each is taken in between two steps and advanced at the top of every RK stage of fb_model_step and fb_slab_step, from the state the
 // vorticity's stage starts from, through the record workspace (record_advect, fb_record.h): the step's own buffers are only read.  A
@@ -267,6 +268,7 @@ extern "C" int fb_slab_get_tracer_eddy_diffusivity(fb_slab *s, int nbins, double
 #include "fb_beside_tangent.h"
 #include "fb_beside_particles.h"
 #include "fb_beside_adjoint.h"
+#include "fb_beside_forcing.h"
 
 // ---- what the step and the model's end know of all of them (declared in fftbaro.hip) ----
 // At the top of RK stage `stage`, from the state the vorticity's stage starts from: the tracer's stage, the particles', the
@@ -296,4 +298,5 @@ static void beside_free_all(fb_model *m)
     adjoint_free(m);
     adjoint_tape_free(m);
     obs_free(m);
+    forcing_free(m);
 }

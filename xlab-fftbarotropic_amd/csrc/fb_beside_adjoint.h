@@ -351,11 +351,14 @@ static int tangent_replay(fb_model *m, fb_slab *s, int first, int nsteps)
 
 // a slab of one rank goes through the same code; on several ranks the adjoint model is refused
 constexpr unsigned ADJOINT = NEED_TRANSPORT | ONE_RANK_ADJOINT, ADJOINT_SET = ADJOINT | NEED_ADJOINT;
+// the transpose through D and the replay of a window's noise are not built: no tape and no window while forcing is set
+static const char *const FORCING_NO_ADJOINT = "not while forcing is set: the adjoint of the split stage is not built (fb_model_set_forcing)";
 
 static int adjoint_record(const Call &k, int depth)
 {
     if (depth < 0 || depth > (1 << 20)) return refuse(k, "depth outside [0, 2^20]");
     if (int rc = enter(k, ADJOINT)) return rc;
+    if (depth && k.m->fr_on) return refuse(k, FORCING_NO_ADJOINT, FB_EUNSUPPORTED);
     return adjoint_record(k.m, depth);
 }
 extern "C" int fb_model_adjoint_record(fb_model *m, int depth) { return adjoint_record(on_model("fb_model_adjoint_record", m), depth); }
@@ -367,6 +370,7 @@ static int adjoint_checkpoint(const Call &k, int every, int max_steps)
     if (every && max_steps < 1) return refuse(k, "max_steps < 1");
     if (every && ((long long)max_steps + every - 1) / every > (1 << 20)) return refuse(k, "more than 2^20 checkpoints (ceil(max_steps / every))");
     if (int rc = enter(k, ADJOINT)) return rc;
+    if (every && k.m->fr_on) return refuse(k, FORCING_NO_ADJOINT, FB_EUNSUPPORTED);
     return adjoint_checkpoint(k.m, every, max_steps);
 }
 extern "C" int fb_model_adjoint_checkpoint(fb_model *m, int every, int max_steps)

@@ -23,6 +23,8 @@ enum : unsigned {
     ONE_RANK_TANGENT = 32, ONE_RANK_ADJOINT = 64, ONE_RANK_PARTICLES = 128,         // refused on a slab of several ranks
     NEED_DEFORMATION = 256,     // the particles carry their deformation gradient (after NEED_PARTICLES: no particles is the first refusal)
     ONE_RANK_CENSUS = 512,      // refused on a slab of several ranks
+    ONE_RANK_FORCING = 1024,    // likewise
+    NEED_FORCING = 2048,        // forcing, drag or hyperviscosity is set (fb_model_set_forcing)
 };
 static const struct { unsigned need; const char *who; int code; } ONE_RANK[] = {
     {ONE_RANK_TANGENT, "the tangent-linear model is", FB_EINVAL},
@@ -31,6 +33,8 @@ static const struct { unsigned need; const char *who; int code; } ONE_RANK[] = {
     {ONE_RANK_PARTICLES, "particles are", FB_EUNSUPPORTED},
     // a structure that crosses the ranks' row slabs would need a border merge over the ranks
     {ONE_RANK_CENSUS, "the vortex census is", FB_EUNSUPPORTED},
+    // the budget's sums and the re-priming after the split stage are built for the one column group of one rank
+    {ONE_RANK_FORCING, "the stochastic forcing is", FB_EUNSUPPORTED},
 };
 static const struct { unsigned need; bool (*set)(const fb_model *); const char *refusal; } FEATURE[] = {
     {NEED_TRACER, [](const fb_model *m) { return m->tracer; }, "no tracer is set"},
@@ -38,6 +42,7 @@ static const struct { unsigned need; bool (*set)(const fb_model *); const char *
     {NEED_ADJOINT, [](const fb_model *m) { return m->ad.n != 0; }, "no adjoint is set"},
     {NEED_PARTICLES, [](const fb_model *m) { return m->pt_n != 0; }, "no particles are set"},
     {NEED_DEFORMATION, [](const fb_model *m) { return m->pd != nullptr; }, "no particle deformation is set (fb_model_set_particle_deformation)"},
+    {NEED_FORCING, [](const fb_model *m) { return m->fr_on; }, "no forcing is set (fb_model_set_forcing)"},
 };
 
 // every refusal that depends on the handle alone

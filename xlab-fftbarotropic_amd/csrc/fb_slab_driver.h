@@ -373,7 +373,10 @@ static int slab_steps(fb_slab *s, int nsteps)
     for (int n = 0; n < nsteps; ++n)
         for (int k = 0; k < 4; ++k) {                       // main.cpp:288-317
             if ((rc = beside_stage(s->m, s, k)) || (rc = slab_stage(s, k))) return rc;
-            if (k == 3) beside_step_done(s->m);
+            if (k == 3) {
+                beside_step_done(s->m);
+                if ((rc = forcing_stage(s->m, s))) return rc;
+            }
         }
     return FB_OK;
 }

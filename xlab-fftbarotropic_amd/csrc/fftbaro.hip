@@ -27,6 +27,7 @@
 #include "fb_obs.h"
 #include "fb_lagrangian.h"
 #include "fb_replay.h"
+#include "fb_forcing.h"
 #include "fb_col_full.h"
 #include "fb_row3.h"
 #include "fb_row8.h"
@@ -1144,6 +1145,17 @@ struct fb_model {
     double *pt_tape; int pt_depth, pt_fill;
     double *pa;
     unsigned long long *pa_acc;
+    // the split stage after every step (fb_forcing.h; host side in fb_beside_forcing.h): stochastic ring forcing, linear drag and
+    // hyperviscosity.  fr: the kernels' arguments; fr_nring: the ring's modes over the full spectrum; fr_work: the vorticity in the
+    // 3-pass layout where the state arrays are in another (NULL where the stage runs in place); fr_part: [max_wg][4] float64 partial
+    // sums of the budget; fr_dev: the 64-bit forcing clock, then the four running totals (float64).  All allocated when the forcing is
+    // set, so that a step allocates nothing and a captured step reads its clock from the device; NULL and fr_on false without
+    bool fr_on;
+    ForcingArgs fr;
+    int fr_nring;
+    cf *fr_work;
+    double *fr_part;
+    unsigned long long *fr_dev;
 };
 
 // one rank of the multi-GPU model (fb_slab_driver.h)
@@ -1199,6 +1211,8 @@ extern "C" int fb_model_create(fb_model **out, fb_ctx *c, float nu, float dt)
 // the fields stepped beside the vorticity (fb_beside.h and the headers it includes): what the step and the model's end know of them
 static int beside_stage(fb_model *m, fb_slab *s, int stage);            // at the top of RK stage `stage` of fb_model_step and fb_slab_step
 static void beside_step_done(fb_model *m);                              // after the step's fourth stage
+static int forcing_stage(fb_model *m, fb_slab *s);                      // and after that: the split stage, where forcing is set (fb_beside_forcing.h)
+static size_t forcing_bytes(const fb_model *m);                         // what fb_model_info counts for it
 static void beside_free_all(fb_model *m);
 static size_t adjoint_bytes(const fb_model *m);                         // what fb_model_info counts for the adjoint variables
 static size_t adjoint_tape_bytes(const fb_model *m);                    // and for the tape, or the tape segment, the checkpoints and the live copy
@@ -1276,6 +1290,7 @@ extern "C" int fb_model_info(fb_model *m, size_t *hbm, size_t *alg)
         n += adjoint_bytes(m) + adjoint_tape_bytes(m);                                                                      // the adjoint variables and their workspace; the tape
         if (m->cs_label) n += 2 * (size_t)c->nx * c->ny * sizeof(int);                                                      // the census's labels and ids
         if (m->cs_part) n += (size_t)c->nx * c->ny / CENSUS_TILE * sizeof(int2);                                           // and its scan partials
+        n += forcing_bytes(m);                                                                                              // the split stage's workspace, sums and clock
         *hbm = n;
     }
     if (alg) *alg = (size_t)320 * c->nx * c->ny;
@@ -1479,6 +1494,7 @@ static int model_step_impl(fb_model *m, int nsteps, StepProf *prof)
             PROF_END(0);
         }
         beside_step_done(m);
+        if ((rc = forcing_stage(m, nullptr))) return rc;
     }
     return FB_OK;
 }

@@ -65,6 +65,12 @@
 // the structures of zeta (or of the Okubo-Weiss parameter W) above (or below) T with at least K cells, always weighted by zeta.  The
 // last file of a record in ./log.  One GPU only: --world P > 1, a missing --census-threshold and arguments that the C ABI would
 // refuse are refused here (exit status 2).
+// --forcing-rate E --forcing-k K --forcing-width W [--forcing-seed S] [--drag MU] [--hyper-nu V --hyper-order P] (no reference
+// counterpart; defaults E = 0, S = 0, MU = 0, V = 0, P = 1) set the split stage of fb_model_set_forcing after every step: stochastic
+// forcing at the energy rate E [m^2 s^-3] in the ring |K - k| <= W [rad/m], linear drag MU [1/s] and hyperviscosity V K^2P.  Every
+// record gains forcing_budget_step_N.bin, six float64 (fb_model_forcing_budget: the forcing clock, dE_forc, dE_diss, dZ_forc,
+// dZ_diss, N_ring), the last file of a record in ./log.  One GPU only: --world P > 1, values that are negative or not finite, P
+// outside [1, 8] and a rate without a ring are refused here (exit status 2).
 #include <fcntl.h>
 #include <getopt.h>
 #include <sys/stat.h>
@@ -116,6 +122,9 @@ struct Config {
     bool dump_census = false, census_have_thr = false, census_ow = false, census_below = false;       // the vortex census (no reference counterpart)
     float census_thr = 0.0f; int census_min = 4, census_max = 256;
     std::string particles_file; int n_particles = 0;                               // the Lagrangian particles' initial positions and their number (no reference counterpart)
+    double forcing_rate = 0.0, forcing_k = 0.0, forcing_width = 0.0, drag = 0.0, hyper_nu = 0.0;     // the split stage after every step (no reference counterpart)
+    unsigned long long forcing_seed = 0; int hyper_order = 1;
+    bool forcing() const { return forcing_rate > 0.0 || drag > 0.0 || hyper_nu > 0.0; }
 };
 
 // --fifo-fanout (multi-GPU, SURVEY.md section 8(e) "rank 0 reads, scatters x-slabs"): ONE producer that writes whole fields -- the
@@ -461,6 +470,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
     const int o_tangent = rows(tangent, "tangent");
     const int o_growth = tangent ? add("tangent_growth", Output::WHOLE, 3 * sizeof(double), false) : -1;          // time, norm, sum of ln(growth): filled by the step loop
     const int o_census = whole(cfg.dump_census, "census", (size_t)cfg.census_max * FB_CENSUS_COLS * sizeof(double));
+    const int o_budget = cfg.forcing() ? add("forcing_budget", Output::WHOLE, 6 * sizeof(double), false) : -1;     // filled by the step loop
     auto F = [&](int o) { return o < 0 ? (float *)nullptr : (float *)outs[o].dev; };   // an entry's device buffer; NULL where the option is off
     auto D = [&](int o) { return o < 0 ? (double *)nullptr : (double *)outs[o].dev; };
 
@@ -550,6 +560,12 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
         if (!(tg_norm0 > 0.0) || !std::isfinite(tg_norm0)) { std::fprintf(stderr, "--tangent: the perturbation's norm is %g\n", tg_norm0); std::exit(1); }
     }
 
+    if (cfg.forcing()) {                                                               // the split stage, after whatever it acts on has been set
+        const int st = fb_model_set_forcing(eng->model, cfg.forcing_rate, cfg.forcing_k, cfg.forcing_width, (size_t)cfg.forcing_seed, cfg.drag, cfg.hyper_nu, cfg.hyper_order);
+        if (st == FB_EINVAL) { std::fprintf(stderr, "--forcing-rate: %s\n", fb_last_error()); std::exit(2); }     // a ring that is empty on this grid, or that leaves the dealiasing circle
+        must(st, "fb_model_set_forcing");
+    }
+
     // [timing] ("add steps/s + GB/s summary"; the reference prints no timing, main.cpp:262-264).  The step loop is
     // never synchronised for it: time-stamped events on the compute stream bracket the stretches BETWEEN record steps -- a stretch ends
     // where the record branch begins, before the host waits for the writer, and the next one begins behind the record kernels -- so
@@ -613,6 +629,7 @@ static void run_rank(const Config &cfg, int rank, void *hub, FILE *log_fd, bool 
                 ENGINE_CALL(*eng, census, census, w, F(o_vort), cfg.census_below ? FB_CENSUS_BELOW : FB_CENSUS_ABOVE, cfg.census_thr, cfg.census_min, cfg.census_max,
                             D(o_census), d_census_count, nullptr);
             }
+            if (o_budget >= 0 && lead) ENGINE_CALL(*eng, forcing_budget, forcing_budget, (double *)outs[o_budget].host[set]);     // (waits for the compute stream)
             eng->record(e_rec);
             must(fb_stream_wait_event(copy, e_rec), "wait");
             h0 = std::chrono::steady_clock::now();
@@ -727,6 +744,8 @@ int main(int argc, char *args[])
                                     {"particle-deformation", 0, 0, 40},
                                     {"dump-census", 0, 0, 41}, {"census-threshold", 1, 0, 42}, {"census-field", 1, 0, 43}, {"census-below", 0, 0, 44},
                                     {"census-min-cells", 1, 0, 45}, {"census-max", 1, 0, 46},
+                                    {"forcing-rate", 1, 0, 47}, {"forcing-k", 1, 0, 48}, {"forcing-width", 1, 0, 49}, {"forcing-seed", 1, 0, 50},
+                                    {"drag", 1, 0, 51}, {"hyper-nu", 1, 0, 52}, {"hyper-order", 1, 0, 53},
                                     {0, 0, 0, 0}};
     int opt;
     while ((opt = getopt_long(argc, args, "I:O:i:s:f:", lopts, NULL)) != EOF) {      // main.cpp:68-80, main-shallow-water.cpp:75-95
@@ -795,6 +814,18 @@ int main(int argc, char *args[])
         case 44: cfg.census_below = true; break;
         case 45: cfg.census_min = int_option(1, 1L << 30, "--census-min-cells: an integer in [1, 2^30]"); break;
         case 46: cfg.census_max = int_option(1, FB_CENSUS_MAX, "--census-max: an integer in [1, 65536]"); break;
+        case 47: cfg.forcing_rate = real_option(false, 0.0, true, DBL_MAX, "--forcing-rate: a finite number >= 0"); break;     // forcing_budget_step_N.bin (one GPU only)
+        case 48: cfg.forcing_k = real_option(false, 0.0, false, DBL_MAX, "--forcing-k: a finite number > 0"); break;
+        case 49: cfg.forcing_width = real_option(false, 0.0, true, DBL_MAX, "--forcing-width: a finite number >= 0"); break;
+        case 50: {
+            char *end = nullptr;
+            cfg.forcing_seed = strtoull(optarg, &end, 0);
+            if (!*optarg || *end || *optarg == '-') { fprintf(stderr, "--forcing-seed: an integer in [0, 2^64)\n"); return 2; }
+            break;
+        }
+        case 51: cfg.drag = real_option(false, 0.0, true, DBL_MAX, "--drag: a finite number >= 0"); break;
+        case 52: cfg.hyper_nu = real_option(false, 0.0, true, DBL_MAX, "--hyper-nu: a finite number >= 0"); break;
+        case 53: cfg.hyper_order = int_option(1, 8, "--hyper-order: an integer in [1, 8]"); break;
         case 25: cfg.pres_rho = (float)atof(optarg); break;
         case 26: cfg.pres_f = (float)atof(optarg); break;
         case 27: case 28:                                // invert_pres.cpp:71-79 (-x, -y)
@@ -843,6 +874,8 @@ int main(int argc, char *args[])
         if (!cfg.census_have_thr) { fprintf(stderr, "--dump-census: needs --census-threshold T\n"); return 2; }
         if (cfg.world > 1) { fprintf(stderr, "--dump-census: one GPU only (the vortex census is not supported with --world P > 1)\n"); return 2; }
     }
+    if (cfg.forcing() && cfg.world > 1) { fprintf(stderr, "--forcing-rate / --drag / --hyper-nu: one GPU only (the stochastic forcing is not supported with --world P > 1)\n"); return 2; }
+    if (cfg.forcing_rate > 0.0 && !(cfg.forcing_k - cfg.forcing_width > 0.0)) { fprintf(stderr, "--forcing-rate: needs --forcing-k K and --forcing-width W with K - W > 0\n"); return 2; }
     if (!cfg.tangent_file.empty() && cfg.world > 1) { fprintf(stderr, "--tangent: one GPU only (the tangent-linear model is not supported with --world P > 1)\n"); return 2; }
     if ((cfg.dump_grad || cfg.dump_dvortdt) && cfg.world > 1) { fprintf(stderr, "--dump-grad-vort / --dump-dvortdt: one GPU only\n"); return 2; }
     if (cfg.total_steps < 0) cfg.total_steps = (int)(60 * 60 / cfg.dt);              // configuration.hpp:36
